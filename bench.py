@@ -8,11 +8,17 @@ split their fp32 operands into f16 halves on the matrix cores (the JSON line's `
 With one GPU the timed steps are submitted to pipeline.DepthMapPipeline (`--streams`, default 3 depth maps in flight: the product's
 inference() default); `one_at_a_time` in the JSON line is the same forward with a single depth map in flight.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, what was timed).
+`--dump-outputs DIR` writes what the timed path returned in its last step (the disparity) as DIR/<name>.npy; the inputs are
+seeded, so two builds can be compared output for output.  `--full` adds everything else the line has carried: the
+one-at-a-time latency, the instrumented kernel pass (`roofline`, `kernels`, `inner_loop`), parity against the committed
+reference capture, the CPU baseline and, for N > 1, the replica context run and rank 0's single-GPU forward.
+
 N > 1 (configs[3]): ONE reference frame is sharded over the ranks.  The default `--mode both` times the two schemes one
-after the other and reports both under "modes" (plus, as context, `replica`: N independent depth maps, weak scaling); the headline
+after the other and reports both under "modes" (plus, with --full, as context `replica`: N independent depth maps, weak scaling); the headline
 (`value`, `ms_per_step`) is a fresh timed run of the faster of the two strong-scaling schemes:
   shard   rank g encodes the source views v with (v-1) % N == g; their feature maps are all-gathered (RCCL over xGMI) while
           the rank encodes the reference view; image rows are sharded for the cost volume and the GRU loop, with the 7-row
@@ -20,7 +26,7 @@ after the other and reports both under "modes" (plus, as context, `replica`: N i
   views   north_star's scheme: views sharded, the view-sum volume all-reduced once per stage, GRU replicated.
 Total work is fixed as N grows => "scaling": "strong".  `--mode replica` runs N independent depth maps (weak scaling).
 
-Rank 0 prints ONE JSON line (see the README of this file's contract in DESIGN.md §Measurement): besides
+Rank 0 prints ONE JSON line (see the README of this file's contract in DESIGN.md §Measurement): with --full, besides
 the driver's keys it carries
   "roofline":     the dominant kernel (the z|r gate convolution, MFMA-bound) - algorithmic FLOPs per launch
                   divided by its average launch duration measured with HIP events on its stream,
@@ -78,7 +84,34 @@ def parse():
                          "4e-6 from fp32; s16: all-f16, fp32-class, one accumulator; f16x3: round-1 kernels), or exact fp32 MFMA.  auto (the "
                          "product's default): s16f8 if the model's first forward agrees with s16 within 2.5e-5 relative L1, else s16 - the "
                          "calibration forward runs in the warm-up; the JSON line says which form the timed region used")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the disparity the timed path returned in its last step to DIR/disparity.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: one-at-a-time latency, instrumented kernel pass and "
+                         "roofline, parity vs the reference capture, CPU baseline (N > 1: replica run, rank 0's single-GPU forward)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirpath, arrays):
+    """Write {name: tensor} as dirpath/<name>.npy in float32 (float64 stays float64).  Over DUMP_LIMIT_BYTES in all, every array is
+    replaced by a fixed, seeded sample of its flattened elements (same positions on every run)."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    host = {k: v.detach().cpu() for k, v in arrays.items()}
+    host = {k: (v.double() if v.dtype == torch.float64 else v.float()).numpy() for k, v in host.items()}
+    total = sum(a.nbytes for a in host.values())
+    for name, a in host.items():
+        if total > DUMP_LIMIT_BYTES:
+            n = max(1, int(a.size * DUMP_LIMIT_BYTES / total))
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=n, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirpath, name + ".npy"), np.ascontiguousarray(a))
 
 
 def kernel_timing(model, inputs, scale):
@@ -316,7 +349,7 @@ def main():
                 elapsed = time.perf_counter() - t0
             else:
                 # S depth maps in flight (DepthMapPipeline: one model replica + one HIP stream each, submitted round-robin): every
-                # step is a complete forward; the steps overlap on the GPU.  One-at-a-time time first, for the record.
+                # step is a complete forward; the steps overlap on the GPU.  --full: one-at-a-time time first, for the record.
                 from cer_mvs_amd.pipeline import DepthMapPipeline
                 pipe = DepthMapPipeline(model, streams=S)
                 for _ in range(max(args.warmup, S)):
@@ -324,20 +357,22 @@ def main():
                 while model.gru_precision == "auto" and any(m._auto_pending() for m in pipe.models):   # (calibration forwards + the replicas' adoption: untimed)
                     out = pipe.result(pipe.submit(*inputs, scale), wait_on_host=False)
                 sync()
-                out = model(*inputs, scale=scale)        # untimed: the caller's stream has its own allocator pool (first use = hipMalloc)
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                for _ in range(min(args.steps, 3)):
-                    out = model(*inputs, scale=scale)
-                torch.cuda.synchronize()
-                lat = (time.perf_counter() - t0) / min(args.steps, 3)
-                sync()
+                if args.full:
+                    out = model(*inputs, scale=scale)        # untimed: the caller's stream has its own allocator pool (first use = hipMalloc)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    for _ in range(min(args.steps, 3)):
+                        out = model(*inputs, scale=scale)
+                    torch.cuda.synchronize()
+                    lat = (time.perf_counter() - t0) / min(args.steps, 3)
+                    sync()
                 t0 = time.perf_counter()
                 handles = [pipe.submit(*inputs, scale) for _ in range(args.steps)]
                 out = pipe.result(handles[-1], wait_on_host=False)
                 sync()
                 elapsed = time.perf_counter() - t0
-                assert all(torch.equal(pipe.result(h_), out) for h_ in handles)      # (same input every step: same output every step)
+                if args.full:
+                    assert all(torch.equal(pipe.result(h_), out) for h_ in handles)      # (same input every step: same output every step)
         assert torch.isfinite(out).all()
         timed_run.one_at_a_time_ms = None if lat is None else 1e3 * lat
         timed_run.streams = S
@@ -362,21 +397,24 @@ def main():
             except Exception as exc:                       # (a scheme the transport refuses must not cost the other scheme's line)
                 modes[m] = {"error": f"{type(exc).__name__}: {exc}"[:300], "parallelism": label}
             torch.cuda.empty_cache()
-        try:
-            # context, never the headline: N independent depth maps, one per GPU, no communication (weak scaling)
-            e_r, out_r, model_r, _, _, _ = timed_run("replica")
-            modes["replica"] = {"value": world * args.steps / e_r, "ms_per_step": 1e3 * e_r / args.steps, "scaling": "weak",
-                                "parallelism": f"replica x{world}: {world} independent depth maps per step"}
-            del model_r, out_r
-        except Exception as exc:
-            modes["replica"] = {"error": f"{type(exc).__name__}: {exc}"[:300]}
-        torch.cuda.empty_cache()
+        if args.full:
+            try:
+                # context, never the headline: N independent depth maps, one per GPU, no communication (weak scaling)
+                e_r, out_r, model_r, _, _, _ = timed_run("replica")
+                modes["replica"] = {"value": world * args.steps / e_r, "ms_per_step": 1e3 * e_r / args.steps, "scaling": "weak",
+                                    "parallelism": f"replica x{world}: {world} independent depth maps per step"}
+                del model_r, out_r
+            except Exception as exc:
+                modes["replica"] = {"error": f"{type(exc).__name__}: {exc}"[:300]}
+            torch.cuda.empty_cache()
         ok = [m for m in ("shard", "views") if "ms_per_step" in modes[m]]
         if not ok:
             raise SystemExit(f"bench.py: both sharding schemes failed: {modes}")
         args.mode = min(ok, key=lambda m: modes[m]["ms_per_step"])
     shard = world > 1 and args.mode in ("shard", "views")
     elapsed, out, model, inputs, scale, sd = timed_run(args.mode)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"disparity": out})
     requested_precision = args.gru_precision
     if args.gru_precision == "auto":     # the form the calibration kept (cer-mvs_amd/raft.py: RAFT._forward_calibrating) is what was timed
         assert model.auto_choice is not None and model.auto_choice.partition("+")[0] in ("s16f6", "s16f8", "s16"), "the warm-up did not calibrate gru_precision='auto'"
@@ -389,7 +427,7 @@ def main():
     # N > 1: the sharded modes keep ONE depth map in flight, the N = 1 headline three - the speed-up of N GPUs has to be taken against
     # the single-GPU one-at-a-time forward (VERDICT r3 "weak" 7).  Rank 0 times it on its own GPU while the other ranks wait.
     n1_ref = None
-    if world > 1:
+    if world > 1 and args.full:
         if rank == 0:
             m1 = RAFT(cascade=cascade, test_mode=True, precision=args.precision, gru_precision=args.gru_precision, encoder_backend=args.encoder,
                       enc_precision="f6" if enc_f6 else "f16x3", cost_precision="x2" if cost_x2 else "x3")
@@ -413,9 +451,10 @@ def main():
 
     result = None
     rec = None
-    if rank == 0 or shard:               # a sharded forward is collective: every rank runs the instrumented pass
+    split = args.gru_precision in ("s16f6", "s16f8", "s16", "f16x3")
+    if args.full and (rank == 0 or shard):          # a sharded forward is collective: every rank runs the instrumented pass
         rec, inst_wall_ms = kernel_timing(model, inputs, scale)
-    if rank == 0:
+    if rank == 0 and args.full:
         h4, w4 = H // 4, W // 4
         P = h4 * w4
         if shard and args.mode == "shard":
@@ -428,7 +467,6 @@ def main():
         Vloc = V if not (shard and args.mode == "views") else (V + world - 1) // world
         C, L_, r_ = 64, 3, 5
         stages = model.stages()
-        split = args.gru_precision in ("s16f6", "s16f8", "s16", "f16x3")
         mfma_peak = F16_MFMA_PEAK_TFLOPS / 3 if split else FP32_MFMA_PEAK_TFLOPS      # encoders, and the 3-term update-block convs
         # update-block convs in the fp8-correction form: per 16-channel tap step one f16 MFMA (32 cycles) + half of one fp8 K = 64
         # MFMA (64 cycles for two steps) = 2 f16-MFMA times of matrix-pipe occupancy per fp32 product instead of 3
@@ -559,6 +597,7 @@ def main():
                  "frac_mfma": 1210368.0 * P * iters / (loop_ms * 1e-3) / 1e12 / gru_peak,
                  "note": "correlation + GRU inner loop against both rooflines with SURVEY.md 8(d)'s unreduced per-iteration figures "
                          "(1.21 MFLOP and 1192 B per pixel): the loop is MFMA-bound, not HBM-bound (SURVEY.md 7, hard part 1)"}
+    if rank == 0:
         result = {
             "metric": "depth-maps/sec (ref+N src views) at DTU 1600x1184; HBM GB/s vs roofline",
             "value": maps / elapsed, "unit": "depth-maps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -606,34 +645,38 @@ def main():
                                           "forward, the steps overlap and fill each other's partially filled last waves of tiles.  The "
                                           "roofline / kernels entries below come from a one-at-a-time instrumented pass"}}
                if getattr(timed_run, "one_at_a_time_ms", None) else {}),
-            "roofline": roofline, "roofline_hbm_kernel": hbm, "inner_loop": inner, "kernels": kern,
-            "instrumented_pass": (lambda sums, enc_t: {
-                "wall_ms": inst_wall_ms,
-                # a REAL sum: every class's event times added up; the encoder classes - short launches whose host-paced
-                # events over-count - replaced by the GPU-paced time of the whole encode() section where it was measured
-                "sum_of_kernels_ms": sum(t for k, t in sums.items() if not (enc_t and k.startswith("enc_"))) + (enc_t or 0.0),
-                "sum_of_kernel_events_ms": sum(sums.values()),
-                "note": "one extra forward after the timed region with HIP events around every library launch and launch plans disabled; "
-                        "its per-launch MEDIANS feed `kernels[*].avg_us` / `roofline`; sum_of_kernels_ms adds the event times themselves "
-                        "(encoder launches: the GPU-paced encode() section, kernels.encoders_total) and is comparable with the rocprofv3 kernel "
-                        "sum of profiles/r05_kernel_stats_s1.md; its wall time is NOT ms_per_step"})(
-                    getattr(kernel_timing, "sums", {}), kern.get("encoders_total", {}).get("total_ms")),
-            "peak_device_memory_gb": torch.cuda.max_memory_allocated(dev) / 2 ** 30,
         }
-        # parity of THIS run's output: the default workload with the default seeds is exactly the configuration the reference
-        # was captured on (tests/golden/e2e_cfg2.npz, tools/gen_golden.py --only e2e_cfg2); committed fixture, no reference needed
-        gpath = os.path.join(REPO, "tests", "golden", "e2e_cfg2.npz")
-        if args.workload == "dtu_1600x1184_v10_it32" and (world == 1 or shard) and os.path.exists(gpath):
-            import numpy as np
-            ref = torch.from_numpy(np.load(gpath)["disp"]).double()
-            got = out.detach().cpu().double()
-            if got.shape == ref.shape:
-                result["parity"] = {"rel_l1_disparity_vs_reference_capture": float((got - ref).abs().sum() / ref.abs().sum()),
-                                    "tolerance": 1e-4, "fixture": "tests/golden/e2e_cfg2.npz"}
-        if world == 1 and not args.no_cpu_baseline:
-            result["cpu_baseline"] = cpu_baseline_guarded(H, W, V, cascade, {k: v.detach().cpu() for k, v in sd.items()})
-        else:
-            result["cpu_baseline"] = None
+        if args.full:
+            result.update({
+                "roofline": roofline, "roofline_hbm_kernel": hbm, "inner_loop": inner, "kernels": kern,
+                "instrumented_pass": (lambda sums, enc_t: {
+                    "wall_ms": inst_wall_ms,
+                    # a REAL sum: every class's event times added up; the encoder classes - short launches whose host-paced
+                    # events over-count - replaced by the GPU-paced time of the whole encode() section where it was measured
+                    "sum_of_kernels_ms": sum(t for k, t in sums.items() if not (enc_t and k.startswith("enc_"))) + (enc_t or 0.0),
+                    "sum_of_kernel_events_ms": sum(sums.values()),
+                    "note": "one extra forward after the timed region with HIP events around every library launch and launch plans disabled; "
+                            "its per-launch MEDIANS feed `kernels[*].avg_us` / `roofline`; sum_of_kernels_ms adds the event times themselves "
+                            "(encoder launches: the GPU-paced encode() section, kernels.encoders_total) and is comparable with the rocprofv3 kernel "
+                            "sum of profiles/r05_kernel_stats_s1.md; its wall time is NOT ms_per_step"})(
+                        getattr(kernel_timing, "sums", {}), kern.get("encoders_total", {}).get("total_ms")),
+            })
+        result["peak_device_memory_gb"] = torch.cuda.max_memory_allocated(dev) / 2 ** 30
+        if args.full:
+            # parity of THIS run's output: the default workload with the default seeds is exactly the configuration the reference
+            # was captured on (tests/golden/e2e_cfg2.npz, tools/gen_golden.py --only e2e_cfg2); committed fixture, no reference needed
+            gpath = os.path.join(REPO, "tests", "golden", "e2e_cfg2.npz")
+            if args.workload == "dtu_1600x1184_v10_it32" and (world == 1 or shard) and os.path.exists(gpath):
+                import numpy as np
+                ref = torch.from_numpy(np.load(gpath)["disp"]).double()
+                got = out.detach().cpu().double()
+                if got.shape == ref.shape:
+                    result["parity"] = {"rel_l1_disparity_vs_reference_capture": float((got - ref).abs().sum() / ref.abs().sum()),
+                                        "tolerance": 1e-4, "fixture": "tests/golden/e2e_cfg2.npz"}
+            if world == 1 and not args.no_cpu_baseline:
+                result["cpu_baseline"] = cpu_baseline_guarded(H, W, V, cascade, {k: v.detach().cpu() for k, v in sd.items()})
+            else:
+                result["cpu_baseline"] = None
         print(json.dumps(result))
     if world > 1:
         import torch.distributed as dist

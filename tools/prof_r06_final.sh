@@ -8,11 +8,11 @@ out=gpurun_out/r06
 mkdir -p $out
 sec=${1:-"bench prof pmc rest"}
 if [[ $sec == *bench* ]]; then
-timeout 900 python bench.py --steps 20 --warmup 5 2>$out/bench.err | grep "^{" > $out/bench.json
+timeout 900 python bench.py --full --steps 20 --warmup 5 2>$out/bench.err | grep "^{" > $out/bench.json
 fi
 if [[ $sec == *prof* ]]; then
-timeout 600 python bench.py --steps 20 --warmup 5 --streams 1 --no-cpu-baseline 2>/dev/null | grep "^{" > $out/streams1_bench.json
-timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --gru-precision s16f6 2>/dev/null | grep "^{" > $out/s16f6_bench.json
+timeout 600 python bench.py --full --steps 20 --warmup 5 --streams 1 --no-cpu-baseline 2>/dev/null | grep "^{" > $out/streams1_bench.json
+timeout 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --gru-precision s16f6 2>/dev/null | grep "^{" > $out/s16f6_bench.json
 tools/prof_r06.sh $out > /dev/null 2>&1
 timeout 600 python tools/r06/whatif.py > $out/whatif.txt 2>&1
 python tools/r06/bench_conv_forms.py > $out/conv_forms.txt 2>&1
@@ -31,7 +31,7 @@ d = json.loads(sys.stdin.read())
 print(json.dumps({'workload': d['config']['workload'], 'depth_maps_in_flight': d['config']['depth_maps_in_flight'], 'value': d['value'], 'ms_per_step': d['ms_per_step'], 'peak_device_memory_gb': d['peak_device_memory_gb'], 'gru_precision': d['gru_precision']['timed'], 'auto_form': d['gru_precision'].get('auto_form'), 'calibration_rel_l1_vs_s16': d['gru_precision'].get('calibration_rel_l1_vs_s16')}))"
   done
 done > $out/other_workloads.jsonl
-timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --backend gloo --steps 4 --warmup 2 --no-cpu-baseline 2> $out/bench_2rank_gloo.err | grep "^{" > $out/bench_2rank_gloo.json
+timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --backend gloo --steps 4 --warmup 2 --no-cpu-baseline 2> $out/bench_2rank_gloo.err | grep "^{" > $out/bench_2rank_gloo.json
 python -m pytest tests/test_hip_parity.py -q -m gpu -k "end_to_end_cfg1 or end_to_end_cfg2" -s 2>&1 | grep -E "rel-L1|passed|failed" > $out/e2e.log
 fi
 python - <<'P'
