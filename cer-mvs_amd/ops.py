@@ -693,3 +693,65 @@ def conv3x3_s16(pc, srcs, h, w, epi, out=None, out2=None, aux=None, aux2=None, i
                                   L.cur_stream())
     L.check(rc, "conv3x3[s16]")
     return (out, out2) if epi == L.EPI_GATES else out
+
+
+# ---- training step (csrc/train_ops.hip): the train-mode lookup and the loss's upsample, each with its atomics-free adjoint
+
+def train_lookup(corr, origin, disp, D, incre, num_levels, radius):
+    """corr [V,D,P] (DirectCorr's output as it lies in memory); origin, disp [P] -> [V, L*(2r+1), P] (core/corr.py:102-143, train
+    branch: pooled levels formed in LDS, bilinear taps, zero outside)."""
+    V, _, P = corr.shape
+    out = torch.empty(V, num_levels * (2 * radius + 1), P, device=corr.device, dtype=torch.float32)
+    L.check(L.load().cer_train_lookup_fwd_f32(L.dev_ptr(corr, "corr"), L.dev_ptr(origin, "origin"), L.dev_ptr(disp, "disp"),
+                                              L.dev_ptr(out, "out"), V, P, D, float(incre), num_levels, radius, L.cur_stream()),
+            "train_lookup")
+    return out
+
+
+def train_lookup_backward(grad_out, origin, disp, D, incre, num_levels, radius):
+    """grad_out [V, L*(2r+1), P] -> the gradient with respect to the level-0 volume [V,D,P] (pyramid adjoint fused; no atomics)."""
+    V, _, P = grad_out.shape
+    g = torch.empty(V, D, P, device=grad_out.device, dtype=torch.float32)
+    L.check(L.load().cer_train_lookup_bwd_f32(L.dev_ptr(grad_out, "grad_out"), L.dev_ptr(origin, "origin"), L.dev_ptr(disp, "disp"),
+                                              L.dev_ptr(g, "grad_corr"), V, P, D, float(incre), num_levels, radius, L.cur_stream()),
+            "train_lookup_backward")
+    return g
+
+
+def upsample_ac_ranges(in_size, out_size):
+    """Host table of the upsample adjoint: int32 [in_size, 2], row j = the half-open range of outputs whose footprint holds input j."""
+    buf = (ctypes.c_int * (2 * in_size))()
+    L.check(L.load().cer_upsample_ac_ranges(int(in_size), int(out_size), buf), "upsample_ac_ranges")
+    return torch.tensor(list(buf), dtype=torch.int32).view(in_size, 2)
+
+
+_RANGES = {}
+
+
+def _device_ranges(in_size, out_size, device):
+    key = (in_size, out_size, str(device))
+    t = _RANGES.get(key)
+    if t is None:
+        t = _RANGES[key] = upsample_ac_ranges(in_size, out_size).to(device)
+    return t
+
+
+def upsample_ac(x, H, W):
+    """x [n,h,w] -> [n,H,W]: F.interpolate(mode="bilinear", align_corners=True) on n planes in one launch."""
+    n, h, w = x.shape
+    out = torch.empty(n, H, W, device=x.device, dtype=torch.float32)
+    L.check(L.load().cer_upsample_bilinear_ac_f32(L.dev_ptr(x, "x"), L.dev_ptr(out, "out"), n, h, w, H, W, L.cur_stream()), "upsample_ac")
+    return out
+
+
+def upsample_ac_backward(grad_out, h, w):
+    """grad_out [n,H,W] -> grad_in [n,h,w], the adjoint of ``upsample_ac`` in gather form (x pass, then y pass; fixed order)."""
+    n, H, W = grad_out.shape
+    dev = grad_out.device
+    gin = torch.empty(n, h, w, device=dev, dtype=torch.float32)
+    work = torch.empty(n, H, w, device=dev, dtype=torch.float32)
+    ry, rx = _device_ranges(h, H, dev), _device_ranges(w, W, dev)
+    L.check(L.load().cer_upsample_bilinear_ac_bwd_f32(L.dev_ptr(grad_out, "grad_out"), L.dev_ptr(gin, "grad_in"), L.dev_ptr(work, "work"),
+                                                      L.dev_ptr(ry, "range_y", torch.int32), L.dev_ptr(rx, "range_x", torch.int32), n, h, w,
+                                                      H, W, L.cur_stream()), "upsample_ac_backward")
+    return gin

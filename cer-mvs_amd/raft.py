@@ -46,12 +46,17 @@ class SaturationError(RuntimeError):
 class RAFT(nn.Module):
     def __init__(self, cascade=[(64, 64, 8), (-1, 320, 8)], encoder_type="HR", dim_fmap=64, dim_net=64, dim_inp=64,
                  test_mode=False, precision="fp32", view_group=None, gru_precision="auto", encoder_backend="hip", shard="slab",
-                 enc_precision="auto", cost_precision="auto"):
+                 enc_precision="auto", cost_precision="auto", train_backend="torch"):
         super().__init__()
         self.cascade = [tuple(c) for c in cascade]
         self.encoder_type = encoder_type
         self.dim_fmap, self.dim_net, self.dim_inp = dim_fmap, dim_net, dim_inp
         self.test_mode = test_mode
+        # train_backend: the lookup and the loss upsample of the training row (train.py): "torch" (grid_sample / F.interpolate) or "hip"
+        # (csrc/train_ops.hip: atomics-free adjoints, runs under torch.use_deterministic_algorithms)
+        if train_backend not in ("torch", "hip"):
+            raise ValueError(f"RAFT: unknown train_backend {train_backend!r}")
+        self.train_backend = train_backend
         self.precision = precision
         self.view_group = view_group
         self.shard = shard

@@ -473,6 +473,34 @@ int cer_geo_consistency_f32(const float* depth_ref, const float* depth_src, cons
 int cer_multires_merge_f32(const float* im1, int h1, int w1, const float* im2, int h2, int w2, double th, float* out, void* stream);
 int cer_resize_linear_f32(const float* src, int h, int w, float* dst, int ho, int wo, void* stream);
 
+/* Training step (ABI 1080; csrc/train_ops.hip, cer-mvs_amd/train.py).  fp32; every output is written whole (no memset needed); no atomics:
+ * the same bits on every run.
+ *
+ * Train-mode lookup (reference: CorrBlock.__call__ core/corr.py:102-143 with test_mode=False, the pyramid core/corr.py:94-97,
+ * utils/bilinear_sampler.py:6-25).  corr [V, D, P] is DirectCorr's output as it lies in memory (D-major); origin, disp [P] (the
+ * disparity is shared by all views); out [V, L*(2r+1), P].  c = max((disp - origin) / incre + D//2, 0); level l (length D >> l) is the
+ * avg-pool by pairs, level by level, formed in LDS; tap t in [-r, r] of level l samples x = t + c / 2^l, bilinear between floor(x)
+ * and floor(x)+1, zero outside [0, len_l - 1].  The backward writes grad_corr [V, D, P], the gradient with respect to level 0 (a
+ * level-l texel hands g * 2^-l to each of its 2^l level-0 texels); disp and origin get none (the reference detaches both).
+ * CER_ESHAPE: D > 128, L > 4, a level shorter than 2 texels, L*(2r+1) > 64, V > 65535.  CER_EINVAL: null pointer, size <= 0,
+ * incre <= 0. */
+int cer_train_lookup_fwd_f32(const float* corr, const float* origin, const float* disp, float* out, int V, long P, int D,
+                             float incre, int num_levels, int radius, void* stream);
+int cer_train_lookup_bwd_f32(const float* grad_out, const float* origin, const float* disp, float* grad_corr, int V, long P, int D,
+                             float incre, int num_levels, int radius, void* stream);
+/* Bilinear upsample with align_corners=True (the loss's F.interpolate, loss.py:18-19), n planes in one launch: in [n, h, w] ->
+ * out [n, H, W] in torch's upsample_bilinear2d arithmetic (scale = (float)(h-1)/(H-1), 0 for H == 1; src = scale * dst; i0 = (int)src,
+ * the +1 neighbour clamped at the last row / column; lambda = src - i0).  The adjoint is a gather: grad_in [n, h, w] from
+ * grad_out [n, H, W] in two passes (x into work [n, H, w], then y); each input texel sums, in ascending order, over the output
+ * columns / rows whose footprint holds it - the ranges [range[2j], range[2j+1]) that cer_upsample_ac_ranges writes (range_x: w
+ * pairs for (w, W), range_y: h pairs for (h, H), copied to the device by the caller). */
+int cer_upsample_bilinear_ac_f32(const float* in, float* out, int n, int h, int w, int H, int W, void* stream);
+int cer_upsample_bilinear_ac_bwd_f32(const float* grad_out, float* grad_in, float* work, const int* range_y, const int* range_x,
+                                     int n, int h, int w, int H, int W, void* stream);
+/* HOST function (range is host memory, 2 * in_size ints): for every input texel j of a resize in_size -> out_size, the half-open range of
+ * outputs whose two source texels include j ([0, 0) if none).  Same float arithmetic as the kernels. */
+int cer_upsample_ac_ranges(int in_size, int out_size, int* range);
+
 /* Multi-GPU row-slab exchange (cer-mvs_amd/slab.py): up to CER_COPY_MAX_SEG contiguous fp32 ranges copied by ONE launch -
  * the pack of a rank's (net, disp) border strips into its send buffer, and the refresh of its halo rows from the gathered
  * strips.  n[i] floats from src[i] to dst[i]; n[i] == 0 skips a segment.  Device pointers; ranges must not overlap. */

@@ -240,6 +240,72 @@ def gen_train_tiny():
     print("train_tiny.npz loss", float(loss), metrics, {k: v.shape for k, v in out.items() if k.startswith("grad_")})
 
 
+def gen_train_step_tiny():
+    """The reference's optimiser step around the training row (train.py:19-27,66-83): its own fetch_optimizer (AdamW + OneCycleLR;
+    `datasets` and `utils.logger` are stubbed with empty modules - import-time roles only), GradScaler, clip_grad_norm_(1.0), two
+    iterations of the loop body on the train_tiny scene and weights.  Recorded: the learning rate after each step, the pre-clip total
+    gradient norm, both losses, and the change of the seven TRAIN_GRADS parameters over the two steps (every stride-th element: ~2 000 per tensor),
+    plus a 20-step learning-rate sequence of a fresh optimiser.  A CPU torch's GradScaler disables itself: scaler_enabled = False."""
+    import warnings
+    sys.modules.setdefault("datasets", types.ModuleType("datasets"))
+    sys.modules["datasets"].get_train_data_loader = None
+    logger = types.ModuleType("utils.logger")
+    logger.Logger = None
+    sys.modules["utils.logger"] = logger
+    import train as ref_train
+    from core.raft import RAFT
+    from cer_mvs_amd.synthetic import fill_state_dict, synthetic_scene, tensor_checksum
+    H, W, V, seed = 64, 96, 3, 2
+    cascade = [(64, 64, 3), (-1, 320, 3)]
+    num_steps = 100
+    images, poses, intr, _ = synthetic_scene(H, W, V, seed=seed)
+    tiny = np.load(os.path.join(OUT, "train_tiny.npz"))
+    gt = torch.from_numpy(tiny["gt"])
+    depths = torch.where(gt > 0, 1.0 / gt.clamp_min(1e-12), torch.zeros_like(gt))                     # [1,1,H,W]: view 0 only
+    model = RAFT(cascade=cascade, test_mode=False)
+    model.load_state_dict(fill_state_dict(model.state_dict(), seed=seed + 5), strict=True)
+    model.train()
+    params = dict(model.named_parameters())
+    before = {n: params[n].detach().clone() for n in TRAIN_GRADS}
+    optimizer, scheduler = ref_train.fetch_optimizer(model, num_steps=num_steps)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        scaler = ref_train.GradScaler(enabled=True)
+    lrs, norms, losses = [], [], []
+    for _ in range(2):                                              # train.py:66-83
+        optimizer.zero_grad()
+        d = depths[:, [0]]
+        disp_gt = torch.where(d > 0, 1.0 / d, torch.zeros_like(d))
+        disp_est = model(images.clone(), poses.clone(), intr.clone())
+        loss, metrics = ref_train.sequence_loss(disp_est, disp_gt, gradual_weight=0.3)
+        scaler.scale(loss).backward()
+        scaler.unscale_(optimizer)
+        norms.append(float(torch.nn.utils.clip_grad_norm_(model.parameters(), 1.0)))
+        scaler.step(optimizer)
+        scheduler.step()
+        scaler.update()
+        lrs.append(scheduler.get_last_lr()[0])
+        losses.append(float(loss))
+    fresh = RAFT(cascade=cascade, test_mode=False)
+    opt2, sch2 = ref_train.fetch_optimizer(fresh, num_steps=num_steps)
+    seq = []
+    for _ in range(20):
+        opt2.step()
+        sch2.step()
+        seq.append(sch2.get_last_lr()[0])
+    out = {"H": H, "W": W, "V": V, "cascade": np.array(cascade), "scene_seed": seed, "weight_seed": seed + 5, "num_steps": num_steps,
+           "images_checksum": np.uint64(tensor_checksum(images)), "depths": depths.numpy(), "gradual_weight": 0.3,
+           "scaler_enabled": bool(scaler.is_enabled()), "lr": np.array(lrs, dtype=np.float64), "grad_norm": np.array(norms, dtype=np.float64),
+           "loss": np.array(losses, dtype=np.float64), "lr_sequence": np.array(seq, dtype=np.float64)}
+    for name in TRAIN_GRADS:
+        u = (params[name].detach() - before[name]).reshape(-1)
+        stride = max(1, u.numel() // 2048)                                                 # ~2 000 elements per tensor
+        out["upd_" + name] = u[::stride].numpy()
+        out["stride_" + name] = stride
+    np.savez_compressed(os.path.join(OUT, "train_step_tiny.npz"), **out)
+    print("train_step_tiny.npz lr", lrs, "norm", norms, "loss", losses, {k: v.shape for k, v in out.items() if k.startswith("upd_")})
+
+
 def gen_e2e_lr():
     """encoder_type="LR" (core/extractor.py:87-90,151; core/raft.py:38: features at 1/8 resolution), end to end at a tiny size."""
     from core.raft import RAFT
@@ -298,6 +364,7 @@ def main():
         "e2e_cfg1": lambda: gen_e2e("e2e_cfg1", 480, 640, 2, [(64, 64, 2), (-1, 320, 2)], seed=0),
         "caller": gen_caller,
         "train_tiny": gen_train_tiny,
+        "train_step_tiny": gen_train_step_tiny,
         "e2e_lr": gen_e2e_lr,
     }
     # BASELINE.json configs[1] - the bench workload itself (1600x1184, 10 source views, 32 GRU iterations; same scene and weight
