@@ -503,7 +503,7 @@ class RAFT(nn.Module):
         if ub.conv_mode == "s16":
             try:
                 for st_ in range(len(self.cascade)):
-                    ub.packed(st_, dev)
+                    ub.loop(st_, dev)
             except RuntimeError as e:                     # weights that do not fit a shared split-f16 scale: wide-range kernels instead
                 import warnings
                 warnings.warn(f"cer-mvs_amd: {e}; this model runs with gru_precision='f16x3'")

@@ -290,15 +290,14 @@ def unpack_halo(net, disp, allbuf, w, g, G, r0, r1, e0, e1, halo=HALO, copy=_dev
 P2P_HALO = True           # halo refresh by neighbour point-to-point exchange (False: one all-gather of every rank's strips)
 
 
-def _finish_overflow(model, ex, dev, workspaces, ub):
+def _finish_overflow(model, ex, dev, workspaces, loop):
     """End-of-forward overflow handling of the sharded path.  "lazy": asynchronous snapshot, polled by the next forward (every rank
     polls its own flag; the ranks run the same GRU on overlapping rows, but a rank can saturate alone - a hit then raises on that
     rank at its next forward).  "raise": the flag is read here and MAX-reduced over the ranks, so that every rank raises together
     instead of one rank leaving the collective sequence.  "fallback" has no sharded form: it is refused up front (sharded_forward)."""
     from . import ops
-    if ub.conv_mode == "s16" and ub.CHECK_OVERFLOW:
-        for ws in workspaces:
-            ops.scan_overflow(ws["c2"])                # (c1: checked inside the lookup kernel since round 5)
+    for ws in workspaces:
+        loop.finish(ws)
     policy = getattr(model, "overflow_policy", "lazy")
     if policy == "lazy":
         ops.overflow_snapshot(dev)
@@ -392,8 +391,7 @@ def sharded_forward(model, images, poses, intrinsics, scale, ex):
         d["hoist"] = ub.hoist_all(d["inp"], e1 - e0, w, len(model.cascade))
         d["ws"] = ub.workspace(e1 - e0, w, dev)
         d["strips"] = torch.zeros(2 * strip_half(w, d["net"].shape[1]), device=dev, dtype=torch.float32)
-        # s16 path: the hidden state lives in the m-tile-major frag16 layout - image rows move through cer_s16_rows_f32
-        d["rows"] = (lambda t, flat, y0, nr, to_t, hs=e1 - e0: ops.s16_rows(t, flat, hs, w, y0, nr, to_t)) if ub.conv_mode == "s16" else None
+        d["rows"] = ub.loop(0, dev).rows(e1 - e0, w)      # (s16 path: the hidden state's image rows move through cer_s16_rows_f32)
 
     for stage, (D, incre, T) in enumerate(model.stages()):
         for g in ex.ranks:
@@ -404,7 +402,7 @@ def sharded_forward(model, images, poses, intrinsics, scale, ex):
             if D > 64:
                 ops.pyramid(vol, D, 1 if model.COMPACT_VOLUME else ub.num_levels, scale=1.0 / V)
             d["vol"], d["origin"] = vol, origin
-        ub.packed(stage, dev)                  # host-side weight packing stays out of the recorded plans
+        loop = ub.loop(stage, dev)             # host-side weight packing stays out of the recorded plans
         for it in range(T):
             record = it == 0 or not update.USE_PLANS
             send = []
@@ -414,7 +412,7 @@ def sharded_forward(model, images, poses, intrinsics, scale, ex):
                     # iteration + pack of the 2 x HALO border rows of (net, disp): recorded once per stage, then replayed
                     d["plan_step"] = L.LaunchPlan(keep=(d["vol"], d["origin"]))
                     with L.recording(d["plan_step"]):
-                        ub.step(d["vol"], d["origin"], d["net"], d["disp"], d["hoist"][stage], stage, d["hs"], w, D, incre, d["ws"])
+                        loop.step(d["vol"], d["origin"], d["net"], d["disp"], d["hoist"][stage], d["hs"], w, D, incre, d["ws"])
                         pack_strips(d["net"], d["disp"], d["strips"], w, d["r0"], d["r1"], d["e0"], rows=d["rows"])
                 else:
                     d["plan_step"].replay()
@@ -436,9 +434,9 @@ def sharded_forward(model, images, poses, intrinsics, scale, ex):
                 else:
                     d["plan_halo"].replay()
 
-    # ---- saturation is never silent on the sharded path either: the slab loop calls ub.step, not ub.run, so the
-    # scans of the corr features happen here; bits 1 / 2 were or-ed into the flag by the kernels themselves
-    _finish_overflow(model, ex, dev, [st[g]["ws"] for g in ex.ranks], ub)
+    # ---- saturation is never silent on the sharded path either: the slab loop calls step, not UpdateBlock.run, so the
+    # loop's scans of the corr features happen here; bits 1 / 2 were or-ed into the flag by the kernels themselves
+    _finish_overflow(model, ex, dev, [st[g]["ws"] for g in ex.ranks], loop)
 
     # ---- gather the owned rows of every rank (persistent send / receive buffers)
     rows_max = (h + G - 1) // G

@@ -1214,3 +1214,99 @@ def test_full_size_properties(dev):
     vb, _ = ops.cost_build(f1, f2b, Pij, d0, D, 0.0025 / 64, True, h1, w1, 3, fold=True)
     vab, _ = ops.cost_build(f1, f2a + f2b, Pij, d0, D, 0.0025 / 64, True, h1, w1, 3, fold=True)
     assert rel_l1((va + vb).cpu(), vab.cpu()) < 1e-5
+
+
+# ------------------------------------------------------------------------------------ arithmetic form of the update block's loop
+_FORM_CASCADE = [(64, 64, 2), (-1, 320, 2)]
+
+
+def _form_model(dev, gru_precision, sd):
+    from cer_mvs_amd import RAFT
+    model = RAFT(cascade=_FORM_CASCADE, test_mode=True, gru_precision=gru_precision)
+    model.load_state_dict(sd)
+    return model.to(dev).eval()
+
+
+def _form_weights(edit=None):
+    from cer_mvs_amd import RAFT
+    from cer_mvs_amd.synthetic import fill_state_dict
+    sd = fill_state_dict(RAFT(cascade=_FORM_CASCADE, test_mode=True).state_dict(), seed=9)
+    if edit is not None:
+        edit(sd)
+    return sd
+
+
+def _form_scene(dev):
+    images, poses, intr, scale = cached_scene(64, 96, 3, 4)
+    return images.to(dev), poses.to(dev), intr.to(dev), scale
+
+
+def test_unscalable_update_weights_switch_to_f16x3(dev):
+    """Update-block weights without a shared split-f16 scale (cer_conv3x3_s16_scale refuses them): the s16 forward warns, leaves the
+    update block on the f16x3 kernels and computes exactly what a gru_precision="f16x3" model with the same weights computes."""
+    import ctypes
+    from cer_mvs_amd import _lib as L, ops
+
+    def shrink(sd):          # the hidden-state source of the z|r conv (net | inp | disp49 | corr), both gates
+        for k in ("update_block.gru.convz.weight", "update_block.gru.convr.weight"):
+            sd[k][:, :64] *= 2.0 ** -30
+    sd = _form_weights(shrink)
+    wzr = torch.cat([sd["update_block.gru.convz.weight"], sd["update_block.gru.convr.weight"]], 0)
+    loop_srcs = wzr[:, list(range(64)) + list(range(128, 241))].contiguous()
+    I3 = ctypes.c_int * 3
+    assert L.load().cer_conv3x3_s16_scale(ctypes.c_void_p(loop_srcs.data_ptr()), 128, 177, I3(64, 49, 64), I3(2, 1, 2),
+                                          I3(L.S16_UNIT, L.S16_DISP, L.S16_RELU), 3) < -1000
+    s16, f16 = _form_model(dev, "s16", sd), _form_model(dev, "f16x3", sd)
+    scene = _form_scene(dev)
+    ops.check_overflow(dev)
+    with torch.no_grad():
+        with pytest.warns(UserWarning, match="gru_precision='f16x3'"):
+            out = s16(*scene[:3], scale=scene[3]).clone()
+        assert s16.update_block.conv_mode == "f16x3"
+        want = f16(*scene[:3], scale=scene[3])
+    assert torch.isfinite(out).all() and torch.equal(out, want)
+
+
+def test_overflow_fallback_repeats_the_forward_in_f16x3(dev):
+    """overflow_policy="fallback": a ReLU-class activation beyond 4094 (one channel of the corr encoder's output at 5000) sets flag bit 4
+    on the s16 kernels; the forward then repeats on the f16x3 kernels, returns exactly what a gru_precision="f16x3" model returns,
+    and leaves the update block on "s16" and the flag clear."""
+    from cer_mvs_amd import ops
+
+    def hot(sd):
+        sd["update_block.corr_encoder.0.bias"][0] = 5000.0
+    sd = _form_weights(hot)
+    s16, f16 = _form_model(dev, "s16", sd), _form_model(dev, "f16x3", sd)
+    scene = _form_scene(dev)
+    ops.check_overflow(dev)
+    with torch.no_grad():
+        s16.overflow_policy = "ignore"
+        s16(*scene[:3], scale=scene[3])
+        assert ops.check_overflow(dev) & 4
+        s16.overflow_policy = "fallback"
+        out = s16(*scene[:3], scale=scene[3]).clone()
+        assert s16.update_block.conv_mode == "s16" and ops.check_overflow(dev) == 0
+        want = f16(*scene[:3], scale=scene[3])
+    assert torch.isfinite(out).all() and torch.equal(out, want)
+
+
+@pytest.mark.parametrize("gru_precision", ["s16", "f16x3", "fp32"])
+def test_update_loop_packs_only_its_own_form(dev, monkeypatch, gru_precision):
+    """A fast-path forward packs the update block's weights for its own arithmetic form only: no PackedConv3x3 (the general kernels'
+    packs) on the default s16 path, no PackedConvS16 in the "f16x3" and "fp32" forms - six convs per cascade stage either way."""
+    from cer_mvs_amd import ops
+    built = {"PackedConv3x3": 0, "PackedConvS16": 0}
+    for name in built:
+        def counted(self, *a, _init=getattr(ops, name).__init__, _name=name, **k):
+            built[_name] += 1
+            _init(self, *a, **k)
+        monkeypatch.setattr(getattr(ops, name), "__init__", counted)
+    model = _form_model(dev, gru_precision, _form_weights())
+    scene = _form_scene(dev)
+    with torch.no_grad():
+        out = model(*scene[:3], scale=scene[3])
+    assert torch.isfinite(out).all()
+    if gru_precision == "s16":
+        assert built == {"PackedConv3x3": 0, "PackedConvS16": 6 * len(_FORM_CASCADE)}
+    else:
+        assert built == {"PackedConv3x3": 6 * len(_FORM_CASCADE), "PackedConvS16": 0}
