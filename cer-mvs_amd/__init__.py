@@ -16,6 +16,8 @@ _LAZY = {
     "alt_cuda_corr": ("alt_cuda_corr", None),
     "inference": ("inference", "inference"),
     "DepthMapPipeline": ("pipeline", "DepthMapPipeline"),
+    "ScanSession": ("scan", "ScanSession"),
+    "inference_scan": ("scan", "inference_scan"),
 }
 
 

@@ -9,7 +9,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CER_MVS_LIB") or os.path.join(_HERE, "csrc", "libcermvs.so")
-ABI_VERSION = 1080
+ABI_VERSION = 1090
 CONV_MAX_SRC = 4
 EPI_LINEAR, EPI_RELU, EPI_GATES, EPI_GRU, EPI_DELTA = 0, 1, 2, 3, 4
 EPI_OUT_SPLIT, EPI_AUX_SPLIT = 0x100, 0x200       # cer_mvs.h: split32 activation layout flags, or-ed into `epi`
@@ -114,6 +114,9 @@ _SIGNATURES = {
     "cer_upsample_bilinear_ac_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "cer_upsample_bilinear_ac_bwd_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "cer_upsample_ac_ranges": (_I, [_I, _I, _c.POINTER(_I)]),
+    "cer_image_prep_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "cer_image_prep_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "cer_feat_ref_rows_f16": (_I, [_P, _P, _I, _I, _I, _P]),
 }
 
 # include/cer_mvs_variants.h: exported by csrc/variants/libcermvs_optin.so only (round 4's opt-in kernel forms; CER_MVS_LIB selects the library)

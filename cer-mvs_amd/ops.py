@@ -755,3 +755,66 @@ def upsample_ac_backward(grad_out, h, w):
                                                       L.dev_ptr(ry, "range_y", torch.int32), L.dev_ptr(rx, "range_x", torch.int32), n, h, w,
                                                       H, W, L.cur_stream()), "upsample_ac_backward")
     return gin
+
+
+# ---------------------------------------------------------------- scan session (csrc/scan_ops.hip, scan.py)
+def prep_geometry(H0, W0, rescale=1, crop=None):
+    """Sizes of the reference driver's scale_operation + crop_operation (inference.py) on an H0 x W0 image -> (H2, W2, y0, x0, H, W):
+    the resized image is int(rescale * H0) x int(rescale * W0) (truncation, as the driver does), the centre-crop window starts at
+    y0 = (H2 - crop_h) // 2, x0 = (W2 - crop_w) // 2 and is crop = (crop_h, crop_w) large (no crop: the whole resized image).  CPU only."""
+    H2, W2 = int(rescale * H0), int(rescale * W0)
+    if H2 <= 0 or W2 <= 0:
+        raise ValueError(f"prep_geometry: rescale {rescale} leaves nothing of a {W0}x{H0} image")
+    if crop is None:
+        return H2, W2, 0, 0, H2, W2
+    H, W = int(crop[0]), int(crop[1])
+    if H <= 0 or W <= 0 or H > H2 or W > W2:
+        raise ValueError(f"prep_geometry: crop {W}x{H} does not fit the rescaled image {W2}x{H2}")
+    return H2, W2, (H2 - H) // 2, (W2 - W) // 2, H, W
+
+
+def image_prep(img, rescale=1, crop=None, out=None, bgr=False):
+    """One source image on the device - uint8 [H0,W0,3] (``bgr``: channels swapped to RGB) or float32 [3,H0,W0], values 0..255 - ->
+    float32 [3,H,W], raw 0..255: bilinear resize (align_corners=True) to int(rescale*H0) x int(rescale*W0) and centre crop in one pass
+    over the crop window (``prep_geometry``); equal sizes: an exact copy.  ``out``: where to write (a slice of a larger buffer)."""
+    if img.dim() != 3:
+        raise RuntimeError("image_prep: one image, uint8 [H,W,3] or float32 [3,H,W]")
+    u8 = img.dtype == torch.uint8
+    if u8:
+        if img.shape[2] != 3:
+            raise RuntimeError("image_prep: a uint8 image must be [H,W,3]")
+        H0, W0 = int(img.shape[0]), int(img.shape[1])
+    else:
+        if img.shape[0] != 3:
+            raise RuntimeError("image_prep: a float image must be [3,H,W]")
+        if bgr:
+            raise ValueError("image_prep: bgr is for the uint8 form")
+        H0, W0 = int(img.shape[1]), int(img.shape[2])
+    H2, W2, y0, x0, H, W = prep_geometry(H0, W0, rescale, crop)
+    if out is None:
+        out = torch.empty(3, H, W, device=img.device, dtype=torch.float32)
+    elif tuple(out.shape) != (3, H, W) or out.device != img.device:
+        raise RuntimeError(f"image_prep: out must be [3,{H},{W}] on {img.device}")
+    lib = L.load()
+    if u8:
+        L.check(lib.cer_image_prep_u8(L.dev_ptr(img, "img", torch.uint8), L.dev_ptr(out, "out"), H0, W0, H2, W2, y0, x0, H, W, int(bool(bgr)),
+                                      L.cur_stream()), "image_prep_u8")
+    else:
+        L.check(lib.cer_image_prep_f32(L.dev_ptr(img, "img"), L.dev_ptr(out, "out"), H0, W0, H2, W2, y0, x0, H, W, L.cur_stream()),
+                "image_prep_f32")
+    return out
+
+
+def feat_ref_rows(slot, h, w, border=2, out=None):
+    """One bordered block of split-f16 operand planes, [(h+2b)*(w+2b), 128] halves (a source-view block of ``features_split`` /
+    ``feat_split``) -> its interior as the plain block [h*w, 128] that ``cost_build(split=...)`` takes for the reference view."""
+    Pb = (h + 2 * border) * (w + 2 * border)
+    if slot.numel() != Pb * 128:
+        raise RuntimeError(f"feat_ref_rows: the block must hold {Pb} x 128 halves")
+    if out is None:
+        out = torch.empty(h * w, 128, device=slot.device, dtype=torch.float16)
+    elif out.numel() != h * w * 128 or out.device != slot.device:
+        raise RuntimeError(f"feat_ref_rows: out must hold {h * w} x 128 halves on {slot.device}")
+    L.check(L.load().cer_feat_ref_rows_f16(L.dev_ptr(slot, "slot", torch.float16), L.dev_ptr(out, "out", torch.float16), h, w, border,
+                                           L.cur_stream()), "feat_ref_rows")
+    return out

@@ -334,6 +334,14 @@ class RAFT(nn.Module):
         batch, num, ch, ht, wd = images.shape
         if batch != 1:
             raise RuntimeError("RAFT.forward: batch must be 1 in test mode")
+        return self._with_policy(dev, lambda: self._forward_fast(images, poses, intrinsics, scale, do_report),
+                                 lambda: self._forward_calibrating(images, poses, intrinsics, scale, do_report))
+
+    def _with_policy(self, dev, run, calibrate=None):
+        """The overflow policy around one forward, shared by ``forward`` and ``forward_cached``.  ``run()``: the forward in the model's
+        current arithmetic form; ``calibrate()``: the calibrating forward of gru_precision="auto" (None: the caller has made sure that no
+        calibration is pending)."""
+        pending = lambda: calibrate is not None and self.gru_precision == "auto" and self._auto_pending()
         if self.overflow_policy == "fallback" and self.view_group is not None:
             raise NotImplementedError("RAFT.overflow_policy='fallback' is not available with view_group (every rank would have to repeat "
                                       "the forward together): use 'lazy' or 'raise'")
@@ -341,28 +349,28 @@ class RAFT(nn.Module):
             bits = ops.overflow_poll(dev)              # what an EARLIER forward left (asynchronous snapshot: never blocks)
             if bits:
                 self._raise_overflow(bits)
-            if self.gru_precision == "auto" and self._auto_pending():
-                return self._forward_calibrating(images, poses, intrinsics, scale, do_report)
+            if pending():
+                return calibrate()
         elif self.overflow_policy in ("raise", "fallback") and self.view_group is None:
-            if self.gru_precision == "auto" and self._auto_pending():
-                self._forward_calibrating(images, poses, intrinsics, scale, do_report)        # (decides the form; the policy's own forward follows)
+            if pending():
+                calibrate()                            # (decides the form; the policy's own forward follows)
                 self.check_overflow(dev, raise_error=False)
-            out = self._forward_fast(images, poses, intrinsics, scale, do_report)
+            out = run()
             bits = self.check_overflow(dev, raise_error=self.overflow_policy == "raise")
             if bits:                                   # fallback: repeat with the wide-range arithmetic
                 from . import _lib as L
                 mode, algo = self.update_block.conv_mode, L.load().cer_cost_build_algo(1 if bits & 1 else -1)
                 self.update_block.conv_mode = "f16x3" if bits & 6 else mode
                 try:
-                    out = self._forward_fast(images, poses, intrinsics, scale, do_report)
+                    out = run()
                 finally:
                     self.update_block.conv_mode = mode
                     L.load().cer_cost_build_algo(algo)
                 ops.check_overflow(dev)
             return out
-        if self.gru_precision == "auto" and self._auto_pending():
-            return self._forward_calibrating(images, poses, intrinsics, scale, do_report)
-        return self._forward_fast(images, poses, intrinsics, scale, do_report)     # ("raise" with a view_group: handled at its end)
+        if pending():
+            return calibrate()
+        return run()     # ("raise" with a view_group: handled at its end)
 
     _CORR_FORM = {"s16f6": 6, "s16f8": True, "s16": False}      # UpdateBlock.corr_fp8 of a split-f16 form
     # gru_precision="auto": candidates, cheapest first (the last one is the fp32-class reference).  "s16f6" is NOT among them by default: built and
@@ -449,6 +457,32 @@ class RAFT(nn.Module):
                           f"gru_precision={cand!r} for these weights")
         return out
 
+    def _split_path(self, dev, V, D0=None):
+        """(pipelined, direct_split) of a single-GPU forward with V source views: which of the two encode forms that hand the cost volume
+        its split-f16 operand planes applies (neither: the plain ``encode``)."""
+        from . import _lib as L
+        if D0 is None:
+            D0 = self.stages()[0][0]
+        pipelined = (self.PIPELINE_BUILD and self.view_group is None and V >= 2 and self.encoder_backend == "hip" and self.precision == "fp32"
+                     and self.encoder_type == "HR" and self.dim_fmap == 64 and D0 <= 64 and L.load().cer_cost_build_algo(-1) != 1)
+        # single-GPU fast path: when every stage builds its volume on the epipolar-line tiles, the feature head writes the split-f16
+        # operand planes itself (encoder_hip.features_split): no fp32 feature maps, no feat_split pass
+        direct_split = (self.DIRECT_SPLIT and not pipelined and self.view_group is None and V >= 1 and self.encoder_backend == "hip"
+                        and self.precision == "fp32" and self.encoder_type == "HR" and self.dim_fmap == 64
+                        and L.load().cer_cost_build_algo(-1) != 1 and all(D_ <= 64 for D_, _, _ in self.stages()))
+        if direct_split:
+            direct_split = self._get_engines(dev)[1].supports_split_head()
+        return bool(pipelined), bool(direct_split)
+
+    def supports_cached(self, dev):
+        """``forward_cached`` applies: a test-mode forward of this model takes the direct-split path (HIP "HR" encoders in fp32, every stage
+        on the epipolar-line tiles, no view_group, view-mean aggregation), whatever the number of views, and its overflow policy does
+        not need the fp32 walk (which reads fp32 source maps that a feature store does not keep)."""
+        agg = self.update_block.aggregation
+        if not self.test_mode or "mean" not in agg or len(agg) != 1 or self.overflow_policy == "fallback":
+            return False
+        return self._split_path(dev, 2) == (False, True) and self._split_path(dev, 1) == (False, True)
+
     def _forward_fast(self, images, poses, intrinsics, scale, do_report):
         self._validate_packs()
         dev = images.device
@@ -483,16 +517,8 @@ class RAFT(nn.Module):
         disp = torch.zeros(P, device=dev, dtype=torch.float32)
         (D0, incre0, _) = self.stages()[0]
         from . import _lib as L
-        pipelined = (self.PIPELINE_BUILD and self.view_group is None and V >= 2 and self.encoder_backend == "hip" and self.precision == "fp32"
-                     and self.encoder_type == "HR" and self.dim_fmap == 64 and D0 <= 64 and L.load().cer_cost_build_algo(-1) != 1)
-        split = None
-        # single-GPU fast path: when every stage builds its volume on the epipolar-line tiles, the feature head writes the split-f16
-        # operand planes itself (encoder_hip.features_split): no fp32 feature maps, no feat_split pass
-        direct_split = (self.DIRECT_SPLIT and not pipelined and self.view_group is None and V >= 1 and self.encoder_backend == "hip"
-                        and self.precision == "fp32" and self.encoder_type == "HR" and self.dim_fmap == 64
-                        and L.load().cer_cost_build_algo(-1) != 1 and all(D_ <= 64 for D_, _, _ in self.stages()))
-        if direct_split:
-            direct_split = self._get_engines(dev)[1].supports_split_head()
+        pipelined, direct_split = self._split_path(dev, V, D0)
+        split, build_done = None, None
         if pipelined:
             net_l, inp_l, f1, f2, split, build_done = self._encode_pipelined(images, V, Pij, disp, D0, incre0, h, w)
         elif direct_split:
@@ -500,6 +526,56 @@ class RAFT(nn.Module):
             f1, f2 = split[0], None                       # (cost_build takes the device from its first argument; the rows are never read)
         else:
             net_l, inp_l, f1, f2 = self.encode(images, views, raw=True)
+        del images
+        return self._run_stages(dev, net_l, inp_l, f1, f2, split, views, V, Pij, disp, h, w, s, do_report, pipelined, build_done)
+
+    def forward_cached(self, ref_image, f1s, store, slots, poses, intrinsics, scale):
+        """A test-mode forward whose fnet features already exist (scan.ScanSession): ``ref_image`` [1,3,H,W] (or [3,H,W]) raw 0..255, the
+        reference view, for ``cnet``; ``f1s`` [h*w,128] f16, the reference view's split-f16 operand planes (ops.feat_ref_rows of its
+        block); ``store`` [M,(h+4)*(w+4),128] f16, bordered blocks as ``HipEncoder.features_split`` writes them; ``slots`` int32 [V] on
+        the device: source view v is block slots[v].  ``poses`` [1,1+V,4,4], ``intrinsics`` [1,1+V,3,3], reference view first, as
+        ``forward`` takes them.  Same stages, same bits and same result as ``forward`` on the stack of those images - without its
+        1 + V fnet passes.  Needs ``supports_cached`` and a decided arithmetic form."""
+        dev = ref_image.device
+        if not self.supports_cached(dev):
+            raise RuntimeError("RAFT.forward_cached: this model's forward does not take the direct-split path (see supports_cached)")
+        if self.gru_precision == "auto" and self._auto_pending():
+            raise RuntimeError("RAFT.forward_cached: gru_precision='auto' is still calibrating these weights; run ordinary forwards first")
+        if scale is None:
+            raise AssertionError("scale is required in test mode (reference: core/raft.py:107)")
+        return self._with_policy(dev, lambda: self._forward_cached(ref_image, f1s, store, slots, poses, intrinsics, scale))
+
+    def _forward_cached(self, ref_image, f1s, store, slots, poses, intrinsics, scale):
+        self._validate_packs()
+        dev = ref_image.device
+        if ref_image.dim() == 3:
+            ref_image = ref_image[None]
+        ht, wd = ref_image.shape[-2:]
+        poses = poses.clone().float()
+        s = float(torch.as_tensor(scale).reshape(-1)[0])
+        poses[..., :3, 3] *= s
+        intrinsics = intrinsics.clone().float()
+        intrinsics[:, :, :2] /= 4
+        if ht % 4 or wd % 4:
+            raise RuntimeError(f"RAFT.forward_cached: image size {wd}x{ht} must be a multiple of 4")
+        h, w = ht // 4, wd // 4
+        V = int(slots.numel())
+        if V < 1 or poses.shape[1] != 1 + V or intrinsics.shape[1] != 1 + V:
+            raise RuntimeError("RAFT.forward_cached: poses and intrinsics must hold the reference view and one entry per slot")
+        if store.dim() != 3 or tuple(store.shape[1:]) != ((h + 4) * (w + 4), 128) or f1s.numel() != h * w * 128:
+            raise RuntimeError("RAFT.forward_cached: f1s / store do not fit the reference image's feature grid")
+        views = list(range(1, V + 1))                     # (1-based: entry 0 of poses / intrinsics is the reference view)
+        Pij = pij_matrices(poses[0], intrinsics[0], [0] * V, views).to(dev)
+        disp = torch.zeros(h * w, device=dev, dtype=torch.float32)
+        net_l, inp_l, _, _ = self._get_engines(dev)[2].context(ref_image.float(), raw=True)
+        return self._run_stages(dev, net_l, inp_l, f1s, None, (f1s, store, slots), views, V, Pij, disp, h, w, s, False, False, None)
+
+    def _run_stages(self, dev, net_l, inp_l, f1, f2, split, views, V, Pij, disp, h, w, s, do_report, pipelined, build_done):
+        """What follows the encoders in a single-GPU or view-sharded forward: the update block's loop objects, the hoisted convolutions,
+        per stage the cost volume and the GRU iterations, the overflow policy's end-of-forward step -> disparity * scale [1,1,h,w]."""
+        from . import _lib as L
+        ub = self.update_block
+        P = h * w
         if ub.conv_mode == "s16":
             try:
                 for st_ in range(len(self.cascade)):
@@ -509,7 +585,6 @@ class RAFT(nn.Module):
                 warnings.warn(f"cer-mvs_amd: {e}; this model runs with gru_precision='f16x3'")
                 ub.conv_mode = "f16x3"
         net_l = ub.prepare_net(net_l, h, w)
-        del images
         # split-f16 operand rows of the cost volume's MFMA products (csrc/cost_lines.hip): the same for every stage
         # (only when the epipolar-line-tile kernel will run for some stage: cer_feat_split_f16 is what raises overflow bit 1, and a
         # forward on the fp32 walk - cer_cost_build_algo(1), the remedy the overflow error names - must not be able to raise it)

@@ -1,0 +1,310 @@
+"""Scan session: every image of a scan is uploaded, prepared and encoded by ``fnet`` ONCE; each depth map then costs ``cnet`` on its
+reference view, the cost volumes and the GRU loop.
+
+``inference()`` mirrors the reference driver's loop (inference.py:37-66): one independent stack per reference view.  A scan of M images
+with ten neighbours per view makes that loop resize (on the CPU), upload and ``fnet``-encode every image about eleven times.  None of
+the three depends on the stack: the resize and the crop are the same for the whole scan, instance norm is per image (a batched
+``fnet`` launch equals per-image launches bit for bit, tests/test_hip_parity.py), and ``scale`` multiplies the poses, not the images.
+
+``ScanSession`` keeps, on the device, the prepared images [M,3,H,W] (``cnet`` needs the reference view; the fallback needs stacks) and
+one block of split-f16 feature planes per image, in the bordered source-view layout that ``HipEncoder.features_split`` writes and
+``ops.cost_build(split=(f1s, store, slots))`` reads through a slot table.  The reference view's plain map is copied out of its block
+(``ops.feat_ref_rows``: the 1x1 feature head computes a texel from that texel alone, so the interior of the bordered form holds the plain
+form's bits), which keeps one layout per image instead of two.  ``RAFT.forward_cached`` runs the stages on them: the same code on the
+same bits as ``RAFT.forward`` on the stack of those images, so the same disparity.
+
+Where the cached path cannot apply - whenever the model's forward would not take its direct-split path (``RAFT.supports_cached``: "LR"
+encoders, ``precision="amp"``, MIOpen encoders, a view_group, a stage with D > 64, the fp32 cost-volume walk, overflow_policy
+"fallback") - the session hands stacks gathered from the prepared images to the ordinary forward (``cached == False``): the single
+upload and the device-side preparation still apply."""
+import time
+from pathlib import Path
+
+import numpy as np
+import torch
+
+from . import ops
+from .raft import RAFT, SaturationError
+
+
+def scan_intrinsics(intrinsics, H0, W0, rescale=1, crop=None):
+    """[M,3,3] intrinsics of H0 x W0 images -> those of the prepared images: rows 0 and 1 times ``rescale``, then the principal point
+    shifted by the crop window's origin - the arithmetic of inference.scale_operation + crop_operation, operation for operation.  Out of
+    place, CPU or device."""
+    _, _, y0, x0, _, _ = ops.prep_geometry(H0, W0, rescale, crop)
+    intrinsics = intrinsics.clone()
+    intrinsics[:, 0] *= rescale
+    intrinsics[:, 1] *= rescale
+    if crop is not None:
+        intrinsics = intrinsics.clone()
+        intrinsics[:, 0, 2] -= x0
+        intrinsics[:, 1, 2] -= y0
+    return intrinsics
+
+
+def _image_hw(img):
+    if img.dim() != 3:
+        raise ValueError("ScanSession: every image is uint8 [H,W,3] or float [3,H,W]")
+    if img.dtype == torch.uint8:
+        return int(img.shape[0]), int(img.shape[1])
+    return int(img.shape[1]), int(img.shape[2])
+
+
+class ScanSession:
+    """``images``: list or tensor of M images, uint8 [H0,W0,3] (``bgr``: as OpenCV reads them) or float [3,H0,W0] with values 0..255, host
+    or device, all of one size.  ``poses`` [M,4,4]; ``intrinsics`` [M,3,3], unscaled.  ``model``: a test-mode RAFT on the GPU.
+
+    ``depth(ref, srcs, scale)`` -> what ``model(stack, poses[idx], intrinsics'[idx], scale=scale)`` returns for idx = [ref] + srcs, the stack
+    gathered from ``self.prepared`` and intrinsics' = ``self.intrinsics``.  ``submit`` / ``result`` keep ``streams`` depth maps in flight
+    (one replica of the model per stream, pipeline.DepthMapPipeline's; the store and the prepared images are shared and read-only)."""
+
+    @staticmethod
+    def bytes_needed(M, H, W):
+        """Device bytes a session keeps for a scan of M prepared images of H x W: the fp32 images and, per image, one bordered block of
+        split-f16 feature planes ((H/4 + 4) * (W/4 + 4) texels x 128 halves).  The model's replicas and the workspaces of the forwards
+        in flight come on top."""
+        h, w = H // 4, W // 4
+        return M * 3 * H * W * 4 + M * (h + 4) * (w + 4) * 128 * 2
+
+    def __init__(self, model, images, poses, intrinsics, rescale=1, crop=None, streams=3, encode_batch=4, max_bytes=None, bgr=False,
+                 force_uncached=False):
+        from .pipeline import DepthMapPipeline
+        core = model.module if hasattr(model, "module") and isinstance(getattr(model, "module"), RAFT) else model
+        if not core.test_mode:
+            raise RuntimeError("ScanSession: the model must be built with test_mode=True")
+        dev = next(core.parameters()).device
+        if dev.type != "cuda":
+            raise RuntimeError("ScanSession: the model must live on a GPU (there is no CPU path)")
+        core.eval()
+        self.model, self.device = core, dev
+        images = list(images) if not isinstance(images, torch.Tensor) else [images[i] for i in range(images.shape[0])]
+        images = [torch.as_tensor(im) for im in images]
+        M = len(images)
+        if M < 2:
+            raise ValueError("ScanSession: a scan has at least two images")
+        H0, W0 = _image_hw(images[0])
+        self.rescale, self.crop = rescale, (None if crop is None else (int(crop[0]), int(crop[1])))
+        _, _, _, _, H, W = ops.prep_geometry(H0, W0, rescale, self.crop)
+        if H % 4 or W % 4:
+            raise RuntimeError(f"ScanSession: the prepared size {W}x{H} must be a multiple of 4 (the cost volume lives at 1/4 resolution)")
+        poses, intrinsics = torch.as_tensor(poses), torch.as_tensor(intrinsics)
+        if tuple(poses.shape) != (M, 4, 4) or tuple(intrinsics.shape) != (M, 3, 3):
+            raise ValueError(f"ScanSession: poses [M,4,4] and intrinsics [M,3,3] expected for M = {M} images")
+        self.M, self.H, self.W, self.h, self.w = M, H, W, H // 4, W // 4
+        need = self.bytes_needed(M, H, W)
+        if max_bytes is not None and need > max_bytes:
+            raise MemoryError(f"ScanSession: a scan of {M} images at {W}x{H} needs {need} bytes resident on the device "
+                              f"({need / 2 ** 30:.2f} GiB), more than max_bytes = {max_bytes}; there is no partial store")
+        self.encode_batch = max(1, int(encode_batch))
+        # the projection matrices are formed on the host (projective.pij_matrices): poses and intrinsics stay there
+        self.poses = poses.detach().to("cpu", torch.float32).clone()
+        self.intrinsics = scan_intrinsics(intrinsics.detach().to("cpu", torch.float32), H0, W0, rescale, self.crop)
+        self.timings = {}
+
+        # ---- once per image: upload, prepare
+        t0 = time.perf_counter()
+        self.prepared = torch.empty(M, 3, H, W, device=dev, dtype=torch.float32)
+        for i, im in enumerate(images):
+            if _image_hw(im) != (H0, W0):
+                raise ValueError(f"ScanSession: image {i} is not {W0}x{H0} like image 0")
+            if im.dtype != torch.uint8:
+                im = im.float()
+            ops.image_prep(im.to(dev).contiguous(), rescale, self.crop, out=self.prepared[i], bgr=bgr and im.dtype == torch.uint8)
+        torch.cuda.current_stream(dev).synchronize()
+        self.timings["upload_prep_s"] = time.perf_counter() - t0
+
+        self.pipe = DepthMapPipeline(core, streams=max(1, int(streams)))
+        self.force_uncached = bool(force_uncached)
+        self.store = None
+        self._store_key = None
+        self._store_ready = None
+        self._slots = {}
+        self._next = 0
+        if self.cached and not self._calibrating(core):
+            self._ensure_store()
+
+    def __len__(self):
+        return len(self.pipe)
+
+    # ---- which path
+    @property
+    def cached(self):
+        """True: depth maps run ``RAFT.forward_cached`` on the feature store; False: the ordinary forward on gathered stacks."""
+        return not self.force_uncached and self.model.supports_cached(self.device)
+
+    @staticmethod
+    def _calibrating(m):
+        return m.gru_precision == "auto" and m._auto_pending()
+
+    def _key(self):
+        m = self.model
+        return (m._params_sig(), bool(m._enc_f6))
+
+    def _ensure_store(self):
+        """(Re-)encode the store when the first model's parameters or encoder form are not the ones it was filled with."""
+        key = self._key()
+        if key == self._store_key:
+            return
+        m, dev = self.model, self.device
+        self.pipe.synchronize()                        # (a re-encode must not overwrite blocks that forwards in flight still read)
+        t0 = time.perf_counter()
+        m._validate_packs()
+        eng_f = m._get_engines(dev)[1]
+        if self.store is None:                         # border texels are written once (zeros) and never touched again
+            self.store = torch.zeros(self.M, (self.h + 4) * (self.w + 4), 128, device=dev, dtype=torch.float16)
+        flag = ops.overflow_flag(dev)
+        with torch.no_grad():
+            for i0 in range(0, self.M, self.encode_batch):
+                i1 = min(self.M, i0 + self.encode_batch)
+                eng_f.features_split(self.prepared[i0:i1], None, self.store[i0:i1], n_ref=0, border=2, scale=0.125, raw=True, flag=flag)
+        self._store_ready = torch.cuda.Event()
+        self._store_ready.record(torch.cuda.current_stream(dev))
+        self._store_key = key
+        self._store_ready.synchronize()
+        self.timings["encode_s"] = time.perf_counter() - t0
+
+    def refresh_weights(self):
+        """After the first model's parameters changed: copy them into the replicas; the store follows on the next depth map."""
+        self.pipe.refresh_weights()
+
+    def _slot_tensor(self, srcs):
+        key = tuple(int(j) for j in srcs)
+        t = self._slots.get(key)
+        if t is None:
+            if not key or min(key) < 0 or max(key) >= self.M:
+                raise IndexError(f"ScanSession: source views {key} outside the scan of {self.M} images")
+            t = self._slots[key] = torch.tensor(key, dtype=torch.int32, device=self.device)
+        return t
+
+    def stack(self, ref, srcs):
+        """The stack the ordinary forward would get for this depth map: [1, 1+V, 3, H, W] gathered from the prepared images."""
+        idx = torch.tensor([int(ref)] + [int(j) for j in srcs], device=self.device)
+        return self.prepared.index_select(0, idx).unsqueeze(0)
+
+    # ---- depth maps
+    def submit(self, ref, srcs, scale):
+        """Enqueue one depth map on the next stream; returns a handle for ``result``."""
+        pipe, ref = self.pipe, int(ref)
+        if not 0 <= ref < self.M:
+            raise IndexError(f"ScanSession: reference view {ref} outside the scan of {self.M} images")
+        srcs = [int(j) for j in srcs]
+        k = self._next % len(pipe.streams)
+        self._next += 1
+        m = pipe.models[k]
+        if k and self._calibrating(m):
+            # one arithmetic form for all replicas: the first model's calibration decides (pipeline.DepthMapPipeline.submit)
+            if not m.adopt_precision(pipe.models[0]) and self._calibrating(pipe.models[0]):
+                k, m = 0, pipe.models[0]
+        use_cached = self.cached and not self._calibrating(m)
+        idx = [ref] + srcs
+        poses, intr = self.poses[idx][None], self.intrinsics[idx][None]
+        if use_cached:
+            self._ensure_store()
+            slots = self._slot_tensor(srcs)
+        st = pipe.streams[k]
+        st.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(st), torch.no_grad():
+            if use_cached:
+                st.wait_event(self._store_ready)
+                f1s = ops.feat_ref_rows(self.store[ref], self.h, self.w, border=2)
+                out = m.forward_cached(self.prepared[ref:ref + 1], f1s, self.store, slots, poses, intr, scale)
+            else:
+                # calibration pending, or a model whose forward does not take the direct-split path: the ordinary forward on a gathered stack
+                out = m(self.stack(ref, srcs), poses, intr, scale=scale)
+            done = torch.cuda.Event()
+            done.record(st)
+        return out, done, st
+
+    def result(self, handle, wait_on_host=True):
+        return self.pipe.result(handle, wait_on_host=wait_on_host)
+
+    def depth(self, ref, srcs, scale):
+        """[1,1,h,w] disparity * scale of reference view ``ref`` against source views ``srcs`` (best first), as ``RAFT.forward`` returns it."""
+        return self.result(self.submit(ref, srcs, scale), wait_on_host=False)
+
+    def synchronize(self):
+        self.pipe.synchronize()
+
+    def poll_overflow(self):
+        return self.pipe.poll_overflow()
+
+    def check_overflow(self, raise_error=True):
+        return self.pipe.check_overflow(raise_error=raise_error)
+
+    def close(self):
+        self.pipe.synchronize()
+        self.pipe.close()
+        self.store = self.prepared = None
+        self._store_key = None
+        self._slots = {}
+
+
+def inference_scan(model_or_ckpt, images, poses, intrinsics, names, pairs, scales, output_folder, rescale=1, crop=None, num_frames=10,
+                   streams=3, write_min_depth=None, bgr=False, encode_batch=4, max_bytes=None, force_uncached=False, timings=None):
+    """``inference()`` for a whole scan held in arrays: one depth map per image i with source views ``pairs[i][:num_frames]`` (best first, as
+    the reference's load_pair orders them) and the loader's per-view ``scales[i]``; same files (``depths/{name}_scale{rescale}_nf{num_frames}.pfm``,
+    the optional min-depth text), same overflow handling.  ``model_or_ckpt``: a RAFT, or a checkpoint path (None: untrained weights).
+    ``timings``: a dict that receives the session's host-side figures.  Returns the list of files written."""
+    from .inference import disp_to_depth, write_pfm
+    if isinstance(model_or_ckpt, torch.nn.Module):
+        model = model_or_ckpt
+    else:
+        model = RAFT(test_mode=True).cuda()
+        if model_or_ckpt is not None:
+            model.load_state_dict(torch.load(model_or_ckpt, map_location="cpu"), strict=True)
+    core = model.module if hasattr(model, "module") and isinstance(getattr(model, "module"), RAFT) else model
+    was_training = core.training
+    output_folder = Path(output_folder)
+    (output_folder / "depths").mkdir(exist_ok=True, parents=True)
+    n_streams = 1 if getattr(core, "view_group", None) is not None else max(1, int(streams))
+    sess = ScanSession(core, images, poses, intrinsics, rescale=rescale, crop=crop, streams=n_streams, encode_batch=encode_batch,
+                       max_bytes=max_bytes, bgr=bgr, force_uncached=force_uncached)
+    M = sess.M
+    if len(names) != M or len(pairs) != M or len(scales) != M:
+        raise ValueError(f"inference_scan: names, pairs and scales need one entry per image ({M})")
+    written, pending = [], []
+    n_flight = len(sess)
+
+    def finish(entry):
+        handle, name = entry
+        disp_est = sess.result(handle)
+        # (as inference(): under the lazy policy the flag of forward k is polled when forward k + streams starts; nothing is written for a
+        # forward whose flag is already known to be set)
+        bits = sess.poll_overflow()
+        if bits:
+            core._raise_overflow(bits)
+        im = disp_to_depth(disp_est.cpu().numpy()[0, 0])
+        path = output_folder / "depths" / f"{name}_scale{rescale}_nf{num_frames}.pfm"
+        write_pfm(path, im)
+        written.append(str(path))
+        if write_min_depth is not None:
+            wm = Path(write_min_depth)
+            wm.mkdir(exist_ok=True)
+            with open(wm / f"{name}.txt", "w") as f:
+                f.write(f"{np.quantile(im[im > 0], 0.1) / 2}\n")
+
+    try:
+        for i in range(M):
+            srcs = [int(j) for j in pairs[i]][:num_frames]
+            pending.append((sess.submit(i, srcs, scales[i]), names[i]))
+            if len(pending) >= n_flight:
+                finish(pending.pop(0))
+        while pending:
+            finish(pending.pop(0))
+        sess.check_overflow()                               # (reads the flag: covers the last forwards, whose snapshots nobody polled)
+    except SaturationError:
+        # the files of the last `streams` forwards were written before their flags could be read (inference())
+        for path in written[-n_flight:]:
+            try:
+                Path(path).unlink()
+            except OSError:
+                pass
+        raise
+    finally:
+        if timings is not None:
+            timings.update(sess.timings)
+            timings["cached"] = bool(sess.cached)
+        sess.close()
+        if was_training:
+            core.train()
+    return written

@@ -501,6 +501,25 @@ int cer_upsample_bilinear_ac_bwd_f32(const float* grad_out, float* grad_in, floa
  * outputs whose two source texels include j ([0, 0) if none).  Same float arithmetic as the kernels. */
 int cer_upsample_ac_ranges(int in_size, int out_size, int* range);
 
+/* Scan session (ABI 1090; csrc/scan_ops.hip, cer-mvs_amd/scan.py): what is done once per image of a scan.  No atomics; the same bits on every run.
+ *
+ * Image preparation: the reference driver's scale_operation followed by crop_operation (utils/data_utils.py:58-78) in one pass that
+ * computes only the crop window.  src: one image on the device - cer_image_prep_u8: [H0, W0, 3] bytes as an image reader returns
+ * them (swap_rb != 0: output channel c reads byte 2 - c, BGR -> RGB); cer_image_prep_f32: [3, H0, W0] floats, values 0..255.
+ * dst [3, H, W] floats, raw 0..255 (the encoders' stem normalises).  (H2, W2): the size after the resize (the caller's int(s * H0),
+ * int(s * W0)); (y0, x0): first row / column of the window inside the resized image; (H, W): the window.  Bilinear with
+ * align_corners=True in torch's upsample_bilinear2d arithmetic, as cer_upsample_bilinear_ac_f32 above (the scale is computed once on the host;
+ * src = scale * dst, i0 = (int)src clamped to the image, lambda = src - i0); l0y * (l0x a + l1x b) + l1y * (l0x c + l1x d).  H2 == H0 and W2 == W0: a copy
+ * (no arithmetic: bit-identical to the source).  CER_EINVAL: null pointer, size <= 0, window outside the resized image;
+ * CER_EALIGN: W % 4 == 0 and dst not 16-byte aligned. */
+int cer_image_prep_u8(const unsigned char* src, float* dst, int H0, int W0, int H2, int W2, int y0, int x0, int H, int W, int swap_rb,
+                      void* stream);
+int cer_image_prep_f32(const float* src, float* dst, int H0, int W0, int H2, int W2, int y0, int x0, int H, int W, void* stream);
+/* Reference rows: the interior h x w of ONE bordered block of split-f16 operand planes (cer_feat_split_f16's layout: 8 planes of
+ * [(h + 2 border) * (w + 2 border)][16 halves], what the encoders' feature head writes for a source view) -> the plain block (8 planes of
+ * [h * w][16]) that cer_cost_lines_f32 takes as fmap1_split.  16-byte loads and stores. */
+int cer_feat_ref_rows_f16(const void* slot, void* out, int h, int w, int border, void* stream);
+
 /* Multi-GPU row-slab exchange (cer-mvs_amd/slab.py): up to CER_COPY_MAX_SEG contiguous fp32 ranges copied by ONE launch -
  * the pack of a rank's (net, disp) border strips into its send buffer, and the refresh of its halo rows from the gathered
  * strips.  n[i] floats from src[i] to dst[i]; n[i] == 0 skips a segment.  Device pointers; ranges must not overlap. */
