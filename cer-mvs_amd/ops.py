@@ -201,7 +201,7 @@ def _lines_workspace(V, h1, w1, D, device):
 
 
 def cost_build(fmap1, fmap2, Pij, disp_in, D, incre, shift, h1, w1, num_levels, fold, vol=None, accumulate=False, src_hw=None, y0=0,
-               pyramid_scale=None, split=None, compact=False, two_term=False):
+               pyramid_scale=None, split=None, compact=False, two_term=False, origin=None):
     """fmap1 [P,C], fmap2 [V,(h2+4)*(w2+4),C] (NHWC, pre-scaled, 2-texel zero border), Pij [V,4,4], disp_in [P].
     (h1, w1): reference grid of this call, first image row ``y0`` (row slabs); ``src_hw``: source-map size (default h1, w1).
     Returns (vol [V,P,rs] or [P,rs], origin [P]).  Level 0 only; call ``pyramid`` next - unless ``pyramid_scale`` is given
@@ -212,7 +212,8 @@ def cost_build(fmap1, fmap2, Pij, disp_in, D, incre, shift, h1, w1, num_levels, 
     rows are block slots[v] of the second element (any leading shape; the sharded forward's gathered buffer) - ``fmap2`` may then
     be None and ``V`` = len(slots).  ``compact``: level-0-only rows (``row_layout``); with ``pyramid_scale`` the epilogue then only
     scales (both builders: ``fuse_levels = 1``).  ``two_term`` (round 6; epipolar-line-tile kernel only, ignored by the walk): the source
-    texels' lo planes are not read - half the tile kernel's fragment bytes, 1.2e-5 relative L1 on the volume (cer_mvs.h)."""
+    texels' lo planes are not read - half the tile kernel's fragment bytes, 1.2e-5 relative L1 on the volume (cer_mvs.h).
+    ``origin``: where to write the hypothesis origins ([P]; default: a new tensor)."""
     if fmap2 is None:
         if split is None or len(split) < 3 or src_hw is None:
             raise ValueError("cost_build: without fmap2 the split rows, their view slots and src_hw are required")
@@ -243,7 +244,10 @@ def cost_build(fmap1, fmap2, Pij, disp_in, D, incre, shift, h1, w1, num_levels, 
                 vol[..., used:] = 0
         else:
             vol = torch.zeros(shape, device=fmap1.device, dtype=torch.float32)     # pooled levels stay 0 until ``pyramid`` runs
-    origin = torch.empty(P, device=fmap1.device, dtype=torch.float32)
+    if origin is None:
+        origin = torch.empty(P, device=fmap1.device, dtype=torch.float32)
+    elif origin.numel() != P or origin.device != fmap1.device:
+        raise RuntimeError(f"cost_build: origin must hold {P} floats on {fmap1.device}")
     mode = (2 if accumulate else 1) if fold else 0
     slots = split[2] if (split is not None and len(split) > 2) else None
     if on_lines:
