@@ -9,7 +9,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CER_MVS_LIB") or os.path.join(_HERE, "csrc", "libcermvs.so")
-ABI_VERSION = 1090
+ABI_VERSION = 1100
 CONV_MAX_SRC = 4
 EPI_LINEAR, EPI_RELU, EPI_GATES, EPI_GRU, EPI_DELTA = 0, 1, 2, 3, 4
 EPI_OUT_SPLIT, EPI_AUX_SPLIT = 0x100, 0x200       # cer_mvs.h: split32 activation layout flags, or-ed into `epi`
@@ -26,6 +26,7 @@ _I = _c.c_int
 _L = _c.c_long
 _F = _c.c_float
 _D = _c.c_double
+_LL = _c.c_longlong
 
 
 class ConvInputs(ctypes.Structure):
@@ -117,6 +118,11 @@ _SIGNATURES = {
     "cer_image_prep_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "cer_image_prep_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "cer_feat_ref_rows_f16": (_I, [_P, _P, _I, _I, _I, _P]),
+    "cer_cloud_partials": (_L, [_I, _I, _I]),
+    "cer_cloud_count_u8": (_I, [_P, _I, _I, _I, _c.POINTER(_I), _I, _P, _P, _P, _P]),
+    "cer_cloud_emit_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _c.POINTER(_I), _I, _P, _LL, _LL, _P, _P, _P]),
+    "cer_color_grid_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
+    "cer_disp_to_depth_f32": (_I, [_P, _P, _L, _P]),
 }
 
 # include/cer_mvs_variants.h: exported by csrc/variants/libcermvs_optin.so only (round 4's opt-in kernel forms; CER_MVS_LIB selects the library)

@@ -1,0 +1,243 @@
+// Point cloud of a fused scan on the device (cer-mvs_amd/fusion.py point_cloud / color_grid, scan.py reconstruct_scan): what fusion() does on
+// the host after the vote loop (reference: fusion.py:262-279) - the masked pixels of every listed view back-projected to world points and
+// paired with their colours - plus the two small producers in front of it: disparity -> depth and the colour planes at the depth grid.
+//
+// Order: the points of view order[0] first, then order[1], ...; row-major inside a view - what numpy's boolean indexing gives the host path.
+// It is a pure function of the masks: a count pass writes one partial count per block (wave ballots), one block scans the partials into
+// 64-bit exclusive offsets, and the emit pass ranks every set pixel inside its wave (ballot + mbcnt), its wave inside the block (LDS) and its
+// block through the scanned offset.  No atomics, no output cursor: the same bytes on every run, whatever the schedule.
+#include "common.hpp"
+
+#define CLOUD_TILE CER_CLOUD_TILE                    // pixels of one view per block
+#define CLOUD_ITER (CLOUD_TILE / 256)                // 64-pixel rows per wave: wave v of a block owns pixels [v, v + 1) * TILE / 4 of the tile
+#define CLOUD_ORDER_CHUNK 128                        // listed views per launch (they travel as kernel arguments: the list is host memory)
+
+struct CloudOrder {
+    int view[CLOUD_ORDER_CHUNK];
+};
+
+__device__ __forceinline__ unsigned cloud_rank(unsigned long long ballot) {     // set lanes below this one
+    return __builtin_amdgcn_mbcnt_hi((unsigned)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)ballot, 0u));
+}
+
+// ---- count: partials[(k0 + blockIdx.y) * bpv + blockIdx.x] = set pixels of the block's tile
+__global__ __launch_bounds__(256) void cloud_count_kernel(const CloudOrder ord, int k0, const unsigned char* __restrict__ masks, unsigned P,
+                                                          int bpv, unsigned* __restrict__ partials) {
+    __shared__ unsigned wave_cnt[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned char* m = masks + (long)ord.view[blockIdx.y] * P;
+    const unsigned seg = blockIdx.x * (unsigned)CLOUD_TILE + wave * (CLOUD_TILE / 4) + lane;
+    unsigned tot = 0;
+#pragma unroll
+    for (int j = 0; j < CLOUD_ITER; ++j) {
+        const unsigned p = seg + 64 * j;
+        const bool set = p < P && m[p] != 0;
+        tot += (unsigned)__popcll(__ballot(set));
+    }
+    if (lane == 0) wave_cnt[wave] = tot;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[(long)(k0 + blockIdx.y) * bpv + blockIdx.x] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+}
+
+// ---- scan: one block; offsets[i] = sum of partials[0 .. i), offsets[n] = the total; view_base[k] = offsets[k * bpv] (k <= views).
+// The partials are walked in chunks of 1024: thread t takes element chunk + t (coalesced loads and stores), the chunk is scanned with
+// shuffles inside a wave and the 16 wave totals through LDS, and the running total is carried to the next chunk.  A 49-view scan at
+// 1600x1184 has 45 325 partials: 45 chunks.
+__global__ __launch_bounds__(1024) void cloud_scan_kernel(const unsigned* __restrict__ partials, long n, int bpv, int views,
+                                                          long long* __restrict__ offsets, long long* __restrict__ view_base) {
+    __shared__ long long wave_tot[16];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    long long carry = 0;
+    for (long c0 = 0; c0 < n; c0 += 1024) {
+        const long i = c0 + t;
+        const long long s = i < n ? (long long)partials[i] : 0;
+        long long inc = s;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const long long v = __shfl_up(inc, d);
+            if (lane >= d) inc += v;
+        }
+        if (lane == 63) wave_tot[wave] = inc;
+        __syncthreads();
+        long long below = 0, all = 0;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const long long v = wave_tot[k];
+            below += k < wave ? v : 0;
+            all += v;
+        }
+        if (i < n) offsets[i] = carry + below + inc - s;
+        carry += all;
+        __syncthreads();                             // (wave_tot is rewritten by the next chunk)
+    }
+    if (t == 0) offsets[n] = carry;
+    __syncthreads();                                 // the block's own global writes are visible to it behind the barrier
+    for (int k = t; k <= views; k += 1024) view_base[k] = offsets[(long)k * bpv];
+}
+
+// ---- emit.  cams: per view CER_CLOUD_CAM_DOUBLES doubles = K^-1 [9] | rows 0-2 of E^-1 [12] (float32 inverses promoted on the host).
+// The coordinate arithmetic is backproject()'s, in fp64: K^-1 (x d, y d, d), then E^-1 (., 1), rounded ONCE to float32.
+__global__ __launch_bounds__(256) void cloud_emit_kernel(const CloudOrder ord, int k0, const unsigned char* __restrict__ masks,
+                                                         const float* __restrict__ depth, const double* __restrict__ cams,
+                                                         const float* __restrict__ colors, unsigned P, int w, int bpv,
+                                                         const long long* __restrict__ offsets, long long capacity, float* __restrict__ xyz,
+                                                         unsigned char* __restrict__ rgb) {
+    __shared__ unsigned wave_cnt[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int view = ord.view[blockIdx.y];
+    const unsigned char* m = masks + (long)view * P;
+    const unsigned seg = blockIdx.x * (unsigned)CLOUD_TILE + wave * (CLOUD_TILE / 4) + lane;
+    unsigned long long bal[CLOUD_ITER];
+    unsigned tot = 0;
+#pragma unroll
+    for (int j = 0; j < CLOUD_ITER; ++j) {
+        const unsigned p = seg + 64 * j;
+        bal[j] = __ballot(p < P && m[p] != 0);
+        tot += (unsigned)__popcll(bal[j]);
+    }
+    if (lane == 0) wave_cnt[wave] = tot;
+    __syncthreads();
+    long long base = offsets[(long)(k0 + blockIdx.y) * bpv + blockIdx.x];
+    for (int i = 0; i < wave; ++i) base += wave_cnt[i];
+    const double* c = cams + (long)view * CER_CLOUD_CAM_DOUBLES;         // wave-uniform: scalar loads
+    const float* dep = depth + (long)view * P;
+    const float* col = colors + (long)view * 3 * P;
+#pragma unroll
+    for (int j = 0; j < CLOUD_ITER; ++j) {
+        const unsigned p = seg + 64 * j;
+        const long long idx = base + cloud_rank(bal[j]);
+        base += __popcll(bal[j]);
+        if (!((bal[j] >> lane) & 1ull) || idx >= capacity) continue;     // (never past what the caller allocated)
+        const unsigned yi = p / (unsigned)w, xi = p - yi * (unsigned)w;
+        const double d = (double)dep[p];
+        const double vx = (double)xi * d, vy = (double)yi * d;           // exact: an integer times a float32 in fp64
+        const double cx = fma(c[2], d, fma(c[1], vy, c[0] * vx));
+        const double cy = fma(c[5], d, fma(c[4], vy, c[3] * vx));
+        const double cz = fma(c[8], d, fma(c[7], vy, c[6] * vx));
+        const double X = fma(c[11], cz, fma(c[10], cy, c[9] * cx)) + c[12];
+        const double Y = fma(c[15], cz, fma(c[14], cy, c[13] * cx)) + c[16];
+        const double Z = fma(c[19], cz, fma(c[18], cy, c[17] * cx)) + c[20];
+        float* o = xyz + idx * 3;
+        o[0] = (float)X;
+        o[1] = (float)Y;
+        o[2] = (float)Z;
+        unsigned char* q = rgb + idx * 3;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) q[ch] = (unsigned char)(int)(col[(long)ch * P + p] * 255.0f);     // fusion(): (img * 255).astype(uint8)
+    }
+}
+
+static int cloud_check(const void* masks, int N, int h, int w, const int* order, int n_order) {
+    if (!masks || !order || N <= 0 || h <= 0 || w <= 0 || n_order <= 0) return CER_EINVAL;
+    if ((long)h * w > 0x7fffffffL - CLOUD_TILE) return CER_ESHAPE;
+    for (int k = 0; k < n_order; ++k)
+        if (order[k] < 0 || order[k] >= N) return CER_EINVAL;
+    return CER_OK;
+}
+
+extern "C" long cer_cloud_partials(int n_order, int h, int w) {
+    if (n_order <= 0 || h <= 0 || w <= 0) return CER_EINVAL;
+    return (long)n_order * (((long)h * w + CLOUD_TILE - 1) / CLOUD_TILE);
+}
+
+extern "C" int cer_cloud_count_u8(const unsigned char* masks, int N, int h, int w, const int* order, int n_order, unsigned int* partials,
+                                  long long* offsets, long long* view_base, void* stream) {
+    const int rc = cloud_check(masks, N, h, w, order, n_order);
+    if (rc != CER_OK) return rc;
+    if (!partials || !offsets || !view_base) return CER_EINVAL;
+    const unsigned P = (unsigned)((long)h * w);
+    const int bpv = (int)((P + CLOUD_TILE - 1) / CLOUD_TILE);
+    hipStream_t st = (hipStream_t)stream;
+    for (int k0 = 0; k0 < n_order; k0 += CLOUD_ORDER_CHUNK) {
+        CloudOrder ord = {};
+        const int nk = n_order - k0 < CLOUD_ORDER_CHUNK ? n_order - k0 : CLOUD_ORDER_CHUNK;
+        for (int k = 0; k < nk; ++k) ord.view[k] = order[k0 + k];
+        hipLaunchKernelGGL(cloud_count_kernel, dim3((unsigned)bpv, (unsigned)nk), dim3(256), 0, st, ord, k0, masks, P, bpv, partials);
+        CER_RETURN_IF_LAUNCH_FAILED();
+    }
+    hipLaunchKernelGGL(cloud_scan_kernel, dim3(1), dim3(1024), 0, st, partials, (long)n_order * bpv, bpv, n_order, offsets, view_base);
+    CER_RETURN_IF_LAUNCH_FAILED();
+    return CER_OK;
+}
+
+extern "C" int cer_cloud_emit_f32(const unsigned char* masks, const float* depth_est, const double* cams, const float* colors, int N, int h,
+                                  int w, const int* order, int n_order, const long long* offsets, long long total, long long capacity,
+                                  float* xyz, unsigned char* rgb, void* stream) {
+    const int rc = cloud_check(masks, N, h, w, order, n_order);
+    if (rc != CER_OK) return rc;
+    if (!depth_est || !cams || !colors || !offsets || total < 0 || capacity < 0) return CER_EINVAL;
+    if (total != capacity) return CER_ESHAPE;        // the caller allocates exactly what the count pass found
+    if (capacity == 0) return CER_OK;                // nothing to write: nothing is launched
+    if (!xyz || !rgb) return CER_EINVAL;
+    const unsigned P = (unsigned)((long)h * w);
+    const int bpv = (int)((P + CLOUD_TILE - 1) / CLOUD_TILE);
+    hipStream_t st = (hipStream_t)stream;
+    for (int k0 = 0; k0 < n_order; k0 += CLOUD_ORDER_CHUNK) {
+        CloudOrder ord = {};
+        const int nk = n_order - k0 < CLOUD_ORDER_CHUNK ? n_order - k0 : CLOUD_ORDER_CHUNK;
+        for (int k = 0; k < nk; ++k) ord.view[k] = order[k0 + k];
+        hipLaunchKernelGGL(cloud_emit_kernel, dim3((unsigned)bpv, (unsigned)nk), dim3(256), 0, st, ord, k0, masks, depth_est, cams, colors, P,
+                           w, bpv, offsets, capacity, xyz, rgb);
+        CER_RETURN_IF_LAUNCH_FAILED();
+    }
+    return CER_OK;
+}
+
+// ---- colour planes at the depth grid: prepared images [n, 3, H, W], values 0..255 -> [n, 3, h, w], values 0..1, H = k h, W = k w.
+// v / 255 is an IEEE division on every tap; then torch's upsample_bilinear2d(align_corners=False) expression (what fusion._resize runs on
+// the host): scale = (float)H / h, src = scale * (dst + 0.5) - 0.5 clamped at 0, i0 = (int)src, the +1 neighbour clamped at the last row /
+// column, l1 = src - i0, l0 = 1 - l1, and ly0 * (lx0 a + lx1 b) + ly1 * (lx0 c + lx1 d) with every product and sum rounded on its own
+// (-ffp-contract=off).  At an integer ratio the weights are 0, 1/2 or 1 - every product is exact, which is why this is the host's result
+// bit for bit there (and why other ratios are refused).
+struct GridTap {
+    int i0, i1;
+    float l0, l1;
+};
+__device__ __forceinline__ GridTap grid_tap(float scale, int d, int in_size) {
+    float s = scale * ((float)d + 0.5f) - 0.5f;
+    s = s < 0.0f ? 0.0f : s;
+    GridTap t;
+    t.i0 = min((int)s, in_size - 1);
+    t.i1 = t.i0 + (t.i0 < in_size - 1 ? 1 : 0);
+    t.l1 = s - (float)t.i0;
+    t.l0 = 1.0f - t.l1;
+    return t;
+}
+// grid: x = 256-column blocks of a row, y = output row, z = plane (image * 3 + channel)
+__global__ __launch_bounds__(256) void color_grid_kernel(const float* __restrict__ src, float* __restrict__ dst, int H, int W, int h, int w,
+                                                         float sy, float sx) {
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= w) return;
+    const long plane = blockIdx.z;
+    const GridTap ty = grid_tap(sy, y, H), tx = grid_tap(sx, x, W);
+    const float* s = src + plane * H * W;
+    const float a = s[(long)ty.i0 * W + tx.i0] / 255.0f, b = s[(long)ty.i0 * W + tx.i1] / 255.0f;
+    const float c = s[(long)ty.i1 * W + tx.i0] / 255.0f, d = s[(long)ty.i1 * W + tx.i1] / 255.0f;
+    dst[(plane * h + y) * w + x] = ty.l0 * (tx.l0 * a + tx.l1 * b) + ty.l1 * (tx.l0 * c + tx.l1 * d);
+}
+
+extern "C" int cer_color_grid_f32(const float* prepared, float* colors, int n, int H, int W, int h, int w, void* stream) {
+    if (!prepared || !colors || n <= 0 || H <= 0 || W <= 0 || h <= 0 || w <= 0) return CER_EINVAL;
+    if (H % h || W % w || H / h != W / w) return CER_ESHAPE;              // one integer ratio for both axes
+    if (h > 65535 || (long)n * 3 > 65535) return CER_ESHAPE;              // rows and planes are grid dimensions
+    hipLaunchKernelGGL(color_grid_kernel, dim3((unsigned)((w + 255) / 256), (unsigned)h, (unsigned)(n * 3)), dim3(256), 0, (hipStream_t)stream,
+                       prepared, colors, H, W, h, w, (float)H / (float)h, (float)W / (float)w);
+    CER_RETURN_IF_LAUNCH_FAILED();
+    return CER_OK;
+}
+
+// ---- disparity -> depth (inference.disp_to_depth): 0 where the disparity is 0, else the correctly rounded 1 / d
+__global__ __launch_bounds__(256) void disp_to_depth_kernel(const float* __restrict__ disp, float* __restrict__ depth, long n) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float d = disp[i];
+    depth[i] = d == 0.0f ? 0.0f : 1.0f / d;
+}
+
+extern "C" int cer_disp_to_depth_f32(const float* disp, float* depth, long n, void* stream) {
+    if (!disp || !depth || n <= 0) return CER_EINVAL;
+    if ((n + 255) / 256 > 0x7fffffffL) return CER_ESHAPE;
+    hipLaunchKernelGGL(disp_to_depth_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, disp, depth, n);
+    CER_RETURN_IF_LAUNCH_FAILED();
+    return CER_OK;
+}

@@ -9,6 +9,9 @@ Mirrors the reference's interface:
   * ``fuse_depth_maps(depths, Ks, Es, pairs, glb)`` - the ten-round bisection of fusion.py:199-262 on device tensors;
   * ``fusion(data_loader, output_folder, suffix, glb, rescale)`` - the reference's driver: reads the ``depths/*.pfm`` that
     ``inference`` wrote, runs the loop, writes ``mask/<view>.png`` and ``result.ply``.
+  * ``point_cloud(masks, depth_est, Ks, Es, colors, order)`` / ``color_grid(prepared, h, w)`` - the driver's tail on the device
+    (csrc/cloud.hip): masked pixels -> world points and colours, in the driver's order; ``scan.reconstruct_scan`` chains them behind
+    ``ScanSession.depths`` and ``fuse_depth_maps`` without a trip through files or the host.
 The camera algebra (3x3 / 4x4 inverses and products, a few hundred flops per view pair) stays on the host in fp32 torch,
 in the reference's order; everything per pixel is in the kernel.  No CPU fallback: tensors must be CUDA tensors."""
 import ctypes
@@ -127,6 +130,78 @@ def backproject(depth, mask, K, E):
     return np.matmul(np.linalg.inv(E), np.vstack((cam, np.ones_like(x))))[:3].transpose((1, 0))
 
 
+CLOUD_CAM_DOUBLES = 24  # cer_mvs.h CER_CLOUD_CAM_DOUBLES
+
+
+def cloud_cams(Ks, Es):
+    """Per view K^-1 [9] | rows 0-2 of E^-1 [12] | padding, float64 [N, 24] (CPU): the float32 inverses ``backproject`` takes
+    (np.linalg.inv of the float32 matrices), promoted - the products with them run in fp64 on the device."""
+    Ks = torch.as_tensor(Ks).detach().to("cpu", torch.float32).numpy()
+    Es = torch.as_tensor(Es).detach().to("cpu", torch.float32).numpy()
+    if Ks.ndim != 3 or Ks.shape[1:] != (3, 3) or Es.shape != (Ks.shape[0], 4, 4):
+        raise ValueError("cloud_cams: Ks [N,3,3] and Es [N,4,4] expected")
+    cams = np.zeros((Ks.shape[0], CLOUD_CAM_DOUBLES), dtype=np.float64)
+    for i in range(Ks.shape[0]):
+        cams[i, :9] = np.linalg.inv(Ks[i]).reshape(9)
+        cams[i, 9:21] = np.linalg.inv(Es[i])[:3].reshape(12)
+    return torch.from_numpy(cams)
+
+
+def point_cloud(masks, depth_est, Ks, Es, colors, order):
+    """The tail of ``fusion()`` on the device: masks uint8 [N,h,w], depth_est float32 [N,h,w], colors float32 [N,3,h,w] with values 0..1 (CUDA),
+    Ks [N,3,3], Es [N,4,4], ``order``: the views to emit.  Returns (xyz float32 [n,3], rgb uint8 [n,3]) on the device, n = set mask pixels
+    of the listed views: view by view in ``order``, row-major inside a view (numpy's boolean-indexing order), xyz = ``backproject``'s fp64
+    arithmetic rounded once to float32, rgb = (uint8)(c * 255).  One device->host read (the per-view totals) sizes the output."""
+    if not (masks.is_cuda and depth_est.is_cuda and colors.is_cuda):
+        raise RuntimeError("point_cloud: masks, depth_est and colors must be CUDA tensors (no CPU fallback)")
+    N, h, w = masks.shape
+    if tuple(depth_est.shape) != (N, h, w) or tuple(colors.shape) != (N, 3, h, w):
+        raise ValueError(f"point_cloud: depth_est [{N},{h},{w}] and colors [{N},3,{h},{w}] expected")
+    order = [int(v) for v in order]
+    if not order or min(order) < 0 or max(order) >= N:
+        raise IndexError(f"point_cloud: order must list views in 0..{N - 1}")
+    dev = masks.device
+    lib = L.load()
+    cams = cloud_cams(Ks, Es)
+    if cams.shape[0] != N:
+        raise ValueError(f"point_cloud: {N} cameras expected")
+    cams = cams.to(dev)
+    order_c = (ctypes.c_int * len(order))(*order)
+    P = int(lib.cer_cloud_partials(len(order), h, w))
+    partials = torch.empty(P, device=dev, dtype=torch.int32)
+    offsets = torch.empty(P + 1, device=dev, dtype=torch.int64)
+    view_base = torch.empty(len(order) + 1, device=dev, dtype=torch.int64)
+    pm, pd, pc = L.dev_ptr(masks, "masks", torch.uint8), L.dev_ptr(depth_est, "depth_est"), L.dev_ptr(colors, "colors")
+    L.check(lib.cer_cloud_count_u8(pm, N, h, w, order_c, len(order), L.dev_ptr(partials, "partials", torch.int32),
+                                   L.dev_ptr(offsets, "offsets", torch.int64), L.dev_ptr(view_base, "view_base", torch.int64), L.cur_stream()),
+            "cloud_count")
+    n = int(view_base.cpu()[-1])                             # the one synchronisation: the output is allocated exactly
+    xyz = torch.empty(n, 3, device=dev, dtype=torch.float32)
+    rgb = torch.empty(n, 3, device=dev, dtype=torch.uint8)
+    L.check(lib.cer_cloud_emit_f32(pm, pd, L.dev_ptr(cams, "cams", torch.float64), pc, N, h, w, order_c, len(order),
+                                   L.dev_ptr(offsets, "offsets", torch.int64), n, n, L.dev_ptr(xyz, "xyz") if n else None,
+                                   L.dev_ptr(rgb, "rgb", torch.uint8) if n else None, L.cur_stream()), "cloud_emit")
+    return xyz, rgb
+
+
+def color_grid(prepared, h, w):
+    """Prepared images float32 [N,3,H,W], values 0..255 (``ScanSession.prepared``) -> the colour planes of ``point_cloud``, [N,3,h,w] with
+    values 0..1: what ``fusion()`` computes per view with ``img / 255`` and ``_resize`` on the host, bit for bit - which holds at integer ratios
+    only (H = k h, W = k w; at other ratios the interpolation weights round and the device and the host differ in the last bit)."""
+    if prepared.dim() != 4 or prepared.shape[1] != 3:
+        raise ValueError("color_grid: prepared images [N,3,H,W] expected")
+    N, _, H, W = (int(v) for v in prepared.shape)
+    h, w = int(h), int(w)
+    if h <= 0 or w <= 0 or H % h or W % w or H // h != W // w:
+        raise ValueError(f"color_grid: {W}x{H} images on a {w}x{h} depth grid is not one integer ratio; only those are bit-identical to the "
+                         "host resize - use fusion() (the file pipeline) for this scan")
+    if not prepared.is_cuda:
+        raise RuntimeError("color_grid: the images must be a CUDA tensor (no CPU fallback)")
+    out = torch.empty(N, 3, h, w, device=prepared.device, dtype=torch.float32)
+    L.check(L.load().cer_color_grid_f32(L.dev_ptr(prepared, "prepared"), L.dev_ptr(out, "colors"), N, H, W, h, w, L.cur_stream()), "color_grid")
+    return out
+
+
 def read_pfm(path):
     """Inverse of inference.write_pfm (reference: utils/frame_utils.py:31-66): float32 [H,W] (or [H,W,3]), top row first."""
     with open(path, "rb") as f:
@@ -164,6 +239,28 @@ def _resize(img, h, w):
     return (out.permute(1, 2, 0) if img.ndim == 3 else out[0]).numpy()
 
 
+def depth_grid_geometry(img_h, img_w, dep_h, dep_w):
+    """How the reference's driver fits an image to its depth map (fusion.py:137-160): -> (scale, flag, rh, rw, index).  The image is resized
+    by ``scale`` to rh x rw (unless scale == 1), the larger of the two axis ratios; flag 0: columns [index, index + dep_w) are kept, flag 1:
+    rows [index, rh - index)."""
+    scale = float(dep_h) / img_h
+    flag = 0
+    if dep_w / img_w > scale:
+        scale = float(dep_w) / img_w
+        flag = 1
+    rh, rw = (int(round(img_h * scale)), int(round(img_w * scale))) if scale != 1.0 else (img_h, img_w)
+    index = int(math.ceil((rw - dep_w) / 2)) if flag == 0 else int(math.ceil((rh - dep_h) / 2))
+    return scale, flag, rh, rw, index
+
+
+def modify_camera_parameters(K, scale, index, flag):
+    """The reference's intrinsics update for that fit (fusion.py:24-30), in place on a [3,3] tensor: rows 0 and 1 times ``scale``, then the
+    principal point of the cropped axis minus ``index``."""
+    K[:2, :] *= scale
+    K[0 if flag == 0 else 1, 2] -= index
+    return K
+
+
 def fusion(data_loader, output_folder, suffix="", glb=0.25, rescale=1, device="cuda", write=True):
     """The reference's driver (fusion.py:110-297).  ``data_loader`` yields (images [1,n,3,H,W], extrinsics [1,n,4,4],
     intrinsics [1,n,3,3], image_names, _) per reference view; the estimated depth of view <name> is read from
@@ -182,21 +279,14 @@ def fusion(data_loader, output_folder, suffix="", glb=0.25, rescale=1, device="c
         h, w = dep.shape
         if rescale != 1:
             dep = _resize(dep, int(h * rescale), int(w * rescale))
-        scale = float(dep.shape[0]) / img.shape[0]
-        flag = 0
-        if dep.shape[1] / img.shape[1] > scale:
-            scale = float(dep.shape[1]) / img.shape[1]
-            flag = 1
+        scale, flag, rh, rw, index = depth_grid_geometry(img.shape[0], img.shape[1], dep.shape[0], dep.shape[1])
         if scale != 1.0:
-            img = _resize(img, int(round(img.shape[0] * scale)), int(round(img.shape[1] * scale)))
+            img = _resize(img, rh, rw)
         if flag == 0:
-            index = int(math.ceil((img.shape[1] - dep.shape[1]) / 2))
             img = img[:, index:dep.shape[1] + index, :]
         else:
-            index = int(math.ceil((img.shape[0] - dep.shape[0]) / 2))
             img = img[index:img.shape[0] - index, :, :]
-        K[:2, :] *= scale                                    # modify_camera_parameters (fusion.py:24-30)
-        K[0 if flag == 0 else 1, 2] -= index
+        modify_camera_parameters(K, scale, index, flag)
         if i > 0 and (img.shape != imgs[0].shape or dep.shape != deps[0].shape):      # fusion.py:176-189: crop / zero-pad to view 0
             ih, iw = imgs[0].shape[:2]
             pi = np.zeros_like(imgs[0]); pi[:min(ih, img.shape[0]), :min(iw, img.shape[1])] = img[:ih, :iw]

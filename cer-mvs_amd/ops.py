@@ -822,3 +822,14 @@ def feat_ref_rows(slot, h, w, border=2, out=None):
     L.check(L.load().cer_feat_ref_rows_f16(L.dev_ptr(slot, "slot", torch.float16), L.dev_ptr(out, "out", torch.float16), h, w, border,
                                            L.cur_stream()), "feat_ref_rows")
     return out
+
+
+def disp_to_depth(disp, out=None):
+    """``inference.disp_to_depth`` on the device: float32 disparity (any shape, dense) -> depth, 0 where the disparity is 0, else the correctly
+    rounded 1 / d - the host function's bits.  ``out``: where to write (a slice of a depth stack), same number of elements."""
+    if out is None:
+        out = torch.empty_like(disp)
+    elif out.numel() != disp.numel() or out.device != disp.device:
+        raise RuntimeError(f"disp_to_depth: out must hold {disp.numel()} floats on {disp.device}")
+    L.check(L.load().cer_disp_to_depth_f32(L.dev_ptr(disp, "disp"), L.dev_ptr(out, "out"), disp.numel(), L.cur_stream()), "disp_to_depth")
+    return out

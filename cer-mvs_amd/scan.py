@@ -222,6 +222,42 @@ class ScanSession:
         """[1,1,h,w] disparity * scale of reference view ``ref`` against source views ``srcs`` (best first), as ``RAFT.forward`` returns it."""
         return self.result(self.submit(ref, srcs, scale), wait_on_host=False)
 
+    def depths(self, pairs, scales, num_frames=10):
+        """One depth map per image i against ``pairs[i][:num_frames]`` with ``scales[i]`` -> float32 [M,h,w] on the device, ``len(self)`` depth maps
+        in flight.  Each disparity is inverted on the stream that produced it (``ops.disp_to_depth``: ``inference.disp_to_depth``'s bits)
+        straight into its slice.  The overflow flag is polled as ``inference_scan`` polls it; a ``SaturationError`` leaves nothing behind."""
+        M = self.M
+        if len(pairs) != M or len(scales) != M:
+            raise ValueError(f"ScanSession.depths: pairs and scales need one entry per image ({M})")
+        stack = torch.empty(M, self.h, self.w, device=self.device, dtype=torch.float32)
+        pending, n_flight = [], len(self)
+        cur = torch.cuda.current_stream(self.device)
+
+        def finish(done):
+            done.synchronize()
+            bits = self.poll_overflow()
+            if bits:
+                self.model._raise_overflow(bits)
+
+        try:
+            for i in range(M):
+                disp, _, st = self.submit(i, [int(j) for j in pairs[i]][:num_frames], scales[i])
+                with torch.cuda.stream(st):
+                    ops.disp_to_depth(disp, out=stack[i])
+                    done = torch.cuda.Event()
+                    done.record(st)
+                pending.append(done)
+                if len(pending) >= n_flight:
+                    finish(pending.pop(0))
+            while pending:
+                finish(pending.pop(0))
+            self.check_overflow()                           # (reads the flag: covers the last forwards, whose snapshots nobody polled)
+        finally:
+            for st in self.pipe.streams:                    # (also on an error: no forward still writes into a stack that is let go)
+                stack.record_stream(st)
+                cur.wait_stream(st)
+        return stack
+
     def synchronize(self):
         self.pipe.synchronize()
 
@@ -308,3 +344,107 @@ def inference_scan(model_or_ckpt, images, poses, intrinsics, names, pairs, scale
         if was_training:
             core.train()
     return written
+
+
+def _write_masks(folder, masks_np, refs, suffix=""):
+    """``mask/<index><suffix>.png`` as ``fusion.fusion`` writes them."""
+    (folder / "mask").mkdir(exist_ok=True, parents=True)
+    try:
+        from PIL import Image
+        for ref in refs:
+            Image.fromarray(masks_np[ref].astype(np.uint8) * 255).save(str(folder / "mask" / f"{ref}{suffix}.png"))
+    except ImportError:                                      # no PNG encoder in this Python: keep the arrays
+        for ref in refs:
+            np.save(str(folder / "mask" / f"{ref}{suffix}.npy"), masks_np[ref])
+
+
+def reconstruct_scan(model_or_ckpt, images, poses, intrinsics, names, pairs, scales, output_folder=None, rescale=1, crop=None, num_frames=10,
+                     glb=0.25, streams=3, write_depths=False, write=True, th=0.02, bgr=False, encode_batch=4, max_bytes=None,
+                     force_uncached=False, timings=None):
+    """A scan to its fused point cloud without leaving the device between the stages: ``ScanSession.depths`` -> ``fusion.fuse_depth_maps`` (view i
+    against ``pairs[i][:num_frames]``) -> ``fusion.point_cloud`` with the colours of ``fusion.color_grid``.  What ``inference_scan`` followed by
+    ``fusion.fusion`` on the session's prepared images computes, without the PFM round trip, the host resize and the float64 numpy tail: same
+    depth maps, masks and colours bit for bit, the points float32 roundings of the same fp64 arithmetic.  Arguments as ``inference_scan``;
+    ``rescale=(s1, s2)`` with s2 = 2 s1 runs two sessions one after the other, merges the two depth stacks (``multires.merge(th=th)``) and fuses
+    at the finer grid with the first session's images and cameras (no ``crop`` in that form).  ``write``: ``result.ply`` and ``mask/<i>.png`` under ``output_folder``;
+    ``write_depths``: also the PFMs of ``inference_scan``, same names.  One device->host copy brings the cloud, the masks and the averaged
+    depths back.  Returns ``fusion.fusion``'s dictionary (``xyz`` is float32 here)."""
+    from . import fusion as FU
+    from .inference import write_pfm
+    two_pass = isinstance(rescale, (tuple, list))
+    passes = [r for r in rescale] if two_pass else [rescale]
+    if two_pass and (len(passes) != 2 or passes[1] != 2 * passes[0]):
+        raise ValueError("reconstruct_scan: the two-pass form takes rescale=(s, 2 s)")
+    if two_pass and crop is not None:
+        raise ValueError("reconstruct_scan: the two-pass form takes no crop (the two passes would need windows that cover the same scene)")
+    M = len(images)
+    if len(names) != M or len(pairs) != M or len(scales) != M:
+        raise ValueError(f"reconstruct_scan: names, pairs and scales need one entry per image ({M})")
+    if (write or write_depths) and output_folder is None:
+        raise ValueError("reconstruct_scan: writing needs an output_folder")
+    if isinstance(model_or_ckpt, torch.nn.Module):
+        model = model_or_ckpt
+    else:
+        model = RAFT(test_mode=True).cuda()
+        if model_or_ckpt is not None:
+            model.load_state_dict(torch.load(model_or_ckpt, map_location="cpu"), strict=True)
+    core = model.module if hasattr(model, "module") and isinstance(getattr(model, "module"), RAFT) else model
+    was_training = core.training
+    n_streams = 1 if getattr(core, "view_group", None) is not None else max(1, int(streams))
+    t = {} if timings is None else timings
+    stacks, colors, Ks, Es = [], None, None, None
+    tic = time.perf_counter()
+    try:
+        for k, s in enumerate(passes):
+            sess = ScanSession(core, images, poses, intrinsics, rescale=s, crop=crop, streams=n_streams, encode_batch=encode_batch, max_bytes=max_bytes, bgr=bgr, force_uncached=force_uncached)
+            try:
+                stacks.append(sess.depths(pairs, scales, num_frames=num_frames))
+                if k == 0:
+                    # colours and cameras as fusion() derives them from the prepared images and their intrinsics, at the grid that is fused
+                    gh, gw = (sess.h * 2, sess.w * 2) if two_pass else (sess.h, sess.w)
+                    colors = FU.color_grid(sess.prepared, gh, gw)
+                    scale, flag, _, _, index = FU.depth_grid_geometry(sess.H, sess.W, gh, gw)
+                    Ks = torch.stack([FU.modify_camera_parameters(sess.intrinsics[i].clone().float(), scale, index, flag) for i in range(sess.M)])
+                    Es = sess.poses.clone().float()
+                    torch.cuda.current_stream(sess.device).synchronize()     # (the session's images go away with it)
+                if timings is not None:
+                    timings.update(sess.timings)
+                    timings["cached"] = bool(sess.cached)
+            finally:
+                sess.close()
+    finally:
+        if was_training:
+            core.train()
+    if two_pass:
+        from .multires import merge
+        if tuple(stacks[1].shape[1:]) != (colors.shape[2], colors.shape[3]):
+            raise ValueError("reconstruct_scan: the second pass's depth grid is not twice the first's")
+        depths = torch.stack([merge(stacks[0][i], stacks[1][i], th=th) for i in range(stacks[0].shape[0])])
+    else:
+        depths = stacks[0]
+    dev = depths.device
+    torch.cuda.current_stream(dev).synchronize()
+    stacks_np = [st.cpu().numpy() for st in stacks] if write_depths else []
+    del stacks                                              # (two-pass: the coarse and the fine stack are not needed behind the merge)
+    t["depths_s"] = time.perf_counter() - tic
+    tic = time.perf_counter()
+    fpairs = [(i, [int(j) for j in pairs[i]][:num_frames]) for i in range(M)]
+    masks, est, thre, hist = FU.fuse_depth_maps(depths, Ks, Es, fpairs, glb=glb)
+    t["fuse_s"] = time.perf_counter() - tic
+    tic = time.perf_counter()
+    xyz, rgb = FU.point_cloud(masks, est, Ks, Es, colors, [ref for ref, _ in fpairs])
+    xyz_np, rgb_np, masks_np, est_np = xyz.cpu().numpy(), rgb.cpu().numpy(), masks.cpu().numpy().astype(bool), est.cpu().numpy()
+    t["d2h_bytes"] = int(xyz.numel() * 4 + rgb.numel() + masks.numel() + est.numel() * 4) + sum(int(a.nbytes) for a in stacks_np)
+    if write or write_depths:
+        output_folder = Path(output_folder)
+        output_folder.mkdir(exist_ok=True, parents=True)
+    if write_depths:
+        (output_folder / "depths").mkdir(exist_ok=True, parents=True)
+        for k, s in enumerate(passes):
+            for i in range(M):
+                write_pfm(output_folder / "depths" / f"{names[i]}_scale{s}_nf{num_frames}.pfm", stacks_np[k][i])
+    if write:
+        _write_masks(output_folder, masks_np, [ref for ref, _ in fpairs])
+        FU.write_ply(str(output_folder / "result.ply"), xyz_np, rgb_np)
+    t["tail_s"] = time.perf_counter() - tic
+    return {"masks": masks_np, "depth_est": est_np, "xyz": xyz_np, "rgb": rgb_np, "threshold": thre, "history": hist}

@@ -520,6 +520,37 @@ int cer_image_prep_f32(const float* src, float* dst, int H0, int W0, int H2, int
  * [h * w][16]) that cer_cost_lines_f32 takes as fmap1_split.  16-byte loads and stores. */
 int cer_feat_ref_rows_f16(const void* slot, void* out, int h, int w, int border, void* stream);
 
+/* Point cloud of a fused scan (ABI 1100; csrc/cloud.hip, cer-mvs_amd/fusion.py point_cloud / color_grid): the host tail of the reference's
+ * fusion() (fusion.py:262-279) on the device.  masks [N, h, w] bytes (non-zero = set), depth_est [N, h, w], colors [N, 3, h, w] floats 0..1,
+ * cams [N, CER_CLOUD_CAM_DOUBLES] DOUBLES per view: K^-1 row-major [9] | rows 0-2 of E^-1 [12] | padding (the float32 inverses, promoted).
+ * `order` is HOST memory: the n_order views to emit, each in 0 .. N-1 (checked before anything is launched).  Output: the set pixels of
+ * view order[0] first, then order[1], ..., row-major inside a view (numpy's boolean-indexing order) - xyz [n, 3] floats =
+ * float(E^-1 (K^-1 (x d, y d, d), 1)), the products and sums in fp64, one rounding; rgb [n, 3] bytes = (uint8)(c * 255.0f), truncated.
+ * The order is a function of the masks alone: per-block counts from wave ballots, one 64-bit exclusive scan, ranks from ballot + mbcnt -
+ * no atomics, the same bytes on every run.
+ *   cer_cloud_partials: HOST function: the number of partial counts, n_order * ceil(h w / CER_CLOUD_TILE), that the workspaces hold:
+ *     partials [that many] unsigned, offsets [that many + 1] and view_base [n_order + 1] 64-bit.
+ *   cer_cloud_count_u8: count pass + scan.  view_base[k] = points in front of view order[k]; view_base[n_order] = n.  The caller reads
+ *     view_base once, allocates exactly n points and passes n as `total` and the allocation as `capacity`.
+ *   cer_cloud_emit_f32: the emit pass over the same masks, order and offsets.  Never writes at or beyond `capacity`.  CER_ESHAPE: total !=
+ *     capacity; capacity == 0: returns 0 and launches nothing (xyz and rgb may then be NULL).
+ * CER_EINVAL: null pointer, size <= 0, an `order` entry outside 0 .. N-1, negative total / capacity.  CER_ESHAPE: h w beyond 2^31 - 1. */
+#define CER_CLOUD_TILE 2048
+#define CER_CLOUD_CAM_DOUBLES 24
+long cer_cloud_partials(int n_order, int h, int w);
+int cer_cloud_count_u8(const unsigned char* masks, int N, int h, int w, const int* order, int n_order, unsigned int* partials,
+                       long long* offsets, long long* view_base, void* stream);
+int cer_cloud_emit_f32(const unsigned char* masks, const float* depth_est, const double* cams, const float* colors, int N, int h, int w,
+                       const int* order, int n_order, const long long* offsets, long long total, long long capacity, float* xyz,
+                       unsigned char* rgb, void* stream);
+/* Colour planes at the depth grid: prepared images [n, 3, H, W], values 0..255 -> colors [n, 3, h, w], values 0..1, for H = k h and W = k w
+ * with one integer k >= 1 (CER_ESHAPE otherwise; also for h or 3 n beyond 65535, which are grid dimensions).  Every tap is divided by 255 (IEEE float32 division), then resized as
+ * F.interpolate(bilinear, align_corners=False) does on the host (fusion._resize): ly0 * (lx0 a + lx1 b) + ly1 * (lx0 c + lx1 d), every
+ * product and sum rounded to float32, no fma.  At an integer ratio the weights are 0, 1/2 or 1 and the result is the host's bit for bit. */
+int cer_color_grid_f32(const float* prepared, float* colors, int n, int H, int W, int h, int w, void* stream);
+/* inference.disp_to_depth (reference: inference.py:57-58) on n floats: depth = disp == 0 ? 0 : 1 / disp, correctly rounded. */
+int cer_disp_to_depth_f32(const float* disp, float* depth, long n, void* stream);
+
 /* Multi-GPU row-slab exchange (cer-mvs_amd/slab.py): up to CER_COPY_MAX_SEG contiguous fp32 ranges copied by ONE launch -
  * the pack of a rank's (net, disp) border strips into its send buffer, and the refresh of its halo rows from the gathered
  * strips.  n[i] floats from src[i] to dst[i]; n[i] == 0 skips a segment.  Device pointers; ranges must not overlap. */
