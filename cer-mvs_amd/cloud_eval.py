@@ -1,0 +1,283 @@
+"""Cloud-to-cloud evaluation on the device (csrc/cloud_eval.hip): the exact nearest neighbour of every point of one cloud in
+another within a cut-off, and the two published protocols built on it - DTU's accuracy / completeness / overall (means of those distances)
+and Tanks-and-Temples' precision / recall / F-score (shares of them below a threshold).
+
+    from cer_mvs_amd.cloud_eval import accuracy_completeness, fscore
+    out = reconstruct_scan(model, ..., write=False)
+    pred = torch.from_numpy(out["xyz"]).cuda()
+    accuracy_completeness(pred, gt, max_dist=20.0, thin=0.2)      # {"accuracy", "completeness", "overall", "n_pred", ...}
+    fscore(pred, gt, tau=0.01)                                    # {"precision", "recall", "fscore", ...}
+
+Clouds are CUDA float32 tensors [n, 3]; there is no CPU fallback.  Sorting (``torch.sort(stable=True)``) and the reductions over the distance
+vector (fp64 ``sum`` / ``count_nonzero``) are torch; keys, the cell table, the record gather and the search are HIP kernels.  Everything is a
+pure function of its inputs: no atomics, the same bytes on every run.  Reading ground-truth files, observability masks and alignment
+transforms of the benchmarks is the caller's business (``keep_pred`` / ``keep_gt`` carry masks in)."""
+import ctypes
+import math
+
+import numpy as np
+import torch
+
+from . import _lib as L
+
+GRID_TILE = 2048                                             # cer_mvs.h CER_GRID_TILE
+GRID_COORD_LIMIT = 1 << 20                                   # cer_mvs.h CER_GRID_COORD_LIMIT
+# cloud_distances' default cell is max_dist / DEFAULT_CELL_DIVISOR.  The search cuts every row of cells to what can still beat the best
+# distance so far, so its work follows the distance to the neighbour, not max_dist; the cell size sets how many points come along with the
+# neighbour (one cell's worth at least) against how many cells an empty query must look up ((2 * divisor + 3)^2 rows).  Measured by
+# tools/bench_cloud_eval.py (profiles/cloud_eval_bench.json "cell_sweep").
+DEFAULT_CELL_DIVISOR = 4
+
+
+def _cloud(t, name):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"{name} must be a CUDA tensor (no CPU fallback)")
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError(f"{name}: points [n, 3] expected")
+    if t.dtype != torch.float32:
+        raise RuntimeError(f"{name} must be float32")
+    if t.shape[0] >= 1 << 31:
+        raise ValueError(f"{name}: fewer than 2^31 points expected")
+    return t.contiguous()
+
+
+def _cell(cell):
+    cell = float(cell)
+    if not (cell > 0.0 and math.isfinite(cell)):
+        raise ValueError("cell must be a positive finite number")
+    return cell
+
+
+class CloudIndex:
+    """Sparse uniform grid over ``points`` (CUDA float32 [n, 3]) with cell edge ``cell``: keys, one stable sort and the cell table, built once.
+    The grid's origin is the per-axis minimum of the finite points, promoted to fp64.  ``n``: the indexed (finite) points; points with a NaN
+    or infinite coordinate are never anybody's neighbour.  ``order``: original indices in sorted order (int64 [n_all]); ``cell_start``: first
+    sorted position of every occupied cell, int64 [cells + 1]."""
+
+    def __init__(self, points, cell):
+        points = _cloud(points, "points")
+        self.cell = _cell(cell)
+        self.points = points
+        dev = points.device
+        n_all = int(points.shape[0])
+        lib = L.load()
+        self.origin = (ctypes.c_double * 3)(0.0, 0.0, 0.0)
+        self.n, self.cells = 0, 0
+        self.records = self.cell_keys = None
+        self.order = torch.empty(0, device=dev, dtype=torch.int64)
+        self.cell_start = torch.zeros(1, device=dev, dtype=torch.int64)
+        if n_all == 0:
+            return
+        finite = torch.isfinite(points).all(1, keepdim=True)
+        lo = torch.where(finite, points, points.new_full((), float("inf"))).amin(0).double().cpu()      # (read 1: the origin travels as an argument)
+        if not bool(torch.isfinite(lo).all()):
+            self.order = torch.arange(n_all, device=dev)
+            return                                           # no finite point: an empty index
+        self.origin = (ctypes.c_double * 3)(*[float(v) for v in lo])
+        keys = torch.empty(n_all, device=dev, dtype=torch.int64)
+        flag = torch.empty(1, device=dev, dtype=torch.int32)
+        rc = lib.cer_grid_keys_f32(L.dev_ptr(points, "points"), n_all, self.origin, self.cell, 0, L.dev_ptr(keys, "keys", torch.int64),
+                                   L.dev_ptr(flag, "flag", torch.int32), L.cur_stream())
+        if rc == -2:
+            raise ValueError(f"CloudIndex: the cloud spans more than 2^20 cells of {self.cell} along an axis; use a larger cell")
+        L.check(rc, "grid_keys")
+        keys, self.order = torch.sort(keys, stable=True)
+        P = int(lib.cer_grid_partials(n_all))
+        partials = torch.empty(P, device=dev, dtype=torch.int32)
+        offsets = torch.empty(P + 1, device=dev, dtype=torch.int64)
+        totals = torch.empty(2, device=dev, dtype=torch.int64)
+        pk = L.dev_ptr(keys, "keys", torch.int64)
+        L.check(lib.cer_grid_cells_count_i64(pk, n_all, L.dev_ptr(partials, "partials", torch.int32), L.dev_ptr(offsets, "offsets", torch.int64),
+                                             L.dev_ptr(totals, "totals", torch.int64), L.cur_stream()), "grid_cells_count")
+        self.cells, self.n = (int(v) for v in totals.cpu())                                              # (read 2: sizes the cell table)
+        self.cell_keys = torch.empty(self.cells, device=dev, dtype=torch.int64)
+        self.cell_start = torch.empty(self.cells + 1, device=dev, dtype=torch.int64)
+        L.check(lib.cer_grid_cells_i64(pk, n_all, L.dev_ptr(offsets, "offsets", torch.int64), self.cells,
+                                       L.dev_ptr(self.cell_keys, "cell_keys", torch.int64), L.dev_ptr(self.cell_start, "cell_start", torch.int64),
+                                       L.cur_stream()), "grid_cells")
+        self.records = torch.empty(n_all, 4, device=dev, dtype=torch.int32)
+        L.check(lib.cer_grid_pack_f32(L.dev_ptr(points, "points"), L.dev_ptr(self.order, "order", torch.int64), n_all,
+                                      L.dev_ptr(self.records, "records", torch.int32), L.cur_stream()), "grid_pack")
+
+    def heads(self):
+        """Original index of the first sorted point of every occupied cell - the lowest index in the cell, as the sort is stable."""
+        return self.order[self.cell_start[:self.cells]]
+
+    def nearest(self, queries, max_dist, sort_queries=True):
+        """-> (dist float32 [m], idx int64 [m]) in the queries' order: the indexed point with the smallest (d2, index), d2 = (dx*dx + dy*dy) +
+        dz*dz in fp64, among those with d2 <= double(max_dist)^2; dist = float32(sqrt(d2)); (inf, -1) where there is none or the query is
+        not finite.  ``sort_queries``: walk the queries in the order of their own cells (faster; the result is the same)."""
+        queries = _cloud(queries, "queries")
+        max_dist = float(np.float32(max_dist))
+        if not max_dist >= 0.0:
+            raise ValueError("max_dist must be >= 0")
+        m, dev = int(queries.shape[0]), queries.device
+        if m == 0 or self.n == 0:                            # (the entry point launches nothing for an empty side)
+            return torch.full((m,), float("inf"), device=dev, dtype=torch.float32), torch.full((m,), -1, device=dev, dtype=torch.int64)
+        dist = torch.empty(m, device=dev, dtype=torch.float32)
+        idx = torch.empty(m, device=dev, dtype=torch.int64)
+        lib = L.load()
+        qorder = None
+        if sort_queries:
+            qkeys = torch.empty(m, device=dev, dtype=torch.int64)
+            L.check(lib.cer_grid_keys_f32(L.dev_ptr(queries, "queries"), m, self.origin, self.cell, 1, L.dev_ptr(qkeys, "keys", torch.int64), None,
+                                          L.cur_stream()), "grid_keys")
+            qorder = torch.sort(qkeys, stable=True).indices
+        rc = lib.cer_grid_nearest_f32(L.dev_ptr(self.records, "records", torch.int32), self.n, L.dev_ptr(self.cell_keys, "cell_keys", torch.int64),
+                                      L.dev_ptr(self.cell_start, "cell_start", torch.int64), self.cells, self.origin, self.cell,
+                                      L.dev_ptr(queries, "queries"), L.dev_ptr(qorder, "qorder", torch.int64), m, max_dist,
+                                      L.dev_ptr(idx, "idx", torch.int64), L.dev_ptr(dist, "dist"), L.cur_stream())
+        if rc == -2:
+            raise ValueError(f"nearest: max_dist {max_dist} is more than 4096 cells of {self.cell}; index the cloud with a larger cell")
+        L.check(rc, "grid_nearest")
+        return dist, idx
+
+
+def voxel_downsample(points, cell):
+    """Indices (int64, ascending) of the lowest-index point of every occupied cell of a grid with edge ``cell`` whose origin is the cloud's
+    per-axis minimum: a VOXEL thinning - deterministic, a pure function of the input.  It is NOT the greedy radius thinning of the DTU MATLAB
+    script (which keeps a point unless an earlier kept point lies within the radius, and so depends on the order of the points): kept points
+    of neighbouring cells may be closer than ``cell``, and no two kept points share a cell.  Points with a non-finite coordinate are dropped."""
+    index = CloudIndex(points, cell)
+    return torch.sort(index.heads()).values
+
+
+def cloud_distances(src, dst, max_dist, cell=None):
+    """float32 [len(src)]: the distance from every ``src`` point to its nearest ``dst`` point within ``max_dist`` (inf where there is none).
+    ``cell`` defaults to ``max_dist / 4`` (DEFAULT_CELL_DIVISOR: measured)."""
+    cell = float(max_dist) / DEFAULT_CELL_DIVISOR if cell is None else cell
+    return CloudIndex(dst, cell).nearest(src, max_dist)[0]
+
+
+def _is_tensor(d):
+    return isinstance(d, torch.Tensor)
+
+
+def _f64(d):
+    return d.double() if _is_tensor(d) else np.asarray(d).astype(np.float64)
+
+
+def _count(mask):
+    return int(torch.count_nonzero(mask)) if _is_tensor(mask) else int(np.count_nonzero(mask))
+
+
+def _mean_below(d, bound):
+    """(mean of the entries < bound - nan if there are none, their count); d is fp64, so the comparison is with ``bound`` itself, not with
+    its float32 rounding"""
+    inside = d < bound
+    k = _count(inside)
+    s = float((torch.where(inside, d, torch.zeros_like(d)) if _is_tensor(d) else np.where(inside, d, 0.0)).sum())
+    return (s / k if k else float("nan")), k
+
+
+def metrics_from_distances(d_pred, d_gt, max_dist, tau=None):
+    """The arithmetic of both protocols on two distance vectors (numpy arrays or tensors; d_pred: predicted -> ground truth, d_gt: the other
+    way).  accuracy = mean of d_pred over d_pred < max_dist, completeness = the same of d_gt, overall = their mean (nan where a mean has no
+    entries); with ``tau``: precision = share of d_pred < tau, recall = share of d_gt < tau (0 for an empty vector), fscore = their harmonic
+    mean, 0 when both are 0.  The distances are promoted to fp64 first: comparisons, sums and counts are fp64."""
+    d_pred, d_gt = _f64(d_pred), _f64(d_gt)
+    acc, n_pred_in = _mean_below(d_pred, max_dist)
+    comp, n_gt_in = _mean_below(d_gt, max_dist)
+    out = {"accuracy": acc, "completeness": comp, "overall": 0.5 * (acc + comp), "n_pred": int(len(d_pred)), "n_gt": int(len(d_gt)),
+           "n_pred_in": n_pred_in, "n_gt_in": n_gt_in}
+    if tau is not None:
+        p = _count(d_pred < tau) / len(d_pred) if len(d_pred) else 0.0
+        r = _count(d_gt < tau) / len(d_gt) if len(d_gt) else 0.0
+        out.update(precision=p, recall=r, fscore=2.0 * p * r / (p + r) if p + r > 0.0 else 0.0, tau=float(tau))
+    return out
+
+
+def _keep(points, keep, name):
+    if keep is None:
+        return None
+    keep = torch.as_tensor(keep, device=points.device)
+    if keep.dtype != torch.bool or tuple(keep.shape) != (points.shape[0],):
+        raise ValueError(f"{name}: a boolean mask with one entry per point expected")
+    return keep
+
+
+def accuracy_completeness(pred, gt, max_dist=20.0, thin=None, keep_pred=None, keep_gt=None, cell=None):
+    """The DTU protocol.  ``pred`` is first thinned with ``voxel_downsample(pred, thin)`` if ``thin`` is given (a voxel thinning, not the MATLAB
+    script's greedy one).  accuracy = mean distance pred -> gt over the points with d < max_dist, completeness = the same gt -> pred, overall =
+    their mean.  ``keep_pred`` / ``keep_gt``: optional boolean masks (one entry per point of ``pred`` as passed in / of ``gt``) selecting
+    which points enter the two means - where a caller applies DTU's observability mask and ground plane; every point still serves as a
+    neighbour.  -> {"accuracy", "completeness", "overall", "n_pred", "n_gt", "n_pred_in", "n_gt_in"}: n_pred / n_gt are the points that were
+    measured (after thinning and masks), n_*_in those within max_dist."""
+    pred, gt = _cloud(pred, "pred"), _cloud(gt, "gt")
+    kp, kg = _keep(pred, keep_pred, "keep_pred"), _keep(gt, keep_gt, "keep_gt")
+    if thin is not None:
+        sel = voxel_downsample(pred, thin)
+        pred = pred.index_select(0, sel)
+        kp = kp.index_select(0, sel) if kp is not None else None
+    cell = float(max_dist) / DEFAULT_CELL_DIVISOR if cell is None else cell
+    d_pred = CloudIndex(gt, cell).nearest(pred, max_dist)[0]
+    d_gt = CloudIndex(pred, cell).nearest(gt, max_dist)[0]
+    if kp is not None:
+        d_pred = d_pred[kp]
+    if kg is not None:
+        d_gt = d_gt[kg]
+    return metrics_from_distances(d_pred, d_gt, max_dist)
+
+
+def fscore(pred, gt, tau, cell=None):
+    """The Tanks-and-Temples protocol: precision = share of ``pred`` within ``tau`` of ``gt`` (d < tau), recall = share of ``gt`` within ``tau``
+    of ``pred``, fscore = their harmonic mean (0 when both are 0).  -> {"precision", "recall", "fscore", "tau", "n_pred", "n_gt"}."""
+    pred, gt = _cloud(pred, "pred"), _cloud(gt, "gt")
+    tau32 = float(np.float32(tau))
+    cut = float(np.nextafter(np.float32(tau32), np.float32(np.inf))) if tau32 < float(tau) else tau32      # a float32 cut-off that is not below tau
+    d_pred = cloud_distances(pred, gt, cut, cell)
+    d_gt = cloud_distances(gt, pred, cut, cell)
+    m = metrics_from_distances(d_pred, d_gt, cut, tau=tau)
+    return {k: m[k] for k in ("precision", "recall", "fscore", "tau", "n_pred", "n_gt")}
+
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "<i2", "int16": "<i2", "ushort": "<u2", "uint16": "<u2",
+              "int": "<i4", "int32": "<i4", "uint": "<u4", "uint32": "<u4", "float": "<f4", "float32": "<f4", "double": "<f8", "float64": "<f8"}
+
+
+def read_ply(path):
+    """-> (xyz float32 [n, 3], rgb uint8 [n, 3] or None): the vertex element of a binary little-endian PLY whose vertex properties are scalars
+    in any order (what ``fusion.write_ply`` writes; extra properties are skipped).  x, y, z must be float, red / green / blue (if all three
+    are there) uchar.  ASCII and big-endian files raise ValueError naming the format."""
+    with open(path, "rb") as f:
+        raw = f.read()
+    end = raw.find(b"end_header\n")
+    if not raw.startswith(b"ply") or end < 0:
+        raise ValueError(f"{path}: not a PLY file")
+    lines = raw[:end].decode("ascii").split("\n")
+    fmt = next((ln.split()[1] for ln in lines if ln.startswith("format ")), None)
+    if fmt != "binary_little_endian":
+        raise ValueError(f"{path}: PLY format {fmt!r} is not supported, only binary_little_endian")
+    n, fields, element, offset = 0, [], None, 0
+    for ln in lines:
+        tok = ln.split()
+        if not tok:
+            continue
+        if tok[0] == "element":
+            if element == "vertex":
+                break                                        # the vertex element is read only if it comes first (it does in every MVS cloud)
+            element = tok[1]
+            if element != "vertex":
+                raise ValueError(f"{path}: element {element!r} in front of the vertices is not supported")
+            n = int(tok[2])
+        elif tok[0] == "property" and element == "vertex":
+            if tok[1] == "list" or tok[1] not in _PLY_TYPES:
+                raise ValueError(f"{path}: vertex property {ln!r} is not supported")
+            fields.append((tok[2], _PLY_TYPES[tok[1]]))
+    names = [k for k, _ in fields]
+    if len(set(names)) != len(names) or not all(k in names for k in "xyz"):
+        raise ValueError(f"{path}: vertex properties x, y, z expected once each")
+    dt = np.dtype(fields)
+    body = raw[end + len(b"end_header\n"):]
+    if len(body) < n * dt.itemsize:
+        raise ValueError(f"{path}: {n} vertices of {dt.itemsize} bytes expected, {len(body)} bytes found")
+    v = np.frombuffer(body, dtype=dt, count=n, offset=offset)
+    if any(dt[k] != np.dtype("<f4") for k in "xyz"):
+        raise ValueError(f"{path}: float x, y, z expected")
+    xyz = np.stack([v["x"], v["y"], v["z"]], 1) if n else np.zeros((0, 3), np.float32)
+    rgb = None
+    if all(k in names for k in ("red", "green", "blue")):
+        if any(dt[k] != np.dtype("u1") for k in ("red", "green", "blue")):
+            raise ValueError(f"{path}: uchar red, green, blue expected")
+        rgb = np.stack([v["red"], v["green"], v["blue"]], 1) if n else np.zeros((0, 3), np.uint8)
+    return np.ascontiguousarray(xyz, dtype=np.float32), rgb

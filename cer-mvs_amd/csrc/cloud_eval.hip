@@ -1,0 +1,358 @@
+// Cloud-to-cloud evaluation on the device (cer-mvs_amd/cloud_eval.py): the exact nearest neighbour of every query point in a target cloud
+// within a cut-off distance - what DTU's accuracy / completeness and Tanks-and-Temples' precision / recall / F-score are means and shares of.
+//
+// The target is indexed by a sparse uniform grid that exists only as sorted keys: cer_grid_keys_f32 gives every point the 63-bit key of its
+// cell, the host sorts the keys (stable) and cer_grid_pack_f32 gathers the points into that order as 16-byte records (x, y, z, original index),
+// cer_grid_cells_count_i64 / cer_grid_cells_i64 list the occupied cells with their first sorted point (cloud.hip's idiom: flags counted per
+// block with wave ballots, one block scans, ranks from ballot + mbcnt), and cer_grid_nearest_f32 searches.  No atomics anywhere: the same
+// bytes on every run.
+//
+// Key layout: (z + B) << 42 | (y + B) << 21 | (x + B), B = CER_GRID_COORD_LIMIT - 1, cell coordinates in -B .. B: every field is at most
+// 2^21 - 2, so no key reaches the sentinel (2^63 - 1, all 63 bits set) and key(x + 1, y, z) = key(x, y, z) + 1 never carries.  x is the
+// lowest field: the cells x0 .. x1 of one (y, z) row are a contiguous run of the cell table and their points a contiguous run of the
+// sorted points, found with two binary searches.
+#include "common.hpp"
+
+#define GRID_TILE CER_GRID_TILE                      // sorted keys per block of the cell passes
+#define GRID_ITER (GRID_TILE / 256)
+#define GRID_B (CER_GRID_COORD_LIMIT - 1)
+#define GRID_SENTINEL 0x7fffffffffffffffLL
+#define GRID_MAX_RINGS 4096                          // ceil(max_dist / cell) beyond this: CER_ESHAPE (the cell is far too small for the cut-off)
+
+__device__ __forceinline__ unsigned grid_rank(unsigned long long ballot) {      // set lanes below this one
+    return __builtin_amdgcn_mbcnt_hi((unsigned)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)ballot, 0u));
+}
+__device__ __forceinline__ long long grid_key(int x, int y, int z) {
+    return ((long long)(z + GRID_B) << 42) | ((long long)(y + GRID_B) << 21) | (long long)(x + GRID_B);
+}
+__device__ __forceinline__ bool grid_finite(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
+
+// ---- keys.  u = (double(p) - origin) / cell with an IEEE fp64 division, c = floor(u).  clamp: coordinates are clamped into -B .. B (the
+// query side: its keys only order the queries, the search never reads them); otherwise a coordinate outside raises *flag (every thread that
+// sees one stores the same 1: a plain store, no atomic) and the point takes the sentinel.
+__global__ __launch_bounds__(256) void grid_keys_kernel(const float* __restrict__ pts, long n, double ox, double oy, double oz, double cell,
+                                                        int clamp, long long* __restrict__ keys, int* __restrict__ flag) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
+    long long key = GRID_SENTINEL;
+    if (grid_finite(x, y, z)) {
+        double cx = floor(((double)x - ox) / cell), cy = floor(((double)y - oy) / cell), cz = floor(((double)z - oz) / cell);
+        const double B = (double)GRID_B;
+        if (clamp) {
+            cx = fmin(fmax(cx, -B), B);
+            cy = fmin(fmax(cy, -B), B);
+            cz = fmin(fmax(cz, -B), B);
+        }
+        if (fabs(cx) <= B && fabs(cy) <= B && fabs(cz) <= B)
+            key = grid_key((int)cx, (int)cy, (int)cz);
+        else
+            *flag = 1;
+    }
+    keys[i] = key;
+}
+
+// ---- pack: rec[i] = (x, y, z, order[i]) of point order[i] - 16 bytes, one load per candidate in the search
+__global__ __launch_bounds__(256) void grid_pack_kernel(const float* __restrict__ pts, const long long* __restrict__ order, long n,
+                                                        uint4* __restrict__ rec) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const long long j = order[i];
+    rec[i] = make_uint4(__float_as_uint(pts[3 * j]), __float_as_uint(pts[3 * j + 1]), __float_as_uint(pts[3 * j + 2]), (unsigned)j);
+}
+
+// ---- cells.  A head is a sorted position whose key is not the sentinel and differs from its predecessor's.
+__device__ __forceinline__ bool grid_head(const long long* __restrict__ keys, long n, long i) {
+    if (i >= n) return false;
+    const long long k = keys[i];
+    return k != GRID_SENTINEL && (i == 0 || keys[i - 1] != k);
+}
+
+__global__ __launch_bounds__(256) void grid_count_kernel(const long long* __restrict__ keys, long n, unsigned* __restrict__ partials) {
+    __shared__ unsigned wave_cnt[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long seg = (long)blockIdx.x * GRID_TILE + wave * (GRID_TILE / 4) + lane;
+    unsigned tot = 0;
+#pragma unroll
+    for (int j = 0; j < GRID_ITER; ++j) tot += (unsigned)__popcll(__ballot(grid_head(keys, n, seg + 64 * j)));
+    if (lane == 0) wave_cnt[wave] = tot;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[blockIdx.x] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+}
+
+// one block: offsets[i] = sum of partials[0 .. i), offsets[np] = totals[0] = the number of cells; totals[1] = the number of keys below the
+// sentinel (the first sentinel's position in the sorted keys: a binary search by one thread)
+__global__ __launch_bounds__(1024) void grid_scan_kernel(const unsigned* __restrict__ partials, long np, const long long* __restrict__ keys, long n,
+                                                         long long* __restrict__ offsets, long long* __restrict__ totals) {
+    __shared__ long long wave_tot[16];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    long long carry = 0;
+    for (long c0 = 0; c0 < np; c0 += 1024) {
+        const long i = c0 + t;
+        const long long s = i < np ? (long long)partials[i] : 0;
+        long long inc = s;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const long long v = __shfl_up(inc, d);
+            if (lane >= d) inc += v;
+        }
+        if (lane == 63) wave_tot[wave] = inc;
+        __syncthreads();
+        long long below = 0, all = 0;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const long long v = wave_tot[k];
+            below += k < wave ? v : 0;
+            all += v;
+        }
+        if (i < np) offsets[i] = carry + below + inc - s;
+        carry += all;
+        __syncthreads();                             // (wave_tot is rewritten by the next chunk)
+    }
+    if (t == 0) {
+        offsets[np] = carry;
+        totals[0] = carry;
+        long lo = 0, hi = n;
+        while (lo < hi) {
+            const long mid = lo + (hi - lo) / 2;
+            if (keys[mid] < GRID_SENTINEL) lo = mid + 1; else hi = mid;
+        }
+        totals[1] = lo;
+    }
+}
+
+// cell_keys[r] = key and cell_start[r] = sorted position of head r; cell_start[ncells] = the number of keys below the sentinel
+__global__ __launch_bounds__(256) void grid_emit_kernel(const long long* __restrict__ keys, long n, const long long* __restrict__ offsets,
+                                                        long long ncells, long long* __restrict__ cell_keys, long long* __restrict__ cell_start) {
+    __shared__ unsigned wave_cnt[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long seg = (long)blockIdx.x * GRID_TILE + wave * (GRID_TILE / 4) + lane;
+    unsigned long long bal[GRID_ITER];
+    unsigned tot = 0;
+#pragma unroll
+    for (int j = 0; j < GRID_ITER; ++j) {
+        bal[j] = __ballot(grid_head(keys, n, seg + 64 * j));
+        tot += (unsigned)__popcll(bal[j]);
+    }
+    if (lane == 0) wave_cnt[wave] = tot;
+    __syncthreads();
+    long long base = offsets[blockIdx.x];
+    for (int i = 0; i < wave; ++i) base += wave_cnt[i];
+#pragma unroll
+    for (int j = 0; j < GRID_ITER; ++j) {
+        const long p = seg + 64 * j;
+        const long long r = base + grid_rank(bal[j]);
+        base += __popcll(bal[j]);
+        if (p < n) {
+            const long long k = keys[p];
+            if (k != GRID_SENTINEL && (p == n - 1 || keys[p + 1] == GRID_SENTINEL)) cell_start[ncells] = p + 1;      // the last real key: one thread
+        }
+        if (!((bal[j] >> lane) & 1ull) || r >= ncells) continue;                 // (never past what the caller allocated)
+        cell_keys[r] = keys[p];
+        cell_start[r] = p;
+    }
+}
+
+// ---- nearest.  One thread per query, the queries in the order of their own cell keys (qorder), so that the lanes of a wave walk the same
+// cells at the same pace: their record loads hit the same cache lines.  Exactness does not rest on the key arithmetic: a cell is skipped
+// only when the TRUE bounds of the points it can hold prove that none of them can win.  A target point in cell c of an axis has a computed
+// u in [c, c + 1); u carries two fp64 roundings (relative 2^-52 of a magnitude below 2^21 + GRID_MAX_RINGS: absolute below 2e-9 cells), and so
+// does the query's.  The per-axis gap between the query and any point of the cell is therefore at least (c - uq - GRID_EPS) cells above the
+// query, (uq - (c + 1) - GRID_EPS) cells below it, with GRID_EPS = 1e-6 hundreds of times that error.  Rows and cells whose gap exceeds the
+// best distance so far are skipped (strictly: a tie on d2 with a lower index must still be seen); the enumeration itself covers
+// ceil(max_dist / cell) + 1 rings, one more than the mathematics needs.
+#define GRID_EPS 1e-6
+
+__device__ __forceinline__ long grid_lower_bound(const long long* __restrict__ a, long lo, long hi, long long k) {     // first i in [lo, hi) with a[i] >= k
+    while (lo < hi) {
+        const long mid = lo + (hi - lo) / 2;
+        if (a[mid] < k) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+struct GridBest {
+    double d2;
+    int idx;
+};
+
+// candidates: the points of cells xa .. xb of row (y, z); winner = smallest (d2, original index), a candidate counts iff d2 <= the limit
+// (best starts at (limit, INT_MAX))
+__device__ __forceinline__ void grid_scan_row(const uint4* __restrict__ rec, const long long* __restrict__ cell_keys,
+                                              const long long* __restrict__ cell_start, long ncells, int xa, int xb, int y, int z, double X,
+                                              double Y, double Z, GridBest& best) {
+    const long long ka = grid_key(xa, y, z), kb = grid_key(xb, y, z) + 1;
+    const long a = grid_lower_bound(cell_keys, 0, ncells, ka);
+    if (a == ncells || cell_keys[a] >= kb) return;
+    const long b = grid_lower_bound(cell_keys, a + 1, ncells, kb);
+    const long long pe = cell_start[b];
+    for (long long j = cell_start[a]; j < pe; ++j) {
+        const uint4 t = rec[j];
+        const double dx = (double)__uint_as_float(t.x) - X, dy = (double)__uint_as_float(t.y) - Y, dz = (double)__uint_as_float(t.z) - Z;
+        const double d2 = (dx * dx + dy * dy) + dz * dz;
+        const int id = (int)t.w;
+        if (d2 < best.d2 || (d2 == best.d2 && id < best.idx)) {
+            best.d2 = d2;
+            best.idx = id;
+        }
+    }
+}
+
+// gap, in cells, between coordinate u and the points of cell c of that axis (0 when u is inside)
+__device__ __forceinline__ double grid_gap(double u, double c) {
+    const double g = u < c ? c - u - GRID_EPS : u - (c + 1.0) - GRID_EPS;
+    return g > 0.0 ? g : 0.0;
+}
+
+__global__ __launch_bounds__(256) void grid_nearest_kernel(const uint4* __restrict__ rec, const long long* __restrict__ cell_keys,
+                                                           const long long* __restrict__ cell_start, long ncells, double ox, double oy, double oz,
+                                                           double cell, const float* __restrict__ queries, const long long* __restrict__ qorder,
+                                                           long m, float max_dist, int rings, long long* __restrict__ idx,
+                                                           float* __restrict__ dist) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= m) return;
+    const long long q = qorder ? qorder[i] : i;
+    const float qx = queries[3 * q], qy = queries[3 * q + 1], qz = queries[3 * q + 2];
+    const double limit = (double)max_dist * (double)max_dist;
+    GridBest best = {limit, 0x7fffffff};
+    if (grid_finite(qx, qy, qz)) {
+        const double X = (double)qx, Y = (double)qy, Z = (double)qz;
+        const double ux = (X - ox) / cell, uy = (Y - oy) / cell, uz = (Z - oz) / cell;
+        const double fx = floor(ux), fy = floor(uy), fz = floor(uz), B = (double)GRID_B, R = (double)rings;
+        // cells to enumerate per axis (doubles: a query may lie anywhere), empty when the query is farther than the rings from the key range
+        const double xlo = fmax(fx - R, -B), xhi = fmin(fx + R, B), ylo = fmax(fy - R, -B), yhi = fmin(fy + R, B);
+        const double zlo = fmax(fz - R, -B), zhi = fmin(fz + R, B);
+        if (xlo <= xhi && ylo <= yhi && zlo <= zhi) {
+            const int cy = (int)fmin(fmax(fy, -B), B), cz = (int)fmin(fmax(fz, -B), B);
+            // the query's own cell first: in a dense cloud it holds the winner, and every row after it is cut to the cells that can still beat it
+            const bool home = fabs(fx) <= B && fabs(fy) <= B && fabs(fz) <= B;
+            if (home) grid_scan_row(rec, cell_keys, cell_start, ncells, (int)fx, (int)fx, cy, cz, X, Y, Z, best);
+            for (int iz = 0; iz <= 2 * rings; ++iz) {                            // 0, +1, -1, +2, -2, ...: near rows first
+                const int z = cz + ((iz & 1) ? (iz + 1) / 2 : -(iz / 2));
+                if ((double)z < zlo || (double)z > zhi) continue;
+                const double gz = grid_gap(uz, (double)z) * cell, gz2 = gz * gz;
+                if (gz2 > best.d2) continue;
+                for (int iy = 0; iy <= 2 * rings; ++iy) {
+                    const int y = cy + ((iy & 1) ? (iy + 1) / 2 : -(iy / 2));
+                    if ((double)y < ylo || (double)y > yhi) continue;
+                    const double gy = grid_gap(uy, (double)y) * cell, g2 = gz2 + gy * gy;
+                    if (g2 > best.d2) continue;
+                    // cells of the row whose gap along x can be within sqrt(best - g2): c + 1 > ux - e and c <= ux + e, e padded by 1e-3 cells
+                    const double e = __builtin_sqrt(best.d2 - g2) / cell + 1e-3;
+                    const double xa = fmax(floor(ux - e), xlo), xb = fmin(floor(ux + e), xhi);
+                    if (xa > xb) continue;
+                    if (home && iz == 0 && iy == 0) {                            // the query's own row: its own cell is done
+                        if (xa < fx) grid_scan_row(rec, cell_keys, cell_start, ncells, (int)xa, (int)fx - 1, y, z, X, Y, Z, best);
+                        if (xb > fx) grid_scan_row(rec, cell_keys, cell_start, ncells, (int)fx + 1, (int)xb, y, z, X, Y, Z, best);
+                        continue;
+                    }
+                    grid_scan_row(rec, cell_keys, cell_start, ncells, (int)xa, (int)xb, y, z, X, Y, Z, best);
+                }
+            }
+        }
+    }
+    const bool found = best.idx != 0x7fffffff;
+    idx[q] = found ? (long long)best.idx : -1;
+    dist[q] = found ? (float)__builtin_sqrt(best.d2) : __builtin_inff();
+}
+
+// ---- entry points.  Sizes: negative -> CER_EINVAL, 2^31 and beyond -> CER_ESHAPE, zero -> nothing to do (CER_OK, nothing launched, before
+// the pointers are looked at); then null pointers -> CER_EINVAL.
+static int grid_size_check(long n) {
+    if (n < 0) return CER_EINVAL;
+    if (n >= 0x80000000L) return CER_ESHAPE;
+    return CER_OK;
+}
+static bool grid_is_finite(double v) { return v - v == 0.0; }
+static bool grid_frame_ok(const double* origin, double cell) {
+    return origin && grid_is_finite(origin[0]) && grid_is_finite(origin[1]) && grid_is_finite(origin[2]) && grid_is_finite(cell) && cell > 0.0;
+}
+static unsigned grid_blocks(long n, long per) { return (unsigned)((n + per - 1) / per); }
+
+extern "C" long cer_grid_partials(long n) {
+    if (n < 0) return CER_EINVAL;
+    if (n >= 0x80000000L) return CER_ESHAPE;
+    return (n + GRID_TILE - 1) / GRID_TILE;
+}
+
+extern "C" int cer_grid_keys_f32(const float* points, long n, const double* origin, double cell, int clamp, long long* keys, int* flag,
+                                 void* stream) {
+    const int rc = grid_size_check(n);
+    if (rc != CER_OK) return rc;
+    if (!grid_frame_ok(origin, cell)) return CER_EINVAL;
+    if (n == 0) return CER_OK;
+    if (!points || !keys || (!clamp && !flag)) return CER_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    if (!clamp && hipMemsetAsync(flag, 0, sizeof(int), st) != hipSuccess) return (int)hipGetLastError();
+    hipLaunchKernelGGL(grid_keys_kernel, dim3(grid_blocks(n, 256)), dim3(256), 0, st, points, n, origin[0], origin[1], origin[2], cell, clamp, keys,
+                       flag);
+    CER_RETURN_IF_LAUNCH_FAILED();
+    if (!clamp) {                                    // the one answer this call owes its caller: was every cell coordinate inside the key range
+        int raised = 0;
+        hipError_t e = hipMemcpyAsync(&raised, flag, sizeof(int), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) return (int)e;
+        if (raised) return CER_ESHAPE;
+    }
+    return CER_OK;
+}
+
+extern "C" int cer_grid_pack_f32(const float* points, const long long* order, long n, void* records, void* stream) {
+    const int rc = grid_size_check(n);
+    if (rc != CER_OK) return rc;
+    if (n == 0) return CER_OK;
+    if (!points || !order || !records) return CER_EINVAL;
+    if ((uintptr_t)records & 15) return CER_EALIGN;
+    hipLaunchKernelGGL(grid_pack_kernel, dim3(grid_blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, points, order, n, (uint4*)records);
+    CER_RETURN_IF_LAUNCH_FAILED();
+    return CER_OK;
+}
+
+extern "C" int cer_grid_cells_count_i64(const long long* keys, long n, unsigned int* partials, long long* offsets, long long* totals,
+                                        void* stream) {
+    const int rc = grid_size_check(n);
+    if (rc != CER_OK) return rc;
+    if (n == 0) return CER_OK;
+    if (!keys || !partials || !offsets || !totals) return CER_EINVAL;
+    const long np = (n + GRID_TILE - 1) / GRID_TILE;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(grid_count_kernel, dim3((unsigned)np), dim3(256), 0, st, keys, n, partials);
+    CER_RETURN_IF_LAUNCH_FAILED();
+    hipLaunchKernelGGL(grid_scan_kernel, dim3(1), dim3(1024), 0, st, partials, np, keys, n, offsets, totals);
+    CER_RETURN_IF_LAUNCH_FAILED();
+    return CER_OK;
+}
+
+extern "C" int cer_grid_cells_i64(const long long* keys, long n, const long long* offsets, long long ncells, long long* cell_keys,
+                                  long long* cell_start, void* stream) {
+    const int rc = grid_size_check(n);
+    if (rc != CER_OK) return rc;
+    if (ncells < 0) return CER_EINVAL;
+    if (ncells > n) return CER_ESHAPE;               // more cells than points: not what the count pass found
+    if (n == 0 || ncells == 0) return CER_OK;        // (no real key: cell_start[0] is the caller's to zero)
+    if (!keys || !offsets || !cell_keys || !cell_start) return CER_EINVAL;
+    hipLaunchKernelGGL(grid_emit_kernel, dim3(grid_blocks(n, GRID_TILE)), dim3(256), 0, (hipStream_t)stream, keys, n, offsets, ncells, cell_keys,
+                       cell_start);
+    CER_RETURN_IF_LAUNCH_FAILED();
+    return CER_OK;
+}
+
+extern "C" int cer_grid_nearest_f32(const void* records, long n, const long long* cell_keys, const long long* cell_start, long ncells,
+                                    const double* origin, double cell, const float* queries, const long long* qorder, long m, float max_dist,
+                                    long long* idx, float* dist, void* stream) {
+    int rc = grid_size_check(n);
+    if (rc == CER_OK) rc = grid_size_check(m);
+    if (rc == CER_OK) rc = grid_size_check(ncells);
+    if (rc != CER_OK) return rc;
+    if (!grid_frame_ok(origin, cell) || !(max_dist >= 0.0f)) return CER_EINVAL;
+    if (ncells > n) return CER_ESHAPE;
+    const double rings = ceil((double)max_dist / cell);
+    if (!(rings <= (double)GRID_MAX_RINGS)) return CER_ESHAPE;
+    if (m == 0 || n == 0 || ncells == 0) return CER_OK;      // (an empty target: the caller fills idx = -1, dist = +inf)
+    if (!records || !cell_keys || !cell_start || !queries || !idx || !dist) return CER_EINVAL;
+    if ((uintptr_t)records & 15) return CER_EALIGN;
+    hipLaunchKernelGGL(grid_nearest_kernel, dim3(grid_blocks(m, 256)), dim3(256), 0, (hipStream_t)stream, (const uint4*)records, cell_keys,
+                       cell_start, ncells, origin[0], origin[1], origin[2], cell, queries, qorder, m, max_dist, (int)rings + 1, idx, dist);
+    CER_RETURN_IF_LAUNCH_FAILED();
+    return CER_OK;
+}

@@ -551,6 +551,53 @@ int cer_color_grid_f32(const float* prepared, float* colors, int n, int H, int W
 /* inference.disp_to_depth (reference: inference.py:57-58) on n floats: depth = disp == 0 ? 0 : 1 / disp, correctly rounded. */
 int cer_disp_to_depth_f32(const float* disp, float* depth, long n, void* stream);
 
+/* Cloud-to-cloud evaluation (ABI 1110; csrc/cloud_eval.hip, cer-mvs_amd/cloud_eval.py): the exact nearest neighbour of every query point in a
+ * target cloud within a cut-off - what DTU's accuracy / completeness and Tanks-and-Temples' precision / recall / F are means and shares of.
+ * The target is indexed by a sparse uniform grid that exists only as sorted keys (memory follows the points, not the scene's extent).  No
+ * atomics; the same bytes on every run.  Points and queries are [n, 3] floats; `origin` is HOST memory, 3 doubles; cell > 0.
+ *
+ * Sizes (n, m, ncells), in every entry point: negative -> CER_EINVAL; 2^31 or more -> CER_ESHAPE; zero -> CER_OK with nothing launched
+ * (decided before the pointers are looked at).  Then: a null pointer, a non-finite origin, a cell that is not a positive finite number, a
+ * max_dist that is negative or NaN -> CER_EINVAL.
+ *
+ *   cer_grid_keys_f32: keys[i] = (cz + B) << 42 | (cy + B) << 21 | (cx + B), B = CER_GRID_COORD_LIMIT - 1, with the cell coordinate
+ *     c = floor((double(p) - origin) / cell) per axis (an IEEE fp64 division).  A point with a non-finite coordinate gets the sentinel
+ *     2^63 - 1, which sorts last and which no cell's key reaches (every field is at most 2^21 - 2).  clamp == 0 (the target side): a
+ *     coordinate with |c| >= CER_GRID_COORD_LIMIT returns CER_ESHAPE - `flag`, one device int of the caller's, carries the finding, and the
+ *     call synchronises the stream to read it.  clamp != 0 (the query side, whose keys only order the queries): coordinates are clamped
+ *     into the range instead, flag may be NULL and nothing is synchronised.
+ *   cer_grid_pack_f32: records[i] = (x, y, z, (int)order[i]) of point order[i], 16 bytes each (CER_EALIGN unless 16-byte aligned): the
+ *     target in the order of its stably sorted keys, `order` being the sort's permutation (the original indices).
+ *   cer_grid_partials: HOST function: ceil(n / CER_GRID_TILE), the partial counts the cell passes need: partials [that many] unsigned,
+ *     offsets [that many + 1] 64-bit.
+ *   cer_grid_cells_count_i64: over the SORTED keys: per-block counts of cell heads (a key that is not the sentinel and differs from its
+ *     predecessor) and their scan; totals[0] = the number of occupied cells, totals[1] = the number of keys below the sentinel.  The caller
+ *     reads totals once and allocates cell_keys [ncells] and cell_start [ncells + 1].
+ *   cer_grid_cells_i64: cell_keys[r] = the r-th distinct key, ascending; cell_start[r] = its first sorted position; cell_start[ncells] =
+ *     totals[1].  Never writes beyond those sizes.  CER_ESHAPE: ncells > n.  ncells == 0 launches nothing.
+ *   cer_grid_nearest_f32: per query, at the query's own position in idx / dist (qorder: the order in which the queries are WALKED, a
+ *     permutation of 0 .. m-1 that puts neighbours in space next to each other, or NULL for the input order - it changes the speed only):
+ *       dx, dy, dz = fp64 differences of the float32 coordinates; d2 = (dx*dx + dy*dy) + dz*dz in fp64, no contraction;
+ *       a target point is a candidate iff d2 <= double(max_dist) * double(max_dist); the winner is the smallest (d2, original index);
+ *       idx = its original index, dist = float(sqrt(d2)) with a correctly rounded fp64 square root; no candidate, or a query with a
+ *       non-finite coordinate: idx = -1, dist = +inf.  Sentinel-keyed (non-finite) target points are beyond cell_start[ncells]: never seen.
+ *     `n` is cell_start[ncells]'s bound (the record count).  The search enumerates ceil(max_dist / cell) + 1 rings of cells around the
+ *     query's cell and skips a row or a cell only when the true bounds of the points it can hold, widened by 1e-6 cells against the two
+ *     roundings of the key arithmetic, exceed the best distance so far - exactness does not rest on the keys.  CER_ESHAPE: more than 4096
+ *     rings (max_dist / cell), ncells > n.  n == 0, ncells == 0 or m == 0: nothing is launched; with m > 0 the caller fills idx = -1 and
+ *     dist = +inf itself. */
+#define CER_GRID_TILE 2048
+#define CER_GRID_COORD_LIMIT (1 << 20)
+long cer_grid_partials(long n);
+int cer_grid_keys_f32(const float* points, long n, const double* origin, double cell, int clamp, long long* keys, int* flag, void* stream);
+int cer_grid_pack_f32(const float* points, const long long* order, long n, void* records, void* stream);
+int cer_grid_cells_count_i64(const long long* keys, long n, unsigned int* partials, long long* offsets, long long* totals, void* stream);
+int cer_grid_cells_i64(const long long* keys, long n, const long long* offsets, long long ncells, long long* cell_keys, long long* cell_start,
+                       void* stream);
+int cer_grid_nearest_f32(const void* records, long n, const long long* cell_keys, const long long* cell_start, long ncells,
+                         const double* origin, double cell, const float* queries, const long long* qorder, long m, float max_dist,
+                         long long* idx, float* dist, void* stream);
+
 /* Multi-GPU row-slab exchange (cer-mvs_amd/slab.py): up to CER_COPY_MAX_SEG contiguous fp32 ranges copied by ONE launch -
  * the pack of a rank's (net, disp) border strips into its send buffer, and the refresh of its halo rows from the gathered
  * strips.  n[i] floats from src[i] to dst[i]; n[i] == 0 skips a segment.  Device pointers; ranges must not overlap. */
