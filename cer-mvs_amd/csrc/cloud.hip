@@ -3,76 +3,38 @@
 // paired with their colours - plus the two small producers in front of it: disparity -> depth and the colour planes at the depth grid.
 //
 // Order: the points of view order[0] first, then order[1], ...; row-major inside a view - what numpy's boolean indexing gives the host path.
-// It is a pure function of the masks: a count pass writes one partial count per block (wave ballots), one block scans the partials into
-// 64-bit exclusive offsets, and the emit pass ranks every set pixel inside its wave (ballot + mbcnt), its wave inside the block (LDS) and its
-// block through the scanned offset.  No atomics, no output cursor: the same bytes on every run, whatever the schedule.
+// It is a pure function of the masks: compact.hpp's count / scan / emit over the set pixels, one tile of a view per block.  No atomics, no
+// output cursor: the same bytes on every run, whatever the schedule.
 #include "common.hpp"
+#include "compact.hpp"
 
 #define CLOUD_TILE CER_CLOUD_TILE                    // pixels of one view per block
-#define CLOUD_ITER (CLOUD_TILE / 256)                // 64-pixel rows per wave: wave v of a block owns pixels [v, v + 1) * TILE / 4 of the tile
+#define CLOUD_ITER (CLOUD_TILE / 256)                // 64-pixel rows per wave
 #define CLOUD_ORDER_CHUNK 128                        // listed views per launch (they travel as kernel arguments: the list is host memory)
 
 struct CloudOrder {
     int view[CLOUD_ORDER_CHUNK];
 };
 
-__device__ __forceinline__ unsigned cloud_rank(unsigned long long ballot) {     // set lanes below this one
-    return __builtin_amdgcn_mbcnt_hi((unsigned)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)ballot, 0u));
+// the tile walk of both passes over view m: bal[j] = the set pixels of the wave's row j; returns the wave's total
+__device__ __forceinline__ unsigned cloud_ballots(const unsigned char* __restrict__ m, unsigned P, unsigned seg, unsigned long long (&bal)[CLOUD_ITER]) {
+    return compact_ballots(seg, [=](unsigned p) { return p < P && m[p] != 0; }, bal);
 }
 
 // ---- count: partials[(k0 + blockIdx.y) * bpv + blockIdx.x] = set pixels of the block's tile
 __global__ __launch_bounds__(256) void cloud_count_kernel(const CloudOrder ord, int k0, const unsigned char* __restrict__ masks, unsigned P,
                                                           int bpv, unsigned* __restrict__ partials) {
-    __shared__ unsigned wave_cnt[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned char* m = masks + (long)ord.view[blockIdx.y] * P;
-    const unsigned seg = blockIdx.x * (unsigned)CLOUD_TILE + wave * (CLOUD_TILE / 4) + lane;
-    unsigned tot = 0;
-#pragma unroll
-    for (int j = 0; j < CLOUD_ITER; ++j) {
-        const unsigned p = seg + 64 * j;
-        const bool set = p < P && m[p] != 0;
-        tot += (unsigned)__popcll(__ballot(set));
-    }
-    if (lane == 0) wave_cnt[wave] = tot;
-    __syncthreads();
-    if (threadIdx.x == 0) partials[(long)(k0 + blockIdx.y) * bpv + blockIdx.x] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+    unsigned long long bal[CLOUD_ITER];
+    const unsigned tot = compact_block_total(cloud_ballots(masks + (long)ord.view[blockIdx.y] * P, P, compact_seg<CLOUD_TILE, unsigned>(), bal));
+    if (threadIdx.x == 0) partials[(long)(k0 + blockIdx.y) * bpv + blockIdx.x] = tot;
 }
 
-// ---- scan: one block; offsets[i] = sum of partials[0 .. i), offsets[n] = the total; view_base[k] = offsets[k * bpv] (k <= views).
-// The partials are walked in chunks of 1024: thread t takes element chunk + t (coalesced loads and stores), the chunk is scanned with
-// shuffles inside a wave and the 16 wave totals through LDS, and the running total is carried to the next chunk.  A 49-view scan at
-// 1600x1184 has 45 325 partials: 45 chunks.
+// ---- scan: one block; offsets[i] = sum of partials[0 .. i), offsets[n] = the total; view_base[k] = offsets[k * bpv] (k <= views)
 __global__ __launch_bounds__(1024) void cloud_scan_kernel(const unsigned* __restrict__ partials, long n, int bpv, int views,
                                                           long long* __restrict__ offsets, long long* __restrict__ view_base) {
-    __shared__ long long wave_tot[16];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    long long carry = 0;
-    for (long c0 = 0; c0 < n; c0 += 1024) {
-        const long i = c0 + t;
-        const long long s = i < n ? (long long)partials[i] : 0;
-        long long inc = s;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const long long v = __shfl_up(inc, d);
-            if (lane >= d) inc += v;
-        }
-        if (lane == 63) wave_tot[wave] = inc;
-        __syncthreads();
-        long long below = 0, all = 0;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const long long v = wave_tot[k];
-            below += k < wave ? v : 0;
-            all += v;
-        }
-        if (i < n) offsets[i] = carry + below + inc - s;
-        carry += all;
-        __syncthreads();                             // (wave_tot is rewritten by the next chunk)
-    }
-    if (t == 0) offsets[n] = carry;
+    compact_scan(partials, n, offsets);
     __syncthreads();                                 // the block's own global writes are visible to it behind the barrier
-    for (int k = t; k <= views; k += 1024) view_base[k] = offsets[(long)k * bpv];
+    for (int k = threadIdx.x; k <= views; k += 1024) view_base[k] = offsets[(long)k * bpv];
 }
 
 // ---- emit.  cams: per view CER_CLOUD_CAM_DOUBLES doubles = K^-1 [9] | rows 0-2 of E^-1 [12] (float32 inverses promoted on the host).
@@ -82,30 +44,19 @@ __global__ __launch_bounds__(256) void cloud_emit_kernel(const CloudOrder ord, i
                                                          const float* __restrict__ colors, unsigned P, int w, int bpv,
                                                          const long long* __restrict__ offsets, long long capacity, float* __restrict__ xyz,
                                                          unsigned char* __restrict__ rgb) {
-    __shared__ unsigned wave_cnt[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
     const int view = ord.view[blockIdx.y];
-    const unsigned char* m = masks + (long)view * P;
-    const unsigned seg = blockIdx.x * (unsigned)CLOUD_TILE + wave * (CLOUD_TILE / 4) + lane;
+    const unsigned seg = compact_seg<CLOUD_TILE, unsigned>();
     unsigned long long bal[CLOUD_ITER];
-    unsigned tot = 0;
-#pragma unroll
-    for (int j = 0; j < CLOUD_ITER; ++j) {
-        const unsigned p = seg + 64 * j;
-        bal[j] = __ballot(p < P && m[p] != 0);
-        tot += (unsigned)__popcll(bal[j]);
-    }
-    if (lane == 0) wave_cnt[wave] = tot;
-    __syncthreads();
-    long long base = offsets[(long)(k0 + blockIdx.y) * bpv + blockIdx.x];
-    for (int i = 0; i < wave; ++i) base += wave_cnt[i];
+    const unsigned tot = cloud_ballots(masks + (long)view * P, P, seg, bal);
+    long long base = compact_wave_base(tot, offsets, (long)(k0 + blockIdx.y) * bpv + blockIdx.x);
     const double* c = cams + (long)view * CER_CLOUD_CAM_DOUBLES;         // wave-uniform: scalar loads
     const float* dep = depth + (long)view * P;
     const float* col = colors + (long)view * 3 * P;
 #pragma unroll
     for (int j = 0; j < CLOUD_ITER; ++j) {
         const unsigned p = seg + 64 * j;
-        const long long idx = base + cloud_rank(bal[j]);
+        const long long idx = base + compact_rank(bal[j]);
         base += __popcll(bal[j]);
         if (!((bal[j] >> lane) & 1ull) || idx >= capacity) continue;     // (never past what the caller allocated)
         const unsigned yi = p / (unsigned)w, xi = p - yi * (unsigned)w;
@@ -135,26 +86,38 @@ static int cloud_check(const void* masks, int N, int h, int w, const int* order,
     return CER_OK;
 }
 
-extern "C" long cer_cloud_partials(int n_order, int h, int w) {
-    if (n_order <= 0 || h <= 0 || w <= 0) return CER_EINVAL;
-    return (long)n_order * (((long)h * w + CLOUD_TILE - 1) / CLOUD_TILE);
-}
+static long cloud_bpv(int h, int w) { return ((long)h * w + CLOUD_TILE - 1) / CLOUD_TILE; }          // blocks (tiles) per view
 
-extern "C" int cer_cloud_count_u8(const unsigned char* masks, int N, int h, int w, const int* order, int n_order, unsigned int* partials,
-                                  long long* offsets, long long* view_base, void* stream) {
-    const int rc = cloud_check(masks, N, h, w, order, n_order);
-    if (rc != CER_OK) return rc;
-    if (!partials || !offsets || !view_base) return CER_EINVAL;
-    const unsigned P = (unsigned)((long)h * w);
-    const int bpv = (int)((P + CLOUD_TILE - 1) / CLOUD_TILE);
-    hipStream_t st = (hipStream_t)stream;
+// launch(ord, k0, nk) for every chunk of CLOUD_ORDER_CHUNK listed views: ord = order[k0 .. k0 + nk)
+template <typename Launch>
+static int cloud_for_chunks(const int* order, int n_order, Launch launch) {
     for (int k0 = 0; k0 < n_order; k0 += CLOUD_ORDER_CHUNK) {
         CloudOrder ord = {};
         const int nk = n_order - k0 < CLOUD_ORDER_CHUNK ? n_order - k0 : CLOUD_ORDER_CHUNK;
         for (int k = 0; k < nk; ++k) ord.view[k] = order[k0 + k];
-        hipLaunchKernelGGL(cloud_count_kernel, dim3((unsigned)bpv, (unsigned)nk), dim3(256), 0, st, ord, k0, masks, P, bpv, partials);
+        launch(ord, k0, nk);
         CER_RETURN_IF_LAUNCH_FAILED();
     }
+    return CER_OK;
+}
+
+extern "C" long cer_cloud_partials(int n_order, int h, int w) {
+    if (n_order <= 0 || h <= 0 || w <= 0) return CER_EINVAL;
+    return (long)n_order * cloud_bpv(h, w);
+}
+
+extern "C" int cer_cloud_count_u8(const unsigned char* masks, int N, int h, int w, const int* order, int n_order, unsigned int* partials,
+                                  long long* offsets, long long* view_base, void* stream) {
+    int rc = cloud_check(masks, N, h, w, order, n_order);
+    if (rc != CER_OK) return rc;
+    if (!partials || !offsets || !view_base) return CER_EINVAL;
+    const unsigned P = (unsigned)((long)h * w);
+    const int bpv = (int)cloud_bpv(h, w);
+    hipStream_t st = (hipStream_t)stream;
+    rc = cloud_for_chunks(order, n_order, [&](const CloudOrder& ord, int k0, int nk) {
+        hipLaunchKernelGGL(cloud_count_kernel, dim3((unsigned)bpv, (unsigned)nk), dim3(256), 0, st, ord, k0, masks, P, bpv, partials);
+    });
+    if (rc != CER_OK) return rc;
     hipLaunchKernelGGL(cloud_scan_kernel, dim3(1), dim3(1024), 0, st, partials, (long)n_order * bpv, bpv, n_order, offsets, view_base);
     CER_RETURN_IF_LAUNCH_FAILED();
     return CER_OK;
@@ -170,17 +133,12 @@ extern "C" int cer_cloud_emit_f32(const unsigned char* masks, const float* depth
     if (capacity == 0) return CER_OK;                // nothing to write: nothing is launched
     if (!xyz || !rgb) return CER_EINVAL;
     const unsigned P = (unsigned)((long)h * w);
-    const int bpv = (int)((P + CLOUD_TILE - 1) / CLOUD_TILE);
+    const int bpv = (int)cloud_bpv(h, w);
     hipStream_t st = (hipStream_t)stream;
-    for (int k0 = 0; k0 < n_order; k0 += CLOUD_ORDER_CHUNK) {
-        CloudOrder ord = {};
-        const int nk = n_order - k0 < CLOUD_ORDER_CHUNK ? n_order - k0 : CLOUD_ORDER_CHUNK;
-        for (int k = 0; k < nk; ++k) ord.view[k] = order[k0 + k];
+    return cloud_for_chunks(order, n_order, [&](const CloudOrder& ord, int k0, int nk) {
         hipLaunchKernelGGL(cloud_emit_kernel, dim3((unsigned)bpv, (unsigned)nk), dim3(256), 0, st, ord, k0, masks, depth_est, cams, colors, P,
                            w, bpv, offsets, capacity, xyz, rgb);
-        CER_RETURN_IF_LAUNCH_FAILED();
-    }
-    return CER_OK;
+    });
 }
 
 // ---- colour planes at the depth grid: prepared images [n, 3, H, W], values 0..255 -> [n, 3, h, w], values 0..1, H = k h, W = k w.

@@ -3,15 +3,15 @@
 //
 // The target is indexed by a sparse uniform grid that exists only as sorted keys: cer_grid_keys_f32 gives every point the 63-bit key of its
 // cell, the host sorts the keys (stable) and cer_grid_pack_f32 gathers the points into that order as 16-byte records (x, y, z, original index),
-// cer_grid_cells_count_i64 / cer_grid_cells_i64 list the occupied cells with their first sorted point (cloud.hip's idiom: flags counted per
-// block with wave ballots, one block scans, ranks from ballot + mbcnt), and cer_grid_nearest_f32 searches.  No atomics anywhere: the same
-// bytes on every run.
+// cer_grid_cells_count_i64 / cer_grid_cells_i64 list the occupied cells with their first sorted point (compact.hpp's count / scan / emit over
+// the heads of the sorted keys), and cer_grid_nearest_f32 searches.  No atomics anywhere: the same bytes on every run.
 //
 // Key layout: (z + B) << 42 | (y + B) << 21 | (x + B), B = CER_GRID_COORD_LIMIT - 1, cell coordinates in -B .. B: every field is at most
 // 2^21 - 2, so no key reaches the sentinel (2^63 - 1, all 63 bits set) and key(x + 1, y, z) = key(x, y, z) + 1 never carries.  x is the
 // lowest field: the cells x0 .. x1 of one (y, z) row are a contiguous run of the cell table and their points a contiguous run of the
 // sorted points, found with two binary searches.
 #include "common.hpp"
+#include "compact.hpp"
 
 #define GRID_TILE CER_GRID_TILE                      // sorted keys per block of the cell passes
 #define GRID_ITER (GRID_TILE / 256)
@@ -19,9 +19,6 @@
 #define GRID_SENTINEL 0x7fffffffffffffffLL
 #define GRID_MAX_RINGS 4096                          // ceil(max_dist / cell) beyond this: CER_ESHAPE (the cell is far too small for the cut-off)
 
-__device__ __forceinline__ unsigned grid_rank(unsigned long long ballot) {      // set lanes below this one
-    return __builtin_amdgcn_mbcnt_hi((unsigned)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)ballot, 0u));
-}
 __device__ __forceinline__ long long grid_key(int x, int y, int z) {
     return ((long long)(z + GRID_B) << 42) | ((long long)(y + GRID_B) << 21) | (long long)(x + GRID_B);
 }
@@ -68,80 +65,48 @@ __device__ __forceinline__ bool grid_head(const long long* __restrict__ keys, lo
     return k != GRID_SENTINEL && (i == 0 || keys[i - 1] != k);
 }
 
+__device__ __forceinline__ long grid_lower_bound(const long long* __restrict__ a, long lo, long hi, long long k) {     // first i in [lo, hi) with a[i] >= k
+    while (lo < hi) {
+        const long mid = lo + (hi - lo) / 2;
+        if (a[mid] < k) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// the tile walk of both passes: bal[j] = the heads of the wave's row j; returns the wave's total
+__device__ __forceinline__ unsigned grid_ballots(const long long* __restrict__ keys, long n, long seg, unsigned long long (&bal)[GRID_ITER]) {
+    return compact_ballots(seg, [=](long i) { return grid_head(keys, n, i); }, bal);
+}
+
 __global__ __launch_bounds__(256) void grid_count_kernel(const long long* __restrict__ keys, long n, unsigned* __restrict__ partials) {
-    __shared__ unsigned wave_cnt[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long seg = (long)blockIdx.x * GRID_TILE + wave * (GRID_TILE / 4) + lane;
-    unsigned tot = 0;
-#pragma unroll
-    for (int j = 0; j < GRID_ITER; ++j) tot += (unsigned)__popcll(__ballot(grid_head(keys, n, seg + 64 * j)));
-    if (lane == 0) wave_cnt[wave] = tot;
-    __syncthreads();
-    if (threadIdx.x == 0) partials[blockIdx.x] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+    unsigned long long bal[GRID_ITER];
+    const unsigned tot = compact_block_total(grid_ballots(keys, n, compact_seg<GRID_TILE, long>(), bal));
+    if (threadIdx.x == 0) partials[blockIdx.x] = tot;
 }
 
 // one block: offsets[i] = sum of partials[0 .. i), offsets[np] = totals[0] = the number of cells; totals[1] = the number of keys below the
 // sentinel (the first sentinel's position in the sorted keys: a binary search by one thread)
 __global__ __launch_bounds__(1024) void grid_scan_kernel(const unsigned* __restrict__ partials, long np, const long long* __restrict__ keys, long n,
                                                          long long* __restrict__ offsets, long long* __restrict__ totals) {
-    __shared__ long long wave_tot[16];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    long long carry = 0;
-    for (long c0 = 0; c0 < np; c0 += 1024) {
-        const long i = c0 + t;
-        const long long s = i < np ? (long long)partials[i] : 0;
-        long long inc = s;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const long long v = __shfl_up(inc, d);
-            if (lane >= d) inc += v;
-        }
-        if (lane == 63) wave_tot[wave] = inc;
-        __syncthreads();
-        long long below = 0, all = 0;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const long long v = wave_tot[k];
-            below += k < wave ? v : 0;
-            all += v;
-        }
-        if (i < np) offsets[i] = carry + below + inc - s;
-        carry += all;
-        __syncthreads();                             // (wave_tot is rewritten by the next chunk)
-    }
-    if (t == 0) {
-        offsets[np] = carry;
-        totals[0] = carry;
-        long lo = 0, hi = n;
-        while (lo < hi) {
-            const long mid = lo + (hi - lo) / 2;
-            if (keys[mid] < GRID_SENTINEL) lo = mid + 1; else hi = mid;
-        }
-        totals[1] = lo;
+    const long long ncells = compact_scan(partials, np, offsets);
+    if (threadIdx.x == 0) {
+        totals[0] = ncells;
+        totals[1] = grid_lower_bound(keys, 0, n, GRID_SENTINEL);
     }
 }
 
 // cell_keys[r] = key and cell_start[r] = sorted position of head r; cell_start[ncells] = the number of keys below the sentinel
 __global__ __launch_bounds__(256) void grid_emit_kernel(const long long* __restrict__ keys, long n, const long long* __restrict__ offsets,
                                                         long long ncells, long long* __restrict__ cell_keys, long long* __restrict__ cell_start) {
-    __shared__ unsigned wave_cnt[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long seg = (long)blockIdx.x * GRID_TILE + wave * (GRID_TILE / 4) + lane;
+    const int lane = threadIdx.x & 63;
+    const long seg = compact_seg<GRID_TILE, long>();
     unsigned long long bal[GRID_ITER];
-    unsigned tot = 0;
-#pragma unroll
-    for (int j = 0; j < GRID_ITER; ++j) {
-        bal[j] = __ballot(grid_head(keys, n, seg + 64 * j));
-        tot += (unsigned)__popcll(bal[j]);
-    }
-    if (lane == 0) wave_cnt[wave] = tot;
-    __syncthreads();
-    long long base = offsets[blockIdx.x];
-    for (int i = 0; i < wave; ++i) base += wave_cnt[i];
+    const unsigned tot = grid_ballots(keys, n, seg, bal);
+    long long base = compact_wave_base(tot, offsets, blockIdx.x);
 #pragma unroll
     for (int j = 0; j < GRID_ITER; ++j) {
         const long p = seg + 64 * j;
-        const long long r = base + grid_rank(bal[j]);
+        const long long r = base + compact_rank(bal[j]);
         base += __popcll(bal[j]);
         if (p < n) {
             const long long k = keys[p];
@@ -162,14 +127,6 @@ __global__ __launch_bounds__(256) void grid_emit_kernel(const long long* __restr
 // best distance so far are skipped (strictly: a tie on d2 with a lower index must still be seen); the enumeration itself covers
 // ceil(max_dist / cell) + 1 rings, one more than the mathematics needs.
 #define GRID_EPS 1e-6
-
-__device__ __forceinline__ long grid_lower_bound(const long long* __restrict__ a, long lo, long hi, long long k) {     // first i in [lo, hi) with a[i] >= k
-    while (lo < hi) {
-        const long mid = lo + (hi - lo) / 2;
-        if (a[mid] < k) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
 
 struct GridBest {
     double d2;
@@ -270,9 +227,8 @@ static bool grid_frame_ok(const double* origin, double cell) {
 static unsigned grid_blocks(long n, long per) { return (unsigned)((n + per - 1) / per); }
 
 extern "C" long cer_grid_partials(long n) {
-    if (n < 0) return CER_EINVAL;
-    if (n >= 0x80000000L) return CER_ESHAPE;
-    return (n + GRID_TILE - 1) / GRID_TILE;
+    const int rc = grid_size_check(n);
+    return rc != CER_OK ? rc : (n + GRID_TILE - 1) / GRID_TILE;
 }
 
 extern "C" int cer_grid_keys_f32(const float* points, long n, const double* origin, double cell, int clamp, long long* keys, int* flag,

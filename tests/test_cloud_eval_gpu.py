@@ -213,12 +213,17 @@ def test_determinism_and_permutations(dev):
 
 
 # ---------------------------------------------------------------- voxel thinning
-def oracle_voxels(points, cell):
+def oracle_keys(points, cell):
+    """(finite [n] bool, packed cell key of every finite point: int64, one dimension, ordered as the device's keys)"""
     P = np.asarray(points, F32).astype(np.float64)
     finite = np.isfinite(P).all(1)
     origin = P[finite].min(0)
     c = np.floor((P[finite] - origin) / np.float64(cell)).astype(np.int64)
-    keys = (c[:, 2] << 42) | (c[:, 1] << 21) | c[:, 0]
+    return finite, (c[:, 2] << 42) | (c[:, 1] << 21) | c[:, 0]
+
+
+def oracle_voxels(points, cell):
+    finite, keys = oracle_keys(points, cell)
     first = np.unique(keys, return_index=True)[1]            # the first occurrence: the lowest index
     return np.sort(np.flatnonzero(finite)[first])
 
@@ -239,6 +244,27 @@ def test_voxel_downsample_keeps_the_lowest_index_of_every_cell(dev, random_pair,
     assert np.array_equal(got, want) and (np.diff(got) > 0).all() and 0 < len(got) < len(pts)
     again = voxel_downsample(torch.from_numpy(pts).to(dev), cell).cpu().numpy()
     assert again.tobytes() == got.tobytes()
+
+
+def test_cell_table_across_the_scan_chunk_edge(dev):
+    """1024 * 2048 + 1 points: 1025 partials, the smallest cloud at which the cell passes' scan carries a total from one 1024-partial chunk into
+    the next.  2^21 points fill the 32^3 cells of the unit cube (every tile of sorted keys holds a few dozen heads); the last point, the
+    highest index, lies alone in a far cell, so its key sorts last: the one key of tile 1024, a head, ranked by the carried total alone."""
+    from cer_mvs_amd.cloud_eval import CloudIndex, voxel_downsample
+    n, cell = 1024 * 2048 + 1, 1.0 / 32
+    pts = np.random.default_rng(31).random((n, 3), dtype=F32)
+    pts[0] = 0.0                                             # (the origin: cell edges at multiples of 2^-5, exact in every format)
+    pts[-1] = 2.0
+    finite, keys = oracle_keys(pts, cell)
+    uniq, first, counts = np.unique(keys, return_index=True, return_counts=True)
+    assert finite.all() and 20000 < len(uniq) <= 32 ** 3 + 1 and uniq[-1] == keys[-1] and counts[-1] == 1
+    d = torch.from_numpy(pts).to(dev)
+    index = CloudIndex(d, cell)
+    assert index.cells == len(uniq) and index.n == n
+    assert np.array_equal(index.cell_start.cpu().numpy(), np.concatenate([[0], np.cumsum(counts)]))
+    assert np.array_equal(index.cell_keys.cpu().numpy() - index.cell_keys[0].item(), uniq - uniq[0])
+    got = voxel_downsample(d, cell).cpu().numpy()
+    assert np.array_equal(got, np.sort(first)) and got[-1] == n - 1
 
 
 # ---------------------------------------------------------------- the protocols

@@ -139,6 +139,23 @@ def test_point_cloud_listed_twice_and_more_views_than_a_launch_takes(dev):
         fusion.point_cloud(masks.to(dev), est.to(dev), K, E, col.to(dev), [0, N])
 
 
+@pytest.mark.parametrize("L", [1023, 1024, 1025, 2049])
+def test_point_cloud_across_the_scan_chunk_edge(dev, L):
+    """19x23 is one tile per view, so the scan sees one partial per listed view: L partials end one short of, on and one past its 1024-partial
+    chunk, and two chunks and one over (the carry handed on twice); view 2 is empty, so zero partials sit inside and at both edges of a chunk
+    (order[0] = order[1026] = 2, order[1023] = 5, order[1024] = 4).  Every list is also cut into launches of 128 views."""
+    from cer_mvs_amd import fusion
+    N, h, w = 6, 19, 23
+    K, E = _cameras(N, h, w)
+    est, col = _inputs(N, h, w, seed=2)
+    masks = _masks("quarter", N, h, w, seed=9)
+    masks[2] = 0
+    order = [(5 * i + 2) % N for i in range(L)]
+    xyz, rgb = fusion.point_cloud(masks.to(dev), est.to(dev), K, E, col.to(dev), order)
+    assert len(xyz) == sum(int(masks[v].bool().sum()) for v in order)
+    assert_cloud(xyz.cpu().numpy(), rgb.cpu().numpy(), masks.numpy(), est.numpy(), K, E, col.numpy(), order, f"{L} listed views")
+
+
 def _golden_scene(g):
     from cer_mvs_amd.synthetic import synthetic_depth_maps, synthetic_scene, tensor_checksum
     H, W, V = int(g["H"]), int(g["W"]), int(g["V"])
