@@ -29,6 +29,7 @@
 //     form (6 single-tap steps), border tiles the literal one (4 half-chunks x 9 taps) - same algebra as round 1;
 //   * the hoisted `init` term / bias is the accumulators' initial value (16-byte loads in the prologue).
 #include "conv_s16_shared.hpp"
+#include "pack.hpp"       // weight layouts: pack.cpp
 #ifndef SX_MT8
 #define SX_MT8 0
 #endif
@@ -963,351 +964,6 @@ __global__ __launch_bounds__(256, (WM_ == 2 && F8 && SX_OCC3) ? 3 : (MT >= 8 ? 1
 }
 
 // ---------------------------------------------------------------------------------------- host side
-
-static int sx_order(const int* kind, int nsrc, int* order) {               // tensors first, the disparity source last
-    int n = 0, nd = 0;
-    for (int s = 0; s < nsrc; ++s) if (kind[s] != 1) order[n++] = s;
-    for (int s = 0; s < nsrc; ++s) if (kind[s] == 1) { order[n++] = s; ++nd; }
-    return nd;
-}
-
-static long sx_steps(const int* ch, const int* kind, int nsrc, int collapsed) {
-    long steps = 0;
-    for (int s = 0; s < nsrc; ++s) steps += kind[s] == 1 ? (collapsed ? 6 : 36) : (ch[s] / 16) * 9;
-    return steps;
-}
-
-extern "C" long cer_conv3x3_s16_packed_size(int Cout, const int* ch, const int* kind, int nsrc, int collapsed) {
-    if (!ch || !kind || nsrc <= 0 || nsrc > CER_CONV_MAX_SRC || Cout <= 0 || Cout % 32) return CER_ESHAPE;
-    int nd = 0;
-    for (int s = 0; s < nsrc; ++s) {
-        if (kind[s] == 1) { ++nd; if (ch[s] != 49) return CER_ESHAPE; }
-        else if (ch[s] % 32) return CER_ESHAPE;
-    }
-    collapsed &= 1;                                        // (bit 1 = fp8-, bit 2 = FP6-correction form: same size)
-    if (nd > 1 || (collapsed && nd == 0)) return CER_ESHAPE;
-    return sx_steps(ch, kind, nsrc, collapsed) * (Cout / 32) * 1024;        // in halves
-}
-
-// collapsed 81-tap filter of the disparity source (see gru_f16x3.hip: cer_conv3x3_f16x3_pack_collapsed), fp64 sums
-static double sx_w9(const float* w, int Cin, int co, int c, int sidx) {
-    if (sidx >= 81) return 0.0;
-    const int sy = sidx / 9, sx = sidx % 9;
-    double acc = 0.0;
-    for (int ty = 0; ty < 3; ++ty)
-        for (int tx = 0; tx < 3; ++tx) {
-            const int uy = sy - ty, ux = sx - tx;
-            if (uy >= 0 && uy < 7 && ux >= 0 && ux < 7) acc += (double)w[((long)co * Cin + c + uy * 7 + ux) * 9 + ty * 3 + tx];
-        }
-    if (sy >= 3 && sy <= 5 && sx >= 3 && sx <= 5) {
-        const int t = (sy - 3) * 3 + (sx - 3);
-        for (int u = 0; u < 49; ++u) acc -= (double)w[((long)co * Cin + c + u) * 9 + t];
-    }
-    return acc;
-}
-
-// log2 of the product scale S shared by all sources: the largest power of two that keeps every scaled weight
-// |w| * S / 2^log2sx(src) below 2^14 (f16 max 65504), for the literal and the collapsed packing alike.  Returns CER_ESHAPE
-// (as a value < -1000) if some source's largest scaled weight would then fall below 2^-3 (its lo halves go subnormal: fewer than 22 bits).
-extern "C" int cer_conv3x3_s16_scale(const float* w, int Cout, int Cin, const int* ch, const int* kind, const int* log2sx, int nsrc) {
-    if (!w || !ch || !kind || !log2sx || nsrc <= 0 || nsrc > CER_CONV_MAX_SRC) return -100000;
-    double wmax[CER_CONV_MAX_SRC];
-    int c = 0;
-    for (int s = 0; s < nsrc; ++s) {
-        double m = 0.0;
-        for (int co = 0; co < Cout; ++co) {
-            for (int i = 0; i < ch[s]; ++i)
-                for (int t = 0; t < 9; ++t) m = fmax(m, fabs((double)w[((long)co * Cin + c + i) * 9 + t]));
-            if (kind[s] == 1) {
-                for (int sidx = 0; sidx < 81; ++sidx) m = fmax(m, fabs(sx_w9(w, Cin, co, c, sidx)));
-                // the rim-correction filters sum at most 3 taps per entry
-                double m3 = 0.0;
-                for (int u = 0; u < 49; ++u) {
-                    for (int ty = 0; ty < 3; ++ty) {
-                        double sr = 0.0;
-                        for (int tx = 0; tx < 3; ++tx) sr += fabs((double)w[((long)co * Cin + c + u) * 9 + ty * 3 + tx]);
-                        m3 = fmax(m3, sr);
-                    }
-                    for (int tx = 0; tx < 3; ++tx) {
-                        double sc = 0.0;
-                        for (int ty = 0; ty < 3; ++ty) sc += fabs((double)w[((long)co * Cin + c + u) * 9 + ty * 3 + tx]);
-                        m3 = fmax(m3, sc);
-                    }
-                }
-                m = fmax(m, m3);
-            }
-        }
-        wmax[s] = m;
-        c += ch[s];
-    }
-    if (c != Cin) return -100000;
-    int best = 1000;
-    for (int s = 0; s < nsrc; ++s) {
-        if (wmax[s] <= 0.0) continue;
-        const int k = (int)floor(log2(16384.0 / wmax[s])) + log2sx[s];
-        best = k < best ? k : best;
-    }
-    if (best == 1000) best = 14;
-    // the shared scale is set by the source with the largest weights.  A source's lo halves are f16 residuals of magnitude <= 2^-11 of
-    // its scaled weights; once they fall into the f16 subnormal range (spacing 2^-24) the source keeps fewer than 22 bits relative to
-    // its own largest weight when that weight, scaled, is below 2^-3: refuse, the caller falls back to the f16x3 kernels (per-tensor splits)
-    for (int s = 0; s < nsrc; ++s)
-        if (wmax[s] > 0.0 && ldexp(wmax[s], best - log2sx[s]) < 0.125) return -100000 + CER_ESHAPE;
-    return best;
-}
-
-// Rim-correction filters of the collapsed disparity form (see the kernel's epilogue), packed like weight slices:
-// [edge 8][k16-step 2][ntile][hi|lo][lane][8] halves of  -sign * Wedge[k][co] * 2^(log2S - log2sx(disparity source)):
-// edges 0-3 = top, bottom, left, right (27 taps: top/bottom k = a * 9 + sx, left/right k = sy * 3 + b), 4-7 = the corner taps two
-// edges share (9 taps, k = i * 3 + j; opposite sign): top-left, top-right, bottom-left, bottom-right.
-extern "C" long cer_conv3x3_s16_edge_size(int Cout) { return (Cout > 0 && Cout % 32 == 0) ? 16L * (Cout / 32) * 1024 : CER_ESHAPE; }
-
-static void sx_pack_slice(_Float16* packed, long step, int NT, int nt, const double* col, double scale);
-
-extern "C" int cer_conv3x3_s16_edge_pack(const float* w, void* out_v, int Cout, int Cin, const int* ch, const int* kind, const int* log2sx, int nsrc,
-                                         int log2S) {
-    if (!w || !out_v || !ch || !kind || !log2sx || nsrc <= 0 || nsrc > CER_CONV_MAX_SRC) return CER_EINVAL;
-    if (Cout % 32) return CER_ESHAPE;
-    int c0 = -1, c = 0, sd = -1;
-    for (int s = 0; s < nsrc; ++s) {
-        if (kind[s] == 1) { if (ch[s] != 49 || c0 >= 0) return CER_ESHAPE; c0 = c; sd = s; }
-        c += ch[s];
-    }
-    if (c != Cin || c0 < 0) return CER_ESHAPE;
-    auto W = [&](int co, int uy, int ux, int ty, int tx) -> double {
-        if (uy < 0 || uy > 6 || ux < 0 || ux > 6) return 0.0;
-        return (double)w[((long)co * Cin + c0 + uy * 7 + ux) * 9 + ty * 3 + tx];
-    };
-    // Wedge[edge][k][co]
-    auto edge_w = [&](int e, int k, int co) -> double {
-        if (e < 4) {
-            if (k >= 27) return 0.0;
-            double v = 0;
-            if (e == 0) { const int a = k / 9, sx = k % 9; for (int tx = 0; tx < 3; ++tx) v += W(co, a + 4, sx - tx, 0, tx); }
-            if (e == 1) { const int a = k / 9, sx = k % 9; for (int tx = 0; tx < 3; ++tx) v += W(co, a, sx - tx, 2, tx); }
-            if (e == 2) { const int sy = k / 3, b = k % 3; for (int ty = 0; ty < 3; ++ty) v += W(co, sy - ty, b + 4, ty, 0); }
-            if (e == 3) { const int sy = k / 3, b = k % 3; for (int ty = 0; ty < 3; ++ty) v += W(co, sy - ty, b, ty, 2); }
-            return -v;                                     // the rim terms are SUBTRACTED from the collapsed result
-        }
-        if (k >= 9) return 0.0;
-        const int i = k / 3, j = k % 3;
-        if (e == 4) return W(co, i + 4, j + 4, 0, 0);      // ... and the shared corner tap is added back once
-        if (e == 5) return W(co, i + 4, j, 0, 2);
-        if (e == 6) return W(co, i, j + 4, 2, 0);
-        return W(co, i, j, 2, 2);
-    };
-    _Float16* packed = (_Float16*)out_v;
-    const int NT = Cout / 32;
-    const double scale = ldexp(1.0, log2S - log2sx[sd]);
-    double col[16 * 32];
-    for (int e = 0; e < 8; ++e)
-        for (int ks = 0; ks < 2; ++ks)
-            for (int nt = 0; nt < NT; ++nt) {
-                for (int k = 0; k < 16; ++k)
-                    for (int j = 0; j < 32; ++j) col[k * 32 + j] = edge_w(e, ks * 16 + k, nt * 32 + j);
-                sx_pack_slice(packed, e * 2 + ks, NT, nt, col, scale);
-            }
-    return CER_OK;
-}
-
-static void sx_pack_slice(_Float16* packed, long step, int NT, int nt, const double* col /* [16 k][32 co] */, double scale) {
-    for (int lane = 0; lane < 64; ++lane)
-        for (int e = 0; e < 8; ++e) {
-            float v = (float)(col[((lane >> 5) * 8 + e) * 32 + (lane & 31)] * scale);
-            v = v > 65504.f ? 65504.f : (v < -65504.f ? -65504.f : v);
-            const _Float16 hi = (_Float16)v;
-            const _Float16 lo = (_Float16)(v - (float)hi);
-            const long base = (step * NT + nt) * 2;
-            packed[(base + 0) * 512 + lane * 8 + e] = hi;
-            packed[(base + 1) * 512 + lane * 8 + e] = lo;
-        }
-}
-
-// OIHW fp32 -> [step][ntile32][hi|lo][lane][8] halves of w * 2^(log2S - log2sx(src)); steps: tensors in source order
-// (32-channel chunk, 16-channel half, tap), then the disparity source (collapsed: 6 single-tap groups of the 81-tap filter;
-// literal: 4 groups x 9 taps of the 49 unfold channels)
-// e4m3 (OCP: bias 7, subnormals, no infinities, largest finite 448), round to nearest even, saturating
-static unsigned char sx_e4m3(double v) {
-    const unsigned sgn = v < 0 ? 0x80u : 0u;
-    double a = fabs(v);
-    if (!(a == a)) return 0x7f;
-    if (a >= 448.0) return (unsigned char)(sgn | 0x7e);
-    if (a < ldexp(1.0, -10)) return (unsigned char)sgn;    // below half the smallest subnormal (ties to even: 0)
-    int e;
-    frexp(a, &e);                                          // a = m * 2^e, m in [0.5, 1)
-    int E = e - 1;                                         // a in [2^E, 2^(E+1))
-    if (E < -6) E = -6;                                    // subnormal range: spacing 2^-9
-    const double q = nearbyint(ldexp(a, 3 - E));           // in units of 2^(E-3) (nearbyint: ties to even in the default mode)
-    int M = (int)q;                                        // 8..16 for normals, 0..8 for subnormals
-    int Eb = E + 7;
-    if (a < ldexp(1.0, -6)) { Eb = 0; if (M == 8) { Eb = 1; M = 0; } }
-    else { if (M == 16) { M = 0; ++Eb; } else M -= 8; }
-    if (Eb > 15 || (Eb == 15 && M > 6)) return (unsigned char)(sgn | 0x7e);
-    return (unsigned char)(sgn | (Eb << 3) | M);
-}
-
-// fp8-correction form of a tensor chunk step (32 channels, one tap): 4 KiB per n-tile = f16 hi halves of half-chunk 0 | of half-chunk 1
-// (each [lane][8], as in sx_pack_slice) | the A operand of v_mfma_scale_f32_32x32x64_f8f6f4, bytes 0-15 | bytes 16-31 of every lane:
-// lane (co = lane & 31, kg = lane >> 5): [wl * 2^5 (8) | wh * 2^-6 (8)] of half-chunk 0's channels 8kg..8kg+7, then the same of half-chunk 1
-static void sx_pack_chunk8(_Float16* packed, long cstep, int NT, int nt, const double* col /* [32 k][32 co] */, double scale) {
-    char* base = reinterpret_cast<char*>(packed) + (cstep * NT + nt) * 4096;
-    for (int lane = 0; lane < 64; ++lane)
-        for (int hc = 0; hc < 2; ++hc)
-            for (int e = 0; e < 8; ++e) {
-                float v = (float)(col[(hc * 16 + (lane >> 5) * 8 + e) * 32 + (lane & 31)] * scale);
-                v = v > 65504.f ? 65504.f : (v < -65504.f ? -65504.f : v);
-                const _Float16 hi = (_Float16)v;
-                const _Float16 lo = (_Float16)(v - (float)hi);
-                reinterpret_cast<_Float16*>(base + hc * 1024)[lane * 8 + e] = hi;
-                unsigned char* q = reinterpret_cast<unsigned char*>(base + 2048 + hc * 1024 + lane * 16);
-                q[e] = sx_e4m3(ldexp((double)(float)lo, 5));
-                q[8 + e] = sx_e4m3(ldexp((double)(float)hi, -6));
-            }
-}
-
-// e2m3 (FP6: 1 sign, 2 exponent, 3 mantissa bits: 0, 0.125 .. 0.875, 1 .. 1.875, 2 .. 3.75, 4 .. 7.5), round to nearest even, saturating
-static unsigned sx_e2m3(double v) {
-    const unsigned sgn = v < 0 ? 32u : 0u;
-    const double a = fabs(v);
-    if (!(a == a)) return sgn | 31u;
-    if (a >= 7.5) return sgn | 31u;
-    const int E = a < 2.0 ? 0 : (a < 4.0 ? 1 : 2);          // steps of 0.125 (subnormals and [1, 2)), 0.25, 0.5
-    const int q = (int)nearbyint(ldexp(a, 3 - E));          // a in units of the step: 0..16 (E = 0), 8..16
-    if (E == 0) return sgn | (unsigned)q;                   // codes 0..15 are linear in the value (q = 16: code 16 = 2.0)
-    return sgn | (unsigned)(8 * E + q);                     // e = E + 1, m = q - 8 (q = 16 carries into the next exponent: 7.5 is the cap above)
-}
-
-// FP6-correction form of a tensor chunk step (round 6; 32 channels, one tap): 4 KiB per n-tile = f16 hi halves of half-chunk 0 | of
-// half-chunk 1 (as in the fp8 form) | bytes 0-15 | bytes 16-31 of every lane's A operand of v_mfma_scale_f32_32x32x64_f8f6f4 in its FP6 form:
-// lane (co = lane & 31, kg = lane >> 5): 32 six-bit e2m3 fields, field i at bit 6 i = [wl * 2^11 (8) | wh (8)] of half-chunk 0's channels
-// 8kg..8kg+7, then the same of half-chunk 1, all divided by ONE power of two t = 2^(e - 2) (e: exponent of the block's largest magnitude; one up
-// where that would land above 7.75) = 24 bytes; byte 24 = E8M0 of t * 2^-11 (the lane's scale operand: it undoes the 2^11 on BOTH correction
-// terms - the activations carry [xh | xl * 2^11] in the same positions), bytes 25-31 zero.
-static void sx_pack_chunk6(_Float16* packed, long cstep, int NT, int nt, const double* col /* [32 k][32 co] */, double scale) {
-    char* base = reinterpret_cast<char*>(packed) + (cstep * NT + nt) * 4096;
-    for (int lane = 0; lane < 64; ++lane) {
-        double f[32];
-        double mx = 0.0;
-        for (int hc = 0; hc < 2; ++hc)
-            for (int e = 0; e < 8; ++e) {
-                float v = (float)(col[(hc * 16 + (lane >> 5) * 8 + e) * 32 + (lane & 31)] * scale);
-                v = v > 65504.f ? 65504.f : (v < -65504.f ? -65504.f : v);
-                const _Float16 hi = (_Float16)v;
-                const _Float16 lo = (_Float16)(v - (float)hi);
-                reinterpret_cast<_Float16*>(base + hc * 1024)[lane * 8 + e] = hi;
-                f[hc * 16 + e] = ldexp((double)(float)lo, 11);
-                f[hc * 16 + 8 + e] = (double)(float)hi;
-                mx = fmax(mx, fmax(fabs(f[hc * 16 + e]), fabs(f[hc * 16 + 8 + e])));
-            }
-        int te = -100;                                       // t = 2^te
-        if (mx > 0.0) {
-            int e2;
-            frexp(mx, &e2);                                  // mx in [2^(e2-1), 2^e2)
-            te = e2 - 1 - 2;
-            if (ldexp(mx, -te) > 7.75) ++te;
-            if (te < -100) te = -100;
-        }
-        unsigned fields[32];
-        for (int i = 0; i < 32; ++i) fields[i] = sx_e2m3(ldexp(f[i], -te));
-        unsigned q[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (int i = 0; i < 32; ++i) {
-            const int bit = 6 * i;
-            q[bit >> 5] |= fields[i] << (bit & 31);
-            if ((bit & 31) > 26) q[(bit >> 5) + 1] |= fields[i] >> (32 - (bit & 31));
-        }
-        q[6] = (unsigned)(te - 11 + 127);
-        memcpy(base + 2048 + lane * 16, q, 16);
-        memcpy(base + 3072 + lane * 16, q + 4, 16);
-    }
-}
-
-extern "C" int cer_conv3x3_s16_pack(const float* w, void* packed_v, int Cout, int Cin, const int* ch, const int* kind, const int* log2sx,
-                                    int nsrc, int collapsed, int log2S) {
-    if (!w || !packed_v || !ch || !kind || !log2sx) return CER_EINVAL;
-    if ((collapsed & 6) == 6) return CER_EINVAL;
-    const int fp6 = (collapsed & 4) != 0;                   // tensor sources in the FP6-correction form (CER_EPI_CORR_FP6 launches)
-    const int fp8 = (collapsed & 2) != 0 || fp6;            // ... in the fp8-correction form (CER_EPI_CORR_FP8 launches): same step structure
-    collapsed &= 1;
-    if (cer_conv3x3_s16_packed_size(Cout, ch, kind, nsrc, collapsed) < 0) return CER_ESHAPE;
-    int order[CER_CONV_MAX_SRC], c0[CER_CONV_MAX_SRC];
-    sx_order(kind, nsrc, order);
-    int c = 0;
-    for (int s = 0; s < nsrc; ++s) { c0[s] = c; c += ch[s]; }
-    if (c != Cin) return CER_ESHAPE;
-    _Float16* packed = (_Float16*)packed_v;
-    const int NT = Cout / 32;
-    double col[16 * 32];
-    long step = 0;
-    for (int oi = 0; oi < nsrc; ++oi) {
-        const int s = order[oi];
-        const double scale = ldexp(1.0, log2S - log2sx[s]);
-        if (kind[s] != 1 && fp8) {
-            double col32[32 * 32];
-            for (int c32 = 0; c32 < ch[s] / 32; ++c32)
-                for (int tap = 0; tap < 9; ++tap, step += 2)
-                    for (int nt = 0; nt < NT; ++nt) {
-                        for (int k = 0; k < 32; ++k)
-                            for (int j = 0; j < 32; ++j) col32[k * 32 + j] = w[((long)(nt * 32 + j) * Cin + c0[s] + c32 * 32 + k) * 9 + tap];
-                        if (fp6) sx_pack_chunk6(packed, step / 2, NT, nt, col32, scale);
-                        else sx_pack_chunk8(packed, step / 2, NT, nt, col32, scale);
-                    }
-        } else if (kind[s] != 1) {
-            for (int g = 0; g < ch[s] / 16; ++g)
-                for (int tap = 0; tap < 9; ++tap, ++step)
-                    for (int nt = 0; nt < NT; ++nt) {
-                        for (int k = 0; k < 16; ++k)
-                            for (int j = 0; j < 32; ++j) col[k * 32 + j] = w[((long)(nt * 32 + j) * Cin + c0[s] + g * 16 + k) * 9 + tap];
-                        sx_pack_slice(packed, step, NT, nt, col, scale);
-                    }
-        } else if (collapsed) {
-            for (int g = 0; g < 6; ++g, ++step)
-                for (int nt = 0; nt < NT; ++nt) {
-                    for (int k = 0; k < 16; ++k)
-                        for (int j = 0; j < 32; ++j) col[k * 32 + j] = sx_w9(w, Cin, nt * 32 + j, c0[s], g * 16 + k);
-                    sx_pack_slice(packed, step, NT, nt, col, scale);
-                }
-        } else {
-            for (int g = 0; g < 4; ++g)
-                for (int tap = 0; tap < 9; ++tap, ++step)
-                    for (int nt = 0; nt < NT; ++nt) {
-                        for (int k = 0; k < 16; ++k)
-                            for (int j = 0; j < 32; ++j) {
-                                const int ci = g * 16 + k;
-                                col[k * 32 + j] = ci < 49 ? w[((long)(nt * 32 + j) * Cin + c0[s] + ci) * 9 + tap] : 0.0;
-                            }
-                        sx_pack_slice(packed, step, NT, nt, col, scale);
-                    }
-        }
-    }
-    return CER_OK;
-}
-
-// delta head projection: w2 OIHW [1, C, 3, 3] -> A fragments [C/32][k16-step 2][hi|lo][lane][8]: lane (tap = lane & 31, kg = lane >> 5)
-// holds channels 32*blk + 16*jp + 8*kg + e, scaled by 2^log2s (tap >= 9: zero)
-extern "C" long cer_delta_proj_s16_packed_size(int C) { return C % 128 ? CER_ESHAPE : (long)(C / 32) * 2 * 2 * 512; }
-
-extern "C" int cer_delta_proj_s16_pack(const float* w2, void* packed_v, int C, int* log2s_out) {
-    if (!w2 || !packed_v || !log2s_out) return CER_EINVAL;
-    if (C % 128) return CER_ESHAPE;
-    double m = 0.0;
-    for (long i = 0; i < (long)C * 9; ++i) m = fmax(m, fabs((double)w2[i]));
-    const int log2s = m > 0.0 ? (int)floor(log2(16384.0 / m)) : 14;
-    *log2s_out = log2s;
-    _Float16* packed = (_Float16*)packed_v;
-    for (int blk = 0; blk < C / 32; ++blk)
-        for (int jp = 0; jp < 2; ++jp)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int e = 0; e < 8; ++e) {
-                    const int tap = lane & 31, c = blk * 32 + jp * 16 + (lane >> 5) * 8 + e;
-                    float v = tap < 9 ? (float)ldexp((double)w2[(long)c * 9 + tap], log2s) : 0.f;
-                    v = v > 65504.f ? 65504.f : (v < -65504.f ? -65504.f : v);
-                    const _Float16 hi = (_Float16)v;
-                    const _Float16 lo = (_Float16)(v - (float)hi);
-                    packed[(((long)blk * 2 + jp) * 2 + 0) * 512 + lane * 8 + e] = hi;
-                    packed[(((long)blk * 2 + jp) * 2 + 1) * 512 + lane * 8 + e] = lo;
-                }
-    return CER_OK;
-}
 
 template <int WM_, int WN_, int MT, int F8>
 static int sx_launch(S16Args& a, int epi, hipStream_t st) {

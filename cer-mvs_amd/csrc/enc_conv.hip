@@ -481,37 +481,6 @@ __global__ __launch_bounds__(ES_NTHR, 2) void enc_conv32_stream_kernel(const Enc
 #endif
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// generic weight packing: OIHW [Cout, Cin, k, k] (k = 1 or 3) -> [chunk32][tap][ntile32][k16-step][hi|lo][lane][8]
-extern "C" long cer_enc_conv_packed_size(int Cout, int Cin, int taps) {
-    if (Cout <= 0 || Cin <= 0 || Cout % 32 || Cin % 32 || (taps != 1 && taps != 9)) return CER_ESHAPE;
-    return (long)(Cin / 32) * taps * (Cout / 32) * 2048;
-}
-
-extern "C" int cer_enc_conv_pack(const float* w, void* packed_v, int Cout, int Cin, int taps) {
-    if (!w || !packed_v) return CER_EINVAL;
-    if (Cout % 32 || Cin % 32 || (taps != 1 && taps != 9)) return CER_ESHAPE;
-    _Float16* packed = (_Float16*)packed_v;
-    const int NT = Cout / 32;
-    for (int kc = 0; kc < Cin / 32; ++kc)
-        for (int tap = 0; tap < taps; ++tap)
-            for (int nt = 0; nt < NT; ++nt)
-                for (int ks = 0; ks < 2; ++ks)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int e = 0; e < 8; ++e) {
-                            const int co = nt * 32 + (lane & 31);
-                            const int ci = kc * 32 + ks * 16 + (lane >> 5) * 8 + e;
-                            float v = w[((long)co * Cin + ci) * taps + tap];
-                            v = v > 65504.f ? 65504.f : (v < -65504.f ? -65504.f : v);
-                            const _Float16 hi = (_Float16)v;
-                            const _Float16 lo = (_Float16)((v - (float)hi) * 2048.0f);
-                            const long base = ((((long)kc * taps + tap) * NT + nt) * 2 + ks) * 2;
-                            packed[(base + 0) * 512 + lane * 8 + e] = hi;
-                            packed[(base + 1) * 512 + lane * 8 + e] = lo;
-                        }
-    return CER_OK;
-}
-
 template <int WAVES_M, int WAVES_N, int WM, int WN, int NBUF, int MINW, int TH, int STRIDE, int TAPS>
 static int ec_launch(EncArgs a, int nimg, int epi, hipStream_t st) {
     constexpr int NB = WAVES_N * WN * 32;

@@ -807,68 +807,6 @@ extern "C" int cer_enc_pc_supported(int Cin, int Cout, int taps, int stride, int
     return 0;
 }
 
-// e2m3 (FP6: 1 sign, 2 exponent, 3 mantissa bits: 0, 0.125 .. 0.875, 1 .. 1.875, 2 .. 3.75, 4 .. 7.5), round to nearest even, saturating
-static unsigned pc_e2m3(double v) {
-    const unsigned sgn = v < 0 ? 32u : 0u;
-    const double m = fabs(v);
-    if (!(m == m) || m >= 7.5) return sgn | 31u;
-    const int E = m < 2.0 ? 0 : (m < 4.0 ? 1 : 2);          // steps of 0.125 (subnormals and [1, 2)), 0.25, 0.5
-    const int q = (int)nearbyint(ldexp(m, 3 - E));          // in units of the step: 0..16 (E = 0: the codes are linear in the value), 8..16
-    return sgn | (unsigned)(E == 0 ? q : 8 * E + q);        // (q = 16 carries into the next exponent's first code)
-}
-
-// Weights of the FP6-correction form (round 6): cer_enc_conv_pack's order and size, [chunk32][tap][ntile32][k16-step][hi | q][lane][16 B]: the hi
-// plane as before (f16 hi halves of channels 16 ks + 8 kg + 0..7 for output channel lane & 31); the q planes of a tap's two steps hold the
-// lane's K block of v_mfma_scale_f32_32x32x64_f8f6f4 in e2m3: 32 six-bit fields, field i at bit 6 i = [wl' (8) | wh (8)] of step 0, then of step
-// 1 (wl' = (w - wh) 2^11), divided by t = 2^(e - 2), e the exponent of the block's largest magnitude (one up where that would land above 7.75):
-// dwords 0-3 in step 0's q plane, dwords 4-5 | E8M0 byte of t 2^-11 | 0 in step 1's.
-extern "C" int cer_enc_conv_pack_f6(const float* w, void* packed_v, int Cout, int Cin, int taps) {
-    if (!w || !packed_v) return CER_EINVAL;
-    if (Cout % 32 || Cin % 32 || (taps != 1 && taps != 9)) return CER_ESHAPE;
-    _Float16* packed = (_Float16*)packed_v;
-    const int NT = Cout / 32;
-    for (int kc = 0; kc < Cin / 32; ++kc)
-        for (int tap = 0; tap < taps; ++tap)
-            for (int nt = 0; nt < NT; ++nt)
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int co = nt * 32 + (lane & 31);
-                    const long base = (((long)kc * taps + tap) * NT + nt) * 4;              // 512-half planes: (ks 0: hi, q), (ks 1: hi, q)
-                    double f[32], mx = 0.0;
-                    for (int ks = 0; ks < 2; ++ks)
-                        for (int e = 0; e < 8; ++e) {
-                            const int ci = kc * 32 + ks * 16 + (lane >> 5) * 8 + e;
-                            float v = w[((long)co * Cin + ci) * taps + tap];
-                            v = v > 65504.f ? 65504.f : (v < -65504.f ? -65504.f : v);
-                            const _Float16 hi = (_Float16)v;
-                            const _Float16 lo = (_Float16)((v - (float)hi) * 2048.0f);
-                            packed[(base + 2 * ks) * 512 + lane * 8 + e] = hi;
-                            f[ks * 16 + e] = (double)(float)lo;
-                            f[ks * 16 + 8 + e] = (double)(float)hi;
-                            mx = fmax(mx, fmax(fabs(f[ks * 16 + e]), fabs(f[ks * 16 + 8 + e])));
-                        }
-                    int te = -100;                                                            // t = 2^te
-                    if (mx > 0.0) {
-                        int e2;
-                        frexp(mx, &e2);                                                       // mx in [2^(e2-1), 2^e2)
-                        te = e2 - 1 - 2;
-                        if (ldexp(mx, -te) > 7.75) ++te;
-                        if (te < -100) te = -100;
-                    }
-                    unsigned q[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-                    for (int i = 0; i < 32; ++i) {
-                        const unsigned fld = pc_e2m3(ldexp(f[i], -te));
-                        const int bit = 6 * i;
-                        q[bit >> 5] |= fld << (bit & 31);
-                        if ((bit & 31) > 26) q[(bit >> 5) + 1] |= fld >> (32 - (bit & 31));
-                    }
-                    q[6] = (unsigned)(te - 11 + 127);
-                    q[7] = 0;
-                    memcpy(reinterpret_cast<char*>(packed + (base + 1) * 512) + lane * 16, q, 16);
-                    memcpy(reinterpret_cast<char*>(packed + (base + 3) * 512) + lane * 16, q + 4, 16);
-                }
-    return CER_OK;
-}
-
 extern "C" int cer_enc_pc_tiles(int ho, int wo, int Cout, int taps, int stride) {
     const int th = pc_tile_rows(Cout, taps, stride);
     return ((wo + 31) / 32) * ((ho + th - 1) / th);

@@ -16,6 +16,7 @@
 // per channel for the instance norm that follows (butterfly over the 32 pixel lanes, combined across the waves in LDS;
 // deterministic: one record per tile, reduced in fp64 by cer_enc_stats_reduce_f32).
 #include "common.hpp"
+#include "pack.hpp"       // SM_STEPS; weight layout: pack.cpp
 #include <math.h>
 #include <stdlib.h>
 #include <type_traits>
@@ -29,7 +30,6 @@ typedef float sm_floatx16 __attribute__((ext_vector_type(16)));
 #define SM_PR (2 * SM_TH + 5)          // patch rows    (21)
 #define SM_PC 72                       // patch columns (2 * 32 + 5 = 69, padded: the last k-group of ox = 31 reads column 69)
 #define SM_PLANE (SM_PR * SM_PC * 8)   // bytes per plane
-#define SM_STEPS 14
 #define SM_XLOG2 14                    // activation scale 2^14 (|x| <= 1 after normalisation)
 
 __global__ __launch_bounds__(256, 2) void enc_stem_s16_kernel(const float* __restrict__ img, const _Float16* __restrict__ wpk,
@@ -390,40 +390,7 @@ __global__ __launch_bounds__(512, 2) void enc_stem_pc_kernel(const float* __rest
 }
 
 // ---------------------------------------------------------------------------------------- host side
-extern "C" long cer_enc_stem_s16_packed_size(void) { return 2L * SM_STEPS * 2 * 64 * 8; }     // halves: two layouts (below)
-
 extern "C" int cer_enc_stem_s16_tiles(int ho, int wo) { return ((ho + SM_TH - 1) / SM_TH) * ((wo + SM_TW - 1) / SM_TW); }
-
-// w_oihw [32][3][7][7] (host) -> A fragments [step][hi | lo][lane][8]: lane (channel = lane & 31, kg = lane >> 5), element e:
-// ky = step >> 1, column = 4 (step & 1) + 2 kg + (e >> 2), input channel = e & 3 (column 7 and channel 3 are padding: zero).
-// A second copy follows with the padding column in FRONT (kernel column = that index - 1): the layout of enc_stem_pc_kernel, whose
-// patch starts one image column earlier (16-byte aligned loads).  *log2s_w = the power-of-two weight scale that was applied.
-extern "C" int cer_enc_stem_s16_pack(const float* w_oihw, void* packed_v, int* log2s_w) {
-    if (!w_oihw || !packed_v || !log2s_w) return CER_EINVAL;
-    double wmax = 0.0;
-    for (int i = 0; i < 32 * 147; ++i) wmax = fmax(wmax, fabs((double)w_oihw[i]));
-    int k = wmax > 0.0 ? (int)floor(log2(16384.0 / wmax)) : 0;
-    if (k > 24) k = 24;
-    if (k < -24) k = -24;
-    *log2s_w = k;
-    const float sc = ldexpf(1.0f, k);
-    _Float16* packed = static_cast<_Float16*>(packed_v);
-    for (int layout = 0; layout < 2; ++layout)
-        for (int s = 0; s < SM_STEPS; ++s)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int e = 0; e < 8; ++e) {
-                    const int ch = lane & 31, kg = lane >> 5;
-                    const int ky = s >> 1, col = 4 * (s & 1) + 2 * kg + (e >> 2) - layout, ci = e & 3;
-                    float v = 0.f;
-                    if (col >= 0 && col < 7 && ci < 3) v = w_oihw[((ch * 3 + ci) * 7 + ky) * 7 + col] * sc;
-                    const _Float16 hi = (_Float16)v;
-                    const _Float16 lo = (_Float16)(v - (float)hi);
-                    _Float16* dst = packed + (long)layout * SM_STEPS * 2 * 64 * 8;
-                    dst[((long)(s * 2 + 0) * 64 + lane) * 8 + e] = hi;
-                    dst[((long)(s * 2 + 1) * 64 + lane) * 8 + e] = lo;
-                }
-    return CER_OK;
-}
 
 extern "C" int cer_enc_stem_s16(const float* images, const void* packed_w, const float* bias, float* out, float* stats_partial, int N, int H,
                                 int W, int normalize, int log2s_w, void* stream) {

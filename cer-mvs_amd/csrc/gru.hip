@@ -17,6 +17,7 @@
 //     is generated while staging (source kind 1);
 //   * gate math (sigmoid / tanh / GRU blend / ReLU) runs in the MFMA epilogue on the accumulators.
 #include "common.hpp"
+#include "pack.hpp"       // weight layout: pack.cpp
 #include <string.h>
 
 typedef float floatx4 __attribute__((ext_vector_type(4)));
@@ -27,6 +28,7 @@ typedef float floatx4 __attribute__((ext_vector_type(4)));
 #define CV_HW (CV_TW + 2)
 #define CV_ROWS (CV_HH * CV_HW)      // 180 halo pixels
 #define CV_KC 32                     // channels per staged chunk
+static_assert(CV_KC == PACK_KC, "padded_channels (pack.hpp) pads to the staged chunk");
 #define CV_LS 40                     // LDS floats per halo pixel (32 + 8 pad)
 
 struct ConvArgs {
@@ -189,46 +191,6 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(const ConvArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------- host side
-
-static int padded_channels(int ch, int kind) { return kind == 1 ? 64 : ((ch + CV_KC - 1) / CV_KC) * CV_KC; }
-
-extern "C" long cer_conv3x3_packed_size(int Cout, int Kpad) {
-    if (Cout <= 0 || Kpad <= 0 || Cout % 16 || Kpad % 16) return CER_ESHAPE;
-    return (long)(Kpad / 16) * 9 * (Cout / 16) * 256;
-}
-
-extern "C" int cer_conv3x3_pack_f32(const float* w, float* packed, int Cout, int Cin, const int* ch, const int* kind, int nsrc) {
-    if (!w || !packed || !ch || !kind || nsrc <= 0 || nsrc > CER_CONV_MAX_SRC) return CER_EINVAL;
-    if (Cout % 16) return CER_ESHAPE;
-    int real = 0, kpad = 0;
-    for (int s = 0; s < nsrc; ++s) {
-        if (kind[s] == 1 && ch[s] != 49) return CER_ESHAPE;
-        real += ch[s];
-        kpad += padded_channels(ch[s], kind[s]);
-    }
-    if (real != Cin) return CER_ESHAPE;
-    // padded K index -> real input channel (or -1)
-    int* map = new int[kpad];
-    int k = 0, c = 0;
-    for (int s = 0; s < nsrc; ++s) {
-        const int pc = padded_channels(ch[s], kind[s]);
-        for (int i = 0; i < pc; ++i) map[k++] = (i < ch[s]) ? c + i : -1;
-        c += ch[s];
-    }
-    const int NT = Cout / 16;
-    for (int kc = 0; kc < kpad / 16; ++kc)
-        for (int tap = 0; tap < 9; ++tap)
-            for (int nt = 0; nt < NT; ++nt)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int s4 = 0; s4 < 4; ++s4) {
-                        const int co = nt * 16 + (lane & 15);
-                        const int ci = map[kc * 16 + (lane >> 4) * 4 + s4];
-                        const float v = ci < 0 ? 0.f : w[((long)co * Cin + ci) * 9 + tap];
-                        packed[((((long)kc * 9 + tap) * NT + nt) * 64 + lane) * 4 + s4] = v;
-                    }
-    delete[] map;
-    return CER_OK;
-}
 
 template <int WAVES_M, int WAVES_N, int WM, int WN>
 static int launch_conv(const ConvArgs& a, int epi, int nby, hipStream_t st) {

@@ -30,6 +30,7 @@
 // Compile-time experiment switches (default off; DESIGN.md roadmap): HX_ABL (phase ablations), HX_TRACE (cycle stamps),
 // HX_CFG / HX_TH (other tilings), HX_EPI2=0 (direct 4-byte epilogue).
 #include "common.hpp"
+#include "pack.hpp"       // weight layouts: pack.cpp
 #include <stdlib.h>
 #include <string.h>
 #ifndef HX_ABL
@@ -50,6 +51,7 @@ typedef float floatx16 __attribute__((ext_vector_type(16)));
 #define HX_HW (HX_TW + 2)
 #define HX_ROWS (HX_HH * HX_HW)        // 204 halo pixels
 #define HX_KC 32                       // channels per chunk
+static_assert(HX_KC == PACK_KC, "padded_channels (pack.hpp) pads to the chunk");
 #define HX_AS 144                      // LDS bytes per halo pixel: 32 hi | 32 lo | 16 pad
 #define HX_A_BYTES (HX_ROWS * HX_AS)   // 29376
 #define HX_EPI_DELTA 4                 // conv + ReLU + projection onto the 9 taps of the 256->1 delta conv (cer_mvs.h: CER_EPI_DELTA)
@@ -650,134 +652,6 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, MINW) void conv3x3_f16x3_ke
 
 // ---------------------------------------------------------------------------------------- host side
 
-static int hx_padded_channels(int ch, int kind) { return kind == 1 ? 64 : ((ch + HX_KC - 1) / HX_KC) * HX_KC; }   // kinds 0 and 3: tensors
-
-extern "C" long cer_conv3x3_f16x3_packed_size(int Cout, int Kpad) {
-    if (Cout <= 0 || Kpad <= 0 || Cout % 32 || Kpad % 32) return CER_ESHAPE;
-    return (long)(Kpad / 32) * 9 * (Cout / 32) * 2048;     // in halves (2 bytes each)
-}
-
-// OIHW fp32 -> [chunk32][tap][ntile32][k16-step][hi|lo][lane][8] halves, lo scaled by 2^11
-extern "C" int cer_conv3x3_f16x3_pack(const float* w, void* packed_v, int Cout, int Cin, const int* ch, const int* kind, int nsrc) {
-    if (!w || !packed_v || !ch || !kind || nsrc <= 0 || nsrc > CER_CONV_MAX_SRC) return CER_EINVAL;
-    if (Cout % 32) return CER_ESHAPE;
-    _Float16* packed = (_Float16*)packed_v;
-    int real = 0, kpad = 0;
-    for (int s = 0; s < nsrc; ++s) {
-        if (kind[s] == 1 && ch[s] != 49) return CER_ESHAPE;
-        real += ch[s];
-        kpad += hx_padded_channels(ch[s], kind[s]);
-    }
-    if (real != Cin) return CER_ESHAPE;
-    int* map = new int[kpad];
-    int k = 0, c = 0;
-    for (int s = 0; s < nsrc; ++s) {
-        const int pc = hx_padded_channels(ch[s], kind[s]);
-        for (int i = 0; i < pc; ++i) map[k++] = (i < ch[s]) ? c + i : -1;
-        c += ch[s];
-    }
-    const int NT = Cout / 32;
-    for (int kc = 0; kc < kpad / 32; ++kc)
-        for (int tap = 0; tap < 9; ++tap)
-            for (int nt = 0; nt < NT; ++nt)
-                for (int ks = 0; ks < 2; ++ks)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int e = 0; e < 8; ++e) {
-                            const int co = nt * 32 + (lane & 31);
-                            const int ci = map[kc * 32 + ks * 16 + (lane >> 5) * 8 + e];
-                            float v = ci < 0 ? 0.f : w[((long)co * Cin + ci) * 9 + tap];
-                            v = v > 65504.f ? 65504.f : (v < -65504.f ? -65504.f : v);
-                            const _Float16 hi = (_Float16)v;
-                            const _Float16 lo = (_Float16)((v - (float)hi) * 2048.0f);
-                            const long base = ((((long)kc * 9 + tap) * NT + nt) * 2 + ks) * 2;   // (hi|lo) plane index
-                            packed[(base + 0) * 512 + lane * 8 + e] = hi;
-                            packed[(base + 1) * 512 + lane * 8 + e] = lo;
-                        }
-    delete[] map;
-    return CER_OK;
-}
-
-// Collapsed packing: same step order as above, except that a kind-1 (disparity) source contributes 3 single-tap steps
-// holding the 81-tap filter  W9[co][s] = sum_{t + u = s} w[co][u][t]  -  [|s - 4| <= 1] * sum_u w[co][u][t = s - 3]
-// (t over the 3x3 conv taps, u over the 7x7 unfold offsets, s over the 9x9 window; the second term is the centre
-// subtraction of core/update.py:84).  Valid for pixels whose 3x3 neighbourhood lies inside the image.
-extern "C" long cer_conv3x3_f16x3_collapsed_size(int Cout, const int* ch, const int* kind, int nsrc) {
-    if (!ch || !kind || nsrc <= 0 || nsrc > CER_CONV_MAX_SRC || Cout <= 0 || Cout % 32) return CER_ESHAPE;
-    long steps = 0;
-    for (int s = 0; s < nsrc; ++s) steps += kind[s] == 1 ? 3 : (hx_padded_channels(ch[s], kind[s]) / 32) * 9;
-    return steps * (Cout / 32) * 2048;
-}
-
-static void hx_pack_step(_Float16* packed, long step, int NT, int nt, const float* col /* [32 k][32 co] */) {
-    for (int ks = 0; ks < 2; ++ks)
-        for (int lane = 0; lane < 64; ++lane)
-            for (int e = 0; e < 8; ++e) {
-                float v = col[(ks * 16 + (lane >> 5) * 8 + e) * 32 + (lane & 31)];
-                v = v > 65504.f ? 65504.f : (v < -65504.f ? -65504.f : v);
-                const _Float16 hi = (_Float16)v;
-                const _Float16 lo = (_Float16)((v - (float)hi) * 2048.0f);
-                const long base = ((step * NT + nt) * 2 + ks) * 2;
-                packed[(base + 0) * 512 + lane * 8 + e] = hi;
-                packed[(base + 1) * 512 + lane * 8 + e] = lo;
-            }
-}
-
-extern "C" int cer_conv3x3_f16x3_pack_collapsed(const float* w, void* packed_v, int Cout, int Cin, const int* ch, const int* kind, int nsrc) {
-    if (!w || !packed_v || !ch || !kind || nsrc <= 0 || nsrc > CER_CONV_MAX_SRC) return CER_EINVAL;
-    if (Cout % 32) return CER_ESHAPE;
-    int real = 0;
-    for (int s = 0; s < nsrc; ++s) {
-        if (kind[s] == 1 && ch[s] != 49) return CER_ESHAPE;
-        real += ch[s];
-    }
-    if (real != Cin) return CER_ESHAPE;
-    _Float16* packed = (_Float16*)packed_v;
-    const int NT = Cout / 32;
-    float col[32 * 32];
-    long step = 0;
-    int c = 0;
-    for (int s = 0; s < nsrc; ++s) {
-        if (kind[s] == 1) {
-            for (int kc = 0; kc < 3; ++kc, ++step)
-                for (int nt = 0; nt < NT; ++nt) {
-                    for (int k = 0; k < 32; ++k)
-                        for (int j = 0; j < 32; ++j) {
-                            const int sidx = kc * 32 + k, co = nt * 32 + j;
-                            double acc = 0.0;
-                            if (sidx < 81) {
-                                const int sy = sidx / 9, sx = sidx % 9;
-                                for (int ty = 0; ty < 3; ++ty)
-                                    for (int tx = 0; tx < 3; ++tx) {
-                                        const int uy = sy - ty, ux = sx - tx;
-                                        if (uy >= 0 && uy < 7 && ux >= 0 && ux < 7) acc += (double)w[((long)co * Cin + c + uy * 7 + ux) * 9 + ty * 3 + tx];
-                                    }
-                                if (sy >= 3 && sy <= 5 && sx >= 3 && sx <= 5) {
-                                    const int t = (sy - 3) * 3 + (sx - 3);
-                                    for (int u = 0; u < 49; ++u) acc -= (double)w[((long)co * Cin + c + u) * 9 + t];
-                                }
-                            }
-                            col[k * 32 + j] = (float)acc;
-                        }
-                    hx_pack_step(packed, step, NT, nt, col);
-                }
-        } else {
-            const int pc = hx_padded_channels(ch[s], kind[s]);
-            for (int kc = 0; kc < pc / 32; ++kc)
-                for (int tap = 0; tap < 9; ++tap, ++step)
-                    for (int nt = 0; nt < NT; ++nt) {
-                        for (int k = 0; k < 32; ++k)
-                            for (int j = 0; j < 32; ++j) {
-                                const int ci = kc * 32 + k;
-                                col[k * 32 + j] = ci < ch[s] ? w[((long)(nt * 32 + j) * Cin + c + ci) * 9 + tap] : 0.f;
-                            }
-                        hx_pack_step(packed, step, NT, nt, col);
-                    }
-        }
-        c += ch[s];
-    }
-    return CER_OK;
-}
-
 template <int WAVES_M, int WAVES_N, int WM, int WN, int NBUF, int MINW, bool PS>
 static int hx_launch_ps(const ConvArgsX& a, int epi, int nby, hipStream_t st) {
     constexpr int NB = WAVES_N * WN * 32;
@@ -837,7 +711,7 @@ extern "C" int cer_conv3x3_f16x3(const cer_conv_inputs* in, const void* packed_w
         a.src[s] = in->src[s];
         a.ch[s] = in->ch[s];
         a.kind[s] = in->kind[s];
-        a.chpad[s] = hx_padded_channels(in->ch[s], in->kind[s]);
+        a.chpad[s] = padded_channels(in->ch[s], in->kind[s]);
     }
     if (!cer_aligned16(packed_w) || !cer_aligned16(packed_collapsed)) return CER_EALIGN;
     a.wpk = (const _Float16*)packed_w;
@@ -875,30 +749,6 @@ extern "C" int cer_conv3x3_f16x3(const cer_conv_inputs* in, const void* packed_w
 }
 
 // ---- delta head tail for the fused path ------------------------------------------------------------------
-// w2 OIHW [1, C, 3, 3] -> B fragments of the [C x 9 (padded to 32)] projection, per 128-channel half:
-// [half][k16-step 8][hi|lo][lane 64][8] halves; lane (tap = lane & 31, kg = lane >> 5) holds channels
-// half*128 + ks*16 + kg*8 + e.
-extern "C" long cer_delta_proj_packed_size(int C) { return C % 128 ? CER_ESHAPE : (long)(C / 128) * 8 * 2 * 512; }
-
-extern "C" int cer_delta_proj_pack(const float* w2, void* packed_v, int C) {
-    if (!w2 || !packed_v) return CER_EINVAL;
-    if (C % 128) return CER_ESHAPE;
-    _Float16* packed = (_Float16*)packed_v;
-    for (int hf = 0; hf < C / 128; ++hf)
-        for (int ks = 0; ks < 8; ++ks)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int e = 0; e < 8; ++e) {
-                    const int tap = lane & 31, c = hf * 128 + ks * 16 + (lane >> 5) * 8 + e;
-                    float v = tap < 9 ? w2[(long)c * 9 + tap] : 0.f;
-                    v = v > 65504.f ? 65504.f : (v < -65504.f ? -65504.f : v);
-                    const _Float16 hi = (_Float16)v;
-                    const _Float16 lo = (_Float16)((v - (float)hi) * 2048.0f);
-                    packed[(((long)hf * 8 + ks) * 2 + 0) * 512 + lane * 8 + e] = hi;
-                    packed[(((long)hf * 8 + ks) * 2 + 1) * 512 + lane * 8 + e] = lo;
-                }
-    return CER_OK;
-}
-
 // delta[p] = 0.01 * (bias + sum_half sum_tap T[half][tap][p + (ky-1, kx-1)]) (zero outside), disp_out = disp_in + delta
 __global__ __launch_bounds__(256) void delta_sum_kernel(const float* __restrict__ T, int nhalf, float bias, const float* __restrict__ disp_in,
                                                         float* __restrict__ disp_out, float* __restrict__ delta, int h, int w) {

@@ -306,7 +306,7 @@ int cer_conv3x3_f16x3(const cer_conv_inputs* in, const void* packed_w, const voi
  * with CER_EPI_CORR_FP8: per 32-channel tap and 32 output channels 4 KiB = f16 hi halves of the two 16-channel halves | the e4m3
  * A operand of v_mfma_scale_f32_32x32x64_f8f6f4: [lo * 2^5 | hi * 2^-6] of each half); same size.  `collapsed | 4` (round 6): the FP6 form for
  * launches with CER_EPI_CORR_FP6 (the instruction's e2m3 A operand: 32 six-bit fields [lo * 2^11 | hi] of each half over one power of two per
- * lane, whose E8M0 byte follows the 24 bytes of fields; csrc/conv_s16.hip sx_pack_chunk6); same size.  A launch with CER_EPI_CORR_FP8 / _FP6
+ * lane, whose E8M0 byte follows the 24 bytes of fields; csrc/pack.cpp pack_chunk6); same size.  A launch with CER_EPI_CORR_FP8 / _FP6
  * and a kind-1 source needs packed_collapsed AND edge_w (the fp8 kernels evaluate the disparity source in the collapsed form with
  * the rim correction only; CER_ESHAPE otherwise); tile_mt = 4 is not available for Cout = 64 in that form (3 is used).
  * cer_conv3x3_s16: bias (fp32 [Cout], plain) or init (acc32 [., Cout]) - at most one - seed the accumulators; epilogues:
