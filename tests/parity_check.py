@@ -1,6 +1,7 @@
 """Element-wise parity checking at production shapes: helpers shared by tests/test_parity_check_cpu.py (which proves on planted
 corruptions that the checker sees what a global mean cannot) and tests/test_fullsize_parity_gpu.py (which applies it to the HIP
-kernels of one GRU iteration and to the cost volume).  Plain module, no fixtures.
+kernels of one GRU iteration and to the cost volume) and tests/test_encoder_parity_gpu.py (the encoder kernels, one launch at a time: the
+float64 pieces and tile geometries at the end of this file).  Plain module, no fixtures.
 
 Conventions: an image tensor is pixel-major, ``[h*w, C]`` or ``[h*w]``; a *tile* is a (rows, columns) block of pixels - 8 x 16 by
 default, the smallest tile the s16 convolutions launch (16 x 16 for the tall ones); a *seam* is the border between two 32-pixel
@@ -225,3 +226,205 @@ def cost_subset(h, w, period=32, tile=(8, 16), interior_fraction=0.05, seed=1):
     must[:th], must[-th:], must[:, :tw], must[:, -tw:] = True, True, True, True
     pick = torch.from_numpy(hash_uniform(h * w, seed) * 0.5 + 0.5).reshape(h, w) < interior_fraction
     return (must | pick).reshape(-1).nonzero().reshape(-1), must
+
+
+# ------------------------------------------------------------------------------------------------ encoder launches in float64
+# Tile geometries of the encoder kernels (rows, columns) - the ``tile=`` argument of the checks above: 8 x 32 everywhere except the
+# stride-2 3 x 3 convolution (2 x 32; the tiled engine's stride-2 1 x 1 too) and the 128-channel context head of csrc/enc_pc.hip (4 x 32).
+ENC_TILE = (8, 32)
+ENC_TILE_S2 = (2, 32)
+ENC_TILE_CTX = (4, 32)
+U24 = 2.0 ** -24             # unit roundoff of fp32
+
+
+def enc_pc_tile(cout, taps, stride):
+    """Tile of cer_enc_pc_conv (csrc/enc_pc.hip: PcCfg::TH, pc_tile_rows)."""
+    return ENC_TILE_S2 if (taps == 9 and stride == 2) else (ENC_TILE_CTX if cout >= 128 else ENC_TILE)
+
+
+def enc_conv_tile(stride):
+    """Tile of cer_enc_conv_f16x3 (csrc/enc_conv.hip: cer_enc_conv_tiles)."""
+    return ENC_TILE_S2 if stride == 2 else ENC_TILE
+
+
+def _enc_term64(X, s, relu):
+    x = X.detach().cpu().double()
+    N, C = x.shape[0], x.shape[-1]
+    if s is not None:
+        st = s.detach().cpu().double().view(N, *([1] * (x.dim() - 2)), C, 2)
+        mean, rstd = st[..., 0], st[..., 1]
+        y, mag = (x - mean) * rstd, (x.abs() + mean.abs()) * rstd
+    else:
+        y, mag = x, x.abs()
+    return (torch.relu(y) if relu else y), mag
+
+
+def enc_input_ref64(A, sA, rA, B=None, sB=None, rB=False, relu_sum=False):
+    """The virtual input of an encoder convolution, relu_s(fa(A) + fb(B)) with f = the optional (x - mean) * rstd of the very stats
+    tensor the kernel is given ([N * C, 2] = (mean, rstd)) followed by the optional ReLU; A, B: [N, ..., C] channels-last.
+    -> (x64, mag_in) with mag_in = (|A| + |mean_A|) * rstd_A [+ the same of B]: the scale of the fp32 roundings in forming x."""
+    y, mag = _enc_term64(A, sA, rA)
+    if B is not None:
+        yb, mb = _enc_term64(B, sB, rB)
+        y, mag = y + yb, mag + mb
+    return (torch.relu(y) if relu_sum else y), mag
+
+
+def enc_conv_ref64(x64, w, b, taps, stride, mag_in=None):
+    """x64 [N, h, w, Cin] channels-last float64, w [Cout, Cin, k, k], b [Cout] or None -> (conv, mag, mag_form), each
+    [N, ho, wo, Cout] float64: the F.conv2d result (3 x 3 with padding 1, or 1 x 1), mag = conv(|x64|, |w|) + |b|, and mag_form =
+    conv(mag_in, |w|) (None without ``mag_in``)."""
+    import torch.nn.functional as F
+    pad = 1 if taps == 9 else 0
+    w64 = w.detach().cpu().double()
+    assert w64.shape[2] * w64.shape[3] == taps
+    b64 = None if b is None else b.detach().cpu().double()
+    xc = x64.permute(0, 3, 1, 2)
+    N = xc.shape[0]
+    ref = F.conv2d(xc, w64, b64, stride=stride, padding=pad).permute(0, 2, 3, 1)
+    mags = [xc.abs()] + ([mag_in.permute(0, 3, 1, 2)] if mag_in is not None else [])
+    m = F.conv2d(torch.cat(mags, 0), w64.abs(), None, stride=stride, padding=pad).permute(0, 2, 3, 1)
+    mag = m[:N] + (0.0 if b64 is None else b64.abs())
+    return ref, mag, (m[N:] if mag_in is not None else None)
+
+
+def enc_head_ref64(conv, epi, scale=1.0, border=0, fill=None):
+    """Head epilogues of the encoder kernels in float64.  "fmap": ``scale * conv`` into a map with ``border`` texels on every side
+    ([N, ho + 2b, wo + 2b, C]; the border keeps ``fill``, a tensor of that shape, or zeros); "ctx": (tanh of the first half of the
+    channels, relu of the second half)."""
+    if epi == "ctx":
+        half = conv.shape[-1] // 2
+        return torch.tanh(conv[..., :half]), torch.relu(conv[..., half:])
+    assert epi == "fmap"
+    N, ho, wo, C = conv.shape
+    out = torch.zeros(N, ho + 2 * border, wo + 2 * border, C, dtype=torch.float64) if fill is None else fill.detach().cpu().double().clone()
+    out[:, border:border + ho, border:border + wo] = scale * conv
+    return out
+
+
+def instance_stats64(y, eps=1e-5):
+    """[N, ..., C] float64 -> [N * C, 2] float64 (mean, rstd) of InstanceNorm2d (biased variance, eps 1e-5)."""
+    N, C = y.shape[0], y.shape[-1]
+    f = y.reshape(N, -1, C)
+    mean = f.mean(1)
+    var = ((f - mean[:, None]) ** 2).mean(1)
+    return torch.stack([mean, 1.0 / torch.sqrt(var + eps)], -1).reshape(N * C, 2)
+
+
+def check_batch(got, ref64, mag, c, abs_term=0.0, where="", h=None, w=None, tile=ENC_TILE):
+    """``check_elementwise`` over a batch [N, h, w, C] (or [N, h * w, C]): every element of every image against c * mag + abs_term.
+    Raises an AssertionError that names the first failing image and, inside it, the tile / row (``ParityReport.message``); otherwise
+    -> {"max_ratio", "p999_ratio", "max_rel", "p999_rel"}: |err| / bound and |err| / mag over the whole batch."""
+    got = torch.as_tensor(got).detach().cpu().double()
+    N, C = got.shape[0], got.shape[-1]
+    got = got.reshape(N, h * w, C)
+    ref64 = ref64.reshape(N, h * w, C)
+    mag = torch.as_tensor(mag, dtype=torch.float64).expand(N, *mag.shape[1:]).reshape(N, h * w, C)
+    abs_term = torch.as_tensor(abs_term, dtype=torch.float64)
+    abs_term = abs_term.reshape(N, h * w, C) if abs_term.dim() >= 3 else abs_term
+    bound = c * mag + abs_term
+    err = (got - ref64).abs()
+    bad = ~(err <= bound)
+    if bool(bad.any()):
+        n = int(bad.reshape(N, -1).any(1).nonzero()[0])
+        rep = check_elementwise(got[n], ref64[n], mag[n], c, abs_term[n] if abs_term.dim() >= 3 else abs_term, f"{where}, image {n} of {N}",
+                                h=h, w=w, tile=tile)
+        raise AssertionError(f"{int(bad.reshape(N, -1).any(1).sum())} of {N} images fail; the first:\n" + rep.message())
+
+    def top(t):
+        flat = t.reshape(-1)
+        k = max(1, int(math.ceil(0.999 * flat.numel())))
+        return float(flat.max()), float(torch.kthvalue(flat, k).values)
+    mr, pr = top(err / bound.clamp_min(1e-300))
+    ml, pl = top(err / mag.clamp_min(1e-300))
+    return {"max_ratio": mr, "p999_ratio": pr, "max_rel": ml, "p999_rel": pl}
+
+
+def assert_covered_batch(out, where, h, w, tile=ENC_TILE):
+    """``assert_covered`` over a batch [N, h * w, C] / [N, h, w, C]: no NaN sentinel may be left in any image."""
+    out = torch.as_tensor(out).detach().cpu()
+    N = out.shape[0]
+    flat = out.reshape(N, h * w, -1)
+    left = (~torch.isfinite(flat)).reshape(N, -1).any(1)
+    if bool(left.any()):
+        n = int(left.nonzero()[0])
+        assert_covered(flat[n], f"{where}, image {n} of {N}", h, w, tile=tile)
+
+
+def stats_records_ref64(out, tile):
+    """out [N, ho, wo, C] (the kernel's own fp32 output) -> per tile, row-major tile id: (sum, sum of squares, sum of |.|), each
+    [N, tiles, C] float64 - what a statistics record of that tile must hold."""
+    o = torch.as_tensor(out).detach().cpu().double()
+    N, ho, wo, C = o.shape
+    th, tw = tile
+    ty, tx = (ho + th - 1) // th, (wo + tw - 1) // tw
+    p = torch.zeros(N, ty * th, tx * tw, C, dtype=torch.float64)
+    p[:, :ho, :wo] = o
+    p = p.view(N, ty, th, tx, tw, C)
+    red = lambda t: t.sum((2, 4)).reshape(N, ty * tx, C)
+    return red(p), red(p * p), red(p.abs())
+
+
+def check_stats_records(part, out, tile, K, where=""):
+    """Statistics partial records ``part`` [N, tiles, C, 2] against the float64 sums of ``out`` [N, ho, wo, C] over each tile's pixels:
+    |sum - S| <= K 2^-24 sum|o|, |sumsq - Q| <= K 2^-24 sum o^2, every record finite.  -> (ok, message, max ratio); the message names
+    the failing tiles as (image, tile_y, tile_x)."""
+    part = torch.as_tensor(part).detach().cpu().double()
+    S, Q, SA = stats_records_ref64(out, tile)
+    N, nt, C = S.shape
+    if tuple(part.shape) != (N, nt, C, 2):
+        raise ValueError(f"{where}: records {tuple(part.shape)} for {(N, nt, C, 2)}")
+    tiles_x = (out.shape[2] + tile[1] - 1) // tile[1]
+    bs, bq = K * U24 * SA, K * U24 * Q
+    es, eq = (part[..., 0] - S).abs(), (part[..., 1] - Q).abs()
+    bad = ~(es <= bs) | ~(eq <= bq)                       # (a NaN record - the sentinel - compares false: it fails)
+    ratio = torch.maximum(es / bs.clamp_min(1e-300), eq / bq.clamp_min(1e-300))
+    ratio = torch.where(torch.isnan(ratio), torch.full_like(ratio, math.inf), ratio)
+    mx = float(ratio.max())
+    if not bool(bad.any()):
+        return True, f"{where}: all {N * nt} statistics records within bound (max ratio {mx:.3g})", mx
+    tiles = sorted({(int(n), int(t) // tiles_x, int(t) % tiles_x) for n, t in bad.any(-1).nonzero().tolist()})
+    msg = (f"{where}: {len(tiles)} of {N * nt} statistics records ({tile[0]} x {tile[1]} tiles) beyond K = {K} roundings of their tile's "
+           f"sums, worst ratio {mx:.4g}; (image, tile_y, tile_x): " + ", ".join(str(t) for t in tiles[:8]) + (" ..." if len(tiles) > 8 else ""))
+    return False, msg, mx
+
+
+def assert_stats_records(part, out, tile, K, where=""):
+    ok, msg, mx = check_stats_records(part, out, tile, K, where)
+    assert ok, msg
+    return mx
+
+
+def enc_chain_ref64(x, sd, prefix, kind, outputs=None):
+    """The whole "HR" encoder (oracle.cer_oracle.encoder) as a chain of ``enc_input_ref64`` and ``enc_conv_ref64`` with float64
+    instance-norm statistics - the schedule of cer-mvs_amd/encoder_hip.py: raw convolution outputs plus statistics, the normalisation
+    applied by the consumer, the residual merge as a two-tensor virtual input.  x [N, 3, H, W] -> [N, Cout, H/4, W/4] float64.
+    ``outputs`` (a dict) receives every trunk convolution's raw output [N, ho, wo, C] by layer name."""
+    import torch.nn.functional as F
+    inorm = kind == "instance"
+    st = lambda y: instance_stats64(y) if inorm else None
+    wb = lambda name: (sd[prefix + name + ".weight"], sd[prefix + name + ".bias"])
+
+    def conv(name, xin, taps, stride):
+        y = enc_conv_ref64(xin, *wb(name), taps, stride)[0]
+        if outputs is not None:
+            outputs[name] = y
+        return y, st(y)
+    w0, b0 = wb("conv1")
+    raw0 = F.conv2d(x.double(), w0.double(), b0.double(), stride=2, padding=3).permute(0, 2, 3, 1)
+    if outputs is not None:
+        outputs["conv1"] = raw0
+    cur = (raw0, st(raw0), True, None, None, False)      # (A, sA, rA, B, sB, rB): relu_s only with a B
+    for layer, stride in (("layer1.0", 1), ("layer1.1", 1), ("layer2.0", 2), ("layer2.1", 1)):
+        A, sA, rA, B, sB, rB = cur
+        xin = enc_input_ref64(A, sA, rA, B, sB, rB, relu_sum=B is not None)[0]
+        r1, s1 = conv(layer + ".conv1", xin, 9, stride)
+        r2, s2 = conv(layer + ".conv2", enc_input_ref64(r1, s1, True)[0], 9, 1)
+        if stride == 2:
+            rd, sd_ = conv(layer + ".downsample.0", xin, 1, 2)
+            cur = (r2, s2, True, rd, sd_, False)
+        else:
+            cur = (r2, s2, True, xin, None, False)
+    A, sA, rA, B, sB, rB = cur
+    xin = enc_input_ref64(A, sA, rA, B, sB, rB, relu_sum=True)[0]
+    return enc_conv_ref64(xin, *wb("conv2"), 1, 1)[0].permute(0, 3, 1, 2)

@@ -1,13 +1,16 @@
 """The element-wise checker of tests/parity_check.py on planted corruptions of a 296 x 400 x 64 reference (the bench's feature map):
 each corruption is of a COPY OF THE REFERENCE, no kernel is involved.  For the stale tile and the wrong last row the global metric the
 end-to-end tests assert (rel_l1 < 1e-4) stays below its bar - the blind spot, written down as a fact - while the
-checker fails and names the tile / the row.  Also pins the float64 cost-volume restatement to the oracle.  CPU only."""
+checker fails and names the tile / the row.  Also pins the float64 cost-volume restatement to the oracle.  The same at the encoder
+kernels' geometries (2 x 32 tiles of a stride-2 output, per-tile statistics records; bar rel_l1 < 1e-5), and the chained float64 encoder
+reference of tests/test_encoder_parity_gpu.py against the oracle.  CPU only."""
 import pytest
 import torch
 
 from conftest import rel_l1
-from parity_check import (assert_covered, assert_elementwise, check_elementwise, cost_subset, cost_volume_ref64, partial_tile_mask, poison_f16,
-                          poison_f32, rim_mask, seam_mask)
+from parity_check import (ENC_TILE_S2, assert_covered, assert_elementwise, check_batch, check_elementwise, check_stats_records, cost_subset,
+                          cost_volume_ref64, enc_chain_ref64, partial_tile_mask, poison_f16, poison_f32, rim_mask, seam_mask,
+                          stats_records_ref64)
 from test_oracle_golden import hashed
 
 H, W, C = 296, 400, 64
@@ -146,3 +149,82 @@ def test_cost_volume_restatement_equals_the_oracle_in_float64(D, N, shift):
     pix = torch.tensor([0, 5, w - 1, h * w - 1])
     sub, _, _ = cost_volume_ref64(fmaps, Pij, D, incre, disp_in, shift, pixels=pix)
     assert torch.equal(sub, vol[:, pix])
+
+
+# ------------------------------------------------------------------------------------------------ encoder geometries
+EN, EH, EW, EC = 40, 10, 67, 64          # a stride-2 3 x 3 output of the encoder parity module: 40 images of 10 x 67, 2 x 32 tiles
+C_ENC = 2e-6                             # the three-term constant of tests/test_hip_parity.py::test_stem_on_matrix_cores
+
+
+@pytest.fixture(scope="module")
+def enc_ref():
+    r = hashed((EN, EH, EW, EC), 4301, -1.0, 1.0).double()
+    return r, r.abs() + 1.0
+
+
+def test_encoder_wrong_stride2_tile_is_invisible_to_rel_l1_and_named(enc_ref):
+    """One 2 x 32 tile of one image 1e-3 off (relative): 64 of 26 800 pixels - the whole-encoder bar rel_l1 < 1e-5 passes it."""
+    r, mag = enc_ref
+    n, ty, tx = 23, 3, 1
+    got = r.clone()
+    got[n, ty * 2:ty * 2 + 2, tx * 32:tx * 32 + 32] *= 1.001
+    assert 0 < rel_l1(got, r) < 1e-5
+    rep = check_elementwise(got[n].reshape(EH * EW, EC), r[n].reshape(EH * EW, EC), mag[n].reshape(EH * EW, EC), C_ENC, where="tile",
+                            h=EH, w=EW, tile=ENC_TILE_S2)
+    assert not rep.ok and rep.only_tile() == (ty, tx)
+    with pytest.raises(AssertionError, match=r"(?s)image 23 of 40.*confined to tile \(3, 1\)"):
+        check_batch(got, r, mag, C_ENC, where="tile", h=EH, w=EW, tile=ENC_TILE_S2)
+    assert check_batch(r.float(), r, mag, C_ENC, where="clean", h=EH, w=EW, tile=ENC_TILE_S2)["max_ratio"] < 0.1
+
+
+def test_encoder_wrong_last_row_is_invisible_to_rel_l1_and_named(enc_ref):
+    """The last row of one image 1e-3 off: 67 of 26 800 pixels."""
+    r, mag = enc_ref
+    got = r.clone()
+    got[EN - 1, EH - 1] *= 1.001
+    assert 0 < rel_l1(got, r) < 1e-5
+    with pytest.raises(AssertionError, match=r"(?s)image 39 of 40.*confined to image row 9 \(the last row\)"):
+        check_batch(got, r, mag, C_ENC, where="row", h=EH, w=EW, tile=ENC_TILE_S2)
+
+
+def test_swapped_statistics_records_are_invisible_to_the_reduce_and_named(enc_ref):
+    """Two neighbouring tiles' (sum, sum of squares) records swapped - a record written under the wrong tile id: the per-image totals,
+    hence the statistics and everything after them, do not change at all; the per-tile check names both tiles."""
+    r, _ = enc_ref
+    out = r.float()
+    S, Q, _ = stats_records_ref64(out, ENC_TILE_S2)
+    part = torch.stack([S, Q], -1).float()
+    assert tuple(part.shape) == (EN, 5 * 3, EC, 2)
+    ok, msg, mx = check_stats_records(part, out, ENC_TILE_S2, 19, "clean")
+    assert ok and mx < 0.1, msg
+    n, ty, tx = 7, 4, 1                                   # the last tile row; (4, 2) is the partial last tile
+    bad = part.clone()
+    a, b = ty * 3 + tx, ty * 3 + tx + 1
+    bad[n, a], bad[n, b] = part[n, b], part[n, a]
+    assert torch.equal(bad.double().sum(1), part.double().sum(1)) and rel_l1(bad.double().sum(1), part.double().sum(1)) < 1e-5
+    ok, msg, _ = check_stats_records(bad, out, ENC_TILE_S2, 19, "swap")
+    assert not ok and "(7, 4, 1), (7, 4, 2)" in msg and msg.count("(7,") == 2
+    nan = part.clone()
+    nan[3, 0, 5, 1] = float("nan")                        # a record nobody wrote keeps its sentinel
+    ok, msg, _ = check_stats_records(nan, out, ENC_TILE_S2, 19, "sentinel")
+    assert not ok and "(3, 0, 0)" in msg
+
+
+@pytest.mark.parametrize("kind,which", [("instance", "fnet"), ("none", "cnet")])
+def test_chained_encoder_reference_equals_the_oracle(kind, which):
+    """enc_input_ref64 / enc_conv_ref64 chained through the whole HR encoder with float64 instance-norm statistics, in the schedule of
+    the HIP engine (raw outputs + statistics, normalisation by the consumer, residual merges as two-tensor inputs) = the oracle's
+    encoder, at 36 x 52 (9 x 13 feature pixels, odd sizes on the way)."""
+    from cer_mvs_amd.synthetic import fill_state_dict, synthetic_scene
+    from oracle import cer_oracle as O
+    from test_oracle_golden import blank_state_dict
+    sd = fill_state_dict(blank_state_dict(), seed=5)
+    images, _, _, _ = synthetic_scene(36, 52, 1, seed=8)
+    x = images[0].float() * (2 / 255.0) - 1
+    ref = O.encoder(x, sd, which + ".", kind)
+    outs = {}
+    got = enc_chain_ref64(x, sd, which + ".", kind, outputs=outs)
+    assert got.shape == ref.shape and len(outs) == 10
+    assert rel_l1(got, ref) < 1e-6
+    ref64 = O.encoder(x.double(), {k: v.double() for k, v in sd.items()}, which + ".", kind)
+    assert rel_l1(got, ref64) < 1e-12
