@@ -6,6 +6,7 @@ and Tanks-and-Temples' precision / recall / F-score (shares of them below a thre
     out = reconstruct_scan(model, ..., write=False)
     pred = torch.from_numpy(out["xyz"]).cuda()
     accuracy_completeness(pred, gt, max_dist=20.0, thin=0.2)      # {"accuracy", "completeness", "overall", "n_pred", ...}
+    accuracy_completeness(pred, gt, max_dist=20.0, thin=0.2, thin_method="greedy")      # DTU's own reduction of pred (radius_thin)
     fscore(pred, gt, tau=0.01)                                    # {"precision", "recall", "fscore", ...}
 
 Clouds are CUDA float32 tensors [n, 3]; there is no CPU fallback.  Sorting (``torch.sort(stable=True)``) and the reductions over the distance
@@ -27,6 +28,10 @@ GRID_COORD_LIMIT = 1 << 20                                   # cer_mvs.h CER_GRI
 # neighbour (one cell's worth at least) against how many cells an empty query must look up ((2 * divisor + 3)^2 rows).  Measured by
 # tools/bench_cloud_eval.py (profiles/cloud_eval_bench.json "cell_sweep").
 DEFAULT_CELL_DIVISOR = 4
+# radius_thin runs this many rounds between two compactions of its active list (each compaction costs three small launches and the one
+# host read that tells the loop whether anything is left).  Measured by tools/bench_cloud_thin.py against 1 and 4
+# (profiles/cloud_thin_bench.json "rounds_per_compaction").
+THIN_ROUNDS_PER_COMPACTION = 2
 
 
 def _cloud(t, name):
@@ -135,11 +140,101 @@ class CloudIndex:
 
 def voxel_downsample(points, cell):
     """Indices (int64, ascending) of the lowest-index point of every occupied cell of a grid with edge ``cell`` whose origin is the cloud's
-    per-axis minimum: a VOXEL thinning - deterministic, a pure function of the input.  It is NOT the greedy radius thinning of the DTU MATLAB
-    script (which keeps a point unless an earlier kept point lies within the radius, and so depends on the order of the points): kept points
-    of neighbouring cells may be closer than ``cell``, and no two kept points share a cell.  Points with a non-finite coordinate are dropped."""
+    per-axis minimum: a VOXEL thinning - deterministic, a pure function of the input.  The greedy radius thinning of the DTU MATLAB script
+    (which keeps a point unless an earlier kept point lies within the radius) is ``radius_thin``; this one guarantees neither of its two
+    properties: kept points of neighbouring cells may be closer than ``cell``, and no two kept points share a cell.  Points with a
+    non-finite coordinate are dropped."""
     index = CloudIndex(points, cell)
     return torch.sort(index.heads()).values
+
+
+def _visit_order(order, seed, n, dev):
+    """the visiting order as an int64 tensor on ``dev`` (None: the points' own order)"""
+    if isinstance(order, str):
+        if order == "index":
+            return None
+        return torch.randperm(n, generator=torch.Generator("cpu").manual_seed(int(seed))).to(dev)      # made on the host: the same on every machine
+    if tuple(order.shape) != (n,):
+        raise ValueError(f"order: a permutation of 0 .. {n - 1} expected, got shape {tuple(order.shape)}")
+    order = order.to(dev).contiguous()
+    if n and not bool((torch.sort(order).values == torch.arange(n, device=dev)).all()):
+        raise ValueError(f"order: a permutation of 0 .. {n - 1} expected")
+    return order
+
+
+def radius_thin(points, radius, order="random", seed=0, cell=None, max_rounds=4096, info=None):
+    """Indices (int64, ascending) of the points that the greedy radius thinning of the DTU evaluation script (``reducePts_haa``) keeps: visit
+    the points in ``order``; a point that is still in the set stays and removes every point within ``radius``.  Exactly: with
+    rank[visit[t]] = t, point i is kept iff it is finite and no kept point j with rank[j] < rank[i] has d2(i, j) <= double(float32(radius))^2,
+    d2 = (dx*dx + dy*dy) + dz*dz in fp64 on the float32 coordinates (``nearest``'s contract; inclusive, as MATLAB's rangesearch is).  Kept
+    points are pairwise farther apart than the radius and every dropped finite point has a kept one within it.  Points with a non-finite
+    coordinate are never kept and remove nobody; of exact duplicates the lowest rank survives.  The set is unique: what the sequential loop
+    yields for that order, whatever the schedule of the device.
+
+    ``order``: "random" - ``torch.randperm(n, generator=torch.Generator("cpu").manual_seed(seed))``, the script's way; "index" - the points'
+    own order; or an int64 tensor, the visiting order itself (a permutation of 0 .. n-1, ValueError otherwise).  ``cell``: the grid's edge,
+    default ``radius``.  The device runs rounds until every point is decided; a random order needs around ten, points that are ordered along
+    a curve and visited in that order two per kept point: more than ``max_rounds`` raises RuntimeError.  ``info``: a dict that receives
+    "rounds", "compactions" (the host reads one number per compaction) and "n_finite"."""
+    radius = float(np.float32(radius))
+    if not (radius > 0.0 and math.isfinite(radius)):
+        raise ValueError("radius must be a positive finite number")
+    if isinstance(order, str):
+        if order not in ("random", "index"):
+            raise ValueError(f'order: "random", "index" or an int64 tensor expected, got {order!r}')
+    elif not isinstance(order, torch.Tensor) or order.dtype != torch.int64 or order.dim() != 1:
+        raise ValueError('order: "random", "index" or an int64 tensor [n] expected')
+    max_rounds = int(max_rounds)
+    if max_rounds < 1:
+        raise ValueError("max_rounds must be >= 1")
+    points = _cloud(points, "points")
+    cell = radius if cell is None else _cell(cell)
+    if math.ceil(radius / cell) > 4096:
+        raise ValueError(f"radius_thin: radius {radius} is more than 4096 cells of {cell}; use a larger cell")
+    n_all, dev = int(points.shape[0]), points.device
+    visit = _visit_order(order, seed, n_all, dev)
+    stats = {"rounds": 0, "compactions": 0, "n_finite": 0}
+    if info is not None:
+        info.update(stats)
+    if n_all == 0:
+        return torch.empty(0, device=dev, dtype=torch.int64)
+    # indexed in visiting order: the fourth word of every record is the point's rank, and the state is indexed by rank
+    index = CloudIndex(points if visit is None else points.index_select(0, visit), cell)
+    stats["n_finite"] = index.n
+    if index.n == 0:
+        if info is not None:
+            info.update(stats)
+        return torch.empty(0, device=dev, dtype=torch.int64)
+    lib = L.load()
+    state = torch.zeros(n_all, device=dev, dtype=torch.uint8)
+    P = int(lib.cer_grid_partials(index.n))
+    partials = torch.empty(P, device=dev, dtype=torch.int32)
+    offsets = torch.empty(P + 1, device=dev, dtype=torch.int64)
+    total = torch.empty(1, device=dev, dtype=torch.int64)
+    lists = [torch.empty(index.n, device=dev, dtype=torch.int32) for _ in range(2)]
+    rec, ck, cs = (L.dev_ptr(index.records, "records", torch.int32), L.dev_ptr(index.cell_keys, "cell_keys", torch.int64),
+                   L.dev_ptr(index.cell_start, "cell_start", torch.int64))
+    pstate = L.dev_ptr(state, "state", torch.uint8)
+    active, n_active = None, index.n                         # (None: the list 0 .. n-1)
+    while n_active:
+        if stats["rounds"] >= max_rounds:
+            raise RuntimeError(f"radius_thin: {n_active} of {index.n} points are undecided after {max_rounds} rounds - the visiting order follows "
+                               'the points along a curve or surface (two rounds per kept point); use order="random", or raise max_rounds')
+        pa = L.dev_ptr(active, "active", torch.int32)
+        for _ in range(min(THIN_ROUNDS_PER_COMPACTION, max_rounds - stats["rounds"])):
+            L.check(lib.cer_grid_thin_round_f32(rec, index.n, ck, cs, index.cells, index.origin, index.cell, pa, n_active, radius, pstate,
+                                                L.cur_stream()), "grid_thin_round")
+            stats["rounds"] += 1
+        out = lists[stats["compactions"] & 1]
+        L.check(lib.cer_grid_thin_compact_i32(rec, index.n, pstate, pa, n_active, L.dev_ptr(partials, "partials", torch.int32),
+                                              L.dev_ptr(offsets, "offsets", torch.int64), L.dev_ptr(out, "out", torch.int32),
+                                              L.dev_ptr(total, "total", torch.int64), L.cur_stream()), "grid_thin_compact")
+        stats["compactions"] += 1
+        active, n_active = out, int(total.cpu())             # (the one read per compaction: is anything left)
+    if info is not None:
+        info.update(stats)
+    ranks = torch.nonzero(state == 1).flatten()
+    return ranks if visit is None else torch.sort(visit.index_select(0, ranks)).values
 
 
 def cloud_distances(src, dst, max_dist, cell=None):
@@ -196,17 +291,24 @@ def _keep(points, keep, name):
     return keep
 
 
-def accuracy_completeness(pred, gt, max_dist=20.0, thin=None, keep_pred=None, keep_gt=None, cell=None):
-    """The DTU protocol.  ``pred`` is first thinned with ``voxel_downsample(pred, thin)`` if ``thin`` is given (a voxel thinning, not the MATLAB
-    script's greedy one).  accuracy = mean distance pred -> gt over the points with d < max_dist, completeness = the same gt -> pred, overall =
+def _thin(pred, thin, thin_method, thin_seed):
+    return radius_thin(pred, thin, seed=thin_seed) if thin_method == "greedy" else voxel_downsample(pred, thin)
+
+
+def accuracy_completeness(pred, gt, max_dist=20.0, thin=None, keep_pred=None, keep_gt=None, cell=None, thin_method="voxel", thin_seed=0):
+    """The DTU protocol.  ``pred`` is first thinned if ``thin`` is given: with ``voxel_downsample(pred, thin)`` (``thin_method="voxel"``, the
+    default: one point per cell of that edge) or with ``radius_thin(pred, thin, seed=thin_seed)`` (``"greedy"``: the MATLAB script's own
+    reduction, visiting the points in a seeded random order).  accuracy = mean distance pred -> gt over the points with d < max_dist, completeness = the same gt -> pred, overall =
     their mean.  ``keep_pred`` / ``keep_gt``: optional boolean masks (one entry per point of ``pred`` as passed in / of ``gt``) selecting
     which points enter the two means - where a caller applies DTU's observability mask and ground plane; every point still serves as a
     neighbour.  -> {"accuracy", "completeness", "overall", "n_pred", "n_gt", "n_pred_in", "n_gt_in"}: n_pred / n_gt are the points that were
     measured (after thinning and masks), n_*_in those within max_dist."""
+    if thin_method not in ("voxel", "greedy"):
+        raise ValueError(f'thin_method: "voxel" or "greedy" expected, got {thin_method!r}')
     pred, gt = _cloud(pred, "pred"), _cloud(gt, "gt")
     kp, kg = _keep(pred, keep_pred, "keep_pred"), _keep(gt, keep_gt, "keep_gt")
     if thin is not None:
-        sel = voxel_downsample(pred, thin)
+        sel = _thin(pred, thin, thin_method, thin_seed)
         pred = pred.index_select(0, sel)
         kp = kp.index_select(0, sel) if kp is not None else None
     cell = float(max_dist) / DEFAULT_CELL_DIVISOR if cell is None else cell

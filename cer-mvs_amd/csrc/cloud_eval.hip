@@ -5,6 +5,7 @@
 // cell, the host sorts the keys (stable) and cer_grid_pack_f32 gathers the points into that order as 16-byte records (x, y, z, original index),
 // cer_grid_cells_count_i64 / cer_grid_cells_i64 list the occupied cells with their first sorted point (compact.hpp's count / scan / emit over
 // the heads of the sorted keys), and cer_grid_nearest_f32 searches.  No atomics anywhere: the same bytes on every run.
+// On the same grid, cer_grid_thin_round_f32 / cer_grid_thin_compact_i32 are the rounds of the DTU script's greedy radius thinning (below).
 //
 // Key layout: (z + B) << 42 | (y + B) << 21 | (x + B), B = CER_GRID_COORD_LIMIT - 1, cell coordinates in -B .. B: every field is at most
 // 2^21 - 2, so no key reaches the sentinel (2^63 - 1, all 63 bits set) and key(x + 1, y, z) = key(x, y, z) + 1 never carries.  x is the
@@ -213,6 +214,120 @@ __global__ __launch_bounds__(256) void grid_nearest_kernel(const uint4* __restri
     dist[q] = found ? (float)__builtin_sqrt(best.d2) : __builtin_inff();
 }
 
+// ---- greedy radius thinning (cloud_eval.radius_thin): the maximal independent set of the radius graph under a visiting order,
+// what the sequential "a point that is still in the set stays and removes everybody within the radius" loop of the DTU script yields.  The
+// cloud is indexed in VISITING order, so the fourth word of a record is the point's rank and state[] is indexed by rank.  A round looks,
+// for every undecided point, at its neighbours of lower rank with d2 <= limit: one of them KEPT -> REMOVED (the walk stops there); else one
+// of them UNDECIDED -> no change; else -> KEPT.  States only ever move from UNDECIDED to their final value, so the round updates state[]
+// in place with plain byte loads and stores: a reader that sees a stale UNDECIDED waits a round, one that sees a final value sees the
+// right one.  The fixed point does not depend on the schedule; only the number of rounds may.  (state is read and written by the same
+// launch: neither const nor __restrict__.)
+#define THIN_UNDECIDED 0
+#define THIN_KEPT 1
+#define THIN_REMOVED 2
+
+// the lower-rank neighbours among the points of cells xa .. xb of row (y, z): true when one of them is KEPT; wait: one of them is UNDECIDED
+__device__ __forceinline__ bool thin_scan_row(const uint4* __restrict__ rec, const long long* __restrict__ cell_keys,
+                                              const long long* __restrict__ cell_start, long ncells, int xa, int xb, int y, int z, double X,
+                                              double Y, double Z, unsigned rank, double limit, const unsigned char* state, bool& wait) {
+    const long long ka = grid_key(xa, y, z), kb = grid_key(xb, y, z) + 1;
+    const long a = grid_lower_bound(cell_keys, 0, ncells, ka);
+    if (a == ncells || cell_keys[a] >= kb) return false;
+    const long b = grid_lower_bound(cell_keys, a + 1, ncells, kb);
+    const long long pe = cell_start[b];
+    for (long long j = cell_start[a]; j < pe; ++j) {
+        const uint4 t = rec[j];
+        if (t.w >= rank) continue;                                               // later in the visiting order, or the point itself
+        const double dx = (double)__uint_as_float(t.x) - X, dy = (double)__uint_as_float(t.y) - Y, dz = (double)__uint_as_float(t.z) - Z;
+        const double d2 = (dx * dx + dy * dy) + dz * dz;
+        if (!(d2 <= limit)) continue;
+        const unsigned char s = state[t.w];
+        if (s == THIN_KEPT) return true;
+        wait |= s == THIN_UNDECIDED;
+    }
+    return false;
+}
+
+// One thread per entry of the active list (sorted positions, ascending: the lanes of a wave sit in the same cells; NULL: 0 .. m-1).  The rows
+// are enumerated as in grid_nearest_kernel, cut by the same true bounds - against the fixed limit radius^2 instead of a best distance: a row
+// or a cell is skipped only when no point it can hold is within the radius (strictly: d2 == limit is a neighbour).
+__global__ __launch_bounds__(256) void grid_thin_round_kernel(const uint4* __restrict__ rec, const long long* __restrict__ cell_keys,
+                                                              const long long* __restrict__ cell_start, long ncells, double ox, double oy,
+                                                              double oz, double cell, const int* __restrict__ active, long m, float radius,
+                                                              int rings, unsigned char* state) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= m) return;
+    const uint4 me = rec[active ? (long)active[i] : i];
+    const unsigned rank = me.w;
+    if (state[rank] != THIN_UNDECIDED) return;                                   // decided since the list was compacted
+    const double limit = (double)radius * (double)radius;
+    const double X = (double)__uint_as_float(me.x), Y = (double)__uint_as_float(me.y), Z = (double)__uint_as_float(me.z);
+    const double ux = (X - ox) / cell, uy = (Y - oy) / cell, uz = (Z - oz) / cell;
+    const double fx = floor(ux), fy = floor(uy), fz = floor(uz), B = (double)GRID_B, R = (double)rings;
+    // (an indexed point: its cell is inside the key range, so every clamped range below is non-empty)
+    const double xlo = fmax(fx - R, -B), xhi = fmin(fx + R, B), ylo = fmax(fy - R, -B), yhi = fmin(fy + R, B);
+    const double zlo = fmax(fz - R, -B), zhi = fmin(fz + R, B);
+    const int cy = (int)fmin(fmax(fy, -B), B), cz = (int)fmin(fmax(fz, -B), B);
+    bool kept_near = false, wait = false;
+    for (int iz = 0; iz <= 2 * rings && !kept_near; ++iz) {                      // 0, +1, -1, +2, -2, ...: near rows first
+        const int z = cz + ((iz & 1) ? (iz + 1) / 2 : -(iz / 2));
+        if ((double)z < zlo || (double)z > zhi) continue;
+        const double gz = grid_gap(uz, (double)z) * cell, gz2 = gz * gz;
+        if (gz2 > limit) continue;
+        for (int iy = 0; iy <= 2 * rings && !kept_near; ++iy) {
+            const int y = cy + ((iy & 1) ? (iy + 1) / 2 : -(iy / 2));
+            if ((double)y < ylo || (double)y > yhi) continue;
+            const double gy = grid_gap(uy, (double)y) * cell, g2 = gz2 + gy * gy;
+            if (g2 > limit) continue;
+            // cells of the row whose gap along x can be within sqrt(limit - g2): c + 1 > ux - e and c <= ux + e, e padded by 1e-3 cells
+            const double e = __builtin_sqrt(limit - g2) / cell + 1e-3;
+            const double xa = fmax(floor(ux - e), xlo), xb = fmin(floor(ux + e), xhi);
+            if (xa > xb) continue;
+            kept_near = thin_scan_row(rec, cell_keys, cell_start, ncells, (int)xa, (int)xb, y, z, X, Y, Z, rank, limit, state, wait);
+        }
+    }
+    if (kept_near) state[rank] = THIN_REMOVED;
+    else if (!wait) state[rank] = THIN_KEPT;
+}
+
+// ---- the active list's compaction: compact.hpp's count / scan / emit with the predicate "still undecided"; the list keeps its order
+__device__ __forceinline__ bool thin_undecided(const uint4* __restrict__ rec, const int* __restrict__ active, long m,
+                                               const unsigned char* __restrict__ state, long i) {
+    return i < m && state[rec[active ? (long)active[i] : i].w] == THIN_UNDECIDED;
+}
+
+__global__ __launch_bounds__(256) void thin_count_kernel(const uint4* __restrict__ rec, const int* __restrict__ active, long m,
+                                                         const unsigned char* __restrict__ state, unsigned* __restrict__ partials) {
+    unsigned long long bal[GRID_ITER];
+    const unsigned tot = compact_block_total(
+        compact_ballots(compact_seg<GRID_TILE, long>(), [=](long i) { return thin_undecided(rec, active, m, state, i); }, bal));
+    if (threadIdx.x == 0) partials[blockIdx.x] = tot;
+}
+
+__global__ __launch_bounds__(1024) void thin_scan_kernel(const unsigned* __restrict__ partials, long np, long long* __restrict__ offsets,
+                                                         long long* __restrict__ total) {
+    const long long t = compact_scan(partials, np, offsets);
+    if (threadIdx.x == 0) *total = t;
+}
+
+__global__ __launch_bounds__(256) void thin_emit_kernel(const uint4* __restrict__ rec, const int* __restrict__ active, long m,
+                                                        const unsigned char* __restrict__ state, const long long* __restrict__ offsets,
+                                                        int* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const long seg = compact_seg<GRID_TILE, long>();
+    unsigned long long bal[GRID_ITER];
+    const unsigned tot = compact_ballots(seg, [=](long i) { return thin_undecided(rec, active, m, state, i); }, bal);
+    long long base = compact_wave_base(tot, offsets, blockIdx.x);
+#pragma unroll
+    for (int j = 0; j < GRID_ITER; ++j) {
+        const long p = seg + 64 * j;
+        const long long r = base + compact_rank(bal[j]);
+        base += __popcll(bal[j]);
+        if (!((bal[j] >> lane) & 1ull) || r >= m) continue;                      // (never past the list's own length: what the caller allocated)
+        out[r] = active ? active[p] : (int)p;
+    }
+}
+
 // ---- entry points.  Sizes: negative -> CER_EINVAL, 2^31 and beyond -> CER_ESHAPE, zero -> nothing to do (CER_OK, nothing launched, before
 // the pointers are looked at); then null pointers -> CER_EINVAL.
 static int grid_size_check(long n) {
@@ -309,6 +424,47 @@ extern "C" int cer_grid_nearest_f32(const void* records, long n, const long long
     if ((uintptr_t)records & 15) return CER_EALIGN;
     hipLaunchKernelGGL(grid_nearest_kernel, dim3(grid_blocks(m, 256)), dim3(256), 0, (hipStream_t)stream, (const uint4*)records, cell_keys,
                        cell_start, ncells, origin[0], origin[1], origin[2], cell, queries, qorder, m, max_dist, (int)rings + 1, idx, dist);
+    CER_RETURN_IF_LAUNCH_FAILED();
+    return CER_OK;
+}
+
+extern "C" int cer_grid_thin_round_f32(const void* records, long n, const long long* cell_keys, const long long* cell_start, long ncells,
+                                       const double* origin, double cell, const int* active, long n_active, float radius,
+                                       unsigned char* state, void* stream) {
+    int rc = grid_size_check(n);
+    if (rc == CER_OK) rc = grid_size_check(n_active);
+    if (rc == CER_OK) rc = grid_size_check(ncells);
+    if (rc != CER_OK) return rc;
+    if (!grid_frame_ok(origin, cell) || !(radius > 0.0f) || !grid_is_finite((double)radius)) return CER_EINVAL;
+    if (ncells > n || n_active > n) return CER_ESHAPE;
+    const double rings = ceil((double)radius / cell);
+    if (!(rings <= (double)GRID_MAX_RINGS)) return CER_ESHAPE;
+    if (n_active == 0 || n == 0 || ncells == 0) return CER_OK;
+    if (!records || !cell_keys || !cell_start || !state) return CER_EINVAL;      // (active may be NULL: the list 0 .. n_active-1)
+    if ((uintptr_t)records & 15) return CER_EALIGN;
+    hipLaunchKernelGGL(grid_thin_round_kernel, dim3(grid_blocks(n_active, 256)), dim3(256), 0, (hipStream_t)stream, (const uint4*)records,
+                       cell_keys, cell_start, ncells, origin[0], origin[1], origin[2], cell, active, n_active, radius, (int)rings + 1, state);
+    CER_RETURN_IF_LAUNCH_FAILED();
+    return CER_OK;
+}
+
+extern "C" int cer_grid_thin_compact_i32(const void* records, long n, const unsigned char* state, const int* active, long n_active,
+                                         unsigned int* partials, long long* offsets, int* out, long long* total, void* stream) {
+    int rc = grid_size_check(n);
+    if (rc == CER_OK) rc = grid_size_check(n_active);
+    if (rc != CER_OK) return rc;
+    if (n_active > n) return CER_ESHAPE;
+    if (n_active == 0) return CER_OK;                // (an empty list: *total is the caller's to zero)
+    if (!records || !state || !partials || !offsets || !out || !total) return CER_EINVAL;
+    if ((uintptr_t)records & 15) return CER_EALIGN;
+    if (out == active) return CER_EINVAL;            // the emit pass reads the list while it writes the new one
+    const long np = (n_active + GRID_TILE - 1) / GRID_TILE;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(thin_count_kernel, dim3((unsigned)np), dim3(256), 0, st, (const uint4*)records, active, n_active, state, partials);
+    CER_RETURN_IF_LAUNCH_FAILED();
+    hipLaunchKernelGGL(thin_scan_kernel, dim3(1), dim3(1024), 0, st, partials, np, offsets, total);
+    CER_RETURN_IF_LAUNCH_FAILED();
+    hipLaunchKernelGGL(thin_emit_kernel, dim3((unsigned)np), dim3(256), 0, st, (const uint4*)records, active, n_active, state, offsets, out);
     CER_RETURN_IF_LAUNCH_FAILED();
     return CER_OK;
 }

@@ -598,6 +598,30 @@ int cer_grid_nearest_f32(const void* records, long n, const long long* cell_keys
                          const double* origin, double cell, const float* queries, const long long* qorder, long m, float max_dist,
                          long long* idx, float* dist, void* stream);
 
+/* Greedy radius thinning on the same grid (ABI 1120; cer-mvs_amd/cloud_eval.py radius_thin): the reduction of the DTU evaluation
+ * script - visit the points in a given order; a point that is still in the set stays and removes every point within the radius - as the
+ * fixed point of parallel rounds.  The cloud is indexed IN VISITING ORDER (cer_grid_keys_f32 .. cer_grid_pack_f32 on the permuted points), so
+ * the fourth word of a record is the point's rank.  `state`: one byte per point of that cloud, non-finite ones included (every record's
+ * fourth word indexes it), indexed by rank, zeroed by the caller: 0 undecided, 1 kept, 2 removed.  Point i ends kept iff no kept point j with
+ * rank j < rank i has d2(i, j) <= double(radius)^2, d2 as in cer_grid_nearest_f32 (inclusive; exact duplicates are neighbours): the set the
+ * sequential loop yields, and the only one.  Sizes and errors as above (n: the record count, n_active <= n; radius must be a positive finite
+ * number: CER_EINVAL; more than 4096 rings (radius / cell), ncells > n or n_active > n: CER_ESHAPE).
+ *
+ *   cer_grid_thin_round_f32: one round.  `active`: n_active sorted positions (indices into records), ascending, or NULL for 0 .. n_active-1.
+ *     Every listed point that is still undecided looks at its neighbours of lower rank: one of them kept -> removed; else one of them
+ *     undecided -> unchanged; else -> kept.  state is updated in place with plain byte loads and stores (states only move from undecided to
+ *     their final value, so a stale read costs a round at most and never a wrong answer): the result of the loop does not depend on the
+ *     schedule, the number of rounds may.  The undecided point of lowest rank decides in every round.  The cells are enumerated and cut as in
+ *     cer_grid_nearest_f32, against the fixed limit radius^2.
+ *   cer_grid_thin_compact_i32: out[0 .. *total) = the entries of `active` (NULL as above) whose point is still undecided, in the list's order;
+ *     *total (one device 64-bit integer) = their number.  compact.hpp's count / scan / emit: partials [cer_grid_partials(n_active)] unsigned,
+ *     offsets [that many + 1] 64-bit, out [n_active] at most, out != active (CER_EINVAL).  n_active == 0 launches nothing. */
+int cer_grid_thin_round_f32(const void* records, long n, const long long* cell_keys, const long long* cell_start, long ncells,
+                            const double* origin, double cell, const int* active, long n_active, float radius, unsigned char* state,
+                            void* stream);
+int cer_grid_thin_compact_i32(const void* records, long n, const unsigned char* state, const int* active, long n_active,
+                              unsigned int* partials, long long* offsets, int* out, long long* total, void* stream);
+
 /* Multi-GPU row-slab exchange (cer-mvs_amd/slab.py): up to CER_COPY_MAX_SEG contiguous fp32 ranges copied by ONE launch -
  * the pack of a rank's (net, disp) border strips into its send buffer, and the refresh of its halo rows from the gathered
  * strips.  n[i] floats from src[i] to dst[i]; n[i] == 0 skips a segment.  Device pointers; ranges must not overlap. */

@@ -1,10 +1,11 @@
 """Two point clouds, one JSON line: DTU's accuracy / completeness / overall and Tanks-and-Temples' precision / recall / F-score of A (the
 prediction) against B (the ground truth), on the device (cer-mvs_amd/cloud_eval.py).
 
-    python tools/compare_clouds.py A.ply B.ply [--max-dist 20.0] [--tau 2.0] [--thin 0.2]
+    python tools/compare_clouds.py A.ply B.ply [--max-dist 20.0] [--tau 2.0] [--thin 0.2] [--thin-method voxel|greedy] [--thin-seed 0]
 
-Binary little-endian PLY files (what `reconstruct_scan` / `fusion` write).  --thin: voxel-thin A first (one point per cell of that edge: NOT the
-DTU script's greedy radius thinning).  The clouds are taken as they are: alignment, observability masks and ground planes of the benchmarks are
+Binary little-endian PLY files (what `reconstruct_scan` / `fusion` write).  --thin: thin A first - --thin-method voxel (the default): one point
+per cell of that edge; greedy: the DTU script's own reduction, `radius_thin` with that radius, visiting the points in the random order of
+--thin-seed.  The clouds are taken as they are: alignment, observability masks and ground planes of the benchmarks are
 the caller's business.  Needs a GPU."""
 import argparse
 import json
@@ -21,7 +22,9 @@ def main():
     ap.add_argument("b", help="ground-truth cloud (PLY)")
     ap.add_argument("--max-dist", type=float, default=20.0, help="distances at or beyond this leave the means (DTU: 20 mm)")
     ap.add_argument("--tau", type=float, default=None, help="F-score threshold (default: max_dist / 10)")
-    ap.add_argument("--thin", type=float, default=None, help="voxel edge for thinning A")
+    ap.add_argument("--thin", type=float, default=None, help="voxel edge / radius for thinning A")
+    ap.add_argument("--thin-method", choices=("voxel", "greedy"), default="voxel", help="voxel_downsample or radius_thin (the DTU script's)")
+    ap.add_argument("--thin-seed", type=int, default=0, help="seed of the greedy thinning's visiting order")
     args = ap.parse_args()
     import torch
     from cer_mvs_amd import cloud_eval as CE
@@ -30,10 +33,10 @@ def main():
     tau = args.max_dist / 10 if args.tau is None else args.tau
     a = torch.from_numpy(CE.read_ply(args.a)[0]).cuda()
     b = torch.from_numpy(CE.read_ply(args.b)[0]).cuda()
-    out = {"a": args.a, "b": args.b, "max_dist": args.max_dist, "thin": args.thin}
-    out.update(CE.accuracy_completeness(a, b, max_dist=args.max_dist, thin=args.thin))
-    if args.thin is not None:
-        a = a.index_select(0, CE.voxel_downsample(a, args.thin))
+    out = {"a": args.a, "b": args.b, "max_dist": args.max_dist, "thin": args.thin, "thin_method": args.thin_method, "thin_seed": args.thin_seed}
+    out.update(CE.accuracy_completeness(a, b, max_dist=args.max_dist, thin=args.thin, thin_method=args.thin_method, thin_seed=args.thin_seed))
+    if args.thin is not None:                                # (the same selection again, for the F-score)
+        a = a.index_select(0, CE.radius_thin(a, args.thin, seed=args.thin_seed) if args.thin_method == "greedy" else CE.voxel_downsample(a, args.thin))
     out.update({k: v for k, v in CE.fscore(a, b, tau).items() if k in ("precision", "recall", "fscore", "tau")})
     print(json.dumps(out))
 
