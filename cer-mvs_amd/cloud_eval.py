@@ -23,6 +23,7 @@ from . import _lib as L
 
 GRID_TILE = 2048                                             # cer_mvs.h CER_GRID_TILE
 GRID_COORD_LIMIT = 1 << 20                                   # cer_mvs.h CER_GRID_COORD_LIMIT
+GRID_MAX_RINGS = 4096                                        # cloud_eval.hip GRID_MAX_RINGS: ceil(reach / cell) beyond this is refused
 # cloud_distances' default cell is max_dist / DEFAULT_CELL_DIVISOR.  The search cuts every row of cells to what can still beat the best
 # distance so far, so its work follows the distance to the neighbour, not max_dist; the cell size sets how many points come along with the
 # neighbour (one cell's worth at least) against how many cells an empty query must look up ((2 * divisor + 3)^2 rows).  Measured by
@@ -51,6 +52,12 @@ def _cell(cell):
     if not (cell > 0.0 and math.isfinite(cell)):
         raise ValueError("cell must be a positive finite number")
     return cell
+
+
+def _compaction_scratch(lib, n, dev, results):
+    """(partials int32, offsets int64, ``results`` int64 words for the host to read): what one count / scan / emit over ``n`` entries needs"""
+    P = int(lib.cer_grid_partials(n))
+    return tuple(torch.empty(k, device=dev, dtype=t) for k, t in ((P, torch.int32), (P + 1, torch.int64), (results, torch.int64)))
 
 
 class CloudIndex:
@@ -87,10 +94,7 @@ class CloudIndex:
             raise ValueError(f"CloudIndex: the cloud spans more than 2^20 cells of {self.cell} along an axis; use a larger cell")
         L.check(rc, "grid_keys")
         keys, self.order = torch.sort(keys, stable=True)
-        P = int(lib.cer_grid_partials(n_all))
-        partials = torch.empty(P, device=dev, dtype=torch.int32)
-        offsets = torch.empty(P + 1, device=dev, dtype=torch.int64)
-        totals = torch.empty(2, device=dev, dtype=torch.int64)
+        partials, offsets, totals = _compaction_scratch(lib, n_all, dev, 2)
         pk = L.dev_ptr(keys, "keys", torch.int64)
         L.check(lib.cer_grid_cells_count_i64(pk, n_all, L.dev_ptr(partials, "partials", torch.int32), L.dev_ptr(offsets, "offsets", torch.int64),
                                              L.dev_ptr(totals, "totals", torch.int64), L.cur_stream()), "grid_cells_count")
@@ -103,6 +107,10 @@ class CloudIndex:
         self.records = torch.empty(n_all, 4, device=dev, dtype=torch.int32)
         L.check(lib.cer_grid_pack_f32(L.dev_ptr(points, "points"), L.dev_ptr(self.order, "order", torch.int64), n_all,
                                       L.dev_ptr(self.records, "records", torch.int32), L.cur_stream()), "grid_pack")
+
+    def grid_args(self):                                     # the argument head of both searches, cer_grid_nearest_f32's first seven
+        return (L.dev_ptr(self.records, "records", torch.int32), self.n, L.dev_ptr(self.cell_keys, "cell_keys", torch.int64),
+                L.dev_ptr(self.cell_start, "cell_start", torch.int64), self.cells, self.origin, self.cell)
 
     def heads(self):
         """Original index of the first sorted point of every occupied cell - the lowest index in the cell, as the sort is stable."""
@@ -128,12 +136,10 @@ class CloudIndex:
             L.check(lib.cer_grid_keys_f32(L.dev_ptr(queries, "queries"), m, self.origin, self.cell, 1, L.dev_ptr(qkeys, "keys", torch.int64), None,
                                           L.cur_stream()), "grid_keys")
             qorder = torch.sort(qkeys, stable=True).indices
-        rc = lib.cer_grid_nearest_f32(L.dev_ptr(self.records, "records", torch.int32), self.n, L.dev_ptr(self.cell_keys, "cell_keys", torch.int64),
-                                      L.dev_ptr(self.cell_start, "cell_start", torch.int64), self.cells, self.origin, self.cell,
-                                      L.dev_ptr(queries, "queries"), L.dev_ptr(qorder, "qorder", torch.int64), m, max_dist,
+        rc = lib.cer_grid_nearest_f32(*self.grid_args(), L.dev_ptr(queries, "queries"), L.dev_ptr(qorder, "qorder", torch.int64), m, max_dist,
                                       L.dev_ptr(idx, "idx", torch.int64), L.dev_ptr(dist, "dist"), L.cur_stream())
         if rc == -2:
-            raise ValueError(f"nearest: max_dist {max_dist} is more than 4096 cells of {self.cell}; index the cloud with a larger cell")
+            raise ValueError(f"nearest: max_dist {max_dist} is more than {GRID_MAX_RINGS} cells of {self.cell}; index the cloud with a larger cell")
         L.check(rc, "grid_nearest")
         return dist, idx
 
@@ -189,8 +195,8 @@ def radius_thin(points, radius, order="random", seed=0, cell=None, max_rounds=40
         raise ValueError("max_rounds must be >= 1")
     points = _cloud(points, "points")
     cell = radius if cell is None else _cell(cell)
-    if math.ceil(radius / cell) > 4096:
-        raise ValueError(f"radius_thin: radius {radius} is more than 4096 cells of {cell}; use a larger cell")
+    if math.ceil(radius / cell) > GRID_MAX_RINGS:
+        raise ValueError(f"radius_thin: radius {radius} is more than {GRID_MAX_RINGS} cells of {cell}; use a larger cell")
     n_all, dev = int(points.shape[0]), points.device
     visit = _visit_order(order, seed, n_all, dev)
     stats = {"rounds": 0, "compactions": 0, "n_finite": 0}
@@ -207,14 +213,9 @@ def radius_thin(points, radius, order="random", seed=0, cell=None, max_rounds=40
         return torch.empty(0, device=dev, dtype=torch.int64)
     lib = L.load()
     state = torch.zeros(n_all, device=dev, dtype=torch.uint8)
-    P = int(lib.cer_grid_partials(index.n))
-    partials = torch.empty(P, device=dev, dtype=torch.int32)
-    offsets = torch.empty(P + 1, device=dev, dtype=torch.int64)
-    total = torch.empty(1, device=dev, dtype=torch.int64)
+    partials, offsets, total = _compaction_scratch(lib, index.n, dev, 1)
     lists = [torch.empty(index.n, device=dev, dtype=torch.int32) for _ in range(2)]
-    rec, ck, cs = (L.dev_ptr(index.records, "records", torch.int32), L.dev_ptr(index.cell_keys, "cell_keys", torch.int64),
-                   L.dev_ptr(index.cell_start, "cell_start", torch.int64))
-    pstate = L.dev_ptr(state, "state", torch.uint8)
+    grid, pstate = index.grid_args(), L.dev_ptr(state, "state", torch.uint8)
     active, n_active = None, index.n                         # (None: the list 0 .. n-1)
     while n_active:
         if stats["rounds"] >= max_rounds:
@@ -222,11 +223,10 @@ def radius_thin(points, radius, order="random", seed=0, cell=None, max_rounds=40
                                'the points along a curve or surface (two rounds per kept point); use order="random", or raise max_rounds')
         pa = L.dev_ptr(active, "active", torch.int32)
         for _ in range(min(THIN_ROUNDS_PER_COMPACTION, max_rounds - stats["rounds"])):
-            L.check(lib.cer_grid_thin_round_f32(rec, index.n, ck, cs, index.cells, index.origin, index.cell, pa, n_active, radius, pstate,
-                                                L.cur_stream()), "grid_thin_round")
+            L.check(lib.cer_grid_thin_round_f32(*grid, pa, n_active, radius, pstate, L.cur_stream()), "grid_thin_round")
             stats["rounds"] += 1
         out = lists[stats["compactions"] & 1]
-        L.check(lib.cer_grid_thin_compact_i32(rec, index.n, pstate, pa, n_active, L.dev_ptr(partials, "partials", torch.int32),
+        L.check(lib.cer_grid_thin_compact_i32(grid[0], index.n, pstate, pa, n_active, L.dev_ptr(partials, "partials", torch.int32),
                                               L.dev_ptr(offsets, "offsets", torch.int64), L.dev_ptr(out, "out", torch.int32),
                                               L.dev_ptr(total, "total", torch.int64), L.cur_stream()), "grid_thin_compact")
         stats["compactions"] += 1

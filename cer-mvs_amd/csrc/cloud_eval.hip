@@ -119,32 +119,76 @@ __global__ __launch_bounds__(256) void grid_emit_kernel(const long long* __restr
     }
 }
 
-// ---- nearest.  One thread per query, the queries in the order of their own cell keys (qorder), so that the lanes of a wave walk the same
-// cells at the same pace: their record loads hit the same cache lines.  Exactness does not rest on the key arithmetic: a cell is skipped
-// only when the TRUE bounds of the points it can hold prove that none of them can win.  A target point in cell c of an axis has a computed
-// u in [c, c + 1); u carries two fp64 roundings (relative 2^-52 of a magnitude below 2^21 + GRID_MAX_RINGS: absolute below 2e-9 cells), and so
-// does the query's.  The per-axis gap between the query and any point of the cell is therefore at least (c - uq - GRID_EPS) cells above the
-// query, (uq - (c + 1) - GRID_EPS) cells below it, with GRID_EPS = 1e-6 hundreds of times that error.  Rows and cells whose gap exceeds the
-// best distance so far are skipped (strictly: a tie on d2 with a lower index must still be seen); the enumeration itself covers
-// ceil(max_dist / cell) + 1 rings, one more than the mathematics needs.
+// ---- the row walk under the search and the thinning.  Exactness does not rest on the key arithmetic: a cell is skipped only when the TRUE
+// bounds of the points it can hold prove that none of them can matter.  A target point in cell c of an axis has a computed u in [c, c + 1);
+// u carries two fp64 roundings (relative 2^-52 of a magnitude below 2^21 + GRID_MAX_RINGS: absolute below 2e-9 cells), and so does the
+// query's.  The per-axis gap between the query and any point of the cell is therefore at least (c - uq - GRID_EPS) cells above the query,
+// (uq - (c + 1) - GRID_EPS) cells below it, with GRID_EPS = 1e-6 hundreds of times that error.  Rows and cells whose squared gap exceeds
+// the caller's bound are skipped - strictly: for the search's best distance so far a tie on d2 with a lower index must still be seen, for
+// the thinning's fixed radius^2 d2 == limit is a neighbour; the enumeration itself covers ceil(reach / cell) + 1 rings, one more than the
+// mathematics needs.
 #define GRID_EPS 1e-6
 
-struct GridBest {
-    double d2;
-    int idx;
-};
+// gap, in cells, between coordinate u and the points of cell c of that axis (0 when u is inside)
+__device__ __forceinline__ double grid_gap(double u, double c) {
+    const double g = u < c ? c - u - GRID_EPS : u - (c + 1.0) - GRID_EPS;
+    return g > 0.0 ? g : 0.0;
+}
+
+// [pb, pe): the sorted records of cells xa .. xb of row (y, z) - one run, found with two binary searches; false when the row holds none
+__device__ __forceinline__ bool grid_row_span(const long long* __restrict__ cell_keys, const long long* __restrict__ cell_start, long ncells,
+                                              int xa, int xb, int y, int z, long long& pb, long long& pe) {
+    const long long ka = grid_key(xa, y, z), kb = grid_key(xb, y, z) + 1;
+    const long a = grid_lower_bound(cell_keys, 0, ncells, ka);
+    if (a == ncells || cell_keys[a] >= kb) return false;
+    const long b = grid_lower_bound(cell_keys, a + 1, ncells, kb);
+    pb = cell_start[a], pe = cell_start[b];
+    return true;
+}
+
+// The rows of cells around point (X, Y, Z) that can hold a point within sqrt(bound()), near rows first (0, +1, -1, +2, -2, ... in z, then
+// in y): row(xa, xb, y, z) gets the cells xa .. xb of row (y, z) and returns whether to stop.  bound() is read anew at every test.  Cell
+// coordinates are doubles until they are clamped (the point may lie anywhere); farther than the rings from the key range: no row at all.
+template <class Bound, class Row>
+__device__ __forceinline__ void grid_walk_rows(double X, double Y, double Z, double ox, double oy, double oz, double cell, int rings,
+                                               Bound bound, Row row) {
+    const double ux = (X - ox) / cell, uy = (Y - oy) / cell, uz = (Z - oz) / cell;
+    const double fx = floor(ux), fy = floor(uy), fz = floor(uz), B = (double)GRID_B, R = (double)rings;
+    const double xlo = fmax(fx - R, -B), xhi = fmin(fx + R, B), ylo = fmax(fy - R, -B), yhi = fmin(fy + R, B);
+    const double zlo = fmax(fz - R, -B), zhi = fmin(fz + R, B);
+    if (!(xlo <= xhi && ylo <= yhi && zlo <= zhi)) return;
+    const int cy = (int)fmin(fmax(fy, -B), B), cz = (int)fmin(fmax(fz, -B), B);
+    for (int iz = 0; iz <= 2 * rings; ++iz) {
+        const int z = cz + ((iz & 1) ? (iz + 1) / 2 : -(iz / 2));
+        if ((double)z < zlo || (double)z > zhi) continue;
+        const double gz = grid_gap(uz, (double)z) * cell, gz2 = gz * gz;
+        if (gz2 > bound()) continue;
+        for (int iy = 0; iy <= 2 * rings; ++iy) {
+            const int y = cy + ((iy & 1) ? (iy + 1) / 2 : -(iy / 2));
+            if ((double)y < ylo || (double)y > yhi) continue;
+            const double gy = grid_gap(uy, (double)y) * cell, g2 = gz2 + gy * gy, b2 = bound();
+            if (g2 > b2) continue;
+            // cells of the row whose gap along x can be within sqrt(b2 - g2): c + 1 > ux - e and c <= ux + e, e padded by 1e-3 cells
+            const double e = __builtin_sqrt(b2 - g2) / cell + 1e-3;
+            const double xa = fmax(floor(ux - e), xlo), xb = fmin(floor(ux + e), xhi);
+            if (xa > xb) continue;
+            if (row((int)xa, (int)xb, y, z)) return;
+        }
+    }
+}
+
+// ---- nearest.  One thread per query, the queries in the order of their own cell keys (qorder), so that the lanes of a wave walk the same
+// cells at the same pace: their record loads hit the same cache lines.
+struct GridBest { double d2; int idx; };
 
 // candidates: the points of cells xa .. xb of row (y, z); winner = smallest (d2, original index), a candidate counts iff d2 <= the limit
 // (best starts at (limit, INT_MAX))
 __device__ __forceinline__ void grid_scan_row(const uint4* __restrict__ rec, const long long* __restrict__ cell_keys,
                                               const long long* __restrict__ cell_start, long ncells, int xa, int xb, int y, int z, double X,
                                               double Y, double Z, GridBest& best) {
-    const long long ka = grid_key(xa, y, z), kb = grid_key(xb, y, z) + 1;
-    const long a = grid_lower_bound(cell_keys, 0, ncells, ka);
-    if (a == ncells || cell_keys[a] >= kb) return;
-    const long b = grid_lower_bound(cell_keys, a + 1, ncells, kb);
-    const long long pe = cell_start[b];
-    for (long long j = cell_start[a]; j < pe; ++j) {
+    long long j, pe;
+    if (!grid_row_span(cell_keys, cell_start, ncells, xa, xb, y, z, j, pe)) return;
+    for (; j < pe; ++j) {
         const uint4 t = rec[j];
         const double dx = (double)__uint_as_float(t.x) - X, dy = (double)__uint_as_float(t.y) - Y, dz = (double)__uint_as_float(t.z) - Z;
         const double d2 = (dx * dx + dy * dy) + dz * dz;
@@ -154,12 +198,6 @@ __device__ __forceinline__ void grid_scan_row(const uint4* __restrict__ rec, con
             best.idx = id;
         }
     }
-}
-
-// gap, in cells, between coordinate u and the points of cell c of that axis (0 when u is inside)
-__device__ __forceinline__ double grid_gap(double u, double c) {
-    const double g = u < c ? c - u - GRID_EPS : u - (c + 1.0) - GRID_EPS;
-    return g > 0.0 ? g : 0.0;
 }
 
 __global__ __launch_bounds__(256) void grid_nearest_kernel(const uint4* __restrict__ rec, const long long* __restrict__ cell_keys,
@@ -175,39 +213,18 @@ __global__ __launch_bounds__(256) void grid_nearest_kernel(const uint4* __restri
     GridBest best = {limit, 0x7fffffff};
     if (grid_finite(qx, qy, qz)) {
         const double X = (double)qx, Y = (double)qy, Z = (double)qz;
-        const double ux = (X - ox) / cell, uy = (Y - oy) / cell, uz = (Z - oz) / cell;
-        const double fx = floor(ux), fy = floor(uy), fz = floor(uz), B = (double)GRID_B, R = (double)rings;
-        // cells to enumerate per axis (doubles: a query may lie anywhere), empty when the query is farther than the rings from the key range
-        const double xlo = fmax(fx - R, -B), xhi = fmin(fx + R, B), ylo = fmax(fy - R, -B), yhi = fmin(fy + R, B);
-        const double zlo = fmax(fz - R, -B), zhi = fmin(fz + R, B);
-        if (xlo <= xhi && ylo <= yhi && zlo <= zhi) {
-            const int cy = (int)fmin(fmax(fy, -B), B), cz = (int)fmin(fmax(fz, -B), B);
-            // the query's own cell first: in a dense cloud it holds the winner, and every row after it is cut to the cells that can still beat it
-            const bool home = fabs(fx) <= B && fabs(fy) <= B && fabs(fz) <= B;
-            if (home) grid_scan_row(rec, cell_keys, cell_start, ncells, (int)fx, (int)fx, cy, cz, X, Y, Z, best);
-            for (int iz = 0; iz <= 2 * rings; ++iz) {                            // 0, +1, -1, +2, -2, ...: near rows first
-                const int z = cz + ((iz & 1) ? (iz + 1) / 2 : -(iz / 2));
-                if ((double)z < zlo || (double)z > zhi) continue;
-                const double gz = grid_gap(uz, (double)z) * cell, gz2 = gz * gz;
-                if (gz2 > best.d2) continue;
-                for (int iy = 0; iy <= 2 * rings; ++iy) {
-                    const int y = cy + ((iy & 1) ? (iy + 1) / 2 : -(iy / 2));
-                    if ((double)y < ylo || (double)y > yhi) continue;
-                    const double gy = grid_gap(uy, (double)y) * cell, g2 = gz2 + gy * gy;
-                    if (g2 > best.d2) continue;
-                    // cells of the row whose gap along x can be within sqrt(best - g2): c + 1 > ux - e and c <= ux + e, e padded by 1e-3 cells
-                    const double e = __builtin_sqrt(best.d2 - g2) / cell + 1e-3;
-                    const double xa = fmax(floor(ux - e), xlo), xb = fmin(floor(ux + e), xhi);
-                    if (xa > xb) continue;
-                    if (home && iz == 0 && iy == 0) {                            // the query's own row: its own cell is done
-                        if (xa < fx) grid_scan_row(rec, cell_keys, cell_start, ncells, (int)xa, (int)fx - 1, y, z, X, Y, Z, best);
-                        if (xb > fx) grid_scan_row(rec, cell_keys, cell_start, ncells, (int)fx + 1, (int)xb, y, z, X, Y, Z, best);
-                        continue;
-                    }
-                    grid_scan_row(rec, cell_keys, cell_start, ncells, (int)xa, (int)xb, y, z, X, Y, Z, best);
-                }
-            }
-        }
+        // the query's own cell first: in a dense cloud it holds the winner, and every row after it is cut to the cells that can still beat it
+        const double fx = floor((X - ox) / cell), fy = floor((Y - oy) / cell), fz = floor((Z - oz) / cell), B = (double)GRID_B;
+        const bool home = fabs(fx) <= B && fabs(fy) <= B && fabs(fz) <= B;
+        if (home) grid_scan_row(rec, cell_keys, cell_start, ncells, (int)fx, (int)fx, (int)fy, (int)fz, X, Y, Z, best);
+        grid_walk_rows(X, Y, Z, ox, oy, oz, cell, rings, [&] { return best.d2; }, [&](int xa, int xb, int y, int z) {
+            if (home && (double)y == fy && (double)z == fz) {                    // the query's own row: its own cell is done
+                const int hx = (int)fx;
+                if (xa < hx) grid_scan_row(rec, cell_keys, cell_start, ncells, xa, hx - 1, y, z, X, Y, Z, best);
+                if (xb > hx) grid_scan_row(rec, cell_keys, cell_start, ncells, hx + 1, xb, y, z, X, Y, Z, best);
+            } else grid_scan_row(rec, cell_keys, cell_start, ncells, xa, xb, y, z, X, Y, Z, best);
+            return false;
+        });
     }
     const bool found = best.idx != 0x7fffffff;
     idx[q] = found ? (long long)best.idx : -1;
@@ -230,12 +247,9 @@ __global__ __launch_bounds__(256) void grid_nearest_kernel(const uint4* __restri
 __device__ __forceinline__ bool thin_scan_row(const uint4* __restrict__ rec, const long long* __restrict__ cell_keys,
                                               const long long* __restrict__ cell_start, long ncells, int xa, int xb, int y, int z, double X,
                                               double Y, double Z, unsigned rank, double limit, const unsigned char* state, bool& wait) {
-    const long long ka = grid_key(xa, y, z), kb = grid_key(xb, y, z) + 1;
-    const long a = grid_lower_bound(cell_keys, 0, ncells, ka);
-    if (a == ncells || cell_keys[a] >= kb) return false;
-    const long b = grid_lower_bound(cell_keys, a + 1, ncells, kb);
-    const long long pe = cell_start[b];
-    for (long long j = cell_start[a]; j < pe; ++j) {
+    long long j, pe;
+    if (!grid_row_span(cell_keys, cell_start, ncells, xa, xb, y, z, j, pe)) return false;
+    for (; j < pe; ++j) {
         const uint4 t = rec[j];
         if (t.w >= rank) continue;                                               // later in the visiting order, or the point itself
         const double dx = (double)__uint_as_float(t.x) - X, dy = (double)__uint_as_float(t.y) - Y, dz = (double)__uint_as_float(t.z) - Z;
@@ -248,9 +262,8 @@ __device__ __forceinline__ bool thin_scan_row(const uint4* __restrict__ rec, con
     return false;
 }
 
-// One thread per entry of the active list (sorted positions, ascending: the lanes of a wave sit in the same cells; NULL: 0 .. m-1).  The rows
-// are enumerated as in grid_nearest_kernel, cut by the same true bounds - against the fixed limit radius^2 instead of a best distance: a row
-// or a cell is skipped only when no point it can hold is within the radius (strictly: d2 == limit is a neighbour).
+// One thread per entry of the active list (sorted positions, ascending: the lanes of a wave sit in the same cells; NULL: 0 .. m-1).  The walk
+// runs against the fixed limit radius^2 and stops at the first KEPT neighbour.
 __global__ __launch_bounds__(256) void grid_thin_round_kernel(const uint4* __restrict__ rec, const long long* __restrict__ cell_keys,
                                                               const long long* __restrict__ cell_start, long ncells, double ox, double oy,
                                                               double oz, double cell, const int* __restrict__ active, long m, float radius,
@@ -262,30 +275,10 @@ __global__ __launch_bounds__(256) void grid_thin_round_kernel(const uint4* __res
     if (state[rank] != THIN_UNDECIDED) return;                                   // decided since the list was compacted
     const double limit = (double)radius * (double)radius;
     const double X = (double)__uint_as_float(me.x), Y = (double)__uint_as_float(me.y), Z = (double)__uint_as_float(me.z);
-    const double ux = (X - ox) / cell, uy = (Y - oy) / cell, uz = (Z - oz) / cell;
-    const double fx = floor(ux), fy = floor(uy), fz = floor(uz), B = (double)GRID_B, R = (double)rings;
-    // (an indexed point: its cell is inside the key range, so every clamped range below is non-empty)
-    const double xlo = fmax(fx - R, -B), xhi = fmin(fx + R, B), ylo = fmax(fy - R, -B), yhi = fmin(fy + R, B);
-    const double zlo = fmax(fz - R, -B), zhi = fmin(fz + R, B);
-    const int cy = (int)fmin(fmax(fy, -B), B), cz = (int)fmin(fmax(fz, -B), B);
     bool kept_near = false, wait = false;
-    for (int iz = 0; iz <= 2 * rings && !kept_near; ++iz) {                      // 0, +1, -1, +2, -2, ...: near rows first
-        const int z = cz + ((iz & 1) ? (iz + 1) / 2 : -(iz / 2));
-        if ((double)z < zlo || (double)z > zhi) continue;
-        const double gz = grid_gap(uz, (double)z) * cell, gz2 = gz * gz;
-        if (gz2 > limit) continue;
-        for (int iy = 0; iy <= 2 * rings && !kept_near; ++iy) {
-            const int y = cy + ((iy & 1) ? (iy + 1) / 2 : -(iy / 2));
-            if ((double)y < ylo || (double)y > yhi) continue;
-            const double gy = grid_gap(uy, (double)y) * cell, g2 = gz2 + gy * gy;
-            if (g2 > limit) continue;
-            // cells of the row whose gap along x can be within sqrt(limit - g2): c + 1 > ux - e and c <= ux + e, e padded by 1e-3 cells
-            const double e = __builtin_sqrt(limit - g2) / cell + 1e-3;
-            const double xa = fmax(floor(ux - e), xlo), xb = fmin(floor(ux + e), xhi);
-            if (xa > xb) continue;
-            kept_near = thin_scan_row(rec, cell_keys, cell_start, ncells, (int)xa, (int)xb, y, z, X, Y, Z, rank, limit, state, wait);
-        }
-    }
+    grid_walk_rows(X, Y, Z, ox, oy, oz, cell, rings, [=] { return limit; }, [&](int xa, int xb, int y, int z) {
+        return kept_near = thin_scan_row(rec, cell_keys, cell_start, ncells, xa, xb, y, z, X, Y, Z, rank, limit, state, wait);
+    });
     if (kept_near) state[rank] = THIN_REMOVED;
     else if (!wait) state[rank] = THIN_KEPT;
 }
@@ -408,22 +401,32 @@ extern "C" int cer_grid_cells_i64(const long long* keys, long n, const long long
     return CER_OK;
 }
 
-extern "C" int cer_grid_nearest_f32(const void* records, long n, const long long* cell_keys, const long long* cell_start, long ncells,
-                                    const double* origin, double cell, const float* queries, const long long* qorder, long m, float max_dist,
-                                    long long* idx, float* dist, void* stream) {
+// what both searches check, in the order the tests pin: the three sizes; frame and reach -> CER_EINVAL; more cells than records, !shape_ok,
+// too many rings -> CER_ESHAPE; an empty side -> CER_OK (0: nothing to launch); null pointers; alignment.  Else -> the walk's rings (>= 1).
+static int grid_search_rings(const void* records, long n, const long long* cell_keys, const long long* cell_start, long ncells,
+                             const double* origin, double cell, long m, float reach, bool reach_ok, bool shape_ok, bool pointers_ok) {
     int rc = grid_size_check(n);
     if (rc == CER_OK) rc = grid_size_check(m);
     if (rc == CER_OK) rc = grid_size_check(ncells);
     if (rc != CER_OK) return rc;
-    if (!grid_frame_ok(origin, cell) || !(max_dist >= 0.0f)) return CER_EINVAL;
-    if (ncells > n) return CER_ESHAPE;
-    const double rings = ceil((double)max_dist / cell);
+    if (!grid_frame_ok(origin, cell) || !reach_ok) return CER_EINVAL;
+    if (ncells > n || !shape_ok) return CER_ESHAPE;
+    const double rings = ceil((double)reach / cell);
     if (!(rings <= (double)GRID_MAX_RINGS)) return CER_ESHAPE;
-    if (m == 0 || n == 0 || ncells == 0) return CER_OK;      // (an empty target: the caller fills idx = -1, dist = +inf)
-    if (!records || !cell_keys || !cell_start || !queries || !idx || !dist) return CER_EINVAL;
+    if (m == 0 || n == 0 || ncells == 0) return CER_OK;
+    if (!records || !cell_keys || !cell_start || !pointers_ok) return CER_EINVAL;
     if ((uintptr_t)records & 15) return CER_EALIGN;
+    return (int)rings + 1;
+}
+
+extern "C" int cer_grid_nearest_f32(const void* records, long n, const long long* cell_keys, const long long* cell_start, long ncells,
+                                    const double* origin, double cell, const float* queries, const long long* qorder, long m, float max_dist,
+                                    long long* idx, float* dist, void* stream) {
+    const int rings = grid_search_rings(records, n, cell_keys, cell_start, ncells, origin, cell, m, max_dist, max_dist >= 0.0f, true,
+                                        queries && idx && dist);
+    if (rings <= 0) return rings;                            // (an empty target: the caller fills idx = -1, dist = +inf)
     hipLaunchKernelGGL(grid_nearest_kernel, dim3(grid_blocks(m, 256)), dim3(256), 0, (hipStream_t)stream, (const uint4*)records, cell_keys,
-                       cell_start, ncells, origin[0], origin[1], origin[2], cell, queries, qorder, m, max_dist, (int)rings + 1, idx, dist);
+                       cell_start, ncells, origin[0], origin[1], origin[2], cell, queries, qorder, m, max_dist, rings, idx, dist);
     CER_RETURN_IF_LAUNCH_FAILED();
     return CER_OK;
 }
@@ -431,19 +434,11 @@ extern "C" int cer_grid_nearest_f32(const void* records, long n, const long long
 extern "C" int cer_grid_thin_round_f32(const void* records, long n, const long long* cell_keys, const long long* cell_start, long ncells,
                                        const double* origin, double cell, const int* active, long n_active, float radius,
                                        unsigned char* state, void* stream) {
-    int rc = grid_size_check(n);
-    if (rc == CER_OK) rc = grid_size_check(n_active);
-    if (rc == CER_OK) rc = grid_size_check(ncells);
-    if (rc != CER_OK) return rc;
-    if (!grid_frame_ok(origin, cell) || !(radius > 0.0f) || !grid_is_finite((double)radius)) return CER_EINVAL;
-    if (ncells > n || n_active > n) return CER_ESHAPE;
-    const double rings = ceil((double)radius / cell);
-    if (!(rings <= (double)GRID_MAX_RINGS)) return CER_ESHAPE;
-    if (n_active == 0 || n == 0 || ncells == 0) return CER_OK;
-    if (!records || !cell_keys || !cell_start || !state) return CER_EINVAL;      // (active may be NULL: the list 0 .. n_active-1)
-    if ((uintptr_t)records & 15) return CER_EALIGN;
+    const int rings = grid_search_rings(records, n, cell_keys, cell_start, ncells, origin, cell, n_active, radius,
+                                        radius > 0.0f && grid_is_finite((double)radius), n_active <= n, state != nullptr);
+    if (rings <= 0) return rings;                            // (active may be NULL: the list 0 .. n_active-1)
     hipLaunchKernelGGL(grid_thin_round_kernel, dim3(grid_blocks(n_active, 256)), dim3(256), 0, (hipStream_t)stream, (const uint4*)records,
-                       cell_keys, cell_start, ncells, origin[0], origin[1], origin[2], cell, active, n_active, radius, (int)rings + 1, state);
+                       cell_keys, cell_start, ncells, origin[0], origin[1], origin[2], cell, active, n_active, radius, rings, state);
     CER_RETURN_IF_LAUNCH_FAILED();
     return CER_OK;
 }
