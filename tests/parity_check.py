@@ -428,3 +428,274 @@ def enc_chain_ref64(x, sd, prefix, kind, outputs=None):
     A, sA, rA, B, sB, rB = cur
     xin = enc_input_ref64(A, sA, rA, B, sB, rB, relu_sum=True)[0]
     return enc_conv_ref64(xin, *wb("conv2"), 1, 1)[0].permute(0, 3, 1, 2)
+
+
+# ------------------------------------------------------------------------------------------------ training row in float64
+# References of the training-row kernels: csrc/alt_corr.hip (alt_cuda_corr/correlation_kernel.cu:18-119 forward, 122-256
+# backward), csrc/train_ops.hip (core/corr.py:94-97,102-143 with test_mode=False, utils/bilinear_sampler.py:6-25; loss.py:18-19).  Plain
+# torch on the CPU, no autograd.  Each takes the tensors the kernel reads, forms INDICES from the fp32 inputs with the kernel's own fp32
+# steps (floorf and x - floorf(x), exact; the lookup's max((disp - origin) / incre + D//2, 0) chain; the upsample's fl32((in-1)/(out-1))
+# and fl32(scale * dst)) and does everything else in float64.  ``mag`` = the sum of absolute products behind an output element;
+# ``n`` = the number of terms added into it one after the other.  tests/test_train_parity_{cpu,gpu}.py.
+K_COEF = 8                   # roundings of one tuple coefficient, see alt_corr_tuples_ref64
+K_UP_FWD = 7                 # roundings of the upsample's two-by-two blend, see upsample_ac_ref64
+C_CONV = 1e-6                # the project's per-element constant of an fp32 dot (tests/test_fullsize_parity_gpu.py: holds at 1593 terms)
+
+
+def _corr_floor(coords):
+    """coords [..., 2] fp32 -> (finite, floor x, floor y as fp32, fl32(x - floor x), fl32(y - floor y) as float64; 0 where the coordinate
+    is not finite) - csrc/alt_corr.hip, the first lines of every sample loop.  The subtraction is an fp32 one, as in the kernel and in
+    correlation_kernel.cu: exact for x >= 0 and x <= -1, one rounding for -1 < x < 0 (the fraction has more bits than x)."""
+    c = coords.detach().cpu().float()
+    x, y = c[..., 0], c[..., 1]
+    finite = (x.abs() <= 3.0e38) & (y.abs() <= 3.0e38)                       # (a NaN compares false)
+    fx, fy = torch.floor(x), torch.floor(y)
+    zero = torch.zeros_like(x)
+    dx = torch.where(finite, x - fx, zero).double()
+    dy = torch.where(finite, y - fy, zero).double()
+    return finite, fx, fy, dx, dy
+
+
+def alt_corr_ref64(f1, f2, coords, r):
+    """alt_corr_fwd_kernel (correlation_kernel.cu:18-119): f1 [B,H1,W1,C], f2 [B,H2,W2,C], coords [B,N,H1,W1,2] -> (corr, mag), each
+    [B,N,(2r+1)^2,H1,W1] float64.  Channel ky + rd*kx is the bilinear sample of f2 at (x - r + kx, y - r + ky) dotted with f1; texels
+    outside the map are zero; a sample whose coordinate is not finite is 0 (deliberate deviations)."""
+    B, H1, W1, C = f1.shape
+    _, H2, W2, _ = f2.shape
+    N, rd, P1, T = coords.shape[1], 2 * r + 1, H1 * W1, H2 * W2
+    finite, fx, fy, dx, dy = (t.reshape(B, N, P1) for t in _corr_floor(coords))
+    a = f1.detach().cpu().double().reshape(B, 1, P1, C)
+    t = torch.cat([f2.detach().cpu().double().reshape(B, T, C), torch.zeros(B, 1, C, dtype=torch.float64)], 1)       # (row T: the zero texel)
+    aa, ta = a.abs(), t.abs()
+    bidx = torch.arange(B).view(B, 1, 1)
+    corr = torch.zeros(B, N, rd * rd, P1, dtype=torch.float64)
+    mag = torch.zeros_like(corr)
+    for kx in range(rd):
+        for ky in range(rd):
+            sx, sy = fx + float(kx - r), fy + float(ky - r)                  # fp32 adds, as cer_bilerp_dot receives them
+            near = finite & (sx >= -1.0) & (sx <= float(W2)) & (sy >= -1.0) & (sy <= float(H2))
+            ix, iy = torch.where(near, sx, torch.zeros_like(sx)).long(), torch.where(near, sy, torch.zeros_like(sy)).long()
+            for oy, ox, wt in ((0, 0, (1 - dy) * (1 - dx)), (0, 1, (1 - dy) * dx), (1, 0, dy * (1 - dx)), (1, 1, dy * dx)):
+                xi, yi = ix + ox, iy + oy
+                ok = near & (xi >= 0) & (xi < W2) & (yi >= 0) & (yi < H2)
+                idx = torch.where(ok, yi * W2 + xi, torch.full_like(xi, T))
+                corr[:, :, ky + rd * kx] += wt * (t[bidx, idx] * a).sum(-1)
+                mag[:, :, ky + rd * kx] += wt * (ta[bidx, idx] * aa).sum(-1)
+    return corr.view(B, N, rd * rd, H1, W1), mag.view(B, N, rd * rd, H1, W1)
+
+
+def alt_corr_tuples_ref64(coords, g, r, H2, W2):
+    """alt_corr_bwd_tuples_kernel: one (key, coefficient, source pixel) per (sample, footprint texel), sample (b, n, p) major, footprint
+    (iy, ix) in [0, rd]^2 row-major.  coords [B,N,H1,W1,2], g = corr_grad [B,N,rd^2,H1,W1] -> (keys int64, coef, coef_mag float64, src
+    int32), each [S, (rd+1)^2].  Texel (iy0 + iy, ix0 + ix) with (ix0, iy0) = floor - r gathers the up to four outputs whose footprint
+    holds it:  g[(iy-1) + rd (ix-1)] dy dx + g[(iy-1) + rd ix] dy (1-dx) + g[iy + rd (ix-1)] (1-dy) dx + g[iy + rd ix] (1-dy)(1-dx).
+    key = (b H2 + h2) W2 + w2, or the sentinel B H2 W2 (coefficient 0) when the texel is outside the map, the coordinate is not finite
+    or |floor| > 2e9.  In fp32 a term is (g * wy) * wx with wy or wx = 1 - d rounded: 4 roundings at most; three more for adding four
+    terms; one for their second-order products: K_COEF = 8, relative to coef_mag = sum |g| wy wx."""
+    B, N, H1, W1, _ = coords.shape
+    rd, P1 = 2 * r + 1, H1 * W1
+    S, fp = B * N * P1, (rd + 1) ** 2
+    finite, fx, fy, dx, dy = (t.reshape(S) for t in _corr_floor(coords))
+    ok = finite & (fx.abs() <= 2.0e9) & (fy.abs() <= 2.0e9)
+    z = torch.zeros_like(fx)
+    ix0, iy0 = torch.where(ok, fx, z).long() - r, torch.where(ok, fy, z).long() - r
+    s = torch.arange(S)
+    b, p = s // (N * P1), s % P1
+    gs = g.detach().cpu().double().reshape(B, N, rd * rd, P1).permute(0, 1, 3, 2).reshape(S, rd * rd)
+    keys = torch.empty(S, fp, dtype=torch.int64)
+    coef = torch.zeros(S, fp, dtype=torch.float64)
+    cmag = torch.zeros(S, fp, dtype=torch.float64)
+    for iy in range(rd + 1):
+        for ix in range(rd + 1):
+            h2, w2 = iy0 + iy, ix0 + ix
+            inb = ok & (h2 >= 0) & (h2 < H2) & (w2 >= 0) & (w2 < W2)
+            c, m = torch.zeros(S, dtype=torch.float64), torch.zeros(S, dtype=torch.float64)
+            for cy, cx, wy, wx in ((iy - 1, ix - 1, dy, dx), (iy - 1, ix, dy, 1 - dx), (iy, ix - 1, 1 - dy, dx), (iy, ix, 1 - dy, 1 - dx)):
+                if 0 <= cy < rd and 0 <= cx < rd:
+                    c += gs[:, cy + rd * cx] * wy * wx
+                    m += gs[:, cy + rd * cx].abs() * wy * wx
+            o = iy * (rd + 1) + ix
+            keys[:, o] = torch.where(inb, (b * H2 + h2) * W2 + w2, torch.full_like(h2, B * H2 * W2))
+            coef[:, o] = torch.where(inb, c, torch.zeros_like(c))
+            cmag[:, o] = torch.where(inb, m, torch.zeros_like(m))
+    src = (b * P1 + p).to(torch.int32)[:, None].expand(S, fp).contiguous()
+    return keys, coef, cmag, src
+
+
+def alt_corr_adjoint_ref64(f1, f2, coords, g, r):
+    """alt_corr_bwd_kernel / the tuples + sorted reduction (correlation_kernel.cu:122-256) -> (g1, mag1, n1, g2, mag2, n2, keys, coef, src):
+    g1 [B,H1,W1,C] = sum over the pixel's samples and their in-map footprint texels of coef * f2[texel] (n1 [B,H1,W1] terms, one fma
+    each); g2 [B,H2,W2,C] = sum over the tuples of a texel of coef * f1[src] (n2 [B,H2,W2] = the texel's segment length); keys, coef, src
+    flat in the order of cer_alt_corr_bwd_tuples_f32.  A sample with a non-finite coordinate or |floor| > 2e9 contributes nothing."""
+    B, H1, W1, C = f1.shape
+    _, H2, W2, _ = f2.shape
+    P1, T = H1 * W1, H2 * W2
+    keys, coef, cmag, src = alt_corr_tuples_ref64(coords, g, r, H2, W2)
+    a = f1.detach().cpu().double().reshape(B * P1, C)
+    t = torch.cat([f2.detach().cpu().double().reshape(B * T, C), torch.zeros(1, C, dtype=torch.float64)], 0)           # (row B*T: the sentinel)
+    g1, mag1 = torch.zeros(B * P1, C, dtype=torch.float64), torch.zeros(B * P1, C, dtype=torch.float64)
+    g2, mag2 = torch.zeros(B * T + 1, C, dtype=torch.float64), torch.zeros(B * T + 1, C, dtype=torch.float64)
+    n1, n2 = torch.zeros(B * P1, dtype=torch.int64), torch.zeros(B * T + 1, dtype=torch.int64)
+    sl = src[:, 0].long()
+    for o in range(keys.shape[1]):
+        k, c, m = keys[:, o], coef[:, o, None], cmag[:, o, None]
+        inb = (k < B * T).long()
+        g1.index_add_(0, sl, c * t[k])
+        mag1.index_add_(0, sl, m * t[k].abs())
+        n1.index_add_(0, sl, inb)
+        g2.index_add_(0, k, c * a[sl])
+        mag2.index_add_(0, k, m * a[sl].abs())
+        n2.index_add_(0, k, inb)
+    return (g1.view(B, H1, W1, C), mag1.view(B, H1, W1, C), n1.view(B, H1, W1), g2[:-1].view(B, H2, W2, C), mag2[:-1].view(B, H2, W2, C),
+            n2[:-1].view(B, H2, W2), keys.reshape(-1), coef.reshape(-1), src.reshape(-1))
+
+
+def tl_coord32(origin, disp, D, incre):
+    """tl_coord (core/corr.py:107) in torch fp32: max((disp - origin) / incre + D//2, 0) - subtract, true division by fl32(incre), add,
+    clamp, one fp32 rounding each, as __fsub_rn / __fdiv_rn / __fadd_rn."""
+    inc = torch.tensor(float(incre), dtype=torch.float32)
+    return torch.clamp_min((disp.detach().cpu().float() - origin.detach().cpu().float()) / inc + float(D // 2), 0.0)
+
+
+def _tl_taps(c, D, L, r):
+    """Every (level, tap) of the lookup: x = fl32((j - r) + c / 2^level) (the division is exact), i0 = floor x, w = x - i0 (exact) ->
+    (level, j, length, i0 clamped into the level, mask of texel i0 in the level, i0 + 1 clamped, its mask, w as float64)."""
+    for lv in range(L):
+        n = D >> lv
+        cl = c / float(1 << lv)
+        for j in range(2 * r + 1):
+            x = float(j - r) + cl
+            fx = torch.floor(x)
+            valid = (fx >= -1.0) & (fx <= float(n - 1))
+            i0 = torch.where(valid, fx, torch.zeros_like(fx)).long()
+            yield lv, j, n, i0.clamp(0, n - 1), valid & (i0 >= 0), (i0 + 1).clamp(0, n - 1), valid & (i0 + 1 < n), (x - fx).double()
+
+
+def train_lookup_ref64(vol, origin, disp, D, incre, L, r):
+    """train_lookup_fwd_kernel (core/corr.py:94-97,102-143; utils/bilinear_sampler.py:6-25): vol [V,D,P], origin, disp [P] ->
+    (out, mag) [V, L (2r+1), P] float64.  Level l+1 = (a + b) * 0.5 of neighbouring pairs of level l, floor halving (the kernel's
+    association; float64 here, so the kernel's level l carries l roundings); tap k = l (2r+1) + j is a (1 - w) + b w between texels i0
+    and i0 + 1 of level l, zero outside it (1 - w, two products, one add: 4 roundings)."""
+    V, _, P = vol.shape
+    c = tl_coord32(origin, disp, D, incre)
+    lev = [(vol.detach().cpu().double(), vol.detach().cpu().double().abs())]
+    for _ in range(1, L):
+        a, m = lev[-1]
+        n = a.shape[1] // 2
+        lev.append(((a[:, 0:2 * n:2] + a[:, 1:2 * n:2]) * 0.5, (m[:, 0:2 * n:2] + m[:, 1:2 * n:2]) * 0.5))
+    taps = 2 * r + 1
+    out = torch.zeros(V, L * taps, P, dtype=torch.float64)
+    mag = torch.zeros_like(out)
+    for lv, j, n, ia, oka, ib, okb, w in _tl_taps(c, D, L, r):
+        for src, dst in zip(lev[lv], (out, mag)):
+            a = src.gather(1, ia.view(1, 1, P).expand(V, 1, P))[:, 0] * oka
+            b = src.gather(1, ib.view(1, 1, P).expand(V, 1, P))[:, 0] * okb
+            dst[:, lv * taps + j] = a * (1 - w) + b * w
+    return out, mag
+
+
+def train_lookup_level_adjoints64(gout, origin, disp, D, incre, L, r):
+    """The per-level accumulators of train_lookup_bwd_kernel before the fold -> [(acc, mag [V, D >> l, P], count [D >> l, P])]."""
+    V, _, P = gout.shape
+    c = tl_coord32(origin, disp, D, incre)
+    g = gout.detach().cpu().double()
+    taps = 2 * r + 1
+    accs = [(torch.zeros(V, D >> lv, P, dtype=torch.float64), torch.zeros(V, D >> lv, P, dtype=torch.float64),
+             torch.zeros(D >> lv, P, dtype=torch.int64)) for lv in range(L)]
+    for lv, j, n, ia, oka, ib, okb, w in _tl_taps(c, D, L, r):
+        acc, mag, cnt = accs[lv]
+        gj = g[:, lv * taps + j]
+        for idx, ok, wt in ((ia, oka, 1 - w), (ib, okb, w)):
+            e = idx.view(1, 1, P).expand(V, 1, P)
+            acc.scatter_add_(1, e, (gj * wt * ok)[:, None])
+            mag.scatter_add_(1, e, (gj.abs() * wt * ok)[:, None])
+            cnt.scatter_add_(0, idx.view(1, P), ok.long().view(1, P))
+    return accs
+
+
+def train_lookup_adjoint_ref64(gout, origin, disp, D, incre, L, r):
+    """train_lookup_bwd_kernel: gout [V, L (2r+1), P] -> (grad, mag [V,D,P], n [D,P]): the taps of a level added into the level's row
+    (g (1 - w) into i0, g w into i0 + 1, where inside), then level 0 gets  g0[d] + sum_l gl[d >> l] 2^-l  for d >> l < D >> l - an odd
+    length leaves its last element without a partner.  n: the taps added into the element's cells plus the folded levels."""
+    accs = train_lookup_level_adjoints64(gout, origin, disp, D, incre, L, r)
+    grad, mag, n = accs[0][0].clone(), accs[0][1].clone(), accs[0][2].clone()
+    d = torch.arange(D)
+    for lv in range(1, L):
+        i = d >> lv
+        ok = i < (D >> lv)
+        grad[:, d[ok]] += accs[lv][0][:, i[ok]] * 0.5 ** lv
+        mag[:, d[ok]] += accs[lv][1][:, i[ok]] * 0.5 ** lv
+        n[d[ok]] += accs[lv][2][i[ok]] + 1
+    return grad, mag, n
+
+
+def upsample_ac_taps(n_in, n_out):
+    """up_tap of csrc/train_ops.hip (torch's upsample_bilinear2d, align_corners=True) for every output index: scale = fl32((in-1) /
+    (out-1)) (0 for out = 1), s = fl32(scale * dst), i0 = min((int) s, in-1), i1 = i0 + 1 clamped, l1 = s - i0 (exact), l0 = 1 - l1
+    (float64 here; one rounding in the kernel) -> (i0, i1 int64, l0, l1 float64)."""
+    one = torch.tensor(1.0, dtype=torch.float32)
+    scale = (one * float(n_in - 1)) / (one * float(n_out - 1)) if n_out > 1 else one * 0.0
+    s = scale * torch.arange(n_out, dtype=torch.float32)
+    i0 = s.long().clamp_max(n_in - 1)
+    i1 = i0 + (i0 < n_in - 1).long()
+    l1 = (s - i0.float()).double()
+    return i0, i1, 1.0 - l1, l1
+
+
+def upsample_ranges_brute(n_in, n_out):
+    """{X : i0(X) == j or i1(X) == j} for every input texel j as [n_in, 2] int32 half-open ranges ((0, 0) for an empty set); the sets
+    are checked to be contiguous."""
+    i0, i1, _, _ = upsample_ac_taps(n_in, n_out)
+    table = torch.zeros(n_in, 2, dtype=torch.int32)
+    for j in range(n_in):
+        X = ((i0 == j) | (i1 == j)).nonzero().reshape(-1)
+        if X.numel():
+            assert int(X[-1]) - int(X[0]) + 1 == X.numel(), (n_in, n_out, j)
+            table[j, 0], table[j, 1] = int(X[0]), int(X[-1]) + 1
+    return table
+
+
+def upsample_ac_ref64(x, H, W):
+    """upsample_ac_fwd_kernel (loss.py:18-19): x [n,h,w] -> (out, mag) [n,H,W] float64,  l0y (l0x a + l1x b) + l1y (l0x c + l1x d).  On the
+    longest path: 1 - l1x, a product, the inner add, 1 - l1y, a product, the outer add = 6 roundings, one more for their second-order
+    products: K_UP_FWD = 7."""
+    n, h, w = x.shape
+    y0, y1, ly0, ly1 = upsample_ac_taps(h, H)
+    x0, x1, lx0, lx1 = upsample_ac_taps(w, W)
+    res = []
+    for v in (x.detach().cpu().double(), x.detach().cpu().double().abs()):
+        top = v[:, y0][:, :, x0] * lx0 + v[:, y0][:, :, x1] * lx1
+        bot = v[:, y1][:, :, x0] * lx0 + v[:, y1][:, :, x1] * lx1
+        res.append(top * ly0[:, None] + bot * ly1[:, None])
+    return res[0], res[1]
+
+
+def upsample_ac_adjoint_pass64(g, n_in, dim):
+    """One pass of the upsample adjoint (upsample_ac_bwd_{x,y}_kernel) along ``dim`` of g: out[j] = sum over the outputs X of range[j] of
+    (l0(X) if i0(X) == j) + (l1(X) if i1(X) == j) times g[X] -> (out, mag, n [n_in], range table): n = the length of range[j], the
+    trips of the kernel's loop.  Relative to mag, a term carries the rounding of l0 = 1 - l1 and of its product (2), and the n terms are
+    joined by n - 1 adds: n + 1 roundings, and one to spare: (n + 2) u.  A trip adds two terms only where i0 == i1 == j, at the last
+    texel: there l1 = s - (in-1) is 0 (an add of +-0, exact; on an axis with in = 1 every trip is of this kind and l0 = 1 makes the
+    products exact too) or, where scale * dst rounds past in - 1, one ulp of it, and that one further add is the spare rounding."""
+    g = g.detach().cpu().double()
+    i0, i1, l0, l1 = upsample_ac_taps(n_in, g.shape[dim])
+    shape = [1] * g.dim()
+    shape[dim] = -1
+    size = list(g.shape)
+    size[dim] = n_in
+    res = []
+    for v in (g, g.abs()):
+        o = torch.zeros(size, dtype=torch.float64)
+        o.index_add_(dim, i0, v * l0.view(shape))
+        o.index_add_(dim, i1, v * l1.view(shape))
+        res.append(o)
+    table = upsample_ranges_brute(n_in, g.shape[dim])
+    return res[0], res[1], (table[:, 1] - table[:, 0]).long(), table
+
+
+def upsample_ac_adjoint_ref64(g, h, w):
+    """The whole adjoint, x pass then y pass: g [n,H,W] -> (grad, mag [n,h,w], n [h,w] = range lengths of both passes, (range_y, range_x))."""
+    work, wmag, nx, rx = upsample_ac_adjoint_pass64(g, w, 2)
+    grad, _, ny, ry = upsample_ac_adjoint_pass64(work, h, 1)
+    mag = upsample_ac_adjoint_pass64(wmag, h, 1)[0]
+    return grad, mag, ny[:, None] + nx[None, :], (ry, rx)
