@@ -11,8 +11,15 @@ and Tanks-and-Temples' precision / recall / F-score (shares of them below a thre
 
 Clouds are CUDA float32 tensors [n, 3]; there is no CPU fallback.  Sorting (``torch.sort(stable=True)``) and the reductions over the distance
 vector (fp64 ``sum`` / ``count_nonzero``) are torch; keys, the cell table, the record gather and the search are HIP kernels.  Everything is a
-pure function of its inputs: no atomics, the same bytes on every run.  Reading ground-truth files, observability masks and alignment
-transforms of the benchmarks is the caller's business (``keep_pred`` / ``keep_gt`` carry masks in)."""
+pure function of its inputs: no atomics, the same bytes on every run.  Reading ground-truth files, crop volumes, observability masks and
+ground planes of the benchmarks is the caller's business (``keep_pred`` / ``keep_gt`` carry masks in).
+
+Clouds in slightly different frames are registered first (csrc/cloud_align.hip): point-to-point ICP on the same search,
+
+    T = register(pred, gt, stages=((4 * tau, 8 * tau, 30), (None, 3 * tau, 30)))["T"]      # coarse to fine; or icp(pred, gt, max_dist)
+    fscore(pred, gt, tau, align=T)
+
+with ``rigid_transform`` and ``pair_moments`` as its two kernels and ``rigid_from_moments`` (Kabsch, numpy fp64) as its solve."""
 import ctypes
 import math
 
@@ -33,6 +40,9 @@ DEFAULT_CELL_DIVISOR = 4
 # host read that tells the loop whether anything is left).  Measured by tools/bench_cloud_thin.py against 1 and 4
 # (profiles/cloud_thin_bench.json "rounds_per_compaction").
 THIN_ROUNDS_PER_COMPACTION = 2
+MOMENT_TILE = 2048                                           # cer_mvs.h CER_MOMENT_TILE
+MOMENT_COUNT = 17                                            # cer_mvs.h CER_MOMENT_COUNT
+COLLINEAR_RATIO = 1e-12                                      # rigid_from_moments: second singular value / first at or below this -> no rotation
 
 
 def _cloud(t, name):
@@ -295,16 +305,20 @@ def _thin(pred, thin, thin_method, thin_seed):
     return radius_thin(pred, thin, seed=thin_seed) if thin_method == "greedy" else voxel_downsample(pred, thin)
 
 
-def accuracy_completeness(pred, gt, max_dist=20.0, thin=None, keep_pred=None, keep_gt=None, cell=None, thin_method="voxel", thin_seed=0):
+def accuracy_completeness(pred, gt, max_dist=20.0, thin=None, keep_pred=None, keep_gt=None, cell=None, thin_method="voxel", thin_seed=0,
+                          align=None):
     """The DTU protocol.  ``pred`` is first thinned if ``thin`` is given: with ``voxel_downsample(pred, thin)`` (``thin_method="voxel"``, the
     default: one point per cell of that edge) or with ``radius_thin(pred, thin, seed=thin_seed)`` (``"greedy"``: the MATLAB script's own
     reduction, visiting the points in a seeded random order).  accuracy = mean distance pred -> gt over the points with d < max_dist, completeness = the same gt -> pred, overall =
     their mean.  ``keep_pred`` / ``keep_gt``: optional boolean masks (one entry per point of ``pred`` as passed in / of ``gt``) selecting
     which points enter the two means - where a caller applies DTU's observability mask and ground plane; every point still serves as a
     neighbour.  -> {"accuracy", "completeness", "overall", "n_pred", "n_gt", "n_pred_in", "n_gt_in"}: n_pred / n_gt are the points that were
-    measured (after thinning and masks), n_*_in those within max_dist."""
+    measured (after thinning and masks), n_*_in those within max_dist.  ``align``: a 4x4 rigid motion applied to ``pred`` with
+    ``rigid_transform`` before anything else (``icp`` / ``register`` find one)."""
     if thin_method not in ("voxel", "greedy"):
         raise ValueError(f'thin_method: "voxel" or "greedy" expected, got {thin_method!r}')
+    if align is not None:
+        pred = rigid_transform(pred, align)
     pred, gt = _cloud(pred, "pred"), _cloud(gt, "gt")
     kp, kg = _keep(pred, keep_pred, "keep_pred"), _keep(gt, keep_gt, "keep_gt")
     if thin is not None:
@@ -321,9 +335,12 @@ def accuracy_completeness(pred, gt, max_dist=20.0, thin=None, keep_pred=None, ke
     return metrics_from_distances(d_pred, d_gt, max_dist)
 
 
-def fscore(pred, gt, tau, cell=None):
+def fscore(pred, gt, tau, cell=None, align=None):
     """The Tanks-and-Temples protocol: precision = share of ``pred`` within ``tau`` of ``gt`` (d < tau), recall = share of ``gt`` within ``tau``
-    of ``pred``, fscore = their harmonic mean (0 when both are 0).  -> {"precision", "recall", "fscore", "tau", "n_pred", "n_gt"}."""
+    of ``pred``, fscore = their harmonic mean (0 when both are 0).  -> {"precision", "recall", "fscore", "tau", "n_pred", "n_gt"}.
+    ``align``: a 4x4 rigid motion applied to ``pred`` with ``rigid_transform`` before anything else."""
+    if align is not None:
+        pred = rigid_transform(pred, align)
     pred, gt = _cloud(pred, "pred"), _cloud(gt, "gt")
     tau32 = float(np.float32(tau))
     cut = float(np.nextafter(np.float32(tau32), np.float32(np.inf))) if tau32 < float(tau) else tau32      # a float32 cut-off that is not below tau
@@ -331,6 +348,177 @@ def fscore(pred, gt, tau, cell=None):
     d_gt = cloud_distances(gt, pred, cut, cell)
     m = metrics_from_distances(d_pred, d_gt, cut, tau=tau)
     return {k: m[k] for k in ("precision", "recall", "fscore", "tau", "n_pred", "n_gt")}
+
+
+# ---------------------------------------------------------------- rigid registration (csrc/cloud_align.hip)
+def _rigid(T, name="T"):
+    """-> 4x4 float64 numpy; ValueError unless ``T`` is a finite 4x4 whose last row is 0 0 0 1"""
+    if isinstance(T, torch.Tensor):
+        T = T.detach().double().cpu().numpy()
+    try:
+        T = np.array(T, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"{name}: a 4x4 matrix expected") from e
+    if T.shape != (4, 4):
+        raise ValueError(f"{name}: a 4x4 matrix expected, got shape {T.shape}")
+    if not np.isfinite(T).all():
+        raise ValueError(f"{name}: finite entries expected")
+    if not np.array_equal(T[3], (0.0, 0.0, 0.0, 1.0)):
+        raise ValueError(f"{name}: the last row of a rigid motion is 0 0 0 1, got {T[3].tolist()}")
+    return T
+
+
+def _transform(points, T):                                   # points: a checked cloud, T: a checked 4x4
+    n = int(points.shape[0])
+    out = torch.empty(n, 3, device=points.device, dtype=torch.float32)
+    rows = (ctypes.c_double * 12)(*[float(v) for v in T[:3].reshape(-1)])
+    L.check(L.load().cer_cloud_transform_f32(L.dev_ptr(points, "points"), n, rows, L.dev_ptr(out, "out"), L.cur_stream()), "cloud_transform")
+    return out
+
+
+def rigid_transform(points, T):
+    """A new float32 [n, 3]: ``T`` (4x4, numpy or tensor, taken as fp64; last row 0 0 0 1, ValueError otherwise) applied to every point:
+    out[i][r] = float32(((T[r][0] * x + T[r][1] * y) + T[r][2] * z) + T[r][3]) with x, y, z promoted to fp64 - that association, no fused
+    multiply-add, one rounding to float32.  Non-finite coordinates propagate by IEEE rules."""
+    T = _rigid(T)
+    return _transform(_cloud(points, "points"), T)
+
+
+def _pivot(pivot):
+    pivot = np.zeros(3) if pivot is None else np.array(pivot, dtype=np.float64).reshape(-1)
+    if pivot.shape != (3,) or not np.isfinite(pivot).all():
+        raise ValueError("pivot: three finite numbers expected")
+    return pivot
+
+
+def _moments(a, b, idx, pivot):                              # checked clouds, idx int64 [len(a)] on their device, pivot: 3 doubles
+    m, dev = int(a.shape[0]), a.device
+    if m == 0:
+        return np.zeros(MOMENT_COUNT)
+    lib = L.load()
+    partials = torch.empty(MOMENT_COUNT * int(lib.cer_cloud_moment_partials(m)), device=dev, dtype=torch.float64)
+    out = torch.empty(MOMENT_COUNT, device=dev, dtype=torch.float64)
+    L.check(lib.cer_cloud_pair_moments_f64(L.dev_ptr(a, "a"), L.dev_ptr(b, "b"), L.dev_ptr(idx, "idx", torch.int64), m,
+                                           (ctypes.c_double * 3)(*[float(v) for v in pivot]), L.dev_ptr(partials, "partials", torch.float64),
+                                           L.dev_ptr(out, "out", torch.float64), L.cur_stream()), "cloud_pair_moments")
+    return out.cpu().numpy()
+
+
+def pair_moments(a, b, idx, pivot=None):
+    """numpy float64 [17]: the sums over the pairs (a[i], b[idx[i]]), i with idx[i] >= 0 (``nearest``'s -1: no pair) and a finite a[i].  With
+    A = double(a) - pivot and B = double(b) - pivot (``pivot``: three numbers, default 0 0 0; near the clouds it keeps the covariance free of
+    cancellation): [0] k, the number of pairs; [1:4] sum A; [4:7] sum B; [7:16] sum of the outer product A x B (row: A's axis); [16] sum of
+    |a - b|^2 as ``nearest`` forms d2.  fp64, a fixed summation tree: the same bits on every run.  Returning them is the one
+    host read.  ``idx``: int64 [len(a)], every entry -1 or a row of ``b`` (ValueError otherwise)."""
+    pivot = _pivot(pivot)
+    a, b = _cloud(a, "a"), _cloud(b, "b")
+    if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int64 or tuple(idx.shape) != (a.shape[0],):
+        raise ValueError("idx: an int64 tensor with one entry per point of a expected")
+    idx = idx.to(a.device).contiguous()
+    if len(idx) and (int(idx.max()) >= int(b.shape[0]) or int(idx.min()) < -1):
+        raise ValueError(f"idx: entries in -1 .. {int(b.shape[0]) - 1} expected")
+    return _moments(a, b, idx, pivot)
+
+
+def rigid_from_moments(mom, pivot=(0.0, 0.0, 0.0)):
+    """The least-squares rigid motion of the pairs behind ``mom`` (``pair_moments`` taken about ``pivot``) as a 4x4 float64 - Kabsch: with the
+    means Abar, Bbar and H = sum A x B - k Abar x Bbar = U S V^T, R = V diag(1, 1, det(V U^T)) U^T and t = (Bbar + pivot) - R (Abar + pivot).
+    Pure numpy.  ValueError for fewer than 3 pairs and for collinear pairs (second singular value <= 1e-12 of the first: the rotation about
+    their line is not determined); planar pairs are fine, the det term picks the proper rotation."""
+    mom = np.array(mom, dtype=np.float64).reshape(-1)
+    if mom.shape != (MOMENT_COUNT,):
+        raise ValueError(f"mom: {MOMENT_COUNT} sums expected")
+    pivot = _pivot(pivot)
+    k = mom[0]
+    if not k >= 3:
+        raise ValueError(f"rigid_from_moments: at least 3 pairs expected, got {k:g}")
+    abar, bbar = mom[1:4] / k, mom[4:7] / k
+    H = mom[7:16].reshape(3, 3) - k * np.outer(abar, bbar)
+    U, S, Vt = np.linalg.svd(H)
+    if not S[1] > COLLINEAR_RATIO * S[0]:
+        raise ValueError("rigid_from_moments: the pairs are collinear (or coincide); the rotation is not determined")
+    V = Vt.T
+    R = V @ np.diag((1.0, 1.0, float(np.sign(np.linalg.det(V @ U.T))))) @ U.T
+    T = np.eye(4)
+    T[:3, :3] = R
+    T[:3, 3] = (bbar + pivot) - R @ (abar + pivot)
+    return T
+
+
+def _icp_args(max_dist, init, max_iter, tol_fitness, tol_rmse):
+    max_dist = float(np.float32(max_dist))
+    if not (max_dist > 0.0 and math.isfinite(max_dist)):
+        raise ValueError("max_dist must be a positive finite number")
+    max_iter = int(max_iter)
+    if max_iter < 1:
+        raise ValueError("max_iter must be >= 1")
+    tol_fitness, tol_rmse = float(tol_fitness), float(tol_rmse)
+    if not (tol_fitness >= 0.0 and tol_rmse >= 0.0):
+        raise ValueError("tol_fitness and tol_rmse must be >= 0")
+    return max_dist, (np.eye(4) if init is None else _rigid(init, "init")), max_iter, tol_fitness, tol_rmse
+
+
+def icp(src, dst, max_dist, init=None, max_iter=50, tol_fitness=1e-6, tol_rmse=1e-6, cell=None, index=None):
+    """Point-to-point ICP of ``src`` onto ``dst`` (CUDA float32 [n, 3] each), from ``init`` (4x4, default the identity).  ``dst`` is indexed
+    once (``CloudIndex(dst, cell)``, ``cell`` default ``max_dist / 4``; or the caller's ``index``, which must be over ``dst``).  An iteration:
+    cur = rigid_transform(src, T) - always from the original ``src`` with the accumulated fp64 T: one rounding, no drift; index.nearest(cur,
+    max_dist); the moments of the pairs about the index's origin; fitness = pairs / len(src), rmse = sqrt(mean d2 of the pairs); stop when
+    both moved by less than their tolerance since the iteration before (Open3D's criterion, which the Tanks-and-Temples script uses), else
+    T <- rigid_from_moments(...) @ T on the host.  One host read per iteration, at most ``max_iter`` iterations.
+
+    -> {"T": 4x4 float64 numpy, src -> dst's frame; "iterations": evaluations made; "converged"; "fitness", "rmse", "n_pairs": of the last
+    evaluation (when ``max_iter`` ends the loop: the one before the last update of T); "history": [(fitness, rmse), ...]}.  Fewer than 3
+    pairs (empty clouds included) stop the loop with converged = False and T as it stands; collinear pairs raise ValueError."""
+    max_dist, T, max_iter, tol_fitness, tol_rmse = _icp_args(max_dist, init, max_iter, tol_fitness, tol_rmse)
+    src, dst = _cloud(src, "src"), _cloud(dst, "dst")
+    if index is None:
+        index = CloudIndex(dst, float(max_dist) / DEFAULT_CELL_DIVISOR if cell is None else cell)
+    elif not isinstance(index, CloudIndex) or index.points.shape != dst.shape or index.points.device != dst.device:
+        raise ValueError("index: a CloudIndex over dst expected")
+    n = int(src.shape[0])
+    out = {"T": T, "iterations": 0, "converged": False, "fitness": 0.0, "rmse": 0.0, "n_pairs": 0, "history": []}
+    if n == 0 or index.n == 0:
+        return out
+    pivot = np.array([float(v) for v in index.origin])
+    for _ in range(max_iter):
+        cur = _transform(src, T)
+        mom = _moments(cur, index.points, index.nearest(cur, max_dist)[1], pivot)      # (the one host read)
+        k = int(mom[0])
+        fitness, rmse = k / n, (math.sqrt(mom[16] / k) if k else 0.0)
+        moved = (abs(fitness - out["fitness"]), abs(rmse - out["rmse"])) if out["iterations"] else None
+        out["history"].append((fitness, rmse))
+        out.update(iterations=out["iterations"] + 1, fitness=fitness, rmse=rmse, n_pairs=k)
+        if k < 3:
+            break
+        if moved is not None and moved[0] < tol_fitness and moved[1] < tol_rmse:
+            out["converged"] = True
+            break
+        T = rigid_from_moments(mom, pivot) @ T
+        out["T"] = T
+    return out
+
+
+def register(src, dst, stages, init=None):
+    """Coarse-to-fine ICP: ``stages`` is a sequence of (voxel, max_dist, max_iter); every stage runs ``icp`` on ``voxel_downsample`` of both
+    clouds with that edge (voxel None: the clouds as they are) from the stage before's T (the first from ``init``).  -> the last stage's dict
+    plus "stages", the list of every stage's dict."""
+    try:
+        stages = [(None if v is None else _cell(v), float(d), int(it)) for v, d, it in stages]
+    except (TypeError, ValueError) as e:
+        raise ValueError("stages: a sequence of (voxel or None, max_dist, max_iter) expected") from e
+    if not stages:
+        raise ValueError("stages: at least one stage expected")
+    for _, d, it in stages:
+        _icp_args(d, None, it, 0.0, 0.0)
+    T = np.eye(4) if init is None else _rigid(init, "init")
+    src, dst = _cloud(src, "src"), _cloud(dst, "dst")
+    done = []
+    for voxel, max_dist, max_iter in stages:
+        s = src if voxel is None else src.index_select(0, voxel_downsample(src, voxel))
+        d = dst if voxel is None else dst.index_select(0, voxel_downsample(dst, voxel))
+        done.append(icp(s, d, max_dist, init=T, max_iter=max_iter))
+        T = done[-1]["T"]
+    return {**done[-1], "stages": done}
 
 
 _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "<i2", "int16": "<i2", "ushort": "<u2", "uint16": "<u2",

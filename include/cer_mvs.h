@@ -622,6 +622,30 @@ int cer_grid_thin_round_f32(const void* records, long n, const long long* cell_k
 int cer_grid_thin_compact_i32(const void* records, long n, const unsigned char* state, const int* active, long n_active,
                               unsigned int* partials, long long* offsets, int* out, long long* total, void* stream);
 
+/* Rigid registration of two clouds (ABI 1130; csrc/cloud_align.hip, cer-mvs_amd/cloud_eval.py rigid_transform / pair_moments / icp, DESIGN.md
+ * 3w): what point-to-point ICP needs beside cer_grid_nearest_f32.  fp64 arithmetic on float32 coordinates with every association fixed, no
+ * atomics, grids and summation trees that depend on the sizes alone: the same bits on every run and every machine.  Sizes and errors as
+ * above: negative -> CER_EINVAL, 2^31 and beyond -> CER_ESHAPE; then T / pivot null or with a non-finite entry -> CER_EINVAL; zero -> CER_OK
+ * with nothing launched; then null pointers -> CER_EINVAL.  Every check runs before any launch.
+ *
+ *   cer_cloud_transform_f32: out[i][r] = float(((T[4r] * x + T[4r+1] * y) + T[4r+2] * z) + T[4r+3]), (x, y, z) = points[i] promoted to fp64;
+ *     T: 12 HOST doubles, the upper 3 x 4 of the motion, row-major.  No fused multiply-add.  Non-finite coordinates propagate by IEEE rules.
+ *     out [n, 3] is written whole and may not overlap points (CER_EINVAL).
+ *   cer_cloud_moment_partials: HOST function: ceil(m / CER_MOMENT_TILE), the blocks of the first pass; `partials` below holds
+ *     CER_MOMENT_COUNT * that many doubles.
+ *   cer_cloud_pair_moments_f64: a pair is (a[i], b[idx[i]]) for every i < m with idx[i] >= 0 (cer_grid_nearest_f32's -1: no pair) and a
+ *     finite a[i]; idx[i] must be a valid row of b.  pivot: 3 HOST doubles.  With A = double(a) - pivot, B = double(b) - pivot and D =
+ *     double(a) - double(b), out (CER_MOMENT_COUNT DEVICE doubles, written whole) = [k, the number of pairs | sum A (3) | sum B (3) | sum
+ *     A[r] * B[c] at 7 + 3 r + c | sum (Dx*Dx + Dy*Dy) + Dz*Dz, the d2 of cer_grid_nearest_f32].  Two passes: every 256-thread block sums
+ *     CER_MOMENT_TILE consecutive pairs (a thread its pairs t, t + 256, ... in ascending order, the wave a butterfly, the four waves (w0 + w1)
+ *     + (w2 + w3)), then one block of 1024 threads sums the partials (a thread p, p + 1024, ...; butterfly; a pairwise tree over 16 waves). */
+#define CER_MOMENT_TILE 2048
+#define CER_MOMENT_COUNT 17
+int cer_cloud_transform_f32(const float* points, long n, const double* T, float* out, void* stream);
+long cer_cloud_moment_partials(long m);
+int cer_cloud_pair_moments_f64(const float* a, const float* b, const long long* idx, long m, const double* pivot, double* partials,
+                               double* out, void* stream);
+
 /* Multi-GPU row-slab exchange (cer-mvs_amd/slab.py): up to CER_COPY_MAX_SEG contiguous fp32 ranges copied by ONE launch -
  * the pack of a rank's (net, disp) border strips into its send buffer, and the refresh of its halo rows from the gathered
  * strips.  n[i] floats from src[i] to dst[i]; n[i] == 0 skips a segment.  Device pointers; ranges must not overlap. */
