@@ -19,7 +19,15 @@ Clouds in slightly different frames are registered first (csrc/cloud_align.hip, 
     T = register(pred, gt, stages=((4 * tau, 8 * tau, 30), (None, 3 * tau, 30)))["T"]      # coarse to fine; or icp(pred, gt, max_dist)
     fscore(pred, gt, tau, align=T)
 
-with ``rigid_transform`` and ``pair_moments`` as its two kernels and ``rigid_from_moments`` (Kabsch, numpy fp64) as its solve."""
+with ``rigid_transform`` and ``pair_moments`` as its two kernels and ``rigid_from_moments`` (Kabsch, numpy fp64) as its solve.
+
+The same index answers two more queries: ``CloudIndex.knn`` / ``knn_mean_distance`` - the k <= 32 nearest points of every query
+in ascending (d2, index) order, or only their mean distance - and ``CloudIndex.count_within``, the number of points within a radius; same
+contract: fp64 distances, lowest index on ties, inclusive cut-off, no atomics.  The two standard outlier filters for fused clouds rest on them:
+
+    keep = remove_statistical_outliers(pred, k=20, std_ratio=2.0)      # or remove_radius_outliers(pred, radius, min_neighbours)
+    pred = pred.index_select(0, keep)
+    reconstruct_scan(model, ..., clean={"method": "statistical", "k": 20, "std_ratio": 2.0})      # the same, before the cloud leaves the device"""
 import ctypes
 import math
 
@@ -40,6 +48,11 @@ DEFAULT_CELL_DIVISOR = 4
 # host read that tells the loop whether anything is left).  Measured by tools/bench_cloud_thin.py against 1 and 4
 # (profiles/cloud_thin_bench.json "rounds_per_compaction").
 THIN_ROUNDS_PER_COMPACTION = 2
+KNN_MAX = 32                                                 # cer_mvs.h CER_KNN_MAX: the widest neighbour list the search keeps in registers
+# The outlier filters' default cell is max_dist (or radius) / this.  Twenty neighbours reach farther than one, so the divisor measured for
+# ``nearest`` need not have held: tools/bench_cloud_knn.py sweeps 1, 2, 4, 8 at k = 20, and 4 wins there too (profiles/cloud_knn_bench.json
+# "cell_sweep").
+KNN_CELL_DIVISOR = DEFAULT_CELL_DIVISOR
 MOMENT_TILE = 2048                                           # cer_mvs.h CER_MOMENT_TILE
 MOMENT_COUNT = 17                                            # cer_mvs.h CER_MOMENT_COUNT
 COLLINEAR_RATIO = 1e-12                                      # rigid_from_moments: second singular value / first at or below this -> no rotation
@@ -153,6 +166,72 @@ class CloudIndex:
         L.check(rc, "grid_nearest")
         return dist, idx
 
+    def _walk_order(self, queries, m):                       # the queries' positions in the order of their own cell keys
+        qkeys = torch.empty(m, device=queries.device, dtype=torch.int64)
+        L.check(L.load().cer_grid_keys_f32(L.dev_ptr(queries, "queries"), m, self.origin, self.cell, 1, L.dev_ptr(qkeys, "keys", torch.int64), None,
+                                           L.cur_stream()), "grid_keys")
+        return torch.sort(qkeys, stable=True).indices
+
+    def _knn(self, queries, k, max_dist, sort_queries, lists, mean):
+        k = int(k)
+        if not 1 <= k <= KNN_MAX:
+            raise ValueError(f"k: 1 .. {KNN_MAX} expected, got {k}")
+        max_dist = float(np.float32(max_dist))
+        if not max_dist >= 0.0:
+            raise ValueError("max_dist must be >= 0")
+        queries = _cloud(queries, "queries")
+        m, dev = int(queries.shape[0]), queries.device
+        inf = float("inf")
+        if m == 0 or self.n == 0:                            # (the entry point launches nothing for an empty side)
+            return (torch.full((m, k), inf, device=dev, dtype=torch.float32) if lists else None,
+                    torch.full((m, k), -1, device=dev, dtype=torch.int64) if lists else None, torch.zeros(m, device=dev, dtype=torch.int32),
+                    torch.full((m,), inf, device=dev, dtype=torch.float64) if mean else None)
+        dist = torch.empty(m, k, device=dev, dtype=torch.float32) if lists else None
+        idx = torch.empty(m, k, device=dev, dtype=torch.int64) if lists else None
+        count = torch.empty(m, device=dev, dtype=torch.int32)
+        avg = torch.empty(m, device=dev, dtype=torch.float64) if mean else None
+        qorder = self._walk_order(queries, m) if sort_queries else None
+        rc = L.load().cer_grid_knn_f32(*self.grid_args(), L.dev_ptr(queries, "queries"), L.dev_ptr(qorder, "qorder", torch.int64), m, k, max_dist,
+                                       L.dev_ptr(idx, "idx", torch.int64), L.dev_ptr(dist, "dist"), L.dev_ptr(count, "count", torch.int32),
+                                       L.dev_ptr(avg, "mean", torch.float64), L.cur_stream())
+        if rc == -2:
+            raise ValueError(f"nearest: max_dist {max_dist} is more than {GRID_MAX_RINGS} cells of {self.cell}; index the cloud with a larger cell")
+        L.check(rc, "grid_knn")
+        return dist, idx, count, avg
+
+    def knn(self, queries, k, max_dist, sort_queries=True):
+        """-> (dist float32 [m, k], idx int64 [m, k], count int32 [m]): per query the min(k, candidates) indexed points with the smallest (d2,
+        index), in that order; d2, the candidates (d2 <= double(float32(max_dist))^2) and dist as ``nearest`` defines them.  Unused slots are
+        (inf, -1); count = the used ones, 0 for a query that is not finite.  A query that is itself an indexed point finds itself (or a
+        duplicate of lower index) first, at 0.  ``k``: 1 .. 32 (KNN_MAX), ValueError otherwise; k = 1 is ``nearest``."""
+        dist, idx, count, _ = self._knn(queries, k, max_dist, sort_queries, True, False)
+        return dist, idx, count
+
+    def knn_mean_distance(self, queries, k, max_dist, sort_queries=True):
+        """-> (mean float64 [m], count int32 [m]): the mean of the fp64 distances sqrt(d2) to the neighbours ``knn`` lists, added in ascending
+        order and divided by their number (inf where count = 0) - without the [m, k] lists ever being written."""
+        _, _, count, mean = self._knn(queries, k, max_dist, sort_queries, False, True)
+        return mean, count
+
+    def count_within(self, queries, radius, sort_queries=True):
+        """-> int32 [m]: the number of indexed points with d2 <= double(float32(radius))^2 (``nearest``'s d2; inclusive; the query itself when it
+        is an indexed point); 0 for a query that is not finite."""
+        radius = float(np.float32(radius))
+        if not radius >= 0.0:
+            raise ValueError("radius must be >= 0")
+        queries = _cloud(queries, "queries")
+        m, dev = int(queries.shape[0]), queries.device
+        if m == 0 or self.n == 0:
+            return torch.zeros(m, device=dev, dtype=torch.int32)
+        count = torch.empty(m, device=dev, dtype=torch.int32)
+        qorder = self._walk_order(queries, m) if sort_queries else None
+        rc = L.load().cer_grid_count_within_f32(*self.grid_args(), L.dev_ptr(queries, "queries"), L.dev_ptr(qorder, "qorder", torch.int64), m, radius,
+                                                L.dev_ptr(count, "count", torch.int32), L.cur_stream())
+        if rc == -2:
+            raise ValueError(f"nearest: max_dist {radius} is more than {GRID_MAX_RINGS} cells of {self.cell}; index the cloud with a larger cell")
+        L.check(rc, "grid_count_within")
+        return count
+
 
 def voxel_downsample(points, cell):
     """Indices (int64, ascending) of the lowest-index point of every occupied cell of a grid with edge ``cell`` whose origin is the cloud's
@@ -245,6 +324,104 @@ def radius_thin(points, radius, order="random", seed=0, cell=None, max_rounds=40
         info.update(stats)
     ranks = torch.nonzero(state == 1).flatten()
     return ranks if visit is None else torch.sort(visit.index_select(0, ranks)).values
+
+
+# ---------------------------------------------------------------- outlier removal
+def remove_statistical_outliers(points, k=20, std_ratio=2.0, max_dist=None, cell=None, info=None):
+    """Indices (int64, ascending) of the points that the statistical outlier filter keeps - Open3D's ``remove_statistical_outlier``, stated
+    here in full.  The cloud is indexed on itself, so every point is one of its own ``k`` neighbours (at distance 0).  mean_i =
+    ``knn_mean_distance(points, k, max_dist)``; point i is VALID iff it has k neighbours within ``max_dist`` (count_i == k).  mu = the mean of
+    the valid mean_i, sigma = sqrt(sum (mean_i - mu)^2 / (n_valid - 1)) over them (fp64 reductions on the device); point i is kept iff it is
+    valid and mean_i < mu + std_ratio * sigma.  A point with fewer than k points within ``max_dist``, itself included, is isolated at the scale
+    the caller named: it is dropped and enters neither mu nor sigma (nor does a point with a non-finite coordinate).  With fewer than 2 valid
+    points every valid point is kept.
+
+    ``max_dist=None``: 1 % of the diagonal of the bounding box of the finite points - distant floaters widen that box, and the scale with it:
+    name ``max_dist`` when the cloud's extent is not the surface's.  ``cell=None``: ``max_dist / 4``.  ``info``: a dict that receives "mu",
+    "sigma", "threshold", "n_valid", "n_kept", "max_dist" and "cell"."""
+    k, std_ratio = int(k), float(std_ratio)
+    if not 1 <= k <= KNN_MAX:
+        raise ValueError(f"k: 1 .. {KNN_MAX} expected, got {k}")
+    if not math.isfinite(std_ratio):
+        raise ValueError("std_ratio must be finite")
+    if max_dist is not None:
+        max_dist = float(np.float32(max_dist))
+        if not (max_dist >= 0.0 and math.isfinite(max_dist)):
+            raise ValueError("max_dist must be a finite number >= 0")
+    cell = None if cell is None else _cell(cell)
+    points = _cloud(points, "points")
+    n, dev = int(points.shape[0]), points.device
+    if max_dist is None:
+        finite = torch.isfinite(points).all(1, keepdim=True)
+        if n and bool(finite.any()):
+            lo = torch.where(finite, points, points.new_full((), float("inf"))).amin(0).double()
+            hi = torch.where(finite, points, points.new_full((), float("-inf"))).amax(0).double()
+            max_dist = float(np.float32(0.01 * float((hi - lo).norm())))
+        else:
+            max_dist = 0.0
+    if cell is None:
+        cell = max_dist / KNN_CELL_DIVISOR if max_dist > 0.0 else 1.0        # (a cloud without extent: any cell will do)
+    stats = {"mu": float("nan"), "sigma": float("nan"), "threshold": float("inf"), "n_valid": 0, "n_kept": 0, "max_dist": max_dist, "cell": cell}
+    keep = torch.empty(0, device=dev, dtype=torch.int64)
+    if n:
+        mean, count = CloudIndex(points, cell).knn_mean_distance(points, k, max_dist)
+        valid = count == k
+        n_valid = int(torch.count_nonzero(valid))
+        stats["n_valid"] = n_valid
+        if n_valid >= 2:
+            zero = torch.zeros_like(mean)
+            mu = float(torch.where(valid, mean, zero).sum()) / n_valid
+            dev2 = torch.where(valid, mean - mu, zero)
+            sigma = math.sqrt(float((dev2 * dev2).sum()) / (n_valid - 1))
+            stats.update(mu=mu, sigma=sigma, threshold=mu + std_ratio * sigma)
+            valid = valid & (mean < stats["threshold"])
+        keep = torch.nonzero(valid).flatten()
+    stats["n_kept"] = int(keep.shape[0])
+    if info is not None:
+        info.update(stats)
+    return keep
+
+
+def remove_radius_outliers(points, radius, min_neighbours, cell=None, info=None):
+    """Indices (int64, ascending) of the points with more than ``min_neighbours`` points of the cloud within ``radius`` of them
+    (``count_within`` on the cloud itself, so the count includes the point: Open3D's ``remove_radius_outlier``).  Points with a non-finite
+    coordinate count nothing and are dropped.  ``cell=None``: ``radius / 4``.  ``info``: a dict that receives "n_kept", "radius" and "cell"."""
+    radius = float(np.float32(radius))
+    if not (radius >= 0.0 and math.isfinite(radius)):
+        raise ValueError("radius must be a finite number >= 0")
+    min_neighbours = int(min_neighbours)
+    if min_neighbours < 0:
+        raise ValueError("min_neighbours must be >= 0")
+    if cell is None:
+        cell = radius / KNN_CELL_DIVISOR if radius > 0.0 else 1.0
+    cell = _cell(cell)
+    points = _cloud(points, "points")
+    if int(points.shape[0]):
+        keep = torch.nonzero(CloudIndex(points, cell).count_within(points, radius) > min_neighbours).flatten()
+    else:
+        keep = torch.empty(0, device=points.device, dtype=torch.int64)
+    if info is not None:
+        info.update(n_kept=int(keep.shape[0]), radius=radius, cell=cell)
+    return keep
+
+
+def clean_cloud(points, clean):
+    """The filter a ``clean`` dictionary names, on a CUDA float32 cloud -> (kept indices, info): {"method": "statistical", "k", "std_ratio",
+    "max_dist"} or {"method": "radius", "radius", "min_neighbours"} (``cell`` is accepted by both; what is left out takes the filter's
+    default).  ValueError for another method, a missing ``radius`` / ``min_neighbours`` or a key the filter does not take."""
+    if not isinstance(clean, dict) or clean.get("method") not in ("statistical", "radius"):
+        raise ValueError('clean: a dict with "method": "statistical" or "radius" expected')
+    args = {key: v for key, v in clean.items() if key != "method"}
+    allowed = ("k", "std_ratio", "max_dist", "cell") if clean["method"] == "statistical" else ("radius", "min_neighbours", "cell")
+    extra = sorted(set(args) - set(allowed))
+    if extra:
+        raise ValueError(f'clean: method "{clean["method"]}" takes {", ".join(allowed)}; got {", ".join(extra)}')
+    info = {"method": clean["method"]}
+    if clean["method"] == "statistical":
+        return remove_statistical_outliers(points, info=info, **args), info
+    if "radius" not in args or "min_neighbours" not in args:
+        raise ValueError('clean: method "radius" needs "radius" and "min_neighbours"')
+    return remove_radius_outliers(points, info=info, **args), info
 
 
 def cloud_distances(src, dst, max_dist, cell=None):

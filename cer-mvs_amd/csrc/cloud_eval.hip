@@ -5,7 +5,8 @@
 // cell, the host sorts the keys (stable) and cer_grid_pack_f32 gathers the points into that order as 16-byte records (x, y, z, original index),
 // cer_grid_cells_count_i64 / cer_grid_cells_i64 list the occupied cells with their first sorted point (compact.hpp's count / scan / emit over
 // the heads of the sorted keys), and cer_grid_nearest_f32 searches.  No atomics anywhere: the same bytes on every run.
-// On the same grid, cer_grid_thin_round_f32 / cer_grid_thin_compact_i32 are the rounds of the DTU script's greedy radius thinning (below).
+// On the same grid, cer_grid_thin_round_f32 / cer_grid_thin_compact_i32 are the rounds of the DTU script's greedy radius thinning (below),
+// and cer_grid_knn_f32 / cer_grid_count_within_f32 the k nearest neighbours of a query and the number of points within a radius of it.
 //
 // Key layout: (z + B) << 42 | (y + B) << 21 | (x + B), B = CER_GRID_COORD_LIMIT - 1, cell coordinates in -B .. B: every field is at most
 // 2^21 - 2, so no key reaches the sentinel (2^63 - 1, all 63 bits set) and key(x + 1, y, z) = key(x, y, z) + 1 never carries.  x is the
@@ -126,7 +127,9 @@ __global__ __launch_bounds__(256) void grid_emit_kernel(const long long* __restr
 // (uq - (c + 1) - GRID_EPS) cells below it, with GRID_EPS = 1e-6 hundreds of times that error.  Rows and cells whose squared gap exceeds
 // the caller's bound are skipped - strictly: for the search's best distance so far a tie on d2 with a lower index must still be seen, for
 // the thinning's fixed radius^2 d2 == limit is a neighbour; the enumeration itself covers ceil(reach / cell) + 1 rings, one more than the
-// mathematics needs.
+// mathematics needs.  The k-nearest search hands in the d2 of its k-th entry so far (the limit until k candidates are in): a skipped cell
+// holds only points strictly beyond it, which cannot enter the list, and a tie on the k-th distance with a lower index is still seen; the
+// count within a radius hands in the fixed radius^2 as the thinning does.
 #define GRID_EPS 1e-6
 
 // gap, in cells, between coordinate u and the points of cell c of that axis (0 when u is inside)
@@ -229,6 +232,150 @@ __global__ __launch_bounds__(256) void grid_nearest_kernel(const uint4* __restri
     const bool found = best.idx != 0x7fffffff;
     idx[q] = found ? (long long)best.idx : -1;
     dist[q] = found ? (float)__builtin_sqrt(best.d2) : __builtin_inff();
+}
+
+// ---- k nearest (CloudIndex.knn / knn_mean_distance).  One thread per query, walked in qorder as above.  The list is KMAX
+// (d2, index) pairs in ascending lexicographic order that only compile-time indices in fully unrolled loops ever touch, so it lives in
+// registers (a runtime index would send it to scratch).  For a runtime k <= KMAX the slots 0 .. KMAX-k-1 hold (-1, -1), below any candidate:
+// they never move; the slots KMAX-k .. KMAX-1 start as (limit, INT_MAX), nearest's "empty".  The worst entry is always slot KMAX-1: a
+// candidate counts iff it is lexicographically smaller than that slot, which drops out as the candidate sinks to its place.
+template <int KMAX>
+struct GridList { double d2[KMAX]; int idx[KMAX]; };
+
+// A uniform value, moved into a vector register.  The list starts the same in every lane; left to itself the compiler keeps all of it in
+// scalar registers up to the first insert - more of them than there are - and spills them.
+__device__ __forceinline__ double grid_vreg(double v) { asm("" : "+v"(v)); return v; }
+__device__ __forceinline__ int grid_vreg(int v) { asm("" : "+v"(v)); return v; }
+
+// (d2, id) below (e2, ie), lexicographically; bitwise operators: three compares and no branch
+__device__ __forceinline__ bool knn_less(double d2, int id, double e2, int ie) { return (d2 < e2) | ((d2 == e2) & (id < ie)); }
+
+// The sink, written from the slots' side: with lo / hi = "the candidate is below slot s-1 / slot s" (monotone in s, the list being sorted),
+// slot s takes slot s-1 where lo, the candidate where hi alone, and keeps its entry otherwise - one compare and two selects per slot, two
+// lane masks alive at a time.
+template <int KMAX>
+__device__ __forceinline__ void knn_insert(GridList<KMAX>& l, double d2, int id) {
+    bool hi = knn_less(d2, id, l.d2[KMAX - 1], l.idx[KMAX - 1]);
+    if (!hi) return;
+#pragma unroll
+    for (int s = KMAX - 1; s > 0; --s) {
+        const bool lo = knn_less(d2, id, l.d2[s - 1], l.idx[s - 1]);
+        l.d2[s] = lo ? l.d2[s - 1] : hi ? d2 : l.d2[s];
+        l.idx[s] = lo ? l.idx[s - 1] : hi ? id : l.idx[s];
+        hi = lo;
+    }
+    l.d2[0] = hi ? d2 : l.d2[0];
+    l.idx[0] = hi ? id : l.idx[0];
+}
+
+// candidates: the points of cells xa .. xb of row (y, z), every one of them once
+template <int KMAX>
+__device__ __forceinline__ void knn_scan_row(const uint4* __restrict__ rec, const long long* __restrict__ cell_keys,
+                                             const long long* __restrict__ cell_start, long ncells, int xa, int xb, int y, int z, double X,
+                                             double Y, double Z, GridList<KMAX>& l) {
+    long long j, pe;
+    if (!grid_row_span(cell_keys, cell_start, ncells, xa, xb, y, z, j, pe)) return;
+    for (; j < pe; ++j) {
+        const uint4 t = rec[j];
+        const double dx = (double)__uint_as_float(t.x) - X, dy = (double)__uint_as_float(t.y) - Y, dz = (double)__uint_as_float(t.z) - Z;
+        knn_insert(l, (dx * dx + dy * dy) + dz * dz, (int)t.w);
+    }
+}
+
+// idx / dist [m, k] (slot j of a row: the j-th smallest (d2, index); unused slots -1 / +inf), count [m], mean [m] (the fp64 mean of the
+// row's sqrt(d2), summed in ascending order; +inf for an empty row); idx, dist and mean may each be null.  Every element is written once.
+template <int KMAX>
+__global__ __launch_bounds__(256) void grid_knn_kernel(const uint4* __restrict__ rec, const long long* __restrict__ cell_keys,
+                                                       const long long* __restrict__ cell_start, long ncells, double ox, double oy, double oz,
+                                                       double cell, const float* __restrict__ queries, const long long* __restrict__ qorder,
+                                                       long m, int k, float max_dist, int rings, long long* __restrict__ idx,
+                                                       float* __restrict__ dist, int* __restrict__ count, double* __restrict__ mean) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= m) return;
+    const long long q = qorder ? qorder[i] : i;
+    const float qx = queries[3 * q], qy = queries[3 * q + 1], qz = queries[3 * q + 2];
+    const double limit = (double)max_dist * (double)max_dist;
+    const int first = KMAX - k;                                                  // the list's first live slot
+    GridList<KMAX> l;
+#pragma unroll
+    for (int s = 0; s < KMAX; ++s) {
+        l.d2[s] = grid_vreg(s < first ? -1.0 : limit);
+        l.idx[s] = grid_vreg(s < first ? -1 : 0x7fffffff);
+    }
+    if (grid_finite(qx, qy, qz)) {
+        const double X = (double)qx, Y = (double)qy, Z = (double)qz;
+        // the query's own cell first, as the nearest search does: it fills the list early, and the rows after it are cut to the k-th entry
+        const double fx = floor((X - ox) / cell), fy = floor((Y - oy) / cell), fz = floor((Z - oz) / cell), B = (double)GRID_B;
+        const bool home = fabs(fx) <= B && fabs(fy) <= B && fabs(fz) <= B;
+        if (home) knn_scan_row(rec, cell_keys, cell_start, ncells, (int)fx, (int)fx, (int)fy, (int)fz, X, Y, Z, l);
+        grid_walk_rows(X, Y, Z, ox, oy, oz, cell, rings, [&] { return l.d2[KMAX - 1]; }, [&](int xa, int xb, int y, int z) {
+            int a0 = xa, b0 = xb, a1 = 1, b1 = 0;                                // the query's own row: the cells on either side of its own
+            if (home && (double)y == fy && (double)z == fz) {
+                const int hx = (int)fx;
+                b0 = min(hx - 1, xb), a1 = max(hx + 1, xa), b1 = xb;
+            }
+#pragma unroll 1
+            for (int part = 0; part < 2; ++part) {
+                const int a = part ? a1 : a0, b = part ? b1 : b0;
+                if (a <= b) knn_scan_row(rec, cell_keys, cell_start, ncells, a, b, y, z, X, Y, Z, l);
+            }
+            return false;
+        });
+    }
+    int c = 0;
+    double sum = 0.0;
+#pragma unroll
+    for (int s = 0; s < KMAX; ++s) {
+        if (l.idx[s] == -1) continue;                                            // below the list's first live slot (read off the slot: no 32 flags kept)
+        const bool used = l.idx[s] != 0x7fffffff;
+        const double r = __builtin_sqrt(l.d2[s]);
+        const long o = (long)q * k + (s - first);
+        if (idx) idx[o] = used ? (long long)l.idx[s] : -1;
+        if (dist) dist[o] = used ? (float)r : __builtin_inff();
+        if (used) {
+            sum = sum + r;
+            ++c;
+        }
+    }
+    count[q] = c;
+    if (mean) mean[q] = c ? sum / (double)c : (double)__builtin_inff();
+}
+
+// ---- the number of indexed points within a radius: d2 <= double(radius)^2, inclusive.  The bound is constant and no row stops the walk.
+__device__ __forceinline__ int count_scan_row(const uint4* __restrict__ rec, const long long* __restrict__ cell_keys,
+                                              const long long* __restrict__ cell_start, long ncells, int xa, int xb, int y, int z, double X,
+                                              double Y, double Z, double limit) {
+    long long j, pe;
+    int c = 0;
+    if (!grid_row_span(cell_keys, cell_start, ncells, xa, xb, y, z, j, pe)) return 0;
+    for (; j < pe; ++j) {
+        const uint4 t = rec[j];
+        const double dx = (double)__uint_as_float(t.x) - X, dy = (double)__uint_as_float(t.y) - Y, dz = (double)__uint_as_float(t.z) - Z;
+        const double d2 = (dx * dx + dy * dy) + dz * dz;
+        c += d2 <= limit ? 1 : 0;
+    }
+    return c;
+}
+
+__global__ __launch_bounds__(256) void grid_count_within_kernel(const uint4* __restrict__ rec, const long long* __restrict__ cell_keys,
+                                                                const long long* __restrict__ cell_start, long ncells, double ox, double oy,
+                                                                double oz, double cell, const float* __restrict__ queries,
+                                                                const long long* __restrict__ qorder, long m, float radius, int rings,
+                                                                int* __restrict__ count) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= m) return;
+    const long long q = qorder ? qorder[i] : i;
+    const float qx = queries[3 * q], qy = queries[3 * q + 1], qz = queries[3 * q + 2];
+    const double limit = (double)radius * (double)radius;
+    int c = 0;
+    if (grid_finite(qx, qy, qz)) {
+        const double X = (double)qx, Y = (double)qy, Z = (double)qz;
+        grid_walk_rows(X, Y, Z, ox, oy, oz, cell, rings, [=] { return limit; }, [&](int xa, int xb, int y, int z) {
+            c += count_scan_row(rec, cell_keys, cell_start, ncells, xa, xb, y, z, X, Y, Z, limit);
+            return false;
+        });
+    }
+    count[q] = c;
 }
 
 // ---- greedy radius thinning (cloud_eval.radius_thin): the maximal independent set of the radius graph under a visiting order,
@@ -427,6 +574,38 @@ extern "C" int cer_grid_nearest_f32(const void* records, long n, const long long
     if (rings <= 0) return rings;                            // (an empty target: the caller fills idx = -1, dist = +inf)
     hipLaunchKernelGGL(grid_nearest_kernel, dim3(grid_blocks(m, 256)), dim3(256), 0, (hipStream_t)stream, (const uint4*)records, cell_keys,
                        cell_start, ncells, origin[0], origin[1], origin[2], cell, queries, qorder, m, max_dist, rings, idx, dist);
+    CER_RETURN_IF_LAUNCH_FAILED();
+    return CER_OK;
+}
+
+// k < 1 joins the reach's CER_EINVAL, k > CER_KNN_MAX the shape's CER_ESHAPE, a null count the null pointers' CER_EINVAL
+extern "C" int cer_grid_knn_f32(const void* records, long n, const long long* cell_keys, const long long* cell_start, long ncells,
+                                const double* origin, double cell, const float* queries, const long long* qorder, long m, int k, float max_dist,
+                                long long* idx, float* dist, int* count, double* mean, void* stream) {
+    const int rings = grid_search_rings(records, n, cell_keys, cell_start, ncells, origin, cell, m, max_dist, max_dist >= 0.0f && k >= 1,
+                                        k <= CER_KNN_MAX, queries && count);
+    if (rings <= 0) return rings;                            // (an empty side: the caller fills idx = -1, dist = mean = +inf, count = 0)
+    const dim3 grid(grid_blocks(m, 256)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+#define KNN_LAUNCH(KMAX)                                                                                                                  \
+    hipLaunchKernelGGL(grid_knn_kernel<KMAX>, grid, block, 0, st, (const uint4*)records, cell_keys, cell_start, ncells, origin[0], origin[1], \
+                       origin[2], cell, queries, qorder, m, k, max_dist, rings, idx, dist, count, mean)
+    if (k <= 8) KNN_LAUNCH(8);
+    else if (k <= 16) KNN_LAUNCH(16);
+    else KNN_LAUNCH(32);
+#undef KNN_LAUNCH
+    CER_RETURN_IF_LAUNCH_FAILED();
+    return CER_OK;
+}
+
+extern "C" int cer_grid_count_within_f32(const void* records, long n, const long long* cell_keys, const long long* cell_start, long ncells,
+                                         const double* origin, double cell, const float* queries, const long long* qorder, long m,
+                                         float radius, int* count, void* stream) {
+    const int rings = grid_search_rings(records, n, cell_keys, cell_start, ncells, origin, cell, m, radius, radius >= 0.0f, true,
+                                        queries && count);
+    if (rings <= 0) return rings;                            // (an empty side: the caller fills count = 0)
+    hipLaunchKernelGGL(grid_count_within_kernel, dim3(grid_blocks(m, 256)), dim3(256), 0, (hipStream_t)stream, (const uint4*)records, cell_keys,
+                       cell_start, ncells, origin[0], origin[1], origin[2], cell, queries, qorder, m, radius, rings, count);
     CER_RETURN_IF_LAUNCH_FAILED();
     return CER_OK;
 }

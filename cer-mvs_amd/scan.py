@@ -360,7 +360,7 @@ def _write_masks(folder, masks_np, refs, suffix=""):
 
 def reconstruct_scan(model_or_ckpt, images, poses, intrinsics, names, pairs, scales, output_folder=None, rescale=1, crop=None, num_frames=10,
                      glb=0.25, streams=3, write_depths=False, write=True, th=0.02, bgr=False, encode_batch=4, max_bytes=None,
-                     force_uncached=False, timings=None):
+                     force_uncached=False, timings=None, clean=None):
     """A scan to its fused point cloud without leaving the device between the stages: ``ScanSession.depths`` -> ``fusion.fuse_depth_maps`` (view i
     against ``pairs[i][:num_frames]``) -> ``fusion.point_cloud`` with the colours of ``fusion.color_grid``.  What ``inference_scan`` followed by
     ``fusion.fusion`` on the session's prepared images computes, without the PFM round trip, the host resize and the float64 numpy tail: same
@@ -368,7 +368,13 @@ def reconstruct_scan(model_or_ckpt, images, poses, intrinsics, names, pairs, sca
     ``rescale=(s1, s2)`` with s2 = 2 s1 runs two sessions one after the other, merges the two depth stacks (``multires.merge(th=th)``) and fuses
     at the finer grid with the first session's images and cameras (no ``crop`` in that form).  ``write``: ``result.ply`` and ``mask/<i>.png`` under ``output_folder``;
     ``write_depths``: also the PFMs of ``inference_scan``, same names.  One device->host copy brings the cloud, the masks and the averaged
-    depths back.  Returns ``fusion.fusion``'s dictionary (``xyz`` is float32 here)."""
+    depths back.  Returns ``fusion.fusion``'s dictionary (``xyz`` is float32 here).
+
+    ``clean``: an outlier filter for the fused cloud (``cloud_eval.clean_cloud``), applied on the device between the fusion and
+    that copy: {"method": "statistical", "k", "std_ratio", "max_dist"} (``remove_statistical_outliers``) or {"method": "radius", "radius",
+    "min_neighbours"} (``remove_radius_outliers``).  ``xyz`` and ``rgb`` (and ``result.ply``) then hold the kept points in their fused order and
+    the result gains "clean": {"n_in", "n_kept", and what the filter reports}; ``masks`` and ``depth_est`` stay as fused - a pixel whose point
+    was filtered keeps its mask bit.  None (the default): no filter, no such key."""
     from . import fusion as FU
     from .inference import write_pfm
     two_pass = isinstance(rescale, (tuple, list))
@@ -433,6 +439,12 @@ def reconstruct_scan(model_or_ckpt, images, poses, intrinsics, names, pairs, sca
     t["fuse_s"] = time.perf_counter() - tic
     tic = time.perf_counter()
     xyz, rgb = FU.point_cloud(masks, est, Ks, Es, colors, [ref for ref, _ in fpairs])
+    cleaned = None
+    if clean is not None:
+        from .cloud_eval import clean_cloud
+        kept, cleaned = clean_cloud(xyz, clean)
+        cleaned = {"n_in": int(xyz.shape[0]), **cleaned}
+        xyz, rgb = xyz.index_select(0, kept), rgb.index_select(0, kept)
     xyz_np, rgb_np, masks_np, est_np = xyz.cpu().numpy(), rgb.cpu().numpy(), masks.cpu().numpy().astype(bool), est.cpu().numpy()
     t["d2h_bytes"] = int(xyz.numel() * 4 + rgb.numel() + masks.numel() + est.numel() * 4) + sum(int(a.nbytes) for a in stacks_np)
     if write or write_depths:
@@ -447,4 +459,7 @@ def reconstruct_scan(model_or_ckpt, images, poses, intrinsics, names, pairs, sca
         _write_masks(output_folder, masks_np, [ref for ref, _ in fpairs])
         FU.write_ply(str(output_folder / "result.ply"), xyz_np, rgb_np)
     t["tail_s"] = time.perf_counter() - tic
-    return {"masks": masks_np, "depth_est": est_np, "xyz": xyz_np, "rgb": rgb_np, "threshold": thre, "history": hist}
+    out = {"masks": masks_np, "depth_est": est_np, "xyz": xyz_np, "rgb": rgb_np, "threshold": thre, "history": hist}
+    if cleaned is not None:
+        out["clean"] = cleaned
+    return out

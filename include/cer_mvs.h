@@ -622,6 +622,31 @@ int cer_grid_thin_round_f32(const void* records, long n, const long long* cell_k
 int cer_grid_thin_compact_i32(const void* records, long n, const unsigned char* state, const int* active, long n_active,
                               unsigned int* partials, long long* offsets, int* out, long long* total, void* stream);
 
+/* k nearest neighbours and the count within a radius on the same grid (ABI 1140; cer-mvs_amd/cloud_eval.py CloudIndex.knn / knn_mean_distance
+ * / count_within, remove_statistical_outliers / remove_radius_outliers).  The first seven arguments are the index as
+ * cer_grid_nearest_f32 takes it, queries / qorder / m as there; sizes, errors and their order as there (max_dist and radius: negative or
+ * NaN -> CER_EINVAL; more than 4096 rings, ncells > n -> CER_ESHAPE; n == 0, ncells == 0 or m == 0 -> CER_OK with nothing launched, the
+ * caller fills the outputs; then null pointers -> CER_EINVAL).  No atomics, no LDS; every output element is written exactly once; the same
+ * bytes on every run.  Every check runs before any launch.
+ *
+ *   cer_grid_knn_f32: d2 = (dx*dx + dy*dy) + dz*dz in fp64 on the float32 coordinates, no contraction; a target point is a candidate iff
+ *     d2 <= double(max_dist) * double(max_dist).  Row q of idx / dist ([m, k], at the query's own position) holds the min(k, candidates)
+ *     smallest (d2, original index) pairs in ascending lexicographic order: idx = the original index, dist = float(sqrt(d2)) with a
+ *     correctly rounded fp64 square root; unused slots are idx = -1, dist = +inf; count[q] = the number of used slots.  A query with a
+ *     non-finite coordinate has count 0; a non-finite target point is never a neighbour; a query that is itself an indexed point finds
+ *     itself at d2 = 0 (no self-exclusion).  mean[q] (fp64) = ((s_0 + s_1) + ... + s_{c-1}) / c with s_j = sqrt(d2_j) in fp64, added in
+ *     ascending order, c = count[q]; +inf for c = 0.  idx, dist and mean may each be NULL (nothing is written there); count may not
+ *     (CER_EINVAL).  k < 1 -> CER_EINVAL (with max_dist's check); k > CER_KNN_MAX -> CER_ESHAPE (with ncells > n's).
+ *   cer_grid_count_within_f32: count[q] = the number of indexed points with d2 <= double(radius) * double(radius), inclusive (the point
+ *     itself when the query is an indexed point); 0 for a query with a non-finite coordinate. */
+#define CER_KNN_MAX 32
+int cer_grid_knn_f32(const void* records, long n, const long long* cell_keys, const long long* cell_start, long ncells, const double* origin,
+                     double cell, const float* queries, const long long* qorder, long m, int k, float max_dist, long long* idx, float* dist,
+                     int* count, double* mean, void* stream);
+int cer_grid_count_within_f32(const void* records, long n, const long long* cell_keys, const long long* cell_start, long ncells,
+                              const double* origin, double cell, const float* queries, const long long* qorder, long m, float radius,
+                              int* count, void* stream);
+
 /* Rigid registration of two clouds (ABI 1130; csrc/cloud_align.hip, cer-mvs_amd/cloud_eval.py rigid_transform / pair_moments / icp, DESIGN.md
  * 3w): what point-to-point ICP needs beside cer_grid_nearest_f32.  fp64 arithmetic on float32 coordinates with every association fixed, no
  * atomics, grids and summation trees that depend on the sizes alone: the same bits on every run and every machine.  Sizes and errors as
