@@ -167,7 +167,8 @@ __global__ __launch_bounds__(256) void resize_linear_kernel(const float* __restr
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= (long)ho * wo) return;
     const int y = (int)(i / wo), x = (int)(i - (long)y * wo);
-    dst[i] = mr_sample(src, h, w, y, x, (double)h / ho, (double)w / wo);
+    // equal sizes: cv2.resize copies; the taps' weights (1, 0) would turn -0 into +0 and a neighbour's inf into NaN
+    dst[i] = (h == ho && w == wo) ? src[i] : mr_sample(src, h, w, y, x, (double)h / ho, (double)w / wo);
 }
 
 extern "C" int cer_multires_merge_f32(const float* im1, int h1, int w1, const float* im2, int h2, int w2, double th, float* out, void* stream) {

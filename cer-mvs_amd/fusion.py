@@ -61,7 +61,8 @@ def check_geometric_consistency(depth_ref, intrinsics_ref, extrinsics_ref, depth
         raise RuntimeError("check_geometric_consistency: depth maps must be CUDA tensors (no CPU fallback)")
     S, H, W = depth_src.shape
     dev = depth_ref.device
-    if S > 1 and not (torch.equal(depth_ref[0], depth_ref[-1]) and torch.equal(intrinsics_ref[0], intrinsics_ref[-1])):
+    same = lambda a, b: bool(((a == b) | (torch.isnan(a) & torch.isnan(b))).all())       # (a NaN depth is still the same depth)
+    if S > 1 and not (same(depth_ref[0], depth_ref[-1]) and torch.equal(intrinsics_ref[0], intrinsics_ref[-1])):
         raise ValueError("check_geometric_consistency: the reference view must be the same for every source view of a call")
     cams = compose_cams(intrinsics_ref, extrinsics_ref, intrinsics_src, extrinsics_src).to(dev)
     lit = {"masks9": torch.empty(9, S, H, W, device=dev, dtype=torch.uint8)}

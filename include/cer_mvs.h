@@ -469,7 +469,7 @@ int cer_geo_consistency_f32(const float* depth_ref, const float* depth_src, cons
 
 /* Multi-resolution merge of two depth maps (reference: multires.py:16-40): out [h2, w2] = where(|r - im2| < th * r, im2, r) with
  * r = im1 [h1, w1] resized to [h2, w2] like cv2.resize(INTER_LINEAR) on float32; cer_resize_linear_f32 is that resize alone (the
- * reference's optional down_sample step).  Device pointers, fp32, row-major. */
+ * reference's optional down_sample step; equal sizes: a copy, as cv2.resize returns one).  Device pointers, fp32, row-major. */
 int cer_multires_merge_f32(const float* im1, int h1, int w1, const float* im2, int h2, int w2, double th, float* out, void* stream);
 int cer_resize_linear_f32(const float* src, int h, int w, float* dst, int ho, int wo, void* stream);
 

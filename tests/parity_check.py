@@ -1,7 +1,11 @@
 """Element-wise parity checking at production shapes: helpers shared by tests/test_parity_check_cpu.py (which proves on planted
 corruptions that the checker sees what a global mean cannot) and tests/test_fullsize_parity_gpu.py (which applies it to the HIP
 kernels of one GRU iteration and to the cost volume) and tests/test_encoder_parity_gpu.py (the encoder kernels, one launch at a time: the
-float64 pieces and tile geometries at the end of this file).  Plain module, no fixtures.
+float64 pieces and tile geometries further down), by tests/test_train_parity_{cpu,gpu}.py (the training-row kernels) and by
+tests/test_postproc_parity_{cpu,gpu}.py (the last section: geometric consistency as a float64 chain that carries, next to every value, a
+bound on what a correct fp32 evaluation may deviate by - ``geo_ref64`` / ``check_geo`` / ``GeoReport``: every element is inside its
+bound, decided equal or provably undecidable; the image preparation from torch's fp32 taps - ``prep_ref64`` / ``check_prep``; the bit
+comparison of the multires kernels - ``bits_equal``).  Plain module, no fixtures.
 
 Conventions: an image tensor is pixel-major, ``[h*w, C]`` or ``[h*w]``; a *tile* is a (rows, columns) block of pixels - 8 x 16 by
 default, the smallest tile the s16 convolutions launch (16 x 16 for the tall ones); a *seam* is the border between two 32-pixel
@@ -699,3 +703,398 @@ def upsample_ac_adjoint_ref64(g, h, w):
     grad, _, ny, ry = upsample_ac_adjoint_pass64(work, h, 1)
     mag = upsample_ac_adjoint_pass64(wmag, h, 1)[0]
     return grad, mag, ny[:, None] + nx[None, :], (ry, rx)
+
+
+# ------------------------------------------------------------------------------------------------ post-processing kernels in float64
+# csrc/fusion.hip (geometric consistency, multires merge / resize) and csrc/scan_ops.hip (image preparation); tests/test_postproc_parity_
+# {cpu,gpu}.py.  numpy float64.  Every value of the geometric-consistency chain is a pair (v, e): v the float64 value, e a bound on
+# |fp32 result - v| for ANY correct fp32 evaluation of the same expression (any order of the sums, products fused into the sums or not).
+# With u = 2^-24 and gamma_k = k u / (1 - k u) (Higham, Accuracy and Stability of Numerical Algorithms, lemma 3.1):
+#   product of two pairs      |a| eb + |b| ea + ea eb + u (|a| + ea)(|b| + eb)          (the rounding acts on the perturbed operands)
+#   matrix row, n terms       sum |m_i| e_i + gamma_n sum |m_i| (|v_i| + e_i) [+ |m_3|]   a term passes its product and at most n - 1 adds
+#                             (n = 3: geo_mat3; n = 4: geo_mat34, the constant being the fourth term); an fma only removes roundings
+#   quotient X / Z            needs low = |Z| - eZ > 0, else the element is UNDECIDABLE (e = inf):  ee = (eX + |X / Z| eZ) / low, e = ee + u (|X / Z| + ee)
+#   sample at (xs, ys)        the kernel samples at ix = ((2 px / (w-1) - 1) + 1) / 2 * (w-1): four roundings (the doubling and the halving are
+#                             exact), |ix - px| <= gamma_4 (|px| + (w-1) / 2) (the -1 / +1 pair rounds at the size of px - (w-1) / 2), so the
+#                             coordinate is off by ec = e_px + gamma_4 (|px| + e_px + (w-1) / 2).  The zero-padded bilinear interpolant is
+#                             continuous and, inside a cell, moves by at most |dx| Lx + |dy| Ly with Lx (Ly) the largest difference between
+#                             horizontally (vertically) neighbouring taps of the cell's 2 x 2 footprint, zero padding counting as taps of
+#                             value 0; the rectangle (xs +- ecx, ys +- ecy) meets at most the four cells of its corners (ec < 1/2 is
+#                             required), so the move is bounded with the largest Lx, Ly of those.  The weights ix - floor(ix) and
+#                             (floor(ix) + 1) - ix are exact except in the cells [-1, 0) and [0, 1), where one of each axis rounds by at
+#                             most u / 2: < 2 u T with T the largest |tap| of the reachable cells.  A term tap * (wx * wy) passes 2 products and
+#                             at most 3 adds, and sum |tap| w <= T:  e_ds = ecx Lx + ecy Ly + (gamma_5 + 2 u) T.  Where the reachable cells
+#                             do not agree on holding a NaN tap the sample is undecidable; where all hold one it is NaN for sure.
+#   difference xr - x         e_xr + u (|xr - x| + e_xr);  sum of two squares s: 2 |a| ea + ea^2 (both) + gamma_2 (sum of (|a| + ea)^2)
+#   sqrt                      sqrt(s) - sqrt(max(s - es, 0)) (the larger side, the root being concave), then + u (dist + that)
+#   |drep - d| / d            d is an input: e = (e_drep + u (|drep - d| + e_drep)) / |d|, then + u (|rel| + e);  d = 0 gives +inf where
+#                             |drep| > e_drep (every mask false either way), d < 0 a negative rel as in the reference
+#   (dsum + d) / (cnt + 1)    the S gated adds and the add of d: sum e_drep + gamma_(S+1) (sum (|drep| + e_drep) + |d|), divided by cnt + 1
+#                             (exact), then + u (|v| + e)
+# Nothing is tuned: no constant above comes from a measurement.
+def _gam(k):
+    return k * U24 / (1.0 - k * U24)
+
+
+def _np():
+    import numpy as np
+    return np
+
+
+def _san(e):
+    np = _np()
+    return np.where(np.isnan(e), np.inf, e)
+
+
+def _prod(a, ea, b, eb):
+    np = _np()
+    return a * b, _san(np.abs(a) * eb + np.abs(b) * ea + ea * eb + U24 * (np.abs(a) + ea) * (np.abs(b) + eb))
+
+
+def _rows(m, n, vals, errs):
+    """Three rows of the row-major 3 x n matrix ``m`` (n = 4: the fourth column is the added constant) applied to three (value, bound) pairs."""
+    np = _np()
+    out = []
+    for r in range(3):
+        row = [float(t) for t in m[r * n:(r + 1) * n]]
+        v = row[0] * vals[0] + row[1] * vals[1] + row[2] * vals[2]
+        mag = sum(abs(row[i]) * (np.abs(vals[i]) + errs[i]) for i in range(3) if row[i] != 0.0)
+        ein = sum(abs(row[i]) * errs[i] for i in range(3) if row[i] != 0.0)
+        if n == 4:
+            v, mag = v + row[3], mag + abs(row[3])
+        out.append((v, _san(ein + _gam(n) * mag)))
+    return out
+
+
+def _quot(X, eX, Z, eZ):
+    np = _np()
+    low = np.abs(Z) - eZ
+    ok = low > 0
+    q = X / Z
+    ee = (eX + np.abs(q) * eZ) / np.where(ok, low, 1.0)
+    return q, np.where(ok, _san(ee + U24 * (np.abs(q) + ee)), np.inf)
+
+
+def geo_cameras(N, h, w, seed=3):
+    """The cameras of tests/test_cloud_gpu.py::_cameras: the ring of ``synthetic_scene`` with the focal length of an h x w image and a
+    principal point off the centre -> (K [N,3,3], E [N,4,4]) fp32."""
+    from cer_mvs_amd.synthetic import synthetic_scene
+    _, poses, intr, _ = synthetic_scene(32, 32, N - 1, seed=seed)
+    K, E = intr[0].clone().float(), poses[0].clone().float()
+    K[:, 0, 0] = K[:, 1, 1] = 1.8 * w
+    K[:, 0, 2], K[:, 1, 2] = w / 2.0 + 0.37, h / 2.0 - 0.21
+    return K, E
+
+
+def geo_thresholds(thre1, thre2):
+    """The thresholds as the host forms them (csrc/fusion.hip:122-126): float32(i / thre1), float32(i / thre2), i = 2 .. 10 -> two float64 [9]."""
+    np = _np()
+    i = np.arange(2, 11, dtype=np.float64)
+    return (i / float(thre1)).astype(np.float32).astype(np.float64), (i / float(thre2)).astype(np.float32).astype(np.float64)
+
+
+def _geo_sample64(img, xs, ys, ex, ey):
+    """Zero-padded bilinear sample of img [h, w] at the float64 coordinates (xs, ys) known to +- (ex, ey) -> (value, bound, NaN for sure,
+    undecidable, outside-or-rim): see the table above."""
+    np = _np()
+    h, w = img.shape
+    t = np.zeros((h + 4, w + 4))
+    t[2:-2, 2:-2] = img                                                     # taps -2 .. w + 1; cells -2 .. w
+    finite = np.isfinite(xs) & np.isfinite(ys)
+    x, y = np.where(finite, xs, -9.0), np.where(finite, ys, -9.0)           # (the kernel returns 0 for a coordinate that is not finite)
+    ecx = ex + _gam(4) * (np.abs(x) + ex + (w - 1) / 2.0)
+    ecy = ey + _gam(4) * (np.abs(y) + ey + (h - 1) / 2.0)
+    und = ~finite | ~(ecx < 0.5) | ~(ecy < 0.5)
+    ecx, ecy = np.where(und, 0.0, ecx), np.where(und, 0.0, ecy)
+    cell = lambda c, n: np.clip(np.floor(c), -2, n).astype(np.int64) + 2
+    cx, cy = cell(x, w), cell(y, h)
+    fx, fy = np.clip(x - np.floor(x), 0.0, 1.0), np.clip(y - np.floor(y), 0.0, 1.0)
+    t00, t01, t10, t11 = t[cy, cx], t[cy, cx + 1], t[cy + 1, cx], t[cy + 1, cx + 1]
+    val = (t00 * (1 - fx) + t01 * fx) * (1 - fy) + (t10 * (1 - fx) + t11 * fx) * fy
+    with np.errstate(invalid="ignore"):
+        Lx = np.maximum(np.abs(t[:-1, 1:] - t[:-1, :-1]), np.abs(t[1:, 1:] - t[1:, :-1]))      # per cell [h + 3, w + 3]
+        Ly = np.maximum(np.abs(t[1:, :-1] - t[:-1, :-1]), np.abs(t[1:, 1:] - t[:-1, 1:]))
+        T = np.maximum(np.maximum(np.abs(t[:-1, :-1]), np.abs(t[:-1, 1:])), np.maximum(np.abs(t[1:, :-1]), np.abs(t[1:, 1:])))
+    nanc = np.isnan(t[:-1, :-1]) | np.isnan(t[:-1, 1:]) | np.isnan(t[1:, :-1]) | np.isnan(t[1:, 1:])
+    lx = ly = tt = np.zeros_like(x)
+    n_any, n_all = np.zeros(x.shape, bool), np.ones(x.shape, bool)
+    for sx in (-1.0, 1.0):
+        for sy in (-1.0, 1.0):
+            qx, qy = cell(x + sx * ecx, w), cell(y + sy * ecy, h)
+            lx, ly, tt = np.fmax(lx, Lx[qy, qx]), np.fmax(ly, Ly[qy, qx]), np.fmax(tt, T[qy, qx])
+            n_any, n_all = n_any | nanc[qy, qx], n_all & nanc[qy, qx]
+    und = und | (n_any & ~n_all)
+    nan = n_all & ~und
+    err = ecx * lx + ecy * ly + (_gam(5) + 2 * U24) * tt
+    zero = ~finite
+    val = np.where(zero, 0.0, val)
+    err = np.where(zero, 0.0, np.where(und | nan, np.inf, err))
+    rim = ~finite | (np.floor(xs) < 0) | (np.floor(xs) >= w - 1) | (np.floor(ys) < 0) | (np.floor(ys) >= h - 1)
+    return val, err, nan, und & finite, rim
+
+
+def geo_ref64(depth_ref, depth_src, cams, thre1, thre2):
+    """Float64 restatement of geo_consistency_kernel (csrc/fusion.hip:57-100; reference fusion.py:39-106, :226-236) with a carried
+    bound.  depth_ref [H,W], depth_src [S,H,W], cams [S,60]: the fp32 tensors the kernel is given, promoted; the thresholds as the host
+    rounds them.  Samples directly at (xs, ys).  -> dict:
+      xs, ys, rel, drep, dist   (value, bound) [S,H,W]; bound = inf where undecidable; rel = +inf, bound 0 where d = 0 and drep is not 0 for sure
+      nan_in, nan               [S,H,W] bool: NaN for sure - xs, ys (``nan_in``: d is NaN); drep, dist, rel (``nan``: also a NaN tap)
+      m_lo, m_hi                [9,S,H,W] bool: the mask is true for sure / may be true (equal: decided)
+      geo_lo, geo_hi            [H,W] bool: the vote from the lowest / highest possible counts
+      est, est_ok               (value, bound) [H,W], and where every view's m10 is decided (elsewhere the pixel is undecidable)
+      rim                       [S,H,W] bool: the sample's footprint reaches outside the source image (or the coordinate is not finite)
+      cnt_lo, cnt_hi            [9,H,W] the lowest / highest possible counts"""
+    np = _np()
+    d = np.asarray(depth_ref, dtype=np.float64)
+    src = np.asarray(depth_src, dtype=np.float64)
+    cams = np.asarray(cams, dtype=np.float64)
+    S, H, W = src.shape
+    td, tr = geo_thresholds(thre1, thre2)
+    yy, xx = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+    zero = np.zeros_like(d)
+    keys = ("xs", "ys", "rel", "drep", "dist")
+    out = {k: (np.empty((S, H, W)), np.empty((S, H, W))) for k in keys}
+    out.update(nan_in=np.zeros((S, H, W), bool), nan=np.zeros((S, H, W), bool), rim=np.zeros((S, H, W), bool),
+               m_lo=np.zeros((9, S, H, W), bool), m_hi=np.zeros((9, S, H, W), bool))
+    with np.errstate(all="ignore"):
+        xd, yd = _prod(xx, zero, d, zero), _prod(yy, zero, d, zero)
+        for s in range(S):
+            c = cams[s]
+            p = _rows(c[0:9], 3, [xd[0], yd[0], d], [xd[1], yd[1], zero])
+            p = _rows(c[9:21], 4, [q[0] for q in p], [q[1] for q in p])
+            p = _rows(c[21:30], 3, [q[0] for q in p], [q[1] for q in p])
+            xs, exs = _quot(p[0][0], p[0][1], p[2][0], p[2][1])
+            ys, eys = _quot(p[1][0], p[1][1], p[2][0], p[2][1])
+            nan_in = np.isnan(d)
+            exs, eys = np.where(nan_in, np.inf, exs), np.where(nan_in, np.inf, eys)
+            ds, eds, nan_s, und_s, rim = _geo_sample64(src[s], xs, ys, exs, eys)
+            und_s = und_s | (~nan_in & ~(np.isfinite(exs) & np.isfinite(eys)))    # (Z not bounded away from 0: whatever the kernel samples)
+            nan = (nan_in | nan_s) & ~und_s
+            a, b = _prod(xs, exs, ds, eds), _prod(ys, eys, ds, eds)
+            p = _rows(c[30:39], 3, [a[0], b[0], ds], [a[1], b[1], eds])
+            p = _rows(c[39:51], 4, [q[0] for q in p], [q[1] for q in p])
+            drep, edrep = p[2]
+            q = _rows(c[51:60], 3, [t[0] for t in p], [t[1] for t in p])
+            xr, exr = _quot(q[0][0], q[0][1], q[2][0], q[2][1])
+            yr, eyr = _quot(q[1][0], q[1][1], q[2][0], q[2][1])
+            ex, ey = xr - xx, yr - yy
+            eex, eey = exr + U24 * (np.abs(ex) + exr), eyr + U24 * (np.abs(ey) + eyr)
+            sq = ex * ex + ey * ey
+            esq = _san(2 * np.abs(ex) * eex + eex * eex + 2 * np.abs(ey) * eey + eey * eey + _gam(2) * ((np.abs(ex) + eex) ** 2 + (np.abs(ey) + eey) ** 2))
+            dist = np.sqrt(sq)
+            edist = dist - np.sqrt(np.maximum(sq - esq, 0.0))
+            edist = _san(edist + U24 * (dist + edist))
+            num = np.abs(drep - d)
+            enum = edrep + U24 * (num + edrep)
+            erel = enum / np.abs(d)
+            rel = num / d
+            erel = _san(erel + U24 * (np.abs(rel) + erel))
+            d0 = d == 0
+            rel = np.where(d0, np.inf, rel)
+            erel = np.where(d0, np.where(np.abs(drep) > edrep, 0.0, np.inf), erel)
+            bad = nan | und_s
+            for k, (v, e) in (("xs", (xs, exs)), ("ys", (ys, eys)), ("rel", (rel, erel)), ("drep", (drep, edrep)), ("dist", (dist, edist))):
+                out[k][0][s] = v
+                out[k][1][s] = e if k in ("xs", "ys") else np.where(bad, np.inf, e)
+            out["nan_in"][s], out["nan"][s], out["rim"][s] = nan_in, nan, rim
+            for i in range(9):
+                d_t, d_f = dist + edist < td[i], dist - edist > td[i]               # (an infinite bound decides neither)
+                r_t = np.where(d0, False, rel + erel < tr[i])
+                r_f = np.where(d0, True, rel - erel > tr[i])                       # (d = 0: rel is +inf or NaN, false either way)
+                sure_t = d_t & r_t & ~bad
+                sure_f = ((d_f | r_f) & ~und_s) | nan
+                out["m_lo"][i, s] = sure_t
+                out["m_hi"][i, s] = ~sure_f
+        n = 1 + S
+        cl, ch = out["m_lo"].sum(1), out["m_hi"].sum(1)
+        vote = lambda cnt: np.logical_or.reduce([cnt[8] >= n] + [cnt[i - 2] >= i for i in range(2, min(n, 11))])
+        out["cnt_lo"], out["cnt_hi"] = cl, ch
+        out["geo_lo"], out["geo_hi"] = vote(cl), vote(ch)
+        m10 = out["m_lo"][8]
+        ok = (out["m_lo"][8] == out["m_hi"][8]).all(0)
+        dr, edr = np.where(m10, out["drep"][0], 0.0), np.where(m10, out["drep"][1], 0.0)
+        cnt = m10.sum(0) + 1.0
+        v = (dr.sum(0) + d) / cnt
+        e = (edr.sum(0) + _gam(S + 1) * ((np.abs(dr) + edr).sum(0) + np.abs(d))) / cnt
+        out["est"] = (v, _san(e + U24 * (np.abs(v) + e)))
+        out["est_ok"] = ok
+    return out
+
+
+class GeoReport:
+    """What ``check_geo`` found: ``fails`` = {output: {"n", "views", "levels", "rows", "blocks" (256-pixel launch blocks), "pixels", "index", "worst"}}
+    for every output with an element outside its bound / a decided element that differs; ``undecidable`` = {output: share} (per level for
+    the masks: "masks9[i]"); ``max_ratio`` = {output: worst |err| / bound over the bounded elements}; ``checked`` = the outputs present."""
+
+    def __init__(self, where, H, W):
+        self.where, self.H, self.W = where, H, W
+        self.fails, self.undecidable, self.max_ratio, self.checked = {}, {}, {}, []
+
+    @property
+    def ok(self):
+        return not self.fails
+
+    def add(self, name, bad, und, ratio=None, worst=None):
+        """bad, und: bool [..., H, W] with leading (level, view) / (view) / no axes."""
+        np = _np()
+        self.checked.append(name)
+        lead = bad.ndim - 2
+        if name == "masks9":
+            for i in range(und.shape[0]):
+                self.undecidable[f"masks9[{i}]"] = float(und[i].mean())
+        else:
+            self.undecidable[name] = float(und.mean())
+        if ratio is not None:
+            self.max_ratio[name] = float(ratio)
+        if not bad.any():
+            return
+        idx = np.argwhere(bad)
+        pix = idx[:, -2] * self.W + idx[:, -1]
+        cnt = lambda a: {int(k): int(c) for k, c in zip(*np.unique(a, return_counts=True))}
+        self.fails[name] = {"n": int(bad.sum()), "views": cnt(idx[:, lead - 1]) if lead >= 1 else {}, "levels": cnt(idx[:, 0]) if lead == 2 else {},
+                            "rows": cnt(idx[:, -2]), "blocks": cnt(pix // 256), "pixels": pix, "index": idx, "worst": worst}
+
+    def only(self, name, key):
+        """The single view / level / row / block that holds every failing element of an output, else None."""
+        d = self.fails.get(name, {}).get(key, {})
+        return next(iter(d)) if len(d) == 1 else None
+
+    def message(self):
+        if self.ok:
+            return f"{self.where}: every decided element agrees ({', '.join(self.checked)})"
+        top = lambda d, k=6: ", ".join(f"{key}: {c}" for key, c in sorted(d.items(), key=lambda kv: -kv[1])[:k]) + (" ..." if len(d) > k else "")
+        lines = [f"{self.where}: {self.H} x {self.W}"]
+        for name, f in self.fails.items():
+            lines.append(f"  {name}: {f['n']} decided elements wrong" + (f"; worst |err| / bound = {f['worst']:.4g}" if f["worst"] is not None else ""))
+            if f["levels"]:
+                lines.append(f"    levels - {top(f['levels'])}")
+            if f["views"]:
+                lines.append(f"    views - {top(f['views'])}")
+            lines.append(f"    image rows - {len(f['rows'])}: {top(f['rows'])};  256-pixel blocks - {len(f['blocks'])}: {top(f['blocks'])}")
+            for key, what in (("rows", "image row"), ("blocks", "block"), ("views", "view"), ("levels", "level")):
+                if len(f[key]) == 1:
+                    k = next(iter(f[key]))
+                    lines.append(f"    => confined to {what} {k}" + (" (the last row)" if key == "rows" and k == self.H - 1 else ""))
+        return "\n".join(lines)
+
+
+def _check_pair(got, val, err, nan_sure, zero_ok=None, measure=None):
+    """-> (bad, undecidable, worst ratio): NaN for sure -> got must be NaN; value +-inf with bound 0 -> got must equal it; a finite bound ->
+    |got - val| <= bound; an infinite bound: undecidable.  ``zero_ok``: elements where an exact 0 is accepted as well; ``measure``: the
+    elements the worst ratio is taken over (default: all bounded ones)."""
+    np = _np()
+    got = np.asarray(got, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        und = ~nan_sure & ~np.isfinite(err)
+        diff = np.abs(got - val)
+        inb = np.where(np.isinf(val), got == val, diff <= err)
+        good = np.where(nan_sure, np.isnan(got), inb)
+        if zero_ok is not None:
+            good = good | (zero_ok & (got == 0))
+        bad = ~good & ~und
+        meas = ~nan_sure & ~und & np.isfinite(val) & (err > 0) & (True if measure is None else measure)
+        ratio = np.where(meas, diff / np.where(err > 0, err, 1.0), 0.0)
+        ratio = np.where(np.isnan(ratio), np.inf, ratio)
+    return bad, und, float(ratio.max()) if ratio.size else 0.0
+
+
+def check_geo(ref, where="", xs=None, ys=None, rel=None, drep=None, masks9=None, geo_mask=None, depth_est=None):
+    """The outputs of a launch (whichever are given; numpy or CPU tensors) against ``geo_ref64``'s dict -> GeoReport.
+    xs, ys, rel: inside the bound, NaN where the reference is NaN for sure.  drep (the kernel's ``m10 ? drep : 0``): the bound where m10 is
+    true for sure, exactly 0 where it is false for sure, either where it is open.  masks9: every decided element equal (an element is decided
+    false when dist OR rel is beyond its threshold by more than the bound, true when both are inside by more than it - no weaker than asking
+    both to be decided), any byte other than 0 / 1 fails.  geo_mask: equal wherever the lowest and the highest possible counts give the same
+    vote.  depth_est: inside the bound wherever every view's m10 is decided, NaN where d is."""
+    np = _np()
+    S, H, W = ref["nan"].shape
+    rep = GeoReport(where, H, W)
+    as_np = lambda t: t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+    for name, got, nan in (("xs", xs, ref["nan_in"]), ("ys", ys, ref["nan_in"]), ("rel", rel, ref["nan"])):
+        if got is not None:
+            bad, und, r = _check_pair(as_np(got), ref[name][0], ref[name][1], nan)
+            rep.add(name, bad, und, r, r)
+    if drep is not None:
+        g = as_np(drep).astype(np.float64)
+        lo, hi = ref["m_lo"][8], ref["m_hi"][8]
+        bad, und, r = _check_pair(g, ref["drep"][0], ref["drep"][1], np.zeros_like(lo), zero_ok=~lo, measure=lo)
+        bad = np.where(~hi, g != 0, bad)                      # (a NaN is != 0: a sentinel left behind fails)
+        rep.add("drep", bad, (lo != hi) | (lo & und), r, r)
+    if masks9 is not None:
+        g = as_np(masks9)
+        dec = ref["m_lo"] == ref["m_hi"]
+        rep.add("masks9", (dec & (g != ref["m_lo"])) | (g > 1), ~dec)
+    if geo_mask is not None:
+        g = as_np(geo_mask)
+        dec = ref["geo_lo"] == ref["geo_hi"]
+        rep.add("geo_mask", (dec & (g != ref["geo_lo"])) | (g > 1), ~dec)
+    if depth_est is not None:
+        ok = ref["est_ok"]
+        nan = np.isnan(ref["est"][0]) & ok & ref["nan_in"][0]
+        bad, und, r = _check_pair(as_np(depth_est), ref["est"][0], np.where(ok, ref["est"][1], np.inf), nan)
+        rep.add("depth_est", bad, und, r, r)
+    return rep
+
+
+def geo_census(ref):
+    """The non-vacuity figures of a case, from the reference alone -> dict: per level the share of true / false among the decided mask
+    elements (``true_share`` [9]), the share of samples outside the source image or on its zero-padded rim (``rim_share``), the number of
+    decided pixels whose vote is lit by a lower level (cnt[i-2] >= i for some i < n) while cnt[8] < n (``lit_by_lower``)."""
+    np = _np()
+    dec = ref["m_lo"] == ref["m_hi"]
+    n = 1 + ref["nan"].shape[0]
+    true_share = [float((ref["m_lo"][i] & dec[i]).sum() / max(1, dec[i].sum())) for i in range(9)]
+    decided = ref["geo_lo"] == ref["geo_hi"]
+    lower = ref["geo_lo"] & decided & (ref["cnt_hi"][8] < n)
+    return {"true_share": true_share, "rim_share": float(ref["rim"].mean()), "lit_by_lower": int(lower.sum())}
+
+
+# ---- image preparation (csrc/scan_ops.hip: prep_tap, image_prep_kernel) in float64 from torch's fp32 taps
+def prep_taps(n_in, n_out, first, count):
+    """prep_tap for output indices first .. first + count - 1 of an axis resized from n_in to n_out: scale = fl32((in-1) / (out-1)) (0 for
+    out = 1), s = fl32(scale * dst) - one fp32 product -, i0 = min(trunc(s), in-1), i1 = i0 + 1 clamped, l1 = fl32(s - i0), l0 = fl32(1 - l1)
+    -> (i0, i1 int64, l0, l1 float64 holding fp32 values): torch's upsample_bilinear2d(align_corners=True) taps."""
+    np = _np()
+    scale = np.float32(n_in - 1) / np.float32(n_out - 1) if n_out > 1 else np.float32(0.0)
+    dst = np.arange(first, first + count).astype(np.float32)
+    s = (scale * dst).astype(np.float32)
+    i0 = np.minimum(s.astype(np.int64), n_in - 1)
+    i1 = i0 + (i0 < n_in - 1)
+    l1 = (s - i0.astype(np.float32)).astype(np.float32)
+    l0 = (np.float32(1.0) - l1).astype(np.float32)
+    return i0, i1, l0.astype(np.float64), l1.astype(np.float64)
+
+
+K_PREP = 4                   # tap product, inner sum, row product, outer sum: the roundings on the path of one term
+
+
+def prep_ref64(img, H2, W2, y0, x0, H, W):
+    """img [3,H0,W0] (the fp32 values the kernel reads, channels already in output order) resized to H2 x W2 (bilinear, align_corners=True),
+    window rows y0 .. y0 + H - 1, columns x0 .. x0 + W - 1 -> (value, mag) float64 [3,H,W]: l0y (l0x a + l1x b) + l1y (l0x c + l1x d) from the
+    fp32 weights of ``prep_taps``, and the same on absolute values.  Every term passes at most four fp32 roundings: gamma_4 * mag bounds a
+    correct fp32 evaluation.  Equal sizes: the weights are (1, 0) and the value is the source texel."""
+    np = _np()
+    a = np.asarray(img, dtype=np.float64)
+    ya, yb, ly0, ly1 = prep_taps(a.shape[1], H2, y0, H)
+    xa, xb, lx0, lx1 = prep_taps(a.shape[2], W2, x0, W)
+    res = []
+    for v in (a, np.abs(a)):
+        top = v[:, ya][:, :, xa] * lx0 + v[:, ya][:, :, xb] * lx1
+        bot = v[:, yb][:, :, xa] * lx0 + v[:, yb][:, :, xb] * lx1
+        res.append(top * ly0[None, :, None] + bot * ly1[None, :, None])
+    return res[0], res[1]
+
+
+def check_prep(got, ref, mag, where=""):
+    """[3,H,W] against ``prep_ref64`` at gamma_4 * mag, element by element -> ParityReport over the H x W image (channels as channels)."""
+    got = torch.as_tensor(got).detach().cpu()
+    _, H, W = got.shape
+    flat = lambda t: torch.as_tensor(t, dtype=torch.float64).reshape(3, H * W).t()
+    return check_elementwise(flat(got), flat(ref), flat(mag), _gam(K_PREP), 0.0, where, h=H, w=W, tile=(1, 4))
+
+
+def bits_equal(got, want):
+    """float32 arrays compared through their int32 views -> bool array; a NaN equals a NaN (an invalid operation yields the default NaN
+    with the sign bit set on x86 and clear on the GPU: the payload is not part of the documented sequence)."""
+    np = _np()
+    g, w = np.ascontiguousarray(got, dtype=np.float32), np.ascontiguousarray(want, dtype=np.float32)
+    return (g.view(np.int32) == w.view(np.int32)) | (np.isnan(g) & np.isnan(w))
