@@ -9,7 +9,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CER_MVS_LIB") or os.path.join(_HERE, "csrc", "libcermvs.so")
-ABI_VERSION = 1140
+ABI_VERSION = 1150
 CONV_MAX_SRC = 4
 EPI_LINEAR, EPI_RELU, EPI_GATES, EPI_GRU, EPI_DELTA = 0, 1, 2, 3, 4
 EPI_OUT_SPLIT, EPI_AUX_SPLIT = 0x100, 0x200       # cer_mvs.h: split32 activation layout flags, or-ed into `epi`
@@ -130,6 +130,7 @@ _SIGNATURES = {
     "cer_grid_cells_i64": (_I, [_P, _L, _P, _LL, _P, _P, _P]),
     "cer_grid_nearest_f32": (_I, [_P, _L, _P, _P, _L, _c.POINTER(_D), _D, _P, _P, _L, _F, _P, _P, _P]),
     "cer_grid_knn_f32": (_I, [_P, _L, _P, _P, _L, _c.POINTER(_D), _D, _P, _P, _L, _I, _F, _P, _P, _P, _P, _P]),
+    "cer_grid_normals_f32": (_I, [_P, _L, _P, _P, _L, _c.POINTER(_D), _D, _P, _P, _L, _I, _F, _P, _P, _P, _P, _P, _P, _P]),
     "cer_grid_count_within_f32": (_I, [_P, _L, _P, _P, _L, _c.POINTER(_D), _D, _P, _P, _L, _F, _P, _P]),
     "cer_grid_thin_round_f32": (_I, [_P, _L, _P, _P, _L, _c.POINTER(_D), _D, _P, _L, _F, _P, _P]),
     "cer_grid_thin_compact_i32": (_I, [_P, _L, _P, _P, _L, _P, _P, _P, _P, _P]),

@@ -27,7 +27,14 @@ contract: fp64 distances, lowest index on ties, inclusive cut-off, no atomics.  
 
     keep = remove_statistical_outliers(pred, k=20, std_ratio=2.0)      # or remove_radius_outliers(pred, radius, min_neighbours)
     pred = pred.index_select(0, keep)
-    reconstruct_scan(model, ..., clean={"method": "statistical", "k": 20, "std_ratio": 2.0})      # the same, before the cloud leaves the device"""
+    reconstruct_scan(model, ..., clean={"method": "statistical", "k": 20, "std_ratio": 2.0})      # the same, before the cloud leaves the device
+
+... and a third: ``CloudIndex.normals`` / ``estimate_normals`` - the surface normal and the curvature (surface variation) at every
+point, from the plane through its k nearest neighbours (the eigenvectors of their fp64 covariance, found in the search kernel's registers), turned
+towards a viewpoint when there is one - what a mesher or a relighter asks of a cloud:
+
+    normal, curvature = estimate_normals(pred, k=20, viewpoints=camera_centre)      # float32 [n, 3] (zeros where there is no plane), float32 [n]
+    reconstruct_scan(model, ..., normals=True)      # every point turned towards the camera that produced it; result.ply carries nx ny nz"""
 import ctypes
 import math
 
@@ -56,6 +63,7 @@ KNN_CELL_DIVISOR = DEFAULT_CELL_DIVISOR
 MOMENT_TILE = 2048                                           # cer_mvs.h CER_MOMENT_TILE
 MOMENT_COUNT = 17                                            # cer_mvs.h CER_MOMENT_COUNT
 COLLINEAR_RATIO = 1e-12                                      # rigid_from_moments: second singular value / first at or below this -> no rotation
+NORMAL_DEGENERATE = COLLINEAR_RATIO                          # cloud_eval.hip NORMAL_DEGENERATE: second eigenvalue / largest at or below this -> no normal
 
 
 def _cloud(t, name):
@@ -232,6 +240,50 @@ class CloudIndex:
         L.check(rc, "grid_count_within")
         return count
 
+    def normals(self, queries, k, max_dist, viewpoints=None, sort_queries=True, moments=False):
+        """-> (normal float32 [m, 3], curvature float32 [m], count int32 [m]) and, with ``moments``, mom float64 [m, 9]: the plane through the
+        neighbours ``knn(queries, k, max_dist)`` lists (count of them; a query that is an indexed point is among its own).  In fp64, about the
+        query, in the list's order: S1 = sum d, S2 = sum d_a d_b (xx xy xz yy yz zz) - ``mom`` holds these nine; C = S2 / c - mean mean^T; its
+        eigenvalues l0 <= l1 <= l2 by cyclic Jacobi.  A query is VALID iff it is finite, count >= 3, l2 > 0 and l1 > 1e-12 l2 (not collinear):
+        normal = the unit eigenvector of l0 rounded once to float32, curvature = max(l0, 0) / (l0 + l1 + l2); otherwise (0, 0, 0) and NaN.
+        Sign: the component of largest magnitude is positive (lowest axis on a tie); with ``viewpoints`` (CUDA float32 [3] or [m, 3]) the
+        normal is turned so that normal . (viewpoint - query) >= 0; a non-finite viewpoint leaves the canonical sign.  ``k``: 1 .. 32."""
+        k = int(k)
+        if not 1 <= k <= KNN_MAX:
+            raise ValueError(f"k: 1 .. {KNN_MAX} expected, got {k}")
+        max_dist = float(np.float32(max_dist))
+        if not max_dist >= 0.0:
+            raise ValueError("max_dist must be >= 0")
+        queries = _cloud(queries, "queries")
+        m, dev = int(queries.shape[0]), queries.device
+        if viewpoints is not None:
+            if not isinstance(viewpoints, torch.Tensor) or not viewpoints.is_cuda:
+                raise RuntimeError("viewpoints must be a CUDA tensor (no CPU fallback)")
+            if viewpoints.dtype != torch.float32:
+                raise RuntimeError("viewpoints must be float32")
+            if tuple(viewpoints.shape) == (3,):
+                viewpoints = viewpoints.expand(m, 3)
+            if tuple(viewpoints.shape) != (m, 3):
+                raise ValueError(f"viewpoints: [3] or one per query [{m}, 3] expected, got {tuple(viewpoints.shape)}")
+            viewpoints = viewpoints.contiguous()
+        if m == 0 or self.n == 0:                            # (the entry point launches nothing for an empty side)
+            out = (torch.zeros(m, 3, device=dev, dtype=torch.float32), torch.full((m,), float("nan"), device=dev, dtype=torch.float32),
+                   torch.zeros(m, device=dev, dtype=torch.int32))
+            return out + (torch.zeros(m, 9, device=dev, dtype=torch.float64),) if moments else out
+        normal = torch.empty(m, 3, device=dev, dtype=torch.float32)
+        curvature = torch.empty(m, device=dev, dtype=torch.float32)
+        count = torch.empty(m, device=dev, dtype=torch.int32)
+        mom = torch.empty(m, 9, device=dev, dtype=torch.float64) if moments else None
+        qorder = self._walk_order(queries, m) if sort_queries else None
+        rc = L.load().cer_grid_normals_f32(*self.grid_args(), L.dev_ptr(queries, "queries"), L.dev_ptr(qorder, "qorder", torch.int64), m, k, max_dist,
+                                           L.dev_ptr(self.points, "points"), L.dev_ptr(viewpoints, "viewpoints"), L.dev_ptr(normal, "normal"),
+                                           L.dev_ptr(curvature, "curvature"), L.dev_ptr(count, "count", torch.int32),
+                                           L.dev_ptr(mom, "mom", torch.float64), L.cur_stream())
+        if rc == -2:
+            raise ValueError(f"nearest: max_dist {max_dist} is more than {GRID_MAX_RINGS} cells of {self.cell}; index the cloud with a larger cell")
+        L.check(rc, "grid_normals")
+        return (normal, curvature, count, mom) if moments else (normal, curvature, count)
+
 
 def voxel_downsample(points, cell):
     """Indices (int64, ascending) of the lowest-index point of every occupied cell of a grid with edge ``cell`` whose origin is the cloud's
@@ -327,6 +379,30 @@ def radius_thin(points, radius, order="random", seed=0, cell=None, max_rounds=40
 
 
 # ---------------------------------------------------------------- outlier removal
+def _self_search_scale(points, max_dist, cell):
+    """-> (the checked cloud, max_dist, cell) of a search of a cloud on itself: ``max_dist`` a finite number >= 0 (rounded to float32), or None
+    for 1 % of the diagonal of the bounding box of the finite points (0 without one); ``cell`` a positive finite number, or None for
+    ``max_dist / KNN_CELL_DIVISOR``.  ValueError otherwise, before the cloud is looked at."""
+    if max_dist is not None:
+        max_dist = float(np.float32(max_dist))
+        if not (max_dist >= 0.0 and math.isfinite(max_dist)):
+            raise ValueError("max_dist must be a finite number >= 0")
+    cell = None if cell is None else _cell(cell)
+    points = _cloud(points, "points")
+    n = int(points.shape[0])
+    if max_dist is None:
+        finite = torch.isfinite(points).all(1, keepdim=True)
+        if n and bool(finite.any()):
+            lo = torch.where(finite, points, points.new_full((), float("inf"))).amin(0).double()
+            hi = torch.where(finite, points, points.new_full((), float("-inf"))).amax(0).double()
+            max_dist = float(np.float32(0.01 * float((hi - lo).norm())))
+        else:
+            max_dist = 0.0
+    if cell is None:
+        cell = max_dist / KNN_CELL_DIVISOR if max_dist > 0.0 else 1.0        # (a cloud without extent: any cell will do)
+    return points, max_dist, cell
+
+
 def remove_statistical_outliers(points, k=20, std_ratio=2.0, max_dist=None, cell=None, info=None):
     """Indices (int64, ascending) of the points that the statistical outlier filter keeps - Open3D's ``remove_statistical_outlier``, stated
     here in full.  The cloud is indexed on itself, so every point is one of its own ``k`` neighbours (at distance 0).  mean_i =
@@ -344,23 +420,8 @@ def remove_statistical_outliers(points, k=20, std_ratio=2.0, max_dist=None, cell
         raise ValueError(f"k: 1 .. {KNN_MAX} expected, got {k}")
     if not math.isfinite(std_ratio):
         raise ValueError("std_ratio must be finite")
-    if max_dist is not None:
-        max_dist = float(np.float32(max_dist))
-        if not (max_dist >= 0.0 and math.isfinite(max_dist)):
-            raise ValueError("max_dist must be a finite number >= 0")
-    cell = None if cell is None else _cell(cell)
-    points = _cloud(points, "points")
+    points, max_dist, cell = _self_search_scale(points, max_dist, cell)
     n, dev = int(points.shape[0]), points.device
-    if max_dist is None:
-        finite = torch.isfinite(points).all(1, keepdim=True)
-        if n and bool(finite.any()):
-            lo = torch.where(finite, points, points.new_full((), float("inf"))).amin(0).double()
-            hi = torch.where(finite, points, points.new_full((), float("-inf"))).amax(0).double()
-            max_dist = float(np.float32(0.01 * float((hi - lo).norm())))
-        else:
-            max_dist = 0.0
-    if cell is None:
-        cell = max_dist / KNN_CELL_DIVISOR if max_dist > 0.0 else 1.0        # (a cloud without extent: any cell will do)
     stats = {"mu": float("nan"), "sigma": float("nan"), "threshold": float("inf"), "n_valid": 0, "n_kept": 0, "max_dist": max_dist, "cell": cell}
     keep = torch.empty(0, device=dev, dtype=torch.int64)
     if n:
@@ -422,6 +483,38 @@ def clean_cloud(points, clean):
     if "radius" not in args or "min_neighbours" not in args:
         raise ValueError('clean: method "radius" needs "radius" and "min_neighbours"')
     return remove_radius_outliers(points, info=info, **args), info
+
+
+# ---------------------------------------------------------------- surface normals
+def estimate_normals(points, k=20, max_dist=None, cell=None, viewpoints=None, info=None):
+    """-> (normal float32 [n, 3], curvature float32 [n]): ``CloudIndex(points, cell).normals(points, k, max_dist, viewpoints)`` - the cloud
+    indexed on itself, so every point is one of its own ``k`` neighbours (Open3D's ``estimate_normals`` with a hybrid kNN / radius search,
+    followed by ``orient_normals_towards_camera_location`` when ``viewpoints`` - CUDA float32 [3] or [n, 3] - is given).  A point without a
+    plane (fewer than 3 neighbours within ``max_dist``, collinear or coincident ones, a non-finite coordinate) has normal (0, 0, 0) and
+    curvature NaN.  ``max_dist`` / ``cell``: as ``remove_statistical_outliers`` (None: 1 % of the bounding-box diagonal / ``max_dist / 4``).
+    ``info``: a dict that receives "n_valid" (one host read), "max_dist", "cell" and "k"."""
+    k = int(k)
+    if not 1 <= k <= KNN_MAX:
+        raise ValueError(f"k: 1 .. {KNN_MAX} expected, got {k}")
+    points, max_dist, cell = _self_search_scale(points, max_dist, cell)
+    normal, curvature, _ = CloudIndex(points, cell).normals(points, k, max_dist, viewpoints=viewpoints)
+    if info is not None:
+        info.update(n_valid=int(torch.count_nonzero(~torch.isnan(curvature))), max_dist=max_dist, cell=cell, k=k)
+    return normal, curvature
+
+
+def normals_options(normals):
+    """The arguments of ``estimate_normals`` that ``reconstruct_scan(normals=...)`` names: True -> {}; a dict with any of "k", "max_dist", "cell"
+    -> a copy; ValueError for anything else or a key beyond those."""
+    if normals is True:
+        return {}
+    if not isinstance(normals, dict):
+        raise ValueError('normals: None, True or a dict with "k", "max_dist", "cell" expected')
+    allowed = ("k", "max_dist", "cell")
+    extra = sorted(set(normals) - set(allowed))
+    if extra:
+        raise ValueError(f'normals: takes {", ".join(allowed)}; got {", ".join(str(e) for e in extra)}')
+    return dict(normals)
 
 
 def cloud_distances(src, dst, max_dist, cell=None):
@@ -702,10 +795,11 @@ _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short":
               "int": "<i4", "int32": "<i4", "uint": "<u4", "uint32": "<u4", "float": "<f4", "float32": "<f4", "double": "<f8", "float64": "<f8"}
 
 
-def read_ply(path):
+def read_ply(path, normals=False):
     """-> (xyz float32 [n, 3], rgb uint8 [n, 3] or None): the vertex element of a binary little-endian PLY whose vertex properties are scalars
     in any order (what ``fusion.write_ply`` writes; extra properties are skipped).  x, y, z must be float, red / green / blue (if all three
-    are there) uchar.  ASCII and big-endian files raise ValueError naming the format."""
+    are there) uchar.  ASCII and big-endian files raise ValueError naming the format.  ``normals=True``: a third value, float32 [n, 3] from
+    the float properties nx, ny, nz, or None when the file does not have all three."""
     with open(path, "rb") as f:
         raw = f.read()
     end = raw.find(b"end_header\n")
@@ -747,4 +841,12 @@ def read_ply(path):
         if any(dt[k] != np.dtype("u1") for k in ("red", "green", "blue")):
             raise ValueError(f"{path}: uchar red, green, blue expected")
         rgb = np.stack([v["red"], v["green"], v["blue"]], 1) if n else np.zeros((0, 3), np.uint8)
-    return np.ascontiguousarray(xyz, dtype=np.float32), rgb
+    xyz = np.ascontiguousarray(xyz, dtype=np.float32)
+    if not normals:
+        return xyz, rgb
+    nrm = None
+    if all(k in names for k in ("nx", "ny", "nz")):
+        if any(dt[k] != np.dtype("<f4") for k in ("nx", "ny", "nz")):
+            raise ValueError(f"{path}: float nx, ny, nz expected")
+        nrm = np.ascontiguousarray(np.stack([v["nx"], v["ny"], v["nz"]], 1) if n else np.zeros((0, 3), np.float32), dtype=np.float32)
+    return xyz, rgb, nrm

@@ -6,7 +6,8 @@
 // cer_grid_cells_count_i64 / cer_grid_cells_i64 list the occupied cells with their first sorted point (compact.hpp's count / scan / emit over
 // the heads of the sorted keys), and cer_grid_nearest_f32 searches.  No atomics anywhere: the same bytes on every run.
 // On the same grid, cer_grid_thin_round_f32 / cer_grid_thin_compact_i32 are the rounds of the DTU script's greedy radius thinning (below),
-// and cer_grid_knn_f32 / cer_grid_count_within_f32 the k nearest neighbours of a query and the number of points within a radius of it.
+// and cer_grid_knn_f32 / cer_grid_count_within_f32 the k nearest neighbours of a query and the number of points within a radius of it;
+// cer_grid_normals_f32 turns those neighbours into a surface normal and a curvature (the plane through them, by PCA).
 //
 // Key layout: (z + B) << 42 | (y + B) << 21 | (x + B), B = CER_GRID_COORD_LIMIT - 1, cell coordinates in -B .. B: every field is at most
 // 2^21 - 2, so no key reaches the sentinel (2^63 - 1, all 63 bits set) and key(x + 1, y, z) = key(x, y, z) + 1 never carries.  x is the
@@ -128,8 +129,8 @@ __global__ __launch_bounds__(256) void grid_emit_kernel(const long long* __restr
 // the caller's bound are skipped - strictly: for the search's best distance so far a tie on d2 with a lower index must still be seen, for
 // the thinning's fixed radius^2 d2 == limit is a neighbour; the enumeration itself covers ceil(reach / cell) + 1 rings, one more than the
 // mathematics needs.  The k-nearest search hands in the d2 of its k-th entry so far (the limit until k candidates are in): a skipped cell
-// holds only points strictly beyond it, which cannot enter the list, and a tie on the k-th distance with a lower index is still seen; the
-// count within a radius hands in the fixed radius^2 as the thinning does.
+// holds only points strictly beyond it, which cannot enter the list, and a tie on the k-th distance with a lower index is still seen (the
+// normals' search, grid_normals_kernel, is that search); the count within a radius hands in the fixed radius^2 as the thinning does.
 #define GRID_EPS 1e-6
 
 // gap, in cells, between coordinate u and the points of cell c of that axis (0 when u is inside)
@@ -282,21 +283,14 @@ __device__ __forceinline__ void knn_scan_row(const uint4* __restrict__ rec, cons
     }
 }
 
-// idx / dist [m, k] (slot j of a row: the j-th smallest (d2, index); unused slots -1 / +inf), count [m], mean [m] (the fp64 mean of the
-// row's sqrt(d2), summed in ascending order; +inf for an empty row); idx, dist and mean may each be null.  Every element is written once.
+// The fill both list kernels share: the KMAX slots set up for a runtime k, then the walk.  On return the live slots KMAX-k .. KMAX-1 hold the
+// min(k, candidates) smallest (d2, index) pairs in ascending order and then (limit, INT_MAX); nothing is in them for a query that is not finite.
 template <int KMAX>
-__global__ __launch_bounds__(256) void grid_knn_kernel(const uint4* __restrict__ rec, const long long* __restrict__ cell_keys,
-                                                       const long long* __restrict__ cell_start, long ncells, double ox, double oy, double oz,
-                                                       double cell, const float* __restrict__ queries, const long long* __restrict__ qorder,
-                                                       long m, int k, float max_dist, int rings, long long* __restrict__ idx,
-                                                       float* __restrict__ dist, int* __restrict__ count, double* __restrict__ mean) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= m) return;
-    const long long q = qorder ? qorder[i] : i;
-    const float qx = queries[3 * q], qy = queries[3 * q + 1], qz = queries[3 * q + 2];
+__device__ __forceinline__ void knn_fill(const uint4* __restrict__ rec, const long long* __restrict__ cell_keys,
+                                         const long long* __restrict__ cell_start, long ncells, double ox, double oy, double oz, double cell,
+                                         float qx, float qy, float qz, int k, float max_dist, int rings, GridList<KMAX>& l) {
     const double limit = (double)max_dist * (double)max_dist;
     const int first = KMAX - k;                                                  // the list's first live slot
-    GridList<KMAX> l;
 #pragma unroll
     for (int s = 0; s < KMAX; ++s) {
         l.d2[s] = grid_vreg(s < first ? -1.0 : limit);
@@ -322,6 +316,23 @@ __global__ __launch_bounds__(256) void grid_knn_kernel(const uint4* __restrict__
             return false;
         });
     }
+}
+
+// idx / dist [m, k] (slot j of a row: the j-th smallest (d2, index); unused slots -1 / +inf), count [m], mean [m] (the fp64 mean of the
+// row's sqrt(d2), summed in ascending order; +inf for an empty row); idx, dist and mean may each be null.  Every element is written once.
+template <int KMAX>
+__global__ __launch_bounds__(256) void grid_knn_kernel(const uint4* __restrict__ rec, const long long* __restrict__ cell_keys,
+                                                       const long long* __restrict__ cell_start, long ncells, double ox, double oy, double oz,
+                                                       double cell, const float* __restrict__ queries, const long long* __restrict__ qorder,
+                                                       long m, int k, float max_dist, int rings, long long* __restrict__ idx,
+                                                       float* __restrict__ dist, int* __restrict__ count, double* __restrict__ mean) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= m) return;
+    const long long q = qorder ? qorder[i] : i;
+    const float qx = queries[3 * q], qy = queries[3 * q + 1], qz = queries[3 * q + 2];
+    const int first = KMAX - k;
+    GridList<KMAX> l;
+    knn_fill(rec, cell_keys, cell_start, ncells, ox, oy, oz, cell, qx, qy, qz, k, max_dist, rings, l);
     int c = 0;
     double sum = 0.0;
 #pragma unroll
@@ -339,6 +350,116 @@ __global__ __launch_bounds__(256) void grid_knn_kernel(const uint4* __restrict__
     }
     count[q] = c;
     if (mean) mean[q] = c ? sum / (double)c : (double)__builtin_inff();
+}
+
+// ---- surface normals (CloudIndex.normals / estimate_normals): the plane through the k nearest neighbours of a query, by the
+// eigenvectors of their covariance.  The search is grid_knn_kernel's (knn_fill); the epilogue below runs in the registers the walk leaves
+// free: fp64 throughout, no LDS, no atomics, nothing indexed at run time, every output element written once by the query's thread.
+#define NORMAL_DEGENERATE 1e-12                      // second eigenvalue / largest at or below this: a collinear neighbourhood, no normal
+#define NORMAL_SWEEPS 16                             // cyclic Jacobi sweeps at most (a 3 x 3 matrix needs 4 to 7)
+
+// One Jacobi rotation in the (p, q) plane of a symmetric 3 x 3 matrix; r is the third axis (arp / arq: its entries against p / q) and
+// v*p / v*q are columns p and q of the eigenvector matrix.  An off-diagonal entry that is exactly 0, or that no longer changes either of its
+// two diagonal entries when added to them a hundred times over (below 2^-59 of both), is set to 0 without a rotation; false then.
+__device__ __forceinline__ bool jacobi_rotate(double& app, double& aqq, double& apq, double& arp, double& arq, double& v0p, double& v0q,
+                                              double& v1p, double& v1q, double& v2p, double& v2q) {
+    if (apq == 0.0) return false;
+    const double g = 100.0 * fabs(apq);
+    if (fabs(app) + g == fabs(app) && fabs(aqq) + g == fabs(aqq)) {
+        apq = 0.0;
+        return false;
+    }
+    const double theta = (aqq - app) / (2.0 * apq);                              // (overflows to +-inf for a tiny apq: t = 0, the entry goes)
+    const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + __builtin_sqrt(theta * theta + 1.0));
+    const double c = 1.0 / __builtin_sqrt(t * t + 1.0), s = t * c;
+    app = app - t * apq;
+    aqq = aqq + t * apq;
+    apq = 0.0;
+    const double rp = arp, rq = arq;
+    arp = c * rp - s * rq;
+    arq = s * rp + c * rq;
+    const double p0 = v0p, q0 = v0q, p1 = v1p, q1 = v1q, p2 = v2p, q2 = v2q;
+    v0p = c * p0 - s * q0, v0q = s * p0 + c * q0;
+    v1p = c * p1 - s * q1, v1q = s * p1 + c * q1;
+    v2p = c * p2 - s * q2, v2q = s * p2 + c * q2;
+    return true;
+}
+
+// normal [m, 3] float, curvature [m] float, count [m], mom [m, 9] double (S1 x y z, S2 xx xy xz yy yz zz about the query); normal, curvature
+// and mom may each be null.  points: the indexed cloud's original array (a record's fourth word indexes it); viewpoints [m, 3] or null.
+template <int KMAX>
+__global__ __launch_bounds__(256) void grid_normals_kernel(const uint4* __restrict__ rec, const long long* __restrict__ cell_keys,
+                                                           const long long* __restrict__ cell_start, long ncells, double ox, double oy, double oz,
+                                                           double cell, const float* __restrict__ queries, const long long* __restrict__ qorder,
+                                                           long m, int k, float max_dist, int rings, const float* __restrict__ points,
+                                                           const float* __restrict__ viewpoints, float* __restrict__ normal,
+                                                           float* __restrict__ curvature, int* __restrict__ count, double* __restrict__ mom) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= m) return;
+    const long long q = qorder ? qorder[i] : i;
+    const float qx = queries[3 * q], qy = queries[3 * q + 1], qz = queries[3 * q + 2];
+    GridList<KMAX> l;
+    knn_fill(rec, cell_keys, cell_start, ncells, ox, oy, oz, cell, qx, qy, qz, k, max_dist, rings, l);
+    // the moments about the query, the used slots in ascending order (they are one run of the list; the others read point 0 and add nothing)
+    const double X = (double)qx, Y = (double)qy, Z = (double)qz;
+    int c = 0;
+    double sx = 0.0, sy = 0.0, sz = 0.0, sxx = 0.0, sxy = 0.0, sxz = 0.0, syy = 0.0, syz = 0.0, szz = 0.0;
+#pragma unroll
+    for (int s = 0; s < KMAX; ++s) {
+        const bool used = (l.idx[s] != -1) & (l.idx[s] != 0x7fffffff);
+        const long p = used ? (long)l.idx[s] : 0;
+        const double dx = (double)points[3 * p] - X, dy = (double)points[3 * p + 1] - Y, dz = (double)points[3 * p + 2] - Z;
+        const double xx = dx * dx, xy = dx * dy, xz = dx * dz, yy = dy * dy, yz = dy * dz, zz = dz * dz;
+        sx = used ? sx + dx : sx, sy = used ? sy + dy : sy, sz = used ? sz + dz : sz;
+        sxx = used ? sxx + xx : sxx, sxy = used ? sxy + xy : sxy, sxz = used ? sxz + xz : sxz;
+        syy = used ? syy + yy : syy, syz = used ? syz + yz : syz, szz = used ? szz + zz : szz;
+        c += used ? 1 : 0;
+    }
+    count[q] = c;
+    if (mom) {
+        double* o = mom + 9 * (long)q;
+        o[0] = sx, o[1] = sy, o[2] = sz, o[3] = sxx, o[4] = sxy, o[5] = sxz, o[6] = syy, o[7] = syz, o[8] = szz;
+    }
+    if (!normal && !curvature) return;
+    float nx = 0.0f, ny = 0.0f, nz = 0.0f, curv = __builtin_nanf("");
+    if (c >= 3) {                                                                // (a query that is not finite has c = 0)
+        const double n = (double)c, mx = sx / n, my = sy / n, mz = sz / n;
+        double a00 = sxx / n - mx * mx, a01 = sxy / n - mx * my, a02 = sxz / n - mx * mz;
+        double a11 = syy / n - my * my, a12 = syz / n - my * mz, a22 = szz / n - mz * mz;
+        double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;
+#pragma unroll 1
+        for (int sweep = 0; sweep < NORMAL_SWEEPS; ++sweep) {
+            bool turned = jacobi_rotate(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);
+            turned |= jacobi_rotate(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);
+            turned |= jacobi_rotate(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);
+            if (!turned) break;
+        }
+        // l0 <= l1 <= l2; the eigenvector of l0 is the column of the smallest diagonal entry (the lowest axis on a tie)
+        const bool c0 = a00 <= a11 && a00 <= a22, c1 = !c0 && a11 <= a22;
+        const double l0 = c0 ? a00 : c1 ? a11 : a22, l2 = fmax(fmax(a00, a11), a22);
+        const double l1 = fmax(fmin(a00, a11), fmin(fmax(a00, a11), a22));
+        if (l2 > 0.0 && l1 > NORMAL_DEGENERATE * l2) {
+            double ex = c0 ? v00 : c1 ? v01 : v02, ey = c0 ? v10 : c1 ? v11 : v12, ez = c0 ? v20 : c1 ? v21 : v22;
+            const double len = __builtin_sqrt((ex * ex + ey * ey) + ez * ez);
+            ex = ex / len, ey = ey / len, ez = ez / len;
+            // canonical sign: the component of largest magnitude is positive (the lowest axis on a tie) ...
+            const double ax = fabs(ex), ay = fabs(ey), az = fabs(ez);
+            const double lead = (ax >= ay && ax >= az) ? ex : ay >= az ? ey : ez;
+            bool flip = lead < 0.0;
+            if (viewpoints) {                                                    // ... unless a finite viewpoint says which side the surface was seen from
+                const float vx = viewpoints[3 * q], vy = viewpoints[3 * q + 1], vz = viewpoints[3 * q + 2];
+                if (grid_finite(vx, vy, vz)) {
+                    const double sg = flip ? -1.0 : 1.0;
+                    const double dot = ((sg * ex) * ((double)vx - X) + (sg * ey) * ((double)vy - Y)) + (sg * ez) * ((double)vz - Z);
+                    flip = flip != (dot < 0.0);
+                }
+            }
+            nx = (float)(flip ? -ex : ex), ny = (float)(flip ? -ey : ey), nz = (float)(flip ? -ez : ez);
+            curv = (float)(fmax(l0, 0.0) / ((l0 + l1) + l2));
+        }
+    }
+    if (normal) normal[3 * q] = nx, normal[3 * q + 1] = ny, normal[3 * q + 2] = nz;
+    if (curvature) curvature[q] = curv;
 }
 
 // ---- the number of indexed points within a radius: d2 <= double(radius)^2, inclusive.  The bound is constant and no row stops the walk.
@@ -594,6 +715,27 @@ extern "C" int cer_grid_knn_f32(const void* records, long n, const long long* ce
     else if (k <= 16) KNN_LAUNCH(16);
     else KNN_LAUNCH(32);
 #undef KNN_LAUNCH
+    CER_RETURN_IF_LAUNCH_FAILED();
+    return CER_OK;
+}
+
+// cer_grid_knn_f32's checks, with points beside count among the pointers that may not be null (normal, curvature, mom and viewpoints may)
+extern "C" int cer_grid_normals_f32(const void* records, long n, const long long* cell_keys, const long long* cell_start, long ncells,
+                                    const double* origin, double cell, const float* queries, const long long* qorder, long m, int k,
+                                    float max_dist, const float* points, const float* viewpoints, float* normal, float* curvature, int* count,
+                                    double* mom, void* stream) {
+    const int rings = grid_search_rings(records, n, cell_keys, cell_start, ncells, origin, cell, m, max_dist, max_dist >= 0.0f && k >= 1,
+                                        k <= CER_KNN_MAX, queries && count && points);
+    if (rings <= 0) return rings;                            // (an empty side: the caller fills normal = 0, curvature = NaN, count = 0, mom = 0)
+    const dim3 grid(grid_blocks(m, 256)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+#define NORMALS_LAUNCH(KMAX)                                                                                                                  \
+    hipLaunchKernelGGL(grid_normals_kernel<KMAX>, grid, block, 0, st, (const uint4*)records, cell_keys, cell_start, ncells, origin[0], origin[1], \
+                       origin[2], cell, queries, qorder, m, k, max_dist, rings, points, viewpoints, normal, curvature, count, mom)
+    if (k <= 8) NORMALS_LAUNCH(8);
+    else if (k <= 16) NORMALS_LAUNCH(16);
+    else NORMALS_LAUNCH(32);
+#undef NORMALS_LAUNCH
     CER_RETURN_IF_LAUNCH_FAILED();
     return CER_OK;
 }

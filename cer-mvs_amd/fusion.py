@@ -148,11 +148,12 @@ def cloud_cams(Ks, Es):
     return torch.from_numpy(cams)
 
 
-def point_cloud(masks, depth_est, Ks, Es, colors, order):
+def point_cloud(masks, depth_est, Ks, Es, colors, order, view_base=False):
     """The tail of ``fusion()`` on the device: masks uint8 [N,h,w], depth_est float32 [N,h,w], colors float32 [N,3,h,w] with values 0..1 (CUDA),
     Ks [N,3,3], Es [N,4,4], ``order``: the views to emit.  Returns (xyz float32 [n,3], rgb uint8 [n,3]) on the device, n = set mask pixels
     of the listed views: view by view in ``order``, row-major inside a view (numpy's boolean-indexing order), xyz = ``backproject``'s fp64
-    arithmetic rounded once to float32, rgb = (uint8)(c * 255).  One device->host read (the per-view totals) sizes the output."""
+    arithmetic rounded once to float32, rgb = (uint8)(c * 255).  One device->host read (the per-view totals) sizes the output.
+    ``view_base=True``: a third value, int64 [len(order) + 1] on the device - the points of ``order[k]`` are rows view_base[k] .. view_base[k+1]-1."""
     if not (masks.is_cuda and depth_est.is_cuda and colors.is_cuda):
         raise RuntimeError("point_cloud: masks, depth_est and colors must be CUDA tensors (no CPU fallback)")
     N, h, w = masks.shape
@@ -171,7 +172,7 @@ def point_cloud(masks, depth_est, Ks, Es, colors, order):
     P = int(lib.cer_cloud_partials(len(order), h, w))
     partials = torch.empty(P, device=dev, dtype=torch.int32)
     offsets = torch.empty(P + 1, device=dev, dtype=torch.int64)
-    view_base = torch.empty(len(order) + 1, device=dev, dtype=torch.int64)
+    want_base, view_base = bool(view_base), torch.empty(len(order) + 1, device=dev, dtype=torch.int64)
     pm, pd, pc = L.dev_ptr(masks, "masks", torch.uint8), L.dev_ptr(depth_est, "depth_est"), L.dev_ptr(colors, "colors")
     L.check(lib.cer_cloud_count_u8(pm, N, h, w, order_c, len(order), L.dev_ptr(partials, "partials", torch.int32),
                                    L.dev_ptr(offsets, "offsets", torch.int64), L.dev_ptr(view_base, "view_base", torch.int64), L.cur_stream()),
@@ -182,7 +183,7 @@ def point_cloud(masks, depth_est, Ks, Es, colors, order):
     L.check(lib.cer_cloud_emit_f32(pm, pd, L.dev_ptr(cams, "cams", torch.float64), pc, N, h, w, order_c, len(order),
                                    L.dev_ptr(offsets, "offsets", torch.int64), n, n, L.dev_ptr(xyz, "xyz") if n else None,
                                    L.dev_ptr(rgb, "rgb", torch.uint8) if n else None, L.cur_stream()), "cloud_emit")
-    return xyz, rgb
+    return (xyz, rgb, view_base) if want_base else (xyz, rgb)
 
 
 def color_grid(prepared, h, w):
@@ -219,14 +220,21 @@ def read_pfm(path):
     return np.flipud(data.reshape(shape)).astype(np.float32)
 
 
-def write_ply(path, xyz, rgb):
+def write_ply(path, xyz, rgb, normals=None):
     """Binary little-endian PLY with float x, y, z and uchar red, green, blue - what plyfile's PlyData([...]).write produces
-    for the reference's vertex array (fusion.py:281-294)."""
-    v = np.empty(len(xyz), dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+    for the reference's vertex array (fusion.py:281-294).  ``normals`` ([n, 3]): float nx, ny, nz between the position and the colour, the
+    order MeshLab and Open3D write."""
+    nrm = [] if normals is None else [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+    if normals is not None and tuple(np.shape(normals)) != (len(xyz), 3):
+        raise ValueError(f"write_ply: normals [{len(xyz)}, 3] expected")
+    v = np.empty(len(xyz), dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4")] + nrm + [("red", "u1"), ("green", "u1"), ("blue", "u1")])
     v["x"], v["y"], v["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    if nrm:
+        v["nx"], v["ny"], v["nz"] = normals[:, 0], normals[:, 1], normals[:, 2]
     v["red"], v["green"], v["blue"] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
     header = ("ply\nformat binary_little_endian 1.0\n" f"element vertex {len(v)}\n"
-              "property float x\nproperty float y\nproperty float z\nproperty uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n")
+              "property float x\nproperty float y\nproperty float z\n" + "".join(f"property float {k}\n" for k, _ in nrm)
+              + "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n")
     with open(path, "wb") as f:
         f.write(header.encode("ascii"))
         f.write(v.tobytes())

@@ -360,7 +360,7 @@ def _write_masks(folder, masks_np, refs, suffix=""):
 
 def reconstruct_scan(model_or_ckpt, images, poses, intrinsics, names, pairs, scales, output_folder=None, rescale=1, crop=None, num_frames=10,
                      glb=0.25, streams=3, write_depths=False, write=True, th=0.02, bgr=False, encode_batch=4, max_bytes=None,
-                     force_uncached=False, timings=None, clean=None):
+                     force_uncached=False, timings=None, clean=None, normals=None):
     """A scan to its fused point cloud without leaving the device between the stages: ``ScanSession.depths`` -> ``fusion.fuse_depth_maps`` (view i
     against ``pairs[i][:num_frames]``) -> ``fusion.point_cloud`` with the colours of ``fusion.color_grid``.  What ``inference_scan`` followed by
     ``fusion.fusion`` on the session's prepared images computes, without the PFM round trip, the host resize and the float64 numpy tail: same
@@ -374,7 +374,13 @@ def reconstruct_scan(model_or_ckpt, images, poses, intrinsics, names, pairs, sca
     that copy: {"method": "statistical", "k", "std_ratio", "max_dist"} (``remove_statistical_outliers``) or {"method": "radius", "radius",
     "min_neighbours"} (``remove_radius_outliers``).  ``xyz`` and ``rgb`` (and ``result.ply``) then hold the kept points in their fused order and
     the result gains "clean": {"n_in", "n_kept", and what the filter reports}; ``masks`` and ``depth_est`` stay as fused - a pixel whose point
-    was filtered keeps its mask bit.  None (the default): no filter, no such key."""
+    was filtered keeps its mask bit.  None (the default): no filter, no such key.
+
+    ``normals``: True, or {"k", "max_dist", "cell"} for ``cloud_eval.estimate_normals`` (ValueError for another key): a surface
+    normal for every point of the cloud as it leaves (after ``clean``), still on the device, turned towards the centre of the camera that
+    produced the point - the one piece of information that orients a normal without guessing.  The result gains "normals" (float32 [n, 3];
+    zeros where the neighbourhood has no plane) and "normal_info" ({"n_valid", "max_dist", "cell", "k"}), and ``result.ply`` carries nx ny nz.
+    None (the default): no normals, no such keys, the file as before."""
     from . import fusion as FU
     from .inference import write_pfm
     two_pass = isinstance(rescale, (tuple, list))
@@ -388,6 +394,9 @@ def reconstruct_scan(model_or_ckpt, images, poses, intrinsics, names, pairs, sca
         raise ValueError(f"reconstruct_scan: names, pairs and scales need one entry per image ({M})")
     if (write or write_depths) and output_folder is None:
         raise ValueError("reconstruct_scan: writing needs an output_folder")
+    if normals is not None:
+        from .cloud_eval import normals_options
+        normals = normals_options(normals)
     if isinstance(model_or_ckpt, torch.nn.Module):
         model = model_or_ckpt
     else:
@@ -438,15 +447,31 @@ def reconstruct_scan(model_or_ckpt, images, poses, intrinsics, names, pairs, sca
     masks, est, thre, hist = FU.fuse_depth_maps(depths, Ks, Es, fpairs, glb=glb)
     t["fuse_s"] = time.perf_counter() - tic
     tic = time.perf_counter()
-    xyz, rgb = FU.point_cloud(masks, est, Ks, Es, colors, [ref for ref, _ in fpairs])
-    cleaned = None
+    refs = [ref for ref, _ in fpairs]
+    if normals is None:
+        xyz, rgb = FU.point_cloud(masks, est, Ks, Es, colors, refs)
+    else:
+        xyz, rgb, view_base = FU.point_cloud(masks, est, Ks, Es, colors, refs, view_base=True)
+    cleaned, kept = None, None
     if clean is not None:
         from .cloud_eval import clean_cloud
         kept, cleaned = clean_cloud(xyz, clean)
         cleaned = {"n_in": int(xyz.shape[0]), **cleaned}
         xyz, rgb = xyz.index_select(0, kept), rgb.index_select(0, kept)
+    nrm_np, normal_info = None, None
+    if normals is not None:
+        from .cloud_eval import estimate_normals
+        # the view of a fused row: the last k with view_base[k] <= row (views without a point share their base with the next one)
+        rows = kept if kept is not None else torch.arange(int(xyz.shape[0]), device=dev)
+        slot = torch.searchsorted(view_base, rows, right=True) - 1
+        centres = FU.cloud_cams(Ks, Es)[:, [12, 16, 20]].float()[refs].to(dev)      # inv(E)[:3, 3] of every emitted view
+        normal_info = {}
+        nrm, _ = estimate_normals(xyz, viewpoints=centres.index_select(0, slot), info=normal_info, **normals)
+        nrm_np = nrm.cpu().numpy()
     xyz_np, rgb_np, masks_np, est_np = xyz.cpu().numpy(), rgb.cpu().numpy(), masks.cpu().numpy().astype(bool), est.cpu().numpy()
     t["d2h_bytes"] = int(xyz.numel() * 4 + rgb.numel() + masks.numel() + est.numel() * 4) + sum(int(a.nbytes) for a in stacks_np)
+    if nrm_np is not None:
+        t["d2h_bytes"] += int(nrm_np.nbytes)
     if write or write_depths:
         output_folder = Path(output_folder)
         output_folder.mkdir(exist_ok=True, parents=True)
@@ -456,10 +481,12 @@ def reconstruct_scan(model_or_ckpt, images, poses, intrinsics, names, pairs, sca
             for i in range(M):
                 write_pfm(output_folder / "depths" / f"{names[i]}_scale{s}_nf{num_frames}.pfm", stacks_np[k][i])
     if write:
-        _write_masks(output_folder, masks_np, [ref for ref, _ in fpairs])
-        FU.write_ply(str(output_folder / "result.ply"), xyz_np, rgb_np)
+        _write_masks(output_folder, masks_np, refs)
+        FU.write_ply(str(output_folder / "result.ply"), xyz_np, rgb_np, normals=nrm_np)
     t["tail_s"] = time.perf_counter() - tic
     out = {"masks": masks_np, "depth_est": est_np, "xyz": xyz_np, "rgb": rgb_np, "threshold": thre, "history": hist}
     if cleaned is not None:
         out["clean"] = cleaned
+    if nrm_np is not None:
+        out["normals"], out["normal_info"] = nrm_np, normal_info
     return out

@@ -647,6 +647,27 @@ int cer_grid_count_within_f32(const void* records, long n, const long long* cell
                               const double* origin, double cell, const float* queries, const long long* qorder, long m, float radius,
                               int* count, void* stream);
 
+/* Surface normals on the same grid (ABI 1150; cer-mvs_amd/cloud_eval.py CloudIndex.normals / estimate_normals): the plane through
+ * the k nearest neighbours of every query, by the eigenvectors of their covariance.  The argument head, the sizes, the errors and their order
+ * are cer_grid_knn_f32's; points (the array the index was packed from: a record's fourth word indexes it) joins count among the pointers
+ * that may not be NULL (CER_EINVAL); viewpoints, normal, curvature and mom may each be NULL.  No atomics, no LDS; every output element is
+ * written exactly once; the same bytes on every run.  Every check runs before any launch.
+ *
+ *   Neighbours: exactly the c = count[q] entries cer_grid_knn_f32 lists for (queries, k, max_dist), in its ascending (d2, index) order; a query
+ *     that is an indexed point is among its own neighbours.  Their coordinates are read from points by original index.
+ *   Moments, fp64, no contraction, about the query: d_j = double(p_j) - double(q) per axis; S1 = ((d_0 + d_1) + ...) (3 sums), S2_ab the same
+ *     over d_a * d_b for ab = xx, xy, xz, yy, yz, zz (6 sums).  mom[q] ([m, 9] doubles) = S1 then S2 in that order; zeros for c = 0.
+ *   mean = S1 / c, C_ab = S2_ab / c - mean_a * mean_b; the eigenvalues l0 <= l1 <= l2 and eigenvectors of C by cyclic Jacobi in fp64.
+ *   A query is VALID iff it is finite, c >= 3, l2 > 0 and l1 > 1e-12 * l2 (the last excludes a collinear neighbourhood).  Valid: normal[q]
+ *     ([m, 3] floats) = the unit eigenvector of l0, rounded once from fp64; curvature[q] = float(max(l0, 0) / ((l0 + l1) + l2)), the surface
+ *     variation.  Invalid: normal (0, 0, 0), curvature NaN.
+ *   Sign: canonically the component of largest magnitude is positive (the lowest axis on a tie).  With viewpoints ([m, 3] floats, one per
+ *     query): v = double(viewpoint) - double(q), s = (n_x * v_x + n_y * v_y) + n_z * v_z with n the fp64 eigenvector in canonical sign; the
+ *     normal is negated iff s < 0.  A viewpoint with a non-finite coordinate leaves the canonical sign. */
+int cer_grid_normals_f32(const void* records, long n, const long long* cell_keys, const long long* cell_start, long ncells, const double* origin,
+                         double cell, const float* queries, const long long* qorder, long m, int k, float max_dist, const float* points,
+                         const float* viewpoints, float* normal, float* curvature, int* count, double* mom, void* stream);
+
 /* Rigid registration of two clouds (ABI 1130; csrc/cloud_align.hip, cer-mvs_amd/cloud_eval.py rigid_transform / pair_moments / icp, DESIGN.md
  * 3w): what point-to-point ICP needs beside cer_grid_nearest_f32.  fp64 arithmetic on float32 coordinates with every association fixed, no
  * atomics, grids and summation trees that depend on the sizes alone: the same bits on every run and every machine.  Sizes and errors as
