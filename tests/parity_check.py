@@ -5,7 +5,9 @@ float64 pieces and tile geometries further down), by tests/test_train_parity_{cp
 tests/test_postproc_parity_{cpu,gpu}.py (the last section: geometric consistency as a float64 chain that carries, next to every value, a
 bound on what a correct fp32 evaluation may deviate by - ``geo_ref64`` / ``check_geo`` / ``GeoReport``: every element is inside its
 bound, decided equal or provably undecidable; the image preparation from torch's fp32 taps - ``prep_ref64`` / ``check_prep``; the bit
-comparison of the multires kernels - ``bits_equal``).  Plain module, no fixtures.
+comparison of the multires kernels - ``bits_equal``), and by tests/test_wide_parity_{cpu,gpu}.py (the wide-range loop: the float64 pieces
+of one GRU iteration, which tests/test_fullsize_parity_gpu.py shares, the ``wide_*`` references and bounds, the split32 layout in numpy).
+Plain module, no fixtures.
 
 Conventions: an image tensor is pixel-major, ``[h*w, C]`` or ``[h*w]``; a *tile* is a (rows, columns) block of pixels - 8 x 16 by
 default, the smallest tile the s16 convolutions launch (16 x 16 for the tall ones); a *seam* is the border between two 32-pixel
@@ -13,6 +15,7 @@ segments of the epipolar-line kernel (csrc/cost_lines.hip: tiles of 32 pixels al
 import math
 
 import torch
+import torch.nn.functional as F
 
 F16_NAN_BITS = 0x7E00        # a quiet f16 NaN: what the sentinel puts into every half of a frag16 / split32 plane
 
@@ -1098,3 +1101,207 @@ def bits_equal(got, want):
     np = _np()
     g, w = np.ascontiguousarray(got, dtype=np.float32), np.ascontiguousarray(want, dtype=np.float32)
     return (g.view(np.int32) == w.view(np.int32)) | (np.isnan(g) & np.isnan(w))
+
+
+# ------------------------------------------------------------------------------------------------ update-loop launches in float64
+# The pure float64 pieces of one GRU iteration, shared by tests/test_fullsize_parity_gpu.py (the s16 loop) and
+# tests/test_wide_parity_{cpu,gpu}.py (the wide-range loop): pixel-major [P, C] in and out.
+def nchw(x, h, w):
+    """[P, C] -> [1, C, h, w]"""
+    return x.t().reshape(1, x.shape[1], h, w)
+
+
+def plain(x):
+    """[1, C, h, w] -> [P, C]"""
+    return x[0].permute(1, 2, 0).reshape(-1, x.shape[1])
+
+
+def conv64(x, wt, h, w):
+    """3 x 3, padding 1, float64, pixel-major in and out."""
+    return plain(F.conv2d(nchw(x, h, w), wt.double(), None, padding=1))
+
+
+def conv_ref(x, xmag, wt, bias, h, w, record_as=None, yardstick=None):
+    """-> (conv(x, w) + bias, conv(xmag, |w|) + |bias|) in float64.  When recording (``yardstick``: a dict, ``record_as``: the key): also
+    the reference-only yardstick - the same convolution in float32 on the CPU against the float64 result, normalised like the kernels'
+    errors."""
+    ref = conv64(x, wt, h, w)
+    mag = conv64(xmag, wt.abs(), h, w)
+    if bias is not None:
+        ref, mag = ref + bias.double(), mag + bias.double().abs()
+    if record_as and yardstick is not None:
+        y32 = plain(F.conv2d(nchw(x, h, w).float(), wt.float(), None, padding=1)).double()
+        if bias is not None:
+            y32 = y32 + bias.double()
+        yardstick[record_as] = float(((y32 - ref).abs() / mag.clamp_min(1e-300)).max())
+    return ref, mag
+
+
+def disp_feature_parts(disp, h, w):
+    """disp [P] float64 -> (100 * (unfold7x7(d) - d) [P, 49], 100 * (unfold7x7|d| + |d|) [P, 49]): core/update.py:80-85,97 and the
+    magnitude of the two parts the collapsed form sums separately."""
+    d = disp.reshape(1, 1, h, w)
+    u = F.unfold(d, [7, 7], padding=3).view(1, 49, h, w)
+    ua = F.unfold(d.abs(), [7, 7], padding=3).view(1, 49, h, w)
+    return plain(100 * (u - d)), plain(100 * (ua + d.abs()))
+
+
+def wsum(wt):
+    """sum |w| over a conv's taps and input channels, per output channel: [1, Cout]"""
+    return wt.double().abs().sum((1, 2, 3))[None]
+
+
+def delta_sum64(T, bias, disp, h, w):
+    """T [nhalf, 9, P], disp [P] float64 -> (disp + 0.01 * (bias + sum of the taps at the neighbours, zero outside), its magnitude)."""
+    nh = T.shape[0]
+    img = F.pad(T.reshape(nh, 9, h, w), (1, 1, 1, 1))
+    s = torch.zeros(h, w, dtype=torch.float64)
+    sa = torch.zeros(h, w, dtype=torch.float64)
+    for tap in range(9):
+        dy, dx = tap // 3, tap % 3                     # (padded coordinates: y + dy - 1 + 1)
+        s += img[:, tap, dy:dy + h, dx:dx + w].sum(0)
+        sa += img[:, tap, dy:dy + h, dx:dx + w].abs().sum(0)
+    return disp + 0.01 * (s.reshape(-1) + bias), 0.01 * (sa.reshape(-1) + abs(bias)) + disp.abs()
+
+
+def lookup_ref(vol, origin, disp, w0t, b0, D, incre, L=3, r=5):
+    """vol [P, >=D] level-0 rows, origin, disp [P], w0t [33, 64], b0 [64], all float64 (the fp32 values the kernel read) ->
+    (relu(conv1x1(lookup)), c-scaled magnitude, absolute term of the fp32 index arithmetic): core/corr.py:94-143, core/update.py:61-64."""
+    from oracle import cer_oracle as O
+    P = vol.shape[0]
+    levels = O.pyramid(vol[None, :, :D], L)
+    feats = O.lookup(levels, origin.view(1, P), disp.view(1, P), D, incre, r).reshape(L * (2 * r + 1), P).t()      # [P, 33]
+    ref = torch.relu(feats @ w0t + b0)
+    mag = feats.abs() @ w0t.abs() + b0.abs()
+    t = (disp - origin) / incre
+    dt = 4 * 2.0 ** -24 * (t.abs() + D / 2)
+    idx = torch.zeros(P, w0t.shape[1], dtype=torch.float64)
+    for l, lv in enumerate(levels):
+        row = F.pad(lv[0], (1, 1))
+        step = (row[:, 1:] - row[:, :-1]).abs().max(1).values                     # largest |v[i+1] - v[i]| of the row, zero border included
+        idx += (dt / 2 ** l * step)[:, None] * w0t[l * (2 * r + 1):(l + 1) * (2 * r + 1)].abs().sum(0)[None]
+    return ref, mag, idx
+
+
+# ------------------------------------------------------------------------------------------------ the wide-range loop (_WideLoop)
+# References and bounds of the launches of ``_WideLoop.step`` (cer-mvs_amd/update.py: csrc/gru_f16x3.hip, csrc/gru.hip), shared by
+# tests/test_wide_parity_gpu.py (the kernels) and tests/test_wide_parity_cpu.py (an fp32 emulation with planted corruptions).  Every
+# ``wide_*`` function returns (ref, mag, abs_term) for ``check_elementwise(got, ref, mag, WIDE_C, abs_term)``: no constant is fitted.
+WIDE_C = 2e-6                # per-element constant of an f16x3 / fp32-MFMA dot: tests/test_hip_parity.py::test_conv3x3_f16x3_dynamic_range
+WIDE_ABS = 3e-11             # its absolute companion, per unit of sum|w| (the f16 subnormal step of the scaled lo half), same test
+WIDE_ACT_ABS = 2.0 ** -20    # sigmoid / tanh / exp of the device library, as in the s16 loop's bounds
+WIDE_TILE = (4, 32)          # pixel tile of cer_conv3x3_f16x3 (HX_TH x HX_TW)
+WIDE_TILE_F32 = (8, 16)      # pixel tile of cer_conv3x3_f32 (CV_TH x CV_TW)
+DT_STRIP = 16                # pixels of a cer_delta_tail_f32 strip (one wave); a block holds 4 strips
+C_DSUM = 22 * 2.0 ** -24     # delta_sum: an 18-term fp32 sum, one product, two sums (tests/test_fullsize_parity_gpu.py)
+
+
+def split32_np(x):
+    """The split32 layout (include/cer_mvs.h; csrc/gru_f16x3.hip: hx_store_split8 / cer_split2) restated in numpy: fp32 [P, C], C % 32
+    == 0 -> fp32 [P, C] whose bytes are, per pixel and 32-channel chunk, 32 f16 hi halves | 32 f16 lo halves with hi = f16(clamp(x,
+    +-65504)) and lo = f16((clamp(x) - hi) * 2^11), both conversions round-to-nearest-even."""
+    np = _np()
+    x = np.clip(np.ascontiguousarray(x, dtype=np.float32), np.float32(-65504.0), np.float32(65504.0))
+    P, C = x.shape
+    assert C % 32 == 0
+    hi = x.astype(np.float16)
+    lo = ((x - hi.astype(np.float32)) * np.float32(2048.0)).astype(np.float16)
+    halves = np.concatenate([hi.reshape(P, C // 32, 32), lo.reshape(P, C // 32, 32)], 2)
+    return np.ascontiguousarray(halves).reshape(P, 2 * C).view(np.float32)
+
+
+def split32_inverse_np(s):
+    """split32 [P, C] -> fp32 [P, C]: hi + 2^-11 lo (hx_load_split8; the product is exact, so the fused form rounds once like this one)."""
+    np = _np()
+    s = np.ascontiguousarray(s, dtype=np.float32)
+    P, C = s.shape
+    halves = s.view(np.float16).reshape(P, C // 32, 64).astype(np.float32)
+    return (halves[:, :, 32:] * np.float32(1.0 / 2048.0) + halves[:, :, :32]).reshape(P, C)
+
+
+def split32_quantum(ref):
+    """What storing ``ref`` in the split32 layout may move it by: hi is f16(x), lo is f16 of the residual times 2^11 - the residual is
+    below 2^-11 |x| and keeps 11 bits, so its last bit is 2^-22 |x|; below the f16 normal range the lo half steps by 2^-24, i.e. 2^-35 of x."""
+    return 2.0 ** -22 * ref.abs() + 2.0 ** -35
+
+
+def wide_interior_tiles(h, w, tile=WIDE_TILE):
+    """[tiles_y, tiles_x] bool: the tiles of cer_conv3x3_f16x3 that evaluate a disparity source in the collapsed 81-tap form
+    (conv3x3_f16x3_kernel: ``coll``) - every pixel of the tile has its 3 x 3 neighbourhood inside the image, which also excludes the
+    first tile row and column."""
+    th, tw = tile
+    ty0 = torch.arange((h + th - 1) // th) * th
+    tx0 = torch.arange((w + tw - 1) // tw) * tw
+    return ((ty0 >= 1) & (ty0 + th <= h - 1))[:, None] & ((tx0 >= 1) & (tx0 + tw <= w - 1))[None, :]
+
+
+def wide_conv_parts(x, xmag, wt, bias, h, w, init=None):
+    """Pre-activation of one conv launch of the wide loop -> (pre, mag, abs) with |kernel - pre| <= WIDE_C * mag + abs: ``conv_ref`` on
+    the sources (the disparity source enters ``xmag`` through ``disp_feature_parts``), the accumulator seed ``init`` [P, Cout] added with
+    its own magnitude, abs = WIDE_ABS * sum|w| over the taps inside the image."""
+    pre, mag = conv_ref(x, xmag, wt, bias, h, w)
+    if init is not None:
+        pre, mag = pre + init, mag + init.abs()
+    return pre, mag, WIDE_ABS * conv64(torch.ones_like(x), wt.abs(), h, w)
+
+
+def wide_relu_parts(pre, mag, abs_t, split):
+    ref = torch.relu(pre)
+    return ref, mag, abs_t + (split32_quantum(ref) if split else 0.0)
+
+
+def wide_gates_parts(pre, mag, abs_t, hprev, split):
+    """GATES epilogue -> ((z parts), (r*h parts)).  sigmoid is Lipschitz 1/4 (<= 1 is used), + WIDE_ACT_ABS for the device exp / rcp;
+    r*h: that bound times |h| (``hprev``: the value the kernel read, exact), one rounding of the product, the split32 quantum."""
+    half = pre.shape[1] // 2
+    z = torch.sigmoid(pre[:, :half])
+    rh = torch.sigmoid(pre[:, half:]) * hprev
+    za = abs_t[:, :half] + WIDE_ACT_ABS
+    ra = (abs_t[:, half:] + WIDE_ACT_ABS) * hprev.abs() + 2.0 ** -24 * rh.abs() + (split32_quantum(rh) if split else 0.0)
+    return (z, mag[:, :half], za), (rh, mag[:, half:] * hprev.abs(), ra)
+
+
+def wide_gru_parts(pre, mag, abs_t, z, hprev, split):
+    """GRU epilogue: (1 - z) h + z tanh(pre) with the z and the PREVIOUS hidden state the kernel read.  tanh is Lipschitz 1: |z| *
+    (pre-activation bound + WIDE_ACT_ABS); the blend's four roundings (1 - z, two products, one sum) at 2^-24 of |h| + |z|."""
+    ref = (1 - z) * hprev + z * torch.tanh(pre)
+    a = z.abs() * (abs_t + WIDE_ACT_ABS) + 4 * 2.0 ** -24 * (hprev.abs() + z.abs()) + (split32_quantum(ref) if split else 0.0)
+    return ref, mag * z.abs(), a
+
+
+def wide_delta_parts(pre, mag, abs_t, w2):
+    """Fused delta head (EPI_DELTA): hid = relu(pre) is split to hi|lo f16 in LDS (hx_split: the split32 quantum) and projected with the
+    256 -> 1 conv's weights per channel half and tap, ``w2`` [1, C, 3, 3] -> tap planes [P, nhalf * 9] (column = half * 9 + tap).  The
+    hidden map's bound is projected with |w2|; the projection's own f16x3 products add WIDE_C * sum_c |w2| |hid|."""
+    hid = torch.relu(pre)
+    hb = WIDE_C * mag + abs_t + split32_quantum(hid)
+    C = hid.shape[1]
+    nhalf = C // 128
+    proj = w2.double()[0].reshape(nhalf, 128, 9)                                  # [half, channel, tap]
+    cols = lambda t, p: torch.cat([t[:, hf * 128:(hf + 1) * 128] @ p[hf] for hf in range(nhalf)], 1)
+    return cols(hid, proj), cols(hid, proj.abs()), cols(hb, proj.abs())
+
+
+def delta_tail_depth(C):
+    """Roundings on the longest path of one cer_delta_tail_f32 output sum (csrc/gru.hip: delta_tail_kernel).  A lane owns 4 channels of
+    every 256: per source column and kx it runs ONE fma chain over its C / 256 quads and the three ky taps - 12 * C / 256 fmas, one
+    rounding each; the rolling accumulators add two of those chains' results (accA + c1, accB + c2): 2; cer_row16_sum is four DPP add
+    levels (quad, quad, half-row mirror, row mirror): 4; the two cross-row shuffles: 2.  n = 12 * C / 256 + 8.  (The issue's count of
+    + 12 took the 16-lane sum as eight levels; this one is tighter and is what the tests apply.)"""
+    return 12 * (C // 256) + 8
+
+
+def delta_tail_ref64(hid, w_tap_c, bias, disp, h, w):
+    """cer_delta_tail_f32 in float64 from the values it read: hid [P, C], w_tap_c [9, C] (tap = ky * 3 + kx), disp [P] ->
+    ((disp_out ref, mag, abs), (delta ref, mag, abs)) for a check at c = 3 * 2^-24 (disp_out) / 2 * 2^-24 (delta).  s = 3 x 3 conv (zero padding), S = the same on absolute values.  The kernel's sum
+    deviates by at most gamma_n S with n = ``delta_tail_depth``; then fl(fl(0.01f * fl(s + bias)) + disp): three roundings, each of a
+    value <= 0.01f (S + |bias|) + |disp| (two for the delta output, which has no last sum).  0.01f is the fp32 constant."""
+    C = hid.shape[1]
+    wt = w_tap_c.double().reshape(3, 3, C).permute(2, 0, 1)[None]                  # [1, C, 3, 3]
+    s, S = conv64(hid, wt, h, w)[:, 0], conv64(hid.abs(), wt.abs(), h, w)[:, 0]
+    c01 = float(torch.tensor(0.01, dtype=torch.float32))
+    n = delta_tail_depth(C)
+    gam = n * U24 / (1 - n * U24)
+    dl = c01 * (s + bias)
+    dmag = c01 * (S + abs(bias))
+    return (disp + dl, dmag + disp.abs(), c01 * gam * S), (dl, dmag, c01 * gam * S)

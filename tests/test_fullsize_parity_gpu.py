@@ -36,6 +36,7 @@ bound at 51 x 400), hoisted 4.5e-6, q 2.3e-6, z|r 7.0e-7, delta head 2.3e-7; FP6
 convolution against float64 on the same inputs: 2.1e-7 - the project's constants hold at 1593-term dots, none was replaced.  delta_sum 1.1e-7,
 lookup <= 0.17 of its bound.  Cost volume, |err| / norm, stage 0 / 1: kernel max 4.4e-5 / 3.6e-5, p99.9 8.2e-6 / 7.7e-6; fp32 oracle max
 3.9e-5 / 4.0e-5, p99.9 7.9e-6 / 7.4e-6.  540 x 960 runs the default fp8 form only (48 s of the module's 157 s, nearly all float64 references)."""
+import functools
 import json
 import math
 import os
@@ -43,10 +44,11 @@ import time
 
 import pytest
 import torch
-import torch.nn.functional as F
 
 from conftest import REPO, cached_scene
-from parity_check import assert_covered, assert_elementwise, check_elementwise, cost_subset, cost_volume_ref64, poison_f16, poison_f32
+import parity_check
+from parity_check import (assert_covered, assert_elementwise, check_elementwise, cost_subset, cost_volume_ref64, delta_sum64,
+                          disp_feature_parts, lookup_ref, poison_f16, poison_f32, wsum)
 from test_oracle_golden import hashed
 
 pytestmark = pytest.mark.gpu
@@ -60,6 +62,9 @@ CASES = [(296, 400, "f16x3terms"), (296, 400, "fp8corr"), (296, 400, "fp6corr"),
 STAGES = ((64, 0.0025 / 64), (44, 0.0025 / 320))       # (D, incre) of the bench cascade (64, 64, T), (-1, 320, T)
 CASCADE = [(64, 64, 16), (-1, 320, 16)]
 RECORD = {}                                            # figures for profiles/fullsize_parity.json (written only with CER_PARITY_RECORD)
+# the float64 convolution of tests/parity_check.py; when recording it also leaves the fp32-CPU yardstick of every call in RECORD
+conv_ref = functools.partial(parity_check.conv_ref, yardstick=RECORD.setdefault("yardstick_conv_fp32_cpu", {})
+                             if os.environ.get("CER_PARITY_RECORD") else None)
 
 
 @pytest.fixture(scope="module")
@@ -119,82 +124,6 @@ def frag_poisoned_padding(x, h, w, log2s):
     from cer_mvs_amd import ops
     buf = poison_f16(torch.empty(ops.s16_pixels(h, w), x.shape[1], device=x.device, dtype=torch.float32))
     return ops.to_frag16(x, h, w, log2s, out=buf)
-
-
-def nchw(x, h, w):
-    """[P, C] -> [1, C, h, w]"""
-    return x.t().reshape(1, x.shape[1], h, w)
-
-
-def plain(x):
-    """[1, C, h, w] -> [P, C]"""
-    return x[0].permute(1, 2, 0).reshape(-1, x.shape[1])
-
-
-def conv64(x, wt, h, w):
-    """3 x 3, padding 1, float64, pixel-major in and out."""
-    return plain(F.conv2d(nchw(x, h, w), wt.double(), None, padding=1))
-
-
-def conv_ref(x, xmag, wt, bias, h, w, record_as=None):
-    """-> (conv(x, w) + bias, conv(xmag, |w|) + |bias|) in float64.  When recording: also the reference-only yardstick - the same
-    convolution in float32 on the CPU against the float64 result, normalised like the kernels' errors."""
-    ref = conv64(x, wt, h, w)
-    mag = conv64(xmag, wt.abs(), h, w)
-    if bias is not None:
-        ref, mag = ref + bias.double(), mag + bias.double().abs()
-    if record_as and os.environ.get("CER_PARITY_RECORD"):
-        y32 = plain(F.conv2d(nchw(x, h, w).float(), wt.float(), None, padding=1)).double()
-        if bias is not None:
-            y32 = y32 + bias.double()
-        RECORD.setdefault("yardstick_conv_fp32_cpu", {})[record_as] = float(((y32 - ref).abs() / mag.clamp_min(1e-300)).max())
-    return ref, mag
-
-
-def disp_feature_parts(disp, h, w):
-    """disp [P] float64 -> (100 * (unfold7x7(d) - d) [P, 49], 100 * (unfold7x7|d| + |d|) [P, 49]): core/update.py:80-85,97 and the
-    magnitude of the two parts the collapsed form sums separately."""
-    d = disp.reshape(1, 1, h, w)
-    u = F.unfold(d, [7, 7], padding=3).view(1, 49, h, w)
-    ua = F.unfold(d.abs(), [7, 7], padding=3).view(1, 49, h, w)
-    return plain(100 * (u - d)), plain(100 * (ua + d.abs()))
-
-
-def wsum(wt):
-    """sum |w| over a conv's taps and input channels, per output channel: [1, Cout]"""
-    return wt.double().abs().sum((1, 2, 3))[None]
-
-
-def delta_sum64(T, bias, disp, h, w):
-    """T [nhalf, 9, P], disp [P] float64 -> (disp + 0.01 * (bias + sum of the taps at the neighbours, zero outside), its magnitude)."""
-    nh = T.shape[0]
-    img = F.pad(T.reshape(nh, 9, h, w), (1, 1, 1, 1))
-    s = torch.zeros(h, w, dtype=torch.float64)
-    sa = torch.zeros(h, w, dtype=torch.float64)
-    for tap in range(9):
-        dy, dx = tap // 3, tap % 3                     # (padded coordinates: y + dy - 1 + 1)
-        s += img[:, tap, dy:dy + h, dx:dx + w].sum(0)
-        sa += img[:, tap, dy:dy + h, dx:dx + w].abs().sum(0)
-    return disp + 0.01 * (s.reshape(-1) + bias), 0.01 * (sa.reshape(-1) + abs(bias)) + disp.abs()
-
-
-def lookup_ref(vol, origin, disp, w0t, b0, D, incre, L=3, r=5):
-    """vol [P, >=D] level-0 rows, origin, disp [P], w0t [33, 64], b0 [64], all float64 (the fp32 values the kernel read) ->
-    (relu(conv1x1(lookup)), c-scaled magnitude, absolute term of the fp32 index arithmetic): core/corr.py:94-143, core/update.py:61-64."""
-    from oracle import cer_oracle as O
-    P = vol.shape[0]
-    levels = O.pyramid(vol[None, :, :D], L)
-    feats = O.lookup(levels, origin.view(1, P), disp.view(1, P), D, incre, r).reshape(L * (2 * r + 1), P).t()      # [P, 33]
-    ref = torch.relu(feats @ w0t + b0)
-    mag = feats.abs() @ w0t.abs() + b0.abs()
-    t = (disp - origin) / incre
-    dt = 4 * 2.0 ** -24 * (t.abs() + D / 2)
-    idx = torch.zeros(P, w0t.shape[1], dtype=torch.float64)
-    for l, lv in enumerate(levels):
-        row = F.pad(lv[0], (1, 1))
-        step = (row[:, 1:] - row[:, :-1]).abs().max(1).values                     # largest |v[i+1] - v[i]| of the row, zero border included
-        idx += (dt / 2 ** l * step)[:, None] * w0t[l * (2 * r + 1):(l + 1) * (2 * r + 1)].abs().sum(0)[None]
-    return ref, mag, idx
 
 
 # ------------------------------------------------------------------------------------------------ the production tile choice, restated
