@@ -7,6 +7,8 @@ bound on what a correct fp32 evaluation may deviate by - ``geo_ref64`` / ``check
 bound, decided equal or provably undecidable; the image preparation from torch's fp32 taps - ``prep_ref64`` / ``check_prep``; the bit
 comparison of the multires kernels - ``bits_equal``), and by tests/test_wide_parity_{cpu,gpu}.py (the wide-range loop: the float64 pieces
 of one GRU iteration, which tests/test_fullsize_parity_gpu.py shares, the ``wide_*`` references and bounds, the split32 layout in numpy).
+The last section - the cost volume from restated fp32 coordinates (``fma32``, ``cost_coords32``, ``cost_samples_ref64``, ``cost_rows_ref64``,
+``cost_bound``) - serves tests/test_cost_geometry_{cpu,gpu}.py.
 Plain module, no fixtures.
 
 Conventions: an image tensor is pixel-major, ``[h*w, C]`` or ``[h*w]``; a *tile* is a (rows, columns) block of pixels - 8 x 16 by
@@ -1305,3 +1307,227 @@ def delta_tail_ref64(hid, w_tap_c, bias, disp, h, w):
     dl = c01 * (s + bias)
     dmag = c01 * (S + abs(bias))
     return (disp + dl, dmag + disp.abs(), c01 * gam * S), (dl, dmag, c01 * gam * S)
+
+
+# ------------------------------------------------------------------------------------------------ cost volume from restated fp32 coordinates
+# The projection of both cost-volume builders (csrc/cost_build.hip:41-43, 69-79; ClLane::project / cl_lane_ray of csrc/cost_lines.hip) is
+# written in fully specified fp32 operations - __fmul_rn, __fadd_rn, fmaf, two IEEE divisions, -ffp-contract=off - so it can be restated
+# bit for bit in numpy float32 from the reference's definition (core/corr.py:56-65, utils/projective_ops.py:26-28) as a third
+# implementation that shares no code with either kernel.  With the cell and the two fractions of every sample known exactly, what is left
+# to a kernel is the rounding of the 64-channel dot, the four bilinear weights and the view sum: ``cost_bound``.
+def fma32(a, b, c):
+    """round_to_float32(a * b + c) with ONE rounding, on numpy arrays (this Python has no math.fma).  The product of two float32 is exact
+    in float64 (48 significant bits); s = fl64(p + c) and TwoSum's residual e = (p + c) - s are exact.  s is the double nearest the true
+    sum t, so t lies strictly on the same side of every double as s does - unless s IS that double: rounding s to float32 therefore equals
+    rounding t, except where s sits exactly on a float32 tie (the midpoint of two neighbouring float32, a double) while t does not
+    (e != 0); there the sign of e decides.  A double rounding is then impossible.  Proved against fractions.Fraction in
+    tests/test_cost_geometry_cpu.py."""
+    import numpy as np
+    a, b, c = np.broadcast_arrays(np.asarray(a, dtype=np.float32), np.asarray(b, dtype=np.float32), np.asarray(c, dtype=np.float32))
+    with np.errstate(all="ignore"):
+        p = a.astype(np.float64) * b.astype(np.float64)
+        c64 = c.astype(np.float64)
+        s = p + c64
+        bb = s - p
+        e = (p - (s - bb)) + (c64 - bb)
+        r = s.astype(np.float32)
+        r64 = r.astype(np.float64)
+        d = s - r64                                                           # exact: s and r agree in their leading bits
+        other = np.nextafter(r, np.where(d > 0, np.float32(np.inf), np.float32(-np.inf)).astype(np.float32))
+        tie = (d != 0) & np.isfinite(s) & np.isfinite(other) & ((s - r64) == (other.astype(np.float64) - s))
+        fix = tie & (e != 0)
+        r = np.where(fix, np.where(e > 0, np.maximum(r, other), np.minimum(r, other)), r)
+    return r.astype(np.float32)
+
+
+def cost_coords32(Pij, D, incre, disp_in, shift, h, w, y0=0):
+    """The source coordinates of every (view, pixel, hypothesis) of an h x w reference grid whose first image row is ``y0``, in numpy
+    float32, operation for operation as the kernels and the reference form them:
+      origin = disp_in, raised to lim = fl32((D // 2) * incre) under ``shift`` (core/corr.py:59-62) - equal to O.hypothesis_origin;
+      hyp = fl(fl((k - D // 2) * fl32(incre)) + origin);
+      a = fl(fma(m1, py, fl(m0 * px)) + m2), X = fma(m3, hyp, a), likewise Y (m4..m7) and Z (m8..m11), px = x, py = y + y0;
+      u = X / Z, t = Y / Z (IEEE), ok = u == u and t == t, then both clamped to +-1e4 (fmaxf / fminf: a NaN becomes -1e4).
+    Pij [V, 4, 4]; disp_in [h * w].  -> dict of numpy arrays: ok [V, P, D] bool; iu, iw int32 = floor(u), floor(t) (NOT clamped to the
+    map: a texel outside the map is zero, which is what the kernels' clamp into the zero border computes; -2 where not ok); du, dw float32
+    = u - floor(u), t - floor(t) (0 where not ok; the float32 difference, which can round to 1.0 just below an integer, as on the device);
+    u, t (clamped), Z [V, P, D] float32; hyp [P, D]; origin [P]."""
+    import numpy as np
+    f32 = np.float32
+    m = np.asarray(torch.as_tensor(Pij).detach().cpu().numpy(), dtype=f32).reshape(-1, 16)
+    V, P = m.shape[0], h * w
+    origin = np.asarray(torch.as_tensor(disp_in).detach().cpu().numpy(), dtype=f32).reshape(-1).copy()
+    assert origin.size == P
+    if shift:
+        lim = f32((D // 2) * float(incre))
+        origin = np.where(origin < lim, lim, origin).astype(f32)
+    k = (np.arange(D) - D // 2).astype(f32)
+    hyp = ((k * f32(incre)).astype(f32)[None, :] + origin[:, None]).astype(f32)
+    px, py = (np.arange(P) % w).astype(f32), (np.arange(P) // w + y0).astype(f32)
+    out = {key: np.empty((V, P, D), dtype=dt) for key, dt in (("ok", bool), ("iu", np.int32), ("iw", np.int32), ("du", f32), ("dw", f32),
+                                                               ("u", f32), ("t", f32), ("Z", f32))}
+    with np.errstate(all="ignore"):
+        for v in range(V):
+            def ray(r):
+                a = (fma32(m[v, 4 * r + 1], py, (m[v, 4 * r] * px).astype(f32)) + m[v, 4 * r + 2]).astype(f32)
+                return fma32(m[v, 4 * r + 3], hyp, a[:, None])
+            X, Y, Z = ray(0), ray(1), ray(2)
+            u, t = (X / Z).astype(f32), (Y / Z).astype(f32)
+            ok = ~np.isnan(u) & ~np.isnan(t)
+            u = np.fmin(np.fmax(u, f32(-1e4)), f32(1e4))
+            t = np.fmin(np.fmax(t, f32(-1e4)), f32(1e4))
+            fu, ft = np.floor(u), np.floor(t)
+            out["ok"][v], out["u"][v], out["t"][v], out["Z"][v] = ok, u, t, Z
+            out["du"][v], out["dw"][v] = np.where(ok, (u - fu).astype(f32), f32(0)), np.where(ok, (t - ft).astype(f32), f32(0))
+            out["iu"][v], out["iw"][v] = np.where(ok, fu.astype(np.int32), -2), np.where(ok, ft.astype(np.int32), -2)
+    out["hyp"], out["origin"] = hyp, origin
+    return out
+
+
+CORNERS = ((0, 0), (0, 1), (1, 0), (1, 1))                                    # (dy, dx) of a sample's four texels, in the order of ``dots``
+
+
+def cost_f2_two_term(f2):
+    """The two-term form's definition of a source row (tests/test_hip_parity.py::test_cost_lines_two_term_form): the kernel's operand is
+    x * 2^6 split into f16 hi | lo, and the two-term form reads hi only."""
+    return (f2.float() * 64.0).clamp(-65504.0, 65504.0).half().float() / 64.0
+
+
+def cost_samples_ref64(f1, f2, coords, f2_round=None, views=None, chunk=1024):
+    """The float64 value of every sample from the restated cells and fractions.  f1 [P, C]: the reference rows of the pixel grid of
+    ``coords`` (as the kernels read them: fmaps / 8); f2 [V, h2, w2, C]: the source maps WITHOUT border (the size of the source map is
+    theirs: a row slab's ``src_hw``); views: which source map each view of ``coords`` reads (default 0 .. V - 1: the ``slots``
+    indirection is the caller's business - the reference is told what the kernel should have read).  The four weights are formed from the
+    fp32 fractions in float64, (1 - du)(1 - dw) etc., exactly; a texel outside the source map is zero; a not-ok sample is zero.
+    ``f2_round``: applied to the source maps first (``cost_f2_two_term``).
+    -> dict of [V, P, D] float64 tensors: val; norm = sum_c |f1_c| * (bilinear-weighted |f2_c|), the convention of ``cost_volume_ref64``;
+    l1 = sum_c |f1_c| + bilinear-weighted sum_c |f2_c| (what the absolute term of ``cost_bound`` scales with); and dots [V, P, D, 4], the
+    texel dots of every sample in the order of CORNERS (zero outside the map), so that a failure can be attributed to a corner."""
+    f1 = torch.as_tensor(f1).detach().cpu().double()
+    f2 = torch.as_tensor(f2).detach().cpu()
+    if f2_round is not None:
+        f2 = f2_round(f2)
+    f2 = f2.double()
+    Vs, h2, w2, C = f2.shape
+    V, P, D = coords["ok"].shape
+    views = list(range(V)) if views is None else list(views)
+    T = h2 * w2
+    zero = torch.zeros(1, C, dtype=torch.float64)
+    f1a, s1 = f1.abs(), f1.abs().sum(1)
+    out = {k: torch.zeros(V, P, D, dtype=torch.float64) for k in ("val", "norm", "l1")}
+    out["dots"] = torch.zeros(V, P, D, 4, dtype=torch.float64)
+    tt = lambda a: torch.from_numpy(a)
+    for v in range(V):
+        f2z = torch.cat([f2[views[v]].reshape(T, C), zero], 0)
+        f2za, s2 = f2z.abs(), f2z.abs().sum(1)
+        for s in range(0, P, chunk):
+            e = slice(s, s + chunk)
+            ok, iu, iw = tt(coords["ok"][v, e]), tt(coords["iu"][v, e]).long(), tt(coords["iw"][v, e]).long()
+            du, dw = tt(coords["du"][v, e]).double(), tt(coords["dw"][v, e]).double()
+            for q, (dy, dx) in enumerate(CORNERS):
+                wt = (du if dx else 1.0 - du) * (dw if dy else 1.0 - dw)
+                xi, yi = iu + dx, iw + dy
+                inside = ok & (xi >= 0) & (xi < w2) & (yi >= 0) & (yi < h2)
+                idx = torch.where(inside, yi * w2 + xi, torch.full_like(xi, T))
+                dots = torch.einsum("ndc,nc->nd", f2z[idx], f1[e])
+                out["dots"][v, e, :, q] = dots
+                out["val"][v, e] += wt * dots
+                out["norm"][v, e] += wt * torch.einsum("ndc,nc->nd", f2za[idx], f1a[e])
+                out["l1"][v, e] += wt * s2[idx]
+            out["l1"][v, e] += s1[e, None] * ok
+    return out
+
+
+def cost_rows_ref64(per_view, D, num_levels, scale, compact, preset=None):
+    """Volume rows from per-view samples (``cost_samples_ref64``): the view sum in view order, times ``scale`` (None: the plain sum), the
+    pooled levels of O.pyramid ((a + b) / 2 pairwise, floor) unless ``compact`` or ``preset``; ``preset`` [P, rs]: accumulate - level 0 is
+    preset + sum, every other column of the row stays what it was.  Laid out by ``ops.row_layout``.
+    -> dict of [P, rs] float64: ref, norm, l1 (pad columns and, under ``preset``, the columns beyond level 0: ref = preset or 0, norm = l1
+    = 0), and level [rs] (long): the pyramid level of a column, -1 for a column the builder does not write."""
+    from cer_mvs_amd import ops
+    offs, lens, rs = ops.row_layout(D, num_levels, compact)
+    P = per_view["val"].shape[1]
+    sc = 1.0 if scale is None else float(torch.tensor(float(scale), dtype=torch.float32))       # (the kernels take the scale as a C float)
+    out = {k: torch.zeros(P, rs, dtype=torch.float64) for k in ("ref", "norm", "l1")}
+    level = torch.full((rs,), -1, dtype=torch.long)
+    if preset is not None:
+        pre = torch.as_tensor(preset).detach().cpu().double()
+        out["ref"] = pre.clone()
+        out["norm"][:, :D] = pre[:, :D].abs()
+    for k, src in (("ref", "val"), ("norm", "norm"), ("l1", "l1")):
+        cur = per_view[src].sum(0) * sc
+        out[k][:, :D] += cur
+        if preset is not None:
+            continue
+        for l in range(1, 1 if compact else num_levels):
+            n = cur.shape[1] // 2
+            cur = (cur[:, 0:2 * n:2] + cur[:, 1:2 * n:2]) * 0.5
+            out[k][:, offs[l]:offs[l] + lens[l]] = cur
+    level[:D] = 0
+    if preset is None and not compact:
+        for l in range(1, num_levels):
+            level[offs[l]:offs[l] + lens[l]] = l
+    out["level"] = level
+    return out
+
+
+def _gamma(n):
+    return n * U24 / (1.0 - n * U24)
+
+
+COST_FORMS = ("walk", "three-term", "two-term")
+
+
+def cost_bound(norm, V, form, level=0, accumulate=False, l1=None):
+    """-> (c, abs_term): |kernel - reference| <= c * norm + abs_term for an element of a cost-volume row whose cell and fractions are the
+    restated ones; u = 2^-24, gamma_n = n u / (1 - n u).  Every term is read off the kernel source; nothing is fitted to an output.
+
+    walk (csrc/cost_build.hip, C = 64): a lane owns 4 channels of one corner: ``cer_dot4``, a chain of 4 fmaf from 0: 4 roundings.  Its
+    corner weight: 1 - du and 1 - dw round once each (a single fp32 subtraction: relative u of its result), their product once: 3.
+    ``acc = fmaf(sdot, wgt, acc)`` once per view: V.  The butterfly sums the 64 lanes in 6 levels of one add each: 6.  ``acc * scale``: 1.
+    Every partial sum is bounded by the sum of the absolute terms, which is V * norm / scale: n = 14 + V.
+
+    three-term (csrc/cost_lines.hip): the operand of both maps is x' = 64 x = hi + lo + d, hi = f16(x'), lo = f16(x' - hi):
+    |d| <= 2^-11 |x' - hi| <= 2^-22 |x'| while lo is a normal f16, else |d| <= 2^-25 (half an f16 subnormal step; the same when hi itself
+    is subnormal).  The kernel sums hi hi + hi lo + lo hi: it drops lo1 lo2 (<= 2^-22 |x1' x2'|) and inherits d1 x2' + d2 x1'
+    (<= 2 * 2^-22 |x1' x2'| + 2^-25 (|x1'| + |x2'|)): relative 3 * 2^-22, absolute 2^-25 * 64 / 4096 = 2^-31 per unit of |x1| + |x2|,
+    i.e. 2^-31 * l1.  The 12 MFMAs (v_mfma_f32_32x32x16_f16: f16 products are exact in fp32) add 192 products into one fp32 accumulator;
+    the order inside an instruction is the hardware's, so each of the 192 additions is charged one rounding of a partial sum that is at
+    most the whole sum of absolute terms: 192.  (The direct path - ``cl_direct`` - is a chain of 64 fmaf on (hi + lo) rounded once per
+    operand: 66, inside the same figure, and drops nothing.)  Gather: the weight as above, 3; dot * weight, 1; three adds, 3.  View sum
+    (cost_lines_reduce_kernel: s = 0 + part_0 + ...): V - 1; ``s * scale`` (a power of two folded in): 1.  n = 199 + V.
+
+    two-term: judged against the reference on f16-rounded source rows (``cost_f2_two_term``: its definition, pinned bit for bit by
+    test_cost_lines_two_term_form) with the three-term figure: its lo planes are exactly zero there, its 8 MFMAs a subset of the 12.
+
+    Pooled level l (both epilogues and cer_pyramid_f32: (a + b) * 0.5f, level by level): the children's errors average into c * (pooled
+    norm); the add rounds once and the halving is exact short of underflow - charged two per level.  Accumulate: one more rounding of
+    preset + sum, relative to |preset| + norm - the caller adds |preset| to ``norm``.
+    The factor 1 + 2^-10 covers the products of two error terms.  (The issue's own estimate, (C + 12 + V) u + 3 * 2^-22 ~ 5e-6, charges
+    the MFMA chain one rounding per CHANNEL; per product, which is what the instruction's unspecified inner order allows, it is 1.3e-5.)"""
+    if form not in COST_FORMS:
+        raise ValueError(form)
+    n = (14 + V if form == "walk" else 199 + V) + 2 * int(level) + int(bool(accumulate))
+    split = 0.0 if form == "walk" else 3.0 * 2.0 ** -22
+    c = (_gamma(n) + split) * (1.0 + 2.0 ** -10)
+    a = 0.0 if (form == "walk" or l1 is None) else 2.0 ** -31 * (1.0 + 2.0 ** -10) * torch.as_tensor(l1, dtype=torch.float64)
+    return c, a
+
+
+def check_cost_rows(got, R, V, form, where, h, w, accumulate=False, floor=None):
+    """``check_elementwise`` of volume rows ``got`` [P, rs] against ``R`` (``cost_rows_ref64``) on every column a builder writes: the
+    norm floored at the case's mean |ref| (``floor``: that figure, when ``got`` is part of a larger case), c and the absolute term from
+    ``cost_bound`` column by column (a pooled column has its level's c), 1 x 32 tiles and 32-pixel seams -> ParityReport (its
+    ``channels`` are the row's columns)."""
+    cols = (R["level"] >= 0).nonzero().reshape(-1)
+    ref = R["ref"][:, cols]
+    floor = float(ref.abs().mean()) if floor is None else floor
+    c0, a = cost_bound(None, V, form, 0, accumulate, l1=R["l1"][:, cols])
+    cl = torch.tensor([cost_bound(None, V, form, int(l), accumulate)[0] for l in R["level"][cols]], dtype=torch.float64)
+    mag = R["norm"][:, cols].clamp_min(floor) * (cl / c0)[None, :]
+    return check_elementwise(torch.as_tensor(got).detach().cpu().double()[:, cols], ref, mag, c0, a, where, h=h, w=w, tile=(1, 32), seam=32)
+
+
+def assert_cost_rows(got, R, V, form, where, h, w, **kw):
+    rep = check_cost_rows(got, R, V, form, where, h, w, **kw)
+    assert rep.ok, rep.message()
+    return rep

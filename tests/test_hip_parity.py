@@ -336,45 +336,14 @@ def test_conv3x3_disp_encoder_source(dev):
 
 
 def _lines_case(dev, D, stage0, geom, h1, w1):
+    """The geometries live in tests/cost_geometry_cases.py (which tests/test_cost_geometry_gpu.py holds against a float64 reference)."""
     from cer_mvs_amd.corr import fmaps_to_nhwc
-    V, C = 3, 64
-    fm = hashed((1, V + 1, C, h1, w1), 311, -2, 2).to(dev)
-    f1 = fmaps_to_nhwc(fm[0, 0:1])[0]
-    f2 = fmaps_to_nhwc(fm[0, 1:], border=2)
-    Pij = torch.eye(4).repeat(V, 1, 1)
-    for v in range(V):
-        if geom == "horizontal":
-            Pij[v, 0, 3] = (900.0 if stage0 else 9000.0) * (v + 1) * (1 if v != 1 else -1)
-        elif geom == "vertical":
-            Pij[v, 1, 3] = -(700.0 if stage0 else 7000.0) * (v + 1)
-        elif geom == "diagonal":
-            Pij[v, 0, 3], Pij[v, 1, 3] = 600.0 * (v + 1), (-500.0, 450.0, -80.0)[v] * (v + 1)
-            Pij[v, 0, 1] = 0.05 * v
-        elif geom == "rotation":          # no baseline: every hypothesis of a pixel lands on one point (+ a small homography)
-            Pij[v, 0, 1], Pij[v, 1, 0], Pij[v, 0, 2], Pij[v, 1, 2] = 0.02 * v, -0.02 * v, 1.3 * v, -0.7
-        elif geom == "forward":           # epipole inside the image: lines of every direction within one view
-            Pij[v, 0, 3], Pij[v, 1, 3], Pij[v, 2, 3] = 0.5 * w1 * 400.0, 0.5 * h1 * 400.0, 400.0 * (v + 1)
-        elif geom == "converging":        # rotation + baseline (the bench scene's kind of pair): the epipole is finite, far away
-            th = 0.12 * (v + 1) * (1 if v % 2 else -1)
-            f = 1.8 * w1
-            K = torch.tensor([[f, 0, w1 / 2], [0, f, h1 / 2], [0, 0, 1.0]])
-            R = torch.tensor([[np.cos(th), 0, np.sin(th)], [0, 1, 0], [-np.sin(th), 0, np.cos(th)]], dtype=torch.float32)
-            Rx = torch.tensor([[1, 0, 0], [0, np.cos(0.04 * v), -np.sin(0.04 * v)], [0, np.sin(0.04 * v), np.cos(0.04 * v)]], dtype=torch.float32)
-            R = Rx @ R
-            c = torch.tensor([0.0, 0.0, 600.0])
-            Pij[v, :3, :3] = K @ R @ torch.linalg.inv(K)
-            Pij[v, :3, 3] = K @ (c - R @ c)
-        elif geom == "zoom":              # source view magnified 6x: neighbouring lines are 6 texels apart (eight-line form: todo list)
-            Pij[v, 0, 0] = Pij[v, 1, 1] = 6.0
-            Pij[v, 0, 2], Pij[v, 1, 2] = -2.5 * w1, -2.5 * h1
-            Pij[v, 0, 3] = (2500.0 if stage0 else 25000.0) * (v + 1)
-            Pij[v, 1, 3] = 300.0 * v
-        else:   # wild: Z = 1 + m[11] * hyp crosses zero inside the range; one view entirely behind the camera
-            Pij[v, 0, 3], Pij[v, 2, 3] = 4000.0, (-700.0, -1500.0, 0.0)[v]
-            if v == 2:
-                Pij[v, 2, 2] = -1.0
-    d0 = hashed((h1 * w1,), 312, 0.0005, 0.002).to(dev) if not stage0 else torch.zeros(h1 * w1, device=dev)
-    return f1, f2, Pij.to(dev), d0, V
+    from cost_geometry_cases import V, lines_geometry
+    fm, Pij, d0 = lines_geometry(geom, D, stage0, h1, w1)
+    fm = fm.to(dev)
+    f1 = fmaps_to_nhwc(fm[0:1])[0]
+    f2 = fmaps_to_nhwc(fm[1:], border=2)
+    return f1, f2, Pij.to(dev), d0.to(dev), V
 
 
 @pytest.mark.parametrize("geom", ["horizontal", "diagonal", "vertical", "wild", "rotation", "forward", "converging", "zoom"])

@@ -69,7 +69,8 @@ WALK_SHIFT_PX = 1500.0                                      # focal length x bas
 
 def walk_geometry(geom, h, w, V):
     """-> (poses [V + 1, 4, 4], intrinsics [V + 1, 3, 3]) fp32, view 0 the reference (identity pose).  Z stays positive over every
-    hypothesis range: the fp32 yardstick is bounded (geometries where it is not stay with test_cost_build_edge_cases)."""
+    hypothesis range: the fp32 yardstick is bounded (geometries where it is not are held to a reference built from restated fp32
+    coordinates instead: tests/cost_geometry_cases.py, tests/test_cost_geometry_gpu.py)."""
     f = 1.8 * w
     K = torch.tensor([[f, 0.0, w / 2.0], [0.0, f, h / 2.0], [0.0, 0.0, 1.0]])
     b = WALK_SHIFT_PX / f
