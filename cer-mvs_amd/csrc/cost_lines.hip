@@ -21,7 +21,9 @@
 //   3. every sample was projected ONCE, before the chunk loop, by straight-line code (two IEEE divisions, cell, fractions,
 //      band rows packed into 16 B of LDS per sample); in the loop lane (pixel, hypothesis phase) walks its samples in order
 //      (a cursor) and, for each one whose cell lies in the chunk, reads its 4 dots from LDS (16 B instead of 1 KiB),
-//      applies the bilinear weights and stores the value; samples outside the source image are zeros (the walk's zero border);
+//      applies the bilinear weights and stores the value; samples outside the source image are zeros (the walk's zero border).
+//      Which samples the cursor visits, where their products lie in a chunk and which ones go the direct path instead is settled
+//      in that one pass per sample: the loop's test per iteration is one subtraction and one comparison ("issue");
 //   4. anything the band analysis did not cover (projections blown apart near Z = 0, epipoles inside the image, rough
 //      per-pixel origins that break the cursor's monotonic order, bands wider than 29 texels) takes a per-sample direct path:
 //      correct, slow, rare.
@@ -201,9 +203,15 @@ extern "C" int cer_cost_lines1_stats(unsigned long long* out, int reset) {
 struct ClBand {
     int smaj, nchunks, R, Wc, cmin, cmax, dir;      // nchunks < 0: the tile has no pixel (the tile block returns at once)
     float bm, bl0;                                    // base row of band column c: floor(bl0 + bm * c)
-    int pad[3];
+    unsigned cmagic;                                  // ceil(2^32 / (Wc - 1)): chunk of a cell column = umulhi(columns from the band's first, cmagic) (cl_chunk_magic)
+    int pad[2];
 };
 static_assert(sizeof(ClBand) == 48, "ClBand is read as three 16-byte pieces");
+// The chunk of a cell column without a division per sample: a chunk holds Wc - 1 cell columns, so the column x columns past the band's first one
+// (in travel direction) lies in chunk x / (Wc - 1) = umulhi(x, cmagic) with cmagic = ceil(2^32 / (Wc - 1)).  Exact while
+// x * ((Wc - 1) * cmagic - 2^32) < 2^32: x < 2^15 (cl_check: maps of up to 16000 texels) and Wc - 1 < 2^7 keep the left side below 2^22
+// (tests/test_cost_lines_chunk_cpu.py walks the whole domain).  Every tile that has chunks has R <= 31, so Wc - 1 >= 3.
+__host__ __device__ inline unsigned cl_chunk_magic(int Wc) { return 0xFFFFFFFFu / (unsigned)(Wc - 1 > 2 ? Wc - 1 : 2) + 1u; }
 
 struct ClArgs {
     const _Float16* f1s;      // [8 planes][P][16]   reference map of this call's pixel grid (cer_feat_split_f16 layout)
@@ -391,7 +399,8 @@ __global__ __launch_bounds__(256) void cost_lines_bands_kernel(const ClArgs A, u
         ClBand r;
         r.smaj = smaj; r.nchunks = nchunks; r.R = R; r.Wc = Wc; r.cmin = cmin; r.cmax = cmax; r.dir = dir;
         r.bm = bm; r.bl0 = bl0;
-        r.pad[0] = r.pad[1] = r.pad[2] = 0;
+        r.cmagic = cl_chunk_magic(Wc);
+        r.pad[0] = r.pad[1] = 0;
         *rec = r;
     }
 }
@@ -405,8 +414,11 @@ template <bool F2LO>
 __device__ __forceinline__ void cl_tile(const ClArgs& A, const int v, const int rem, const int seg, const int jj) {
     __shared__ __attribute__((aligned(16))) float prod[CL_T * 32];      // dots[texel of the chunk][pixel of the tile]
     // per (hypothesis, pixel): {packed cell, fraction along the band, fraction across it, value}
-    //   packed: bits 0-15 band column of the cell + 4; bits 30-31 kind: 0 = samples through the band (bits 16-20 / 21-25: band row
-    //   of the cell in its own / the next column), 1 = zero (outside the map / non-finite), 2 = direct path (bits 16-29: cell row + 4)
+    //   packed: bits 0-15 band column of the cell + 4; bits 30-31 kind: 0 = samples through the band (bits 16-20: band row r0 of the
+    //   cell in its own column, bits 21-26: R + r1 - r0, the distance in the band-linear texel order to its row r1 in the next column),
+    //   1 = zero (outside the map / non-finite), 2 = direct path (bits 16-29: cell row + 4).
+    //   Until the value is written its slot holds, for kind 0, the band-linear index of the cell, (column + 4) R + r0: a chunk that
+    //   starts at column cb finds the cell's products at that index - (cb + 4) R.
     extern __shared__ __attribute__((aligned(16))) float desc[];          // [D][CL_DP][4]
     __shared__ int pidx[32];                                             // pixel index of tile slot i, or -1
 
@@ -421,8 +433,9 @@ __device__ __forceinline__ void cl_tile(const ClArgs& A, const int v, const int 
     const ClBand* rec = A.bands + (long)v * A.tpv + rem;
     int smaj = rec->smaj, nchunks = rec->nchunks, R = rec->R, Wc = rec->Wc, cmin = rec->cmin, cmax = rec->cmax, dir = rec->dir;
     float bm = rec->bm, bl0 = rec->bl0;
+    unsigned cmagic = rec->cmagic;
     ClLane L;
-    if (!cl_lane_pixel(A, v, seg, jj, li, L)) return;       // (lanes l and l + 32 share pixel slot li: they own different hypotheses)
+    if (!cl_lane_pixel(A, v, seg, jj, li, L)) return;      // (lanes l and l + 32 share pixel slot li: they own different hypotheses)
     const bool valid = L.valid;
     const long p_me = L.p_me;
     if (wave == 0 && lane < 32) pidx[lane] = valid ? (int)p_me : -1;
@@ -454,6 +467,7 @@ __device__ __forceinline__ void cl_tile(const ClArgs& A, const int v, const int 
     dir = __builtin_amdgcn_readfirstlane(dir);
     bm = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(bm)));
     bl0 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(bl0)));
+    cmagic = (unsigned)__builtin_amdgcn_readfirstlane((int)cmagic);
 
     const _Float16* f2v = A.f2s + (long)(A.slot ? A.slot[v] : v) * 8 * ps2;
 
@@ -475,9 +489,19 @@ __device__ __forceinline__ void cl_tile(const ClArgs& A, const int v, const int 
     };
     if (nchunks > 0) loadA(0);                              // arrives under the projections below
 
-    // ---- the samples of this lane: hypotheses k0, k0 + 8, ... (k0 = 2 wave + kg) of pixel slot li.  Straight-line code, two IEEE
-    // divisions per sample, nothing divergent: cell, fractions and band rows go to LDS; the chunk loop only looks things up
+    // ---- the samples of this lane: hypotheses k0, k0 + 8, ... (k0 = 2 wave + kg) of pixel slot li, sample i at k0 + 8 i.  Straight-line code,
+    // two IEEE divisions per sample, nothing divergent: cell, fractions and band rows go to LDS; the chunk loop only looks things up.
+    // Everything the chunk loop used to rediscover per iteration is settled here, once per sample:
+    //   - a lane walks its band samples in hypothesis order while the chunks advance along the band, so a band sample is taken from the chunk
+    //     products exactly when its chunk is not behind the furthest chunk an earlier band sample of the lane reached (`run`); one that is
+    //     behind goes the direct path, and is packed as a direct sample right away (its cell row is known here);
+    //   - `inmask` / `dmask`: bit i = sample i is gathered from the chunk products / takes the direct path; zero samples are in neither
+    //     (their value, 0, is written here);
+    //   - the band-linear index of the cell and the distance to its second column (the layout of `desc` above).
     const int k0 = 2 * wave + kg;
+    unsigned inmask = 0u, dmask = 0u;
+    int run = 0;
+#pragma clang loop vectorize(disable)
 #pragma unroll 2
     for (int k = k0; k < D; k += 8) {
         float u, w;
@@ -487,30 +511,49 @@ __device__ __forceinline__ void cl_tile(const ClArgs& A, const int v, const int 
         const int iu = ok ? min(max((int)fu, -2), w2) : -2, iw = ok ? min(max((int)fw, -2), h2) : -2;
         const int sc = smaj ? iw : iu, sr = smaj ? iu : iw;
         // cells without a corner inside the map read only border zeros (cost_build.hip clamps them into the zero border)
-        const bool zero = iu < -1 || iu > w2 - 1 || iw < -1 || iw > h2 - 1;
+        // (range tests as one unsigned comparison each, joined without short-circuit branches: iu in [-2, w2], iw in [-2, h2])
+        const bool zero = ((unsigned)(iu + 1) > (unsigned)w2) | ((unsigned)(iw + 1) > (unsigned)h2);      // iu < -1 || iu > w2 - 1 || iw < -1 || iw > h2 - 1
         const int b0 = (int)floorf(fmaf(bm, (float)sc, bl0)), b1 = (int)floorf(fmaf(bm, (float)(sc + 1), bl0));
         const int r0 = sr - b0, r1 = sr - b1;
-        const bool fits = nchunks > 0 && sc >= cmin && sc < cmax && r0 >= 0 && r0 + 1 < R && r1 >= 0 && r1 + 1 < R;
-        const int hi14 = fits ? (r0 + r1 * 32) : (sr + 4);
-        const int kind2 = zero ? 1 : (fits ? 0 : 2);
+        // nchunks > 0 && sc >= cmin && sc < cmax && r0 >= 0 && r0 + 1 < R && r1 >= 0 && r1 + 1 < R   (nchunks > 0 implies cmax > cmin; R >= 1)
+        const bool fits = (nchunks > 0) & ((unsigned)(sc - cmin) < (unsigned)(cmax - cmin)) & ((unsigned)r0 < (unsigned)(R - 1)) & ((unsigned)r1 < (unsigned)(R - 1));
+        // chunk n covers the cell columns cb0 + n cstep .. + Wc - 2: counted from cmin (dir > 0) or back from cmax - 1 (dir < 0)
+        const int nc = (int)__umulhi((unsigned)(dir > 0 ? sc - cmin : cmax - 1 - sc), cmagic);
+        const bool isin = fits & !zero & (nc >= run);
+        run = isin ? nc : run;
+        const int sel = -(int)isin;                         // (selects by mask: no branch around two additions)
+        const int hi14 = ((r0 + (R + r1 - r0) * 32) & sel) | ((sr + 4) & ~sel);
+        const int kind2 = zero ? 1 : (isin ? 0 : 2);
         const unsigned packed = (unsigned)(sc + 4) + ((unsigned)(hi14 & 0x3FFF) << 16) + ((unsigned)kind2 << 30);
-        *reinterpret_cast<float4*>(desc + (k * CL_DP + li) * 4) = make_float4(__uint_as_float(packed), smaj ? dw : du, smaj ? du : dw, 0.f);
+        const int tb = ((sc + 4) * R + r0) & sel;           // (0 = 0.f: the value of a zero sample)
+        *reinterpret_cast<float4*>(desc + (k * CL_DP + li) * 4) = make_float4(__uint_as_float(packed), smaj ? dw : du, smaj ? du : dw, __int_as_float(tb));
+        const unsigned bit = 1u << ((unsigned)(k - k0) >> 3);
+        inmask |= isin ? bit : 0u;
+        dmask |= (!zero && !isin) ? bit : 0u;
     }
+    if (!valid) inmask = dmask = 0u;                        // (a slot without a pixel: nothing to gather, nothing is written out)
 
     const unsigned long long cl_t2 = CL_CLK();
     CL_STAT(4, cl_t2 - cl_t1);
-    // ---- per-lane sample cursor
-    int k = valid ? k0 : D;
-    unsigned pk = 3u << 30;                                 // kind 3: done
+    // ---- per-lane cursor over the samples of `inmask`, lowest hypothesis first (a lane only ever reads descriptors it wrote itself)
+    const int CL_NONE = 0x40000000;                         // band-linear index of "no sample left": outside every chunk (|chunk base| < 2^20)
+    unsigned pk = 0u;
     float fm = 0.f, fn = 0.f;
-    auto load_sample = [&]() {                              // (a lane only ever reads descriptors it wrote itself)
-        if (k >= D) { pk = 3u << 30; return; }
-        const float4 d = *reinterpret_cast<const float4*>(desc + (k * CL_DP + li) * 4);
+    int tb = CL_NONE;
+    float* const dq0 = desc + (k0 * CL_DP + li) * 4;        // the lane's sample 0; sample i lies 8 hypotheses = 8 CL_DP descriptors further
+    float* dq = dq0;                                        // the descriptor of the cursor's sample; its value goes to dq[3]
+    auto next_in = [&]() {
+        if (inmask == 0u) { tb = CL_NONE; return; }
+        const int i = __ffs((int)inmask) - 1;
+        inmask &= inmask - 1u;
+        dq = dq0 + i * (8 * CL_DP * 4);
+        const float4 d = *reinterpret_cast<const float4*>(dq);
         pk = __float_as_uint(d.x);
         fm = d.y;
         fn = d.z;
+        tb = __float_as_int(d.w);
     };
-    load_sample();
+    next_in();
     auto direct_value = [&]() -> float {
         const int sc = (int)(pk & 0xFFFFu) - 4, sr = (int)((pk >> 16) & 0x3FFFu) - 4;
         const _Float16* t00 = f2v + (long)((sc + 2) * smajS + (sr + 2) * sminS) * 16;
@@ -540,38 +583,22 @@ __device__ __forceinline__ void cl_tile(const ClArgs& A, const int v, const int 
         const unsigned long long cl_tb = CL_CLK();
         __syncthreads();
         const unsigned long long cl_tc = CL_CLK();
-        // ---- gather: every lane consumes its samples whose cell lies in this chunk; zeros and direct-path samples as they come
-        const int cbe = cb + Wc - 2, cbR = (cb - 4) * R;    // last cell column of the chunk; band index of (column c, row r) = c R + r - cb R
+        // ---- gather: every lane takes its samples whose cell lies in this chunk.  Band index of (column c, row r) in the chunk =
+        // (c + 4) R + r - (cb + 4) R; the cell columns of the chunk are cb .. cb + Wc - 2 and a cell's row r0 is < R - 1, so the cell
+        // lies in the chunk exactly when that index is in [0, (Wc - 1) R): one unsigned comparison, whose wave-wide result ends the loop
+        const int tbase = (cb + 4) * R;
+        const unsigned tspan = (unsigned)((Wc - 1) * R);
         for (;;) {
-            const unsigned kind = pk >> 30;
-            const int scp = (int)(pk & 0xFFFFu);            // cell column + 4
-            const bool in = kind == 0 && scp >= cb + 4 && scp <= cbe + 4;
-            const bool behind = kind == 0 && (dir > 0 ? scp < cb + 4 : scp > cbe + 4);
-            const bool consume = in || behind || kind == 1 || kind == 2;
-            if (__ballot(consume) == 0ull) break;
-            float val = 0.f;
+            const int t0 = tb - tbase;
+            const bool in = (unsigned)t0 < tspan;
+            if (__ballot(in) == 0ull) break;
             if (in) {
-                const int t0 = scp * R + (int)((pk >> 16) & 31u) - cbR - 8 * R;      // (scp - 4 - cb) R + r0  [cbR = (cb - 4) R]
-                const int t1 = t0 + R + (int)((pk >> 21) & 31u) - (int)((pk >> 16) & 31u);
+                const int t1 = t0 + (int)((pk >> 21) & 63u);
                 const float* d0 = prod + t0 * 32 + li;
                 const float* d1 = prod + t1 * 32 + li;
                 const float wm1 = fm, wm0 = 1.0f - fm, wn1 = fn, wn0 = 1.0f - fn;
-                val = d0[0] * (wn0 * wm0) + d1[0] * (wn0 * wm1) + d0[32] * (wn1 * wm0) + d1[32] * (wn1 * wm1);
-            }
-            if (__ballot(behind || kind == 2) != 0ull) {    // rare: the wave-level test keeps the call off the hot path
-                if (behind || kind == 2) {
-                    if (kind == 0) {                        // re-pack a band sample as a direct one: its cell row from the band row
-                        const int sc = scp - 4;
-                        const int sr = (int)floorf(fmaf(bm, (float)sc, bl0)) + (int)((pk >> 16) & 31u);
-                        pk = (pk & 0xFFFFu) | ((unsigned)(sr + 4) << 16) | (2u << 30);
-                    }
-                    val = direct_value();
-                }
-            }
-            if (consume) {
-                desc[(k * CL_DP + li) * 4 + 3] = val;
-                k += 8;
-                load_sample();
+                dq[3] = d0[0] * (wn0 * wm0) + d1[0] * (wn0 * wm1) + d0[32] * (wn1 * wm0) + d1[32] * (wn1 * wm1);
+                next_in();
             }
         }
         const unsigned long long cl_td = CL_CLK();
@@ -579,21 +606,16 @@ __device__ __forceinline__ void cl_tile(const ClArgs& A, const int v, const int 
         CL_STAT(1, 1); CL_STAT(5, cl_tb - cl_ta); CL_STAT(6, cl_tc - cl_tb); CL_STAT(7, cl_td - cl_tc); CL_STAT(8, CL_CLK() - cl_td);
     }
     const unsigned long long cl_t3 = CL_CLK();
-    // ---- what the chunks did not cover (no band, samples out of order): direct path
-    while (__ballot((pk >> 30) != 3u) != 0ull) {
-        if ((pk >> 30) != 3u) {
-            float val = 0.f;
-            if ((pk >> 30) != 1u) {
-                if ((pk >> 30) == 0u) {
-                    const int sc = (int)(pk & 0xFFFFu) - 4;
-                    const int sr = (int)floorf(fmaf(bm, (float)sc, bl0)) + (int)((pk >> 16) & 31u);
-                    pk = (pk & 0xFFFFu) | ((unsigned)(sr + 4) << 16) | (2u << 30);
-                }
-                val = direct_value();
-            }
-            desc[(k * CL_DP + li) * 4 + 3] = val;
-            k += 8;
-            load_sample();
+    // ---- what the chunks did not cover (no band, samples out of order, bands too wide): direct path, behind a single wave-uniform test
+    while (__ballot(dmask != 0u) != 0ull) {
+        if (dmask != 0u) {
+            const int i = __ffs((int)dmask) - 1;
+            dmask &= dmask - 1u;
+            float* dd = dq0 + i * (8 * CL_DP * 4);
+            pk = __float_as_uint(dd[0]);
+            fm = dd[1];
+            fn = dd[2];
+            dd[3] = direct_value();
         }
     }
     __syncthreads();
@@ -601,8 +623,11 @@ __device__ __forceinline__ void cl_tile(const ClArgs& A, const int v, const int 
     CL_STAT(9, cl_t4 - cl_t3);
     // ---- rows out: wave w writes pixel slots w, w + 4, ...; lane = hypothesis (one coalesced D-float row per store)
     float* pv = A.part + (long)v * ((long)h1 * w1) * D;
-    for (int i = wave; i < 32; i += 4) {
-        const int p = pidx[i];
+    const int pme = pidx[li];                               // one LDS read: lane l holds the pixel of slot l & 31, readlane hands slot i's to the scalar unit
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int i = wave + 4 * j;
+        const int p = __builtin_amdgcn_readlane(pme, i);
         if (p >= 0 && lane < D) pv[(long)p * D + lane] = desc[(lane * CL_DP + i) * 4 + 3];
     }
     CL_STAT(10, CL_CLK() - cl_t4); CL_STAT(2, CL_CLK() - cl_t0);
