@@ -40,6 +40,9 @@ class CopySegments(ctypes.Structure):
     _fields_ = [("src", _P * COPY_MAX_SEG), ("dst", _P * COPY_MAX_SEG), ("n", _L * COPY_MAX_SEG)]
 
 
+# the grid of a cloud index as the cer_grid_* searches take it: records, n, cell_keys, cell_start, ncells, origin, cell
+_GRID = [_P, _L, _P, _P, _L, _c.POINTER(_D), _D]
+
 _SIGNATURES = {
     "cer_abi_version": (_I, []),
     "cer_error_string": (_c.c_char_p, [_I]),
@@ -128,11 +131,11 @@ _SIGNATURES = {
     "cer_grid_pack_f32": (_I, [_P, _P, _L, _P, _P]),
     "cer_grid_cells_count_i64": (_I, [_P, _L, _P, _P, _P, _P]),
     "cer_grid_cells_i64": (_I, [_P, _L, _P, _LL, _P, _P, _P]),
-    "cer_grid_nearest_f32": (_I, [_P, _L, _P, _P, _L, _c.POINTER(_D), _D, _P, _P, _L, _F, _P, _P, _P]),
-    "cer_grid_knn_f32": (_I, [_P, _L, _P, _P, _L, _c.POINTER(_D), _D, _P, _P, _L, _I, _F, _P, _P, _P, _P, _P]),
-    "cer_grid_normals_f32": (_I, [_P, _L, _P, _P, _L, _c.POINTER(_D), _D, _P, _P, _L, _I, _F, _P, _P, _P, _P, _P, _P, _P]),
-    "cer_grid_count_within_f32": (_I, [_P, _L, _P, _P, _L, _c.POINTER(_D), _D, _P, _P, _L, _F, _P, _P]),
-    "cer_grid_thin_round_f32": (_I, [_P, _L, _P, _P, _L, _c.POINTER(_D), _D, _P, _L, _F, _P, _P]),
+    "cer_grid_nearest_f32": (_I, _GRID + [_P, _P, _L, _F, _P, _P, _P]),
+    "cer_grid_knn_f32": (_I, _GRID + [_P, _P, _L, _I, _F, _P, _P, _P, _P, _P]),
+    "cer_grid_normals_f32": (_I, _GRID + [_P, _P, _L, _I, _F, _P, _P, _P, _P, _P, _P, _P]),
+    "cer_grid_count_within_f32": (_I, _GRID + [_P, _P, _L, _F, _P, _P]),
+    "cer_grid_thin_round_f32": (_I, _GRID + [_P, _L, _F, _P, _P]),
     "cer_grid_thin_compact_i32": (_I, [_P, _L, _P, _P, _L, _P, _P, _P, _P, _P]),
     "cer_cloud_transform_f32": (_I, [_P, _L, _c.POINTER(_D), _P, _P]),
     "cer_cloud_moment_partials": (_L, [_L]),

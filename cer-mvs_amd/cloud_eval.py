@@ -85,6 +85,21 @@ def _cell(cell):
     return cell
 
 
+def _knn_k(k):
+    k = int(k)
+    if not 1 <= k <= KNN_MAX:
+        raise ValueError(f"k: 1 .. {KNN_MAX} expected, got {k}")
+    return k
+
+
+def _reach(value, name, finite=False):
+    """a search's reach (``max_dist``, ``radius``) as the float32 the kernels take: >= 0 (+inf allowed unless ``finite``), ValueError otherwise"""
+    value = float(np.float32(value))
+    if not (value >= 0.0 and (math.isfinite(value) or not finite)):
+        raise ValueError(f"{name} must be {'a finite number ' if finite else ''}>= 0")
+    return value
+
+
 def _compaction_scratch(lib, n, dev, results):
     """(partials int32, offsets int64, ``results`` int64 words for the host to read): what one count / scan / emit over ``n`` entries needs"""
     P = int(lib.cer_grid_partials(n))
@@ -147,64 +162,48 @@ class CloudIndex:
         """Original index of the first sorted point of every occupied cell - the lowest index in the cell, as the sort is stable."""
         return self.order[self.cell_start[:self.cells]]
 
-    def nearest(self, queries, max_dist, sort_queries=True):
-        """-> (dist float32 [m], idx int64 [m]) in the queries' order: the indexed point with the smallest (d2, index), d2 = (dx*dx + dy*dy) +
-        dz*dz in fp64, among those with d2 <= double(max_dist)^2; dist = float32(sqrt(d2)); (inf, -1) where there is none or the query is
-        not finite.  ``sort_queries``: walk the queries in the order of their own cells (faster; the result is the same)."""
-        queries = _cloud(queries, "queries")
-        max_dist = float(np.float32(max_dist))
-        if not max_dist >= 0.0:
-            raise ValueError("max_dist must be >= 0")
-        m, dev = int(queries.shape[0]), queries.device
-        if m == 0 or self.n == 0:                            # (the entry point launches nothing for an empty side)
-            return torch.full((m,), float("inf"), device=dev, dtype=torch.float32), torch.full((m,), -1, device=dev, dtype=torch.int64)
-        dist = torch.empty(m, device=dev, dtype=torch.float32)
-        idx = torch.empty(m, device=dev, dtype=torch.int64)
-        lib = L.load()
-        qorder = None
-        if sort_queries:
-            qkeys = torch.empty(m, device=dev, dtype=torch.int64)
-            L.check(lib.cer_grid_keys_f32(L.dev_ptr(queries, "queries"), m, self.origin, self.cell, 1, L.dev_ptr(qkeys, "keys", torch.int64), None,
-                                          L.cur_stream()), "grid_keys")
-            qorder = torch.sort(qkeys, stable=True).indices
-        rc = lib.cer_grid_nearest_f32(*self.grid_args(), L.dev_ptr(queries, "queries"), L.dev_ptr(qorder, "qorder", torch.int64), m, max_dist,
-                                      L.dev_ptr(idx, "idx", torch.int64), L.dev_ptr(dist, "dist"), L.cur_stream())
-        if rc == -2:
-            raise ValueError(f"nearest: max_dist {max_dist} is more than {GRID_MAX_RINGS} cells of {self.cell}; index the cloud with a larger cell")
-        L.check(rc, "grid_nearest")
-        return dist, idx
-
     def _walk_order(self, queries, m):                       # the queries' positions in the order of their own cell keys
         qkeys = torch.empty(m, device=queries.device, dtype=torch.int64)
         L.check(L.load().cer_grid_keys_f32(L.dev_ptr(queries, "queries"), m, self.origin, self.cell, 1, L.dev_ptr(qkeys, "keys", torch.int64), None,
                                            L.cur_stream()), "grid_keys")
         return torch.sort(qkeys, stable=True).indices
 
-    def _knn(self, queries, k, max_dist, sort_queries, lists, mean):
-        k = int(k)
-        if not 1 <= k <= KNN_MAX:
-            raise ValueError(f"k: 1 .. {KNN_MAX} expected, got {k}")
-        max_dist = float(np.float32(max_dist))
-        if not max_dist >= 0.0:
-            raise ValueError("max_dist must be >= 0")
+    def _query(self, method, entry, queries, reach, value, sort_queries, outputs, k=None, inputs=None):
+        """The one path of the four searches, ``cer_<entry>_f32``: the reach (``method``'s argument ``reach``) rounded to float32 and checked,
+        then the queries; ``outputs``: (name, shape of a row, dtype, value on an empty side or None for an output that is not wanted) in the
+        entry point's order -> the list of those tensors [m, *row].  ``k`` (checked by the caller) goes in front of the reach, ``inputs(m)`` ->
+        (tensor, name) pairs between the reach and the outputs."""
+        value = _reach(value, reach)
         queries = _cloud(queries, "queries")
         m, dev = int(queries.shape[0]), queries.device
-        inf = float("inf")
-        if m == 0 or self.n == 0:                            # (the entry point launches nothing for an empty side)
-            return (torch.full((m, k), inf, device=dev, dtype=torch.float32) if lists else None,
-                    torch.full((m, k), -1, device=dev, dtype=torch.int64) if lists else None, torch.zeros(m, device=dev, dtype=torch.int32),
-                    torch.full((m,), inf, device=dev, dtype=torch.float64) if mean else None)
-        dist = torch.empty(m, k, device=dev, dtype=torch.float32) if lists else None
-        idx = torch.empty(m, k, device=dev, dtype=torch.int64) if lists else None
-        count = torch.empty(m, device=dev, dtype=torch.int32)
-        avg = torch.empty(m, device=dev, dtype=torch.float64) if mean else None
+        inputs = inputs(m) if inputs else ()
+        empty = m == 0 or self.n == 0                        # (the entry point launches nothing for an empty side)
+        out = [None if fill is None else torch.full((m,) + row, fill, device=dev, dtype=dt) if empty else torch.empty((m,) + row, device=dev, dtype=dt)
+               for _, row, dt, fill in outputs]
+        if empty:
+            return out
         qorder = self._walk_order(queries, m) if sort_queries else None
-        rc = L.load().cer_grid_knn_f32(*self.grid_args(), L.dev_ptr(queries, "queries"), L.dev_ptr(qorder, "qorder", torch.int64), m, k, max_dist,
-                                       L.dev_ptr(idx, "idx", torch.int64), L.dev_ptr(dist, "dist"), L.dev_ptr(count, "count", torch.int32),
-                                       L.dev_ptr(avg, "mean", torch.float64), L.cur_stream())
+        rc = getattr(L.load(), f"cer_{entry}_f32")(*self.grid_args(), L.dev_ptr(queries, "queries"), L.dev_ptr(qorder, "qorder", torch.int64), m,
+                                                   *(() if k is None else (k,)), value, *[L.dev_ptr(t, name) for t, name in inputs],
+                                                   *[L.dev_ptr(t, o[0], o[2]) for t, o in zip(out, outputs)], L.cur_stream())
         if rc == -2:
-            raise ValueError(f"nearest: max_dist {max_dist} is more than {GRID_MAX_RINGS} cells of {self.cell}; index the cloud with a larger cell")
-        L.check(rc, "grid_knn")
+            raise ValueError(f"{method}: {reach} {value} is more than {GRID_MAX_RINGS} cells of {self.cell}; index the cloud with a larger cell")
+        L.check(rc, entry)
+        return out
+
+    def nearest(self, queries, max_dist, sort_queries=True):
+        """-> (dist float32 [m], idx int64 [m]) in the queries' order: the indexed point with the smallest (d2, index), d2 = (dx*dx + dy*dy) +
+        dz*dz in fp64, among those with d2 <= double(max_dist)^2; dist = float32(sqrt(d2)); (inf, -1) where there is none or the query is
+        not finite.  ``sort_queries``: walk the queries in the order of their own cells (faster; the result is the same)."""
+        idx, dist = self._query("nearest", "grid_nearest", queries, "max_dist", max_dist, sort_queries,
+                                (("idx", (), torch.int64, -1), ("dist", (), torch.float32, float("inf"))))
+        return dist, idx
+
+    def _knn(self, method, queries, k, max_dist, sort_queries, lists, mean):
+        k, inf = _knn_k(k), float("inf")
+        idx, dist, count, avg = self._query(method, "grid_knn", queries, "max_dist", max_dist, sort_queries,
+                                            (("idx", (k,), torch.int64, -1 if lists else None), ("dist", (k,), torch.float32, inf if lists else None),
+                                             ("count", (), torch.int32, 0), ("mean", (), torch.float64, inf if mean else None)), k=k)
         return dist, idx, count, avg
 
     def knn(self, queries, k, max_dist, sort_queries=True):
@@ -212,33 +211,19 @@ class CloudIndex:
         index), in that order; d2, the candidates (d2 <= double(float32(max_dist))^2) and dist as ``nearest`` defines them.  Unused slots are
         (inf, -1); count = the used ones, 0 for a query that is not finite.  A query that is itself an indexed point finds itself (or a
         duplicate of lower index) first, at 0.  ``k``: 1 .. 32 (KNN_MAX), ValueError otherwise; k = 1 is ``nearest``."""
-        dist, idx, count, _ = self._knn(queries, k, max_dist, sort_queries, True, False)
+        dist, idx, count, _ = self._knn("knn", queries, k, max_dist, sort_queries, True, False)
         return dist, idx, count
 
     def knn_mean_distance(self, queries, k, max_dist, sort_queries=True):
         """-> (mean float64 [m], count int32 [m]): the mean of the fp64 distances sqrt(d2) to the neighbours ``knn`` lists, added in ascending
         order and divided by their number (inf where count = 0) - without the [m, k] lists ever being written."""
-        _, _, count, mean = self._knn(queries, k, max_dist, sort_queries, False, True)
+        _, _, count, mean = self._knn("knn_mean_distance", queries, k, max_dist, sort_queries, False, True)
         return mean, count
 
     def count_within(self, queries, radius, sort_queries=True):
         """-> int32 [m]: the number of indexed points with d2 <= double(float32(radius))^2 (``nearest``'s d2; inclusive; the query itself when it
         is an indexed point); 0 for a query that is not finite."""
-        radius = float(np.float32(radius))
-        if not radius >= 0.0:
-            raise ValueError("radius must be >= 0")
-        queries = _cloud(queries, "queries")
-        m, dev = int(queries.shape[0]), queries.device
-        if m == 0 or self.n == 0:
-            return torch.zeros(m, device=dev, dtype=torch.int32)
-        count = torch.empty(m, device=dev, dtype=torch.int32)
-        qorder = self._walk_order(queries, m) if sort_queries else None
-        rc = L.load().cer_grid_count_within_f32(*self.grid_args(), L.dev_ptr(queries, "queries"), L.dev_ptr(qorder, "qorder", torch.int64), m, radius,
-                                                L.dev_ptr(count, "count", torch.int32), L.cur_stream())
-        if rc == -2:
-            raise ValueError(f"nearest: max_dist {radius} is more than {GRID_MAX_RINGS} cells of {self.cell}; index the cloud with a larger cell")
-        L.check(rc, "grid_count_within")
-        return count
+        return self._query("count_within", "grid_count_within", queries, "radius", radius, sort_queries, (("count", (), torch.int32, 0),))[0]
 
     def normals(self, queries, k, max_dist, viewpoints=None, sort_queries=True, moments=False):
         """-> (normal float32 [m, 3], curvature float32 [m], count int32 [m]) and, with ``moments``, mom float64 [m, 9]: the plane through the
@@ -248,41 +233,23 @@ class CloudIndex:
         normal = the unit eigenvector of l0 rounded once to float32, curvature = max(l0, 0) / (l0 + l1 + l2); otherwise (0, 0, 0) and NaN.
         Sign: the component of largest magnitude is positive (lowest axis on a tie); with ``viewpoints`` (CUDA float32 [3] or [m, 3]) the
         normal is turned so that normal . (viewpoint - query) >= 0; a non-finite viewpoint leaves the canonical sign.  ``k``: 1 .. 32."""
-        k = int(k)
-        if not 1 <= k <= KNN_MAX:
-            raise ValueError(f"k: 1 .. {KNN_MAX} expected, got {k}")
-        max_dist = float(np.float32(max_dist))
-        if not max_dist >= 0.0:
-            raise ValueError("max_dist must be >= 0")
-        queries = _cloud(queries, "queries")
-        m, dev = int(queries.shape[0]), queries.device
-        if viewpoints is not None:
-            if not isinstance(viewpoints, torch.Tensor) or not viewpoints.is_cuda:
-                raise RuntimeError("viewpoints must be a CUDA tensor (no CPU fallback)")
-            if viewpoints.dtype != torch.float32:
-                raise RuntimeError("viewpoints must be float32")
-            if tuple(viewpoints.shape) == (3,):
-                viewpoints = viewpoints.expand(m, 3)
-            if tuple(viewpoints.shape) != (m, 3):
-                raise ValueError(f"viewpoints: [3] or one per query [{m}, 3] expected, got {tuple(viewpoints.shape)}")
-            viewpoints = viewpoints.contiguous()
-        if m == 0 or self.n == 0:                            # (the entry point launches nothing for an empty side)
-            out = (torch.zeros(m, 3, device=dev, dtype=torch.float32), torch.full((m,), float("nan"), device=dev, dtype=torch.float32),
-                   torch.zeros(m, device=dev, dtype=torch.int32))
-            return out + (torch.zeros(m, 9, device=dev, dtype=torch.float64),) if moments else out
-        normal = torch.empty(m, 3, device=dev, dtype=torch.float32)
-        curvature = torch.empty(m, device=dev, dtype=torch.float32)
-        count = torch.empty(m, device=dev, dtype=torch.int32)
-        mom = torch.empty(m, 9, device=dev, dtype=torch.float64) if moments else None
-        qorder = self._walk_order(queries, m) if sort_queries else None
-        rc = L.load().cer_grid_normals_f32(*self.grid_args(), L.dev_ptr(queries, "queries"), L.dev_ptr(qorder, "qorder", torch.int64), m, k, max_dist,
-                                           L.dev_ptr(self.points, "points"), L.dev_ptr(viewpoints, "viewpoints"), L.dev_ptr(normal, "normal"),
-                                           L.dev_ptr(curvature, "curvature"), L.dev_ptr(count, "count", torch.int32),
-                                           L.dev_ptr(mom, "mom", torch.float64), L.cur_stream())
-        if rc == -2:
-            raise ValueError(f"nearest: max_dist {max_dist} is more than {GRID_MAX_RINGS} cells of {self.cell}; index the cloud with a larger cell")
-        L.check(rc, "grid_normals")
-        return (normal, curvature, count, mom) if moments else (normal, curvature, count)
+        def inputs(m, viewpoints=viewpoints):
+            if viewpoints is not None:
+                if not isinstance(viewpoints, torch.Tensor) or not viewpoints.is_cuda:
+                    raise RuntimeError("viewpoints must be a CUDA tensor (no CPU fallback)")
+                if viewpoints.dtype != torch.float32:
+                    raise RuntimeError("viewpoints must be float32")
+                if tuple(viewpoints.shape) == (3,):
+                    viewpoints = viewpoints.expand(m, 3)
+                if tuple(viewpoints.shape) != (m, 3):
+                    raise ValueError(f"viewpoints: [3] or one per query [{m}, 3] expected, got {tuple(viewpoints.shape)}")
+                viewpoints = viewpoints.contiguous()
+            return (self.points, "points"), (viewpoints, "viewpoints")
+
+        out = self._query("normals", "grid_normals", queries, "max_dist", max_dist, sort_queries,
+                          (("normal", (3,), torch.float32, 0.0), ("curvature", (), torch.float32, float("nan")), ("count", (), torch.int32, 0),
+                           ("mom", (9,), torch.float64, 0.0 if moments else None)), k=_knn_k(k), inputs=inputs)
+        return tuple(out) if moments else tuple(out[:3])
 
 
 def voxel_downsample(points, cell):
@@ -384,9 +351,7 @@ def _self_search_scale(points, max_dist, cell):
     for 1 % of the diagonal of the bounding box of the finite points (0 without one); ``cell`` a positive finite number, or None for
     ``max_dist / KNN_CELL_DIVISOR``.  ValueError otherwise, before the cloud is looked at."""
     if max_dist is not None:
-        max_dist = float(np.float32(max_dist))
-        if not (max_dist >= 0.0 and math.isfinite(max_dist)):
-            raise ValueError("max_dist must be a finite number >= 0")
+        max_dist = _reach(max_dist, "max_dist", finite=True)
     cell = None if cell is None else _cell(cell)
     points = _cloud(points, "points")
     n = int(points.shape[0])
@@ -415,9 +380,7 @@ def remove_statistical_outliers(points, k=20, std_ratio=2.0, max_dist=None, cell
     ``max_dist=None``: 1 % of the diagonal of the bounding box of the finite points - distant floaters widen that box, and the scale with it:
     name ``max_dist`` when the cloud's extent is not the surface's.  ``cell=None``: ``max_dist / 4``.  ``info``: a dict that receives "mu",
     "sigma", "threshold", "n_valid", "n_kept", "max_dist" and "cell"."""
-    k, std_ratio = int(k), float(std_ratio)
-    if not 1 <= k <= KNN_MAX:
-        raise ValueError(f"k: 1 .. {KNN_MAX} expected, got {k}")
+    k, std_ratio = _knn_k(k), float(std_ratio)
     if not math.isfinite(std_ratio):
         raise ValueError("std_ratio must be finite")
     points, max_dist, cell = _self_search_scale(points, max_dist, cell)
@@ -447,9 +410,7 @@ def remove_radius_outliers(points, radius, min_neighbours, cell=None, info=None)
     """Indices (int64, ascending) of the points with more than ``min_neighbours`` points of the cloud within ``radius`` of them
     (``count_within`` on the cloud itself, so the count includes the point: Open3D's ``remove_radius_outlier``).  Points with a non-finite
     coordinate count nothing and are dropped.  ``cell=None``: ``radius / 4``.  ``info``: a dict that receives "n_kept", "radius" and "cell"."""
-    radius = float(np.float32(radius))
-    if not (radius >= 0.0 and math.isfinite(radius)):
-        raise ValueError("radius must be a finite number >= 0")
+    radius = _reach(radius, "radius", finite=True)
     min_neighbours = int(min_neighbours)
     if min_neighbours < 0:
         raise ValueError("min_neighbours must be >= 0")
@@ -493,9 +454,7 @@ def estimate_normals(points, k=20, max_dist=None, cell=None, viewpoints=None, in
     plane (fewer than 3 neighbours within ``max_dist``, collinear or coincident ones, a non-finite coordinate) has normal (0, 0, 0) and
     curvature NaN.  ``max_dist`` / ``cell``: as ``remove_statistical_outliers`` (None: 1 % of the bounding-box diagonal / ``max_dist / 4``).
     ``info``: a dict that receives "n_valid" (one host read), "max_dist", "cell" and "k"."""
-    k = int(k)
-    if not 1 <= k <= KNN_MAX:
-        raise ValueError(f"k: 1 .. {KNN_MAX} expected, got {k}")
+    k = _knn_k(k)
     points, max_dist, cell = _self_search_scale(points, max_dist, cell)
     normal, curvature, _ = CloudIndex(points, cell).normals(points, k, max_dist, viewpoints=viewpoints)
     if info is not None:

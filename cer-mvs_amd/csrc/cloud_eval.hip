@@ -121,7 +121,17 @@ __global__ __launch_bounds__(256) void grid_emit_kernel(const long long* __restr
     }
 }
 
-// ---- the row walk under the search and the thinning.  Exactness does not rest on the key arithmetic: a cell is skipped only when the TRUE
+// ---- what every search reads of the index, by value: the sorted records, the cell table, the frame, and the rings of rows a walk covers
+struct GridView {
+    const uint4* rec;
+    const long long* cell_keys;
+    const long long* cell_start;
+    long ncells;
+    double ox, oy, oz, cell;
+    int rings;
+};
+
+// ---- the row walk under every search.  Exactness does not rest on the key arithmetic: a cell is skipped only when the TRUE
 // bounds of the points it can hold prove that none of them can matter.  A target point in cell c of an axis has a computed u in [c, c + 1);
 // u carries two fp64 roundings (relative 2^-52 of a magnitude below 2^21 + GRID_MAX_RINGS: absolute below 2e-9 cells), and so does the
 // query's.  The per-axis gap between the query and any point of the cell is therefore at least (c - uq - GRID_EPS) cells above the query,
@@ -140,24 +150,43 @@ __device__ __forceinline__ double grid_gap(double u, double c) {
 }
 
 // [pb, pe): the sorted records of cells xa .. xb of row (y, z) - one run, found with two binary searches; false when the row holds none
-__device__ __forceinline__ bool grid_row_span(const long long* __restrict__ cell_keys, const long long* __restrict__ cell_start, long ncells,
-                                              int xa, int xb, int y, int z, long long& pb, long long& pe) {
+__device__ __forceinline__ bool grid_row_span(const GridView& g, int xa, int xb, int y, int z, long long& pb, long long& pe) {
     const long long ka = grid_key(xa, y, z), kb = grid_key(xb, y, z) + 1;
-    const long a = grid_lower_bound(cell_keys, 0, ncells, ka);
-    if (a == ncells || cell_keys[a] >= kb) return false;
-    const long b = grid_lower_bound(cell_keys, a + 1, ncells, kb);
-    pb = cell_start[a], pe = cell_start[b];
+    const long a = grid_lower_bound(g.cell_keys, 0, g.ncells, ka);
+    if (a == g.ncells || g.cell_keys[a] >= kb) return false;
+    const long b = grid_lower_bound(g.cell_keys, a + 1, g.ncells, kb);
+    pb = g.cell_start[a], pe = g.cell_start[b];
     return true;
 }
 
-// The rows of cells around point (X, Y, Z) that can hold a point within sqrt(bound()), near rows first (0, +1, -1, +2, -2, ... in z, then
+// The candidate loop of every search: visit(d2, w) for the records of cells xa .. xb of row (y, z), d2 = (dx*dx + dy*dy) + dz*dz in fp64 from
+// (X, Y, Z) - the association every test pins - and w the record's fourth word; visit returns whether to stop, and so does the loop.
+template <class Visit>
+__device__ __forceinline__ bool grid_for_each(const GridView& g, int xa, int xb, int y, int z, double X, double Y, double Z, Visit visit) {
+    long long j, pe;
+    if (!grid_row_span(g, xa, xb, y, z, j, pe)) return false;
+    for (; j < pe; ++j) {
+        const uint4 t = g.rec[j];
+        const double dx = (double)__uint_as_float(t.x) - X, dy = (double)__uint_as_float(t.y) - Y, dz = (double)__uint_as_float(t.z) - Z;
+        if (visit((dx * dx + dy * dy) + dz * dz, t.w)) return true;
+    }
+    return false;
+}
+
+// a point in cell units, and its cell: doubles, the point may lie anywhere
+struct GridHome { double ux, uy, uz, fx, fy, fz; };
+__device__ __forceinline__ GridHome grid_home(const GridView& g, double X, double Y, double Z) {
+    const double ux = (X - g.ox) / g.cell, uy = (Y - g.oy) / g.cell, uz = (Z - g.oz) / g.cell;
+    return {ux, uy, uz, floor(ux), floor(uy), floor(uz)};
+}
+
+// The rows of cells around the point of h that can hold a point within sqrt(bound()), near rows first (0, +1, -1, +2, -2, ... in z, then
 // in y): row(xa, xb, y, z) gets the cells xa .. xb of row (y, z) and returns whether to stop.  bound() is read anew at every test.  Cell
-// coordinates are doubles until they are clamped (the point may lie anywhere); farther than the rings from the key range: no row at all.
+// coordinates are doubles until they are clamped; farther than the rings from the key range: no row at all.
 template <class Bound, class Row>
-__device__ __forceinline__ void grid_walk_rows(double X, double Y, double Z, double ox, double oy, double oz, double cell, int rings,
-                                               Bound bound, Row row) {
-    const double ux = (X - ox) / cell, uy = (Y - oy) / cell, uz = (Z - oz) / cell;
-    const double fx = floor(ux), fy = floor(uy), fz = floor(uz), B = (double)GRID_B, R = (double)rings;
+__device__ __forceinline__ void grid_walk_rows(const GridView& g, const GridHome& h, Bound bound, Row row) {
+    const double ux = h.ux, uy = h.uy, uz = h.uz, fx = h.fx, fy = h.fy, fz = h.fz, cell = g.cell, B = (double)GRID_B, R = (double)g.rings;
+    const int rings = g.rings;
     const double xlo = fmax(fx - R, -B), xhi = fmin(fx + R, B), ylo = fmax(fy - R, -B), yhi = fmin(fy + R, B);
     const double zlo = fmax(fz - R, -B), zhi = fmin(fz + R, B);
     if (!(xlo <= xhi && ylo <= yhi && zlo <= zhi)) return;
@@ -181,58 +210,68 @@ __device__ __forceinline__ void grid_walk_rows(double X, double Y, double Z, dou
     }
 }
 
-// ---- nearest.  One thread per query, the queries in the order of their own cell keys (qorder), so that the lanes of a wave walk the same
-// cells at the same pace: their record loads hit the same cache lines.
-struct GridBest { double d2; int idx; };
-
-// candidates: the points of cells xa .. xb of row (y, z); winner = smallest (d2, original index), a candidate counts iff d2 <= the limit
-// (best starts at (limit, INT_MAX))
-__device__ __forceinline__ void grid_scan_row(const uint4* __restrict__ rec, const long long* __restrict__ cell_keys,
-                                              const long long* __restrict__ cell_start, long ncells, int xa, int xb, int y, int z, double X,
-                                              double Y, double Z, GridBest& best) {
-    long long j, pe;
-    if (!grid_row_span(cell_keys, cell_start, ncells, xa, xb, y, z, j, pe)) return;
-    for (; j < pe; ++j) {
-        const uint4 t = rec[j];
-        const double dx = (double)__uint_as_float(t.x) - X, dy = (double)__uint_as_float(t.y) - Y, dz = (double)__uint_as_float(t.z) - Z;
-        const double d2 = (dx * dx + dy * dy) + dz * dz;
-        const int id = (int)t.w;
-        if (d2 < best.d2 || (d2 == best.d2 && id < best.idx)) {
-            best.d2 = d2;
-            best.idx = id;
-        }
-    }
+// The walk of a search whose bound shrinks as it finds: scan(xa, xb, y, z) = "visit these cells" gets the point's own cell first - in a dense
+// cloud it holds what the search is after, and every row after it is cut to what can still matter - and then the rows, the own row as the
+// cells on either side of the own cell, so every record is visited once.  kOneSite: every row's cells go through one call of scan in a
+// two-trip loop that is not unrolled, so a large scan (the k-nearest insert is KMAX unrolled steps) exists twice in a kernel, not four
+// times; otherwise the sides are two calls beside the plain row's, which a small scan repays where rows are many.
+template <bool kOneSite, class Bound, class Scan>
+__device__ __forceinline__ void grid_walk_home_first(const GridView& g, double X, double Y, double Z, Bound bound, Scan scan) {
+    const GridHome h = grid_home(g, X, Y, Z);
+    const double B = (double)GRID_B;
+    const bool home = fabs(h.fx) <= B && fabs(h.fy) <= B && fabs(h.fz) <= B;
+    if (home) scan((int)h.fx, (int)h.fx, (int)h.fy, (int)h.fz);
+    grid_walk_rows(g, h, bound, [&](int xa, int xb, int y, int z) {
+        const bool own = home && (double)y == h.fy && (double)z == h.fz;         // the own row: its own cell is done
+        const int hx = (int)h.fx;                                                // (read only where own)
+        if constexpr (kOneSite) {
+            int a0 = xa, b0 = xb, a1 = 1, b1 = 0;
+            if (own) b0 = min(hx - 1, xb), a1 = max(hx + 1, xa), b1 = xb;
+#pragma unroll 1
+            for (int part = 0; part < 2; ++part) {
+                const int a = part ? a1 : a0, b = part ? b1 : b0;
+                if (a <= b) scan(a, b, y, z);
+            }
+        } else if (own) {
+            if (xa < hx) scan(xa, hx - 1, y, z);
+            if (xb > hx) scan(hx + 1, xb, y, z);
+        } else scan(xa, xb, y, z);
+        return false;
+    });
 }
 
-__global__ __launch_bounds__(256) void grid_nearest_kernel(const uint4* __restrict__ rec, const long long* __restrict__ cell_keys,
-                                                           const long long* __restrict__ cell_start, long ncells, double ox, double oy, double oz,
-                                                           double cell, const float* __restrict__ queries, const long long* __restrict__ qorder,
-                                                           long m, float max_dist, int rings, long long* __restrict__ idx,
-                                                           float* __restrict__ dist) {
+// The query of thread i: its position q in the caller's order (the queries are walked in the order of their own cell keys, qorder, so that
+// the lanes of a wave walk the same cells at the same pace and their record loads hit the same cache lines) and its coordinates.
+__device__ __forceinline__ long long grid_query(const float* __restrict__ queries, const long long* __restrict__ qorder, long i, float& qx,
+                                                float& qy, float& qz) {
+    const long long q = qorder ? qorder[i] : i;
+    qx = queries[3 * q], qy = queries[3 * q + 1], qz = queries[3 * q + 2];
+    return q;
+}
+
+// ---- nearest.  One thread per query; winner = smallest (d2, original index), a candidate counts iff d2 <= the limit (the best starts at
+// (limit, INT_MAX)).
+__global__ __launch_bounds__(256) void grid_nearest_kernel(GridView g, const float* __restrict__ queries, const long long* __restrict__ qorder,
+                                                           long m, float max_dist, long long* __restrict__ idx, float* __restrict__ dist) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= m) return;
-    const long long q = qorder ? qorder[i] : i;
-    const float qx = queries[3 * q], qy = queries[3 * q + 1], qz = queries[3 * q + 2];
-    const double limit = (double)max_dist * (double)max_dist;
-    GridBest best = {limit, 0x7fffffff};
+    float qx, qy, qz;
+    const long long q = grid_query(queries, qorder, i, qx, qy, qz);
+    double best = (double)max_dist * (double)max_dist;
+    int best_idx = 0x7fffffff;
     if (grid_finite(qx, qy, qz)) {
         const double X = (double)qx, Y = (double)qy, Z = (double)qz;
-        // the query's own cell first: in a dense cloud it holds the winner, and every row after it is cut to the cells that can still beat it
-        const double fx = floor((X - ox) / cell), fy = floor((Y - oy) / cell), fz = floor((Z - oz) / cell), B = (double)GRID_B;
-        const bool home = fabs(fx) <= B && fabs(fy) <= B && fabs(fz) <= B;
-        if (home) grid_scan_row(rec, cell_keys, cell_start, ncells, (int)fx, (int)fx, (int)fy, (int)fz, X, Y, Z, best);
-        grid_walk_rows(X, Y, Z, ox, oy, oz, cell, rings, [&] { return best.d2; }, [&](int xa, int xb, int y, int z) {
-            if (home && (double)y == fy && (double)z == fz) {                    // the query's own row: its own cell is done
-                const int hx = (int)fx;
-                if (xa < hx) grid_scan_row(rec, cell_keys, cell_start, ncells, xa, hx - 1, y, z, X, Y, Z, best);
-                if (xb > hx) grid_scan_row(rec, cell_keys, cell_start, ncells, hx + 1, xb, y, z, X, Y, Z, best);
-            } else grid_scan_row(rec, cell_keys, cell_start, ncells, xa, xb, y, z, X, Y, Z, best);
-            return false;
+        grid_walk_home_first<false>(g, X, Y, Z, [&] { return best; }, [&](int xa, int xb, int y, int z) {
+            grid_for_each(g, xa, xb, y, z, X, Y, Z, [&](double d2, unsigned w) {
+                const int id = (int)w;
+                if (d2 < best || (d2 == best && id < best_idx)) best = d2, best_idx = id;
+                return false;
+            });
         });
     }
-    const bool found = best.idx != 0x7fffffff;
-    idx[q] = found ? (long long)best.idx : -1;
-    dist[q] = found ? (float)__builtin_sqrt(best.d2) : __builtin_inff();
+    const bool found = best_idx != 0x7fffffff;
+    idx[q] = found ? (long long)best_idx : -1;
+    dist[q] = found ? (float)__builtin_sqrt(best) : __builtin_inff();
 }
 
 // ---- k nearest (CloudIndex.knn / knn_mean_distance).  One thread per query, walked in qorder as above.  The list is KMAX
@@ -269,26 +308,11 @@ __device__ __forceinline__ void knn_insert(GridList<KMAX>& l, double d2, int id)
     l.idx[0] = hi ? id : l.idx[0];
 }
 
-// candidates: the points of cells xa .. xb of row (y, z), every one of them once
+// The fill both list kernels share: the KMAX slots set up for a runtime k, then the walk, own cell first (it fills the list early, and the rows
+// after it are cut to the k-th entry).  On return the live slots KMAX-k .. KMAX-1 hold the min(k, candidates) smallest (d2, index) pairs in
+// ascending order and then (limit, INT_MAX); nothing is in them for a query that is not finite.
 template <int KMAX>
-__device__ __forceinline__ void knn_scan_row(const uint4* __restrict__ rec, const long long* __restrict__ cell_keys,
-                                             const long long* __restrict__ cell_start, long ncells, int xa, int xb, int y, int z, double X,
-                                             double Y, double Z, GridList<KMAX>& l) {
-    long long j, pe;
-    if (!grid_row_span(cell_keys, cell_start, ncells, xa, xb, y, z, j, pe)) return;
-    for (; j < pe; ++j) {
-        const uint4 t = rec[j];
-        const double dx = (double)__uint_as_float(t.x) - X, dy = (double)__uint_as_float(t.y) - Y, dz = (double)__uint_as_float(t.z) - Z;
-        knn_insert(l, (dx * dx + dy * dy) + dz * dz, (int)t.w);
-    }
-}
-
-// The fill both list kernels share: the KMAX slots set up for a runtime k, then the walk.  On return the live slots KMAX-k .. KMAX-1 hold the
-// min(k, candidates) smallest (d2, index) pairs in ascending order and then (limit, INT_MAX); nothing is in them for a query that is not finite.
-template <int KMAX>
-__device__ __forceinline__ void knn_fill(const uint4* __restrict__ rec, const long long* __restrict__ cell_keys,
-                                         const long long* __restrict__ cell_start, long ncells, double ox, double oy, double oz, double cell,
-                                         float qx, float qy, float qz, int k, float max_dist, int rings, GridList<KMAX>& l) {
+__device__ __forceinline__ void knn_fill(const GridView& g, float qx, float qy, float qz, int k, float max_dist, GridList<KMAX>& l) {
     const double limit = (double)max_dist * (double)max_dist;
     const int first = KMAX - k;                                                  // the list's first live slot
 #pragma unroll
@@ -298,22 +322,11 @@ __device__ __forceinline__ void knn_fill(const uint4* __restrict__ rec, const lo
     }
     if (grid_finite(qx, qy, qz)) {
         const double X = (double)qx, Y = (double)qy, Z = (double)qz;
-        // the query's own cell first, as the nearest search does: it fills the list early, and the rows after it are cut to the k-th entry
-        const double fx = floor((X - ox) / cell), fy = floor((Y - oy) / cell), fz = floor((Z - oz) / cell), B = (double)GRID_B;
-        const bool home = fabs(fx) <= B && fabs(fy) <= B && fabs(fz) <= B;
-        if (home) knn_scan_row(rec, cell_keys, cell_start, ncells, (int)fx, (int)fx, (int)fy, (int)fz, X, Y, Z, l);
-        grid_walk_rows(X, Y, Z, ox, oy, oz, cell, rings, [&] { return l.d2[KMAX - 1]; }, [&](int xa, int xb, int y, int z) {
-            int a0 = xa, b0 = xb, a1 = 1, b1 = 0;                                // the query's own row: the cells on either side of its own
-            if (home && (double)y == fy && (double)z == fz) {
-                const int hx = (int)fx;
-                b0 = min(hx - 1, xb), a1 = max(hx + 1, xa), b1 = xb;
-            }
-#pragma unroll 1
-            for (int part = 0; part < 2; ++part) {
-                const int a = part ? a1 : a0, b = part ? b1 : b0;
-                if (a <= b) knn_scan_row(rec, cell_keys, cell_start, ncells, a, b, y, z, X, Y, Z, l);
-            }
-            return false;
+        grid_walk_home_first<true>(g, X, Y, Z, [&] { return l.d2[KMAX - 1]; }, [&](int xa, int xb, int y, int z) {
+            grid_for_each(g, xa, xb, y, z, X, Y, Z, [&](double d2, unsigned w) {
+                knn_insert(l, d2, (int)w);
+                return false;
+            });
         });
     }
 }
@@ -321,18 +334,16 @@ __device__ __forceinline__ void knn_fill(const uint4* __restrict__ rec, const lo
 // idx / dist [m, k] (slot j of a row: the j-th smallest (d2, index); unused slots -1 / +inf), count [m], mean [m] (the fp64 mean of the
 // row's sqrt(d2), summed in ascending order; +inf for an empty row); idx, dist and mean may each be null.  Every element is written once.
 template <int KMAX>
-__global__ __launch_bounds__(256) void grid_knn_kernel(const uint4* __restrict__ rec, const long long* __restrict__ cell_keys,
-                                                       const long long* __restrict__ cell_start, long ncells, double ox, double oy, double oz,
-                                                       double cell, const float* __restrict__ queries, const long long* __restrict__ qorder,
-                                                       long m, int k, float max_dist, int rings, long long* __restrict__ idx,
-                                                       float* __restrict__ dist, int* __restrict__ count, double* __restrict__ mean) {
+__global__ __launch_bounds__(256) void grid_knn_kernel(GridView g, const float* __restrict__ queries, const long long* __restrict__ qorder, long m,
+                                                       int k, float max_dist, long long* __restrict__ idx, float* __restrict__ dist,
+                                                       int* __restrict__ count, double* __restrict__ mean) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= m) return;
-    const long long q = qorder ? qorder[i] : i;
-    const float qx = queries[3 * q], qy = queries[3 * q + 1], qz = queries[3 * q + 2];
+    float qx, qy, qz;
+    const long long q = grid_query(queries, qorder, i, qx, qy, qz);
     const int first = KMAX - k;
     GridList<KMAX> l;
-    knn_fill(rec, cell_keys, cell_start, ncells, ox, oy, oz, cell, qx, qy, qz, k, max_dist, rings, l);
+    knn_fill(g, qx, qy, qz, k, max_dist, l);
     int c = 0;
     double sum = 0.0;
 #pragma unroll
@@ -388,18 +399,16 @@ __device__ __forceinline__ bool jacobi_rotate(double& app, double& aqq, double& 
 // normal [m, 3] float, curvature [m] float, count [m], mom [m, 9] double (S1 x y z, S2 xx xy xz yy yz zz about the query); normal, curvature
 // and mom may each be null.  points: the indexed cloud's original array (a record's fourth word indexes it); viewpoints [m, 3] or null.
 template <int KMAX>
-__global__ __launch_bounds__(256) void grid_normals_kernel(const uint4* __restrict__ rec, const long long* __restrict__ cell_keys,
-                                                           const long long* __restrict__ cell_start, long ncells, double ox, double oy, double oz,
-                                                           double cell, const float* __restrict__ queries, const long long* __restrict__ qorder,
-                                                           long m, int k, float max_dist, int rings, const float* __restrict__ points,
+__global__ __launch_bounds__(256) void grid_normals_kernel(GridView g, const float* __restrict__ queries, const long long* __restrict__ qorder,
+                                                           long m, int k, float max_dist, const float* __restrict__ points,
                                                            const float* __restrict__ viewpoints, float* __restrict__ normal,
                                                            float* __restrict__ curvature, int* __restrict__ count, double* __restrict__ mom) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= m) return;
-    const long long q = qorder ? qorder[i] : i;
-    const float qx = queries[3 * q], qy = queries[3 * q + 1], qz = queries[3 * q + 2];
+    float qx, qy, qz;
+    const long long q = grid_query(queries, qorder, i, qx, qy, qz);
     GridList<KMAX> l;
-    knn_fill(rec, cell_keys, cell_start, ncells, ox, oy, oz, cell, qx, qy, qz, k, max_dist, rings, l);
+    knn_fill(g, qx, qy, qz, k, max_dist, l);
     // the moments about the query, the used slots in ascending order (they are one run of the list; the others read point 0 and add nothing)
     const double X = (double)qx, Y = (double)qy, Z = (double)qz;
     int c = 0;
@@ -463,37 +472,21 @@ __global__ __launch_bounds__(256) void grid_normals_kernel(const uint4* __restri
 }
 
 // ---- the number of indexed points within a radius: d2 <= double(radius)^2, inclusive.  The bound is constant and no row stops the walk.
-__device__ __forceinline__ int count_scan_row(const uint4* __restrict__ rec, const long long* __restrict__ cell_keys,
-                                              const long long* __restrict__ cell_start, long ncells, int xa, int xb, int y, int z, double X,
-                                              double Y, double Z, double limit) {
-    long long j, pe;
-    int c = 0;
-    if (!grid_row_span(cell_keys, cell_start, ncells, xa, xb, y, z, j, pe)) return 0;
-    for (; j < pe; ++j) {
-        const uint4 t = rec[j];
-        const double dx = (double)__uint_as_float(t.x) - X, dy = (double)__uint_as_float(t.y) - Y, dz = (double)__uint_as_float(t.z) - Z;
-        const double d2 = (dx * dx + dy * dy) + dz * dz;
-        c += d2 <= limit ? 1 : 0;
-    }
-    return c;
-}
-
-__global__ __launch_bounds__(256) void grid_count_within_kernel(const uint4* __restrict__ rec, const long long* __restrict__ cell_keys,
-                                                                const long long* __restrict__ cell_start, long ncells, double ox, double oy,
-                                                                double oz, double cell, const float* __restrict__ queries,
-                                                                const long long* __restrict__ qorder, long m, float radius, int rings,
-                                                                int* __restrict__ count) {
+__global__ __launch_bounds__(256) void grid_count_within_kernel(GridView g, const float* __restrict__ queries, const long long* __restrict__ qorder,
+                                                                long m, float radius, int* __restrict__ count) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= m) return;
-    const long long q = qorder ? qorder[i] : i;
-    const float qx = queries[3 * q], qy = queries[3 * q + 1], qz = queries[3 * q + 2];
+    float qx, qy, qz;
+    const long long q = grid_query(queries, qorder, i, qx, qy, qz);
     const double limit = (double)radius * (double)radius;
     int c = 0;
     if (grid_finite(qx, qy, qz)) {
         const double X = (double)qx, Y = (double)qy, Z = (double)qz;
-        grid_walk_rows(X, Y, Z, ox, oy, oz, cell, rings, [=] { return limit; }, [&](int xa, int xb, int y, int z) {
-            c += count_scan_row(rec, cell_keys, cell_start, ncells, xa, xb, y, z, X, Y, Z, limit);
-            return false;
+        grid_walk_rows(g, grid_home(g, X, Y, Z), [=] { return limit; }, [&](int xa, int xb, int y, int z) {
+            return grid_for_each(g, xa, xb, y, z, X, Y, Z, [&](double d2, unsigned) {
+                c += d2 <= limit ? 1 : 0;
+                return false;
+            });
         });
     }
     count[q] = c;
@@ -511,41 +504,26 @@ __global__ __launch_bounds__(256) void grid_count_within_kernel(const uint4* __r
 #define THIN_KEPT 1
 #define THIN_REMOVED 2
 
-// the lower-rank neighbours among the points of cells xa .. xb of row (y, z): true when one of them is KEPT; wait: one of them is UNDECIDED
-__device__ __forceinline__ bool thin_scan_row(const uint4* __restrict__ rec, const long long* __restrict__ cell_keys,
-                                              const long long* __restrict__ cell_start, long ncells, int xa, int xb, int y, int z, double X,
-                                              double Y, double Z, unsigned rank, double limit, const unsigned char* state, bool& wait) {
-    long long j, pe;
-    if (!grid_row_span(cell_keys, cell_start, ncells, xa, xb, y, z, j, pe)) return false;
-    for (; j < pe; ++j) {
-        const uint4 t = rec[j];
-        if (t.w >= rank) continue;                                               // later in the visiting order, or the point itself
-        const double dx = (double)__uint_as_float(t.x) - X, dy = (double)__uint_as_float(t.y) - Y, dz = (double)__uint_as_float(t.z) - Z;
-        const double d2 = (dx * dx + dy * dy) + dz * dz;
-        if (!(d2 <= limit)) continue;
-        const unsigned char s = state[t.w];
-        if (s == THIN_KEPT) return true;
-        wait |= s == THIN_UNDECIDED;
-    }
-    return false;
-}
-
 // One thread per entry of the active list (sorted positions, ascending: the lanes of a wave sit in the same cells; NULL: 0 .. m-1).  The walk
-// runs against the fixed limit radius^2 and stops at the first KEPT neighbour.
-__global__ __launch_bounds__(256) void grid_thin_round_kernel(const uint4* __restrict__ rec, const long long* __restrict__ cell_keys,
-                                                              const long long* __restrict__ cell_start, long ncells, double ox, double oy,
-                                                              double oz, double cell, const int* __restrict__ active, long m, float radius,
-                                                              int rings, unsigned char* state) {
+// runs against the fixed limit radius^2 over the neighbours of lower rank (the rank is in the record: tested first, before d2 is needed, and
+// the state byte is loaded last) and stops at the first KEPT one; wait: one of them is UNDECIDED.
+__global__ __launch_bounds__(256) void grid_thin_round_kernel(GridView g, const int* __restrict__ active, long m, float radius,
+                                                              unsigned char* state) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= m) return;
-    const uint4 me = rec[active ? (long)active[i] : i];
+    const uint4 me = g.rec[active ? (long)active[i] : i];
     const unsigned rank = me.w;
     if (state[rank] != THIN_UNDECIDED) return;                                   // decided since the list was compacted
     const double limit = (double)radius * (double)radius;
     const double X = (double)__uint_as_float(me.x), Y = (double)__uint_as_float(me.y), Z = (double)__uint_as_float(me.z);
     bool kept_near = false, wait = false;
-    grid_walk_rows(X, Y, Z, ox, oy, oz, cell, rings, [=] { return limit; }, [&](int xa, int xb, int y, int z) {
-        return kept_near = thin_scan_row(rec, cell_keys, cell_start, ncells, xa, xb, y, z, X, Y, Z, rank, limit, state, wait);
+    grid_walk_rows(g, grid_home(g, X, Y, Z), [=] { return limit; }, [&](int xa, int xb, int y, int z) {
+        return kept_near = grid_for_each(g, xa, xb, y, z, X, Y, Z, [&](double d2, unsigned w) {
+            if (w >= rank || !(d2 <= limit)) return false;                       // later in the visiting order, the point itself, or too far
+            const unsigned char s = state[w];
+            wait |= s == THIN_UNDECIDED;
+            return s == THIN_KEPT;
+        });
     });
     if (kept_near) state[rank] = THIN_REMOVED;
     else if (!wait) state[rank] = THIN_KEPT;
@@ -669,10 +647,12 @@ extern "C" int cer_grid_cells_i64(const long long* keys, long n, const long long
     return CER_OK;
 }
 
-// what both searches check, in the order the tests pin: the three sizes; frame and reach -> CER_EINVAL; more cells than records, !shape_ok,
-// too many rings -> CER_ESHAPE; an empty side -> CER_OK (0: nothing to launch); null pointers; alignment.  Else -> the walk's rings (>= 1).
+// what every search checks, in the order the tests pin: the three sizes; frame and reach -> CER_EINVAL; more cells than records, !shape_ok,
+// too many rings -> CER_ESHAPE; an empty side -> CER_OK (0: nothing to launch); null pointers; alignment.  Else -> the walk's rings (>= 1),
+// and g is the index as the kernels take it.
 static int grid_search_rings(const void* records, long n, const long long* cell_keys, const long long* cell_start, long ncells,
-                             const double* origin, double cell, long m, float reach, bool reach_ok, bool shape_ok, bool pointers_ok) {
+                             const double* origin, double cell, long m, float reach, bool reach_ok, bool shape_ok, bool pointers_ok,
+                             GridView& g) {
     int rc = grid_size_check(n);
     if (rc == CER_OK) rc = grid_size_check(m);
     if (rc == CER_OK) rc = grid_size_check(ncells);
@@ -684,17 +664,27 @@ static int grid_search_rings(const void* records, long n, const long long* cell_
     if (m == 0 || n == 0 || ncells == 0) return CER_OK;
     if (!records || !cell_keys || !cell_start || !pointers_ok) return CER_EINVAL;
     if ((uintptr_t)records & 15) return CER_EALIGN;
-    return (int)rings + 1;
+    g = {(const uint4*)records, cell_keys, cell_start, ncells, origin[0], origin[1], origin[2], cell, (int)rings + 1};
+    return g.rings;
+}
+
+// the list kernels' three widths: launch(K) with K the integral constant 8, 16 or 32, the narrowest that holds k
+template <class Launch>
+static void knn_dispatch(int k, Launch launch) {
+    if (k <= 8) launch(std::integral_constant<int, 8>());
+    else if (k <= 16) launch(std::integral_constant<int, 16>());
+    else launch(std::integral_constant<int, 32>());
 }
 
 extern "C" int cer_grid_nearest_f32(const void* records, long n, const long long* cell_keys, const long long* cell_start, long ncells,
                                     const double* origin, double cell, const float* queries, const long long* qorder, long m, float max_dist,
                                     long long* idx, float* dist, void* stream) {
+    GridView g;
     const int rings = grid_search_rings(records, n, cell_keys, cell_start, ncells, origin, cell, m, max_dist, max_dist >= 0.0f, true,
-                                        queries && idx && dist);
+                                        queries && idx && dist, g);
     if (rings <= 0) return rings;                            // (an empty target: the caller fills idx = -1, dist = +inf)
-    hipLaunchKernelGGL(grid_nearest_kernel, dim3(grid_blocks(m, 256)), dim3(256), 0, (hipStream_t)stream, (const uint4*)records, cell_keys,
-                       cell_start, ncells, origin[0], origin[1], origin[2], cell, queries, qorder, m, max_dist, rings, idx, dist);
+    hipLaunchKernelGGL(grid_nearest_kernel, dim3(grid_blocks(m, 256)), dim3(256), 0, (hipStream_t)stream, g, queries, qorder, m, max_dist, idx,
+                       dist);
     CER_RETURN_IF_LAUNCH_FAILED();
     return CER_OK;
 }
@@ -703,18 +693,14 @@ extern "C" int cer_grid_nearest_f32(const void* records, long n, const long long
 extern "C" int cer_grid_knn_f32(const void* records, long n, const long long* cell_keys, const long long* cell_start, long ncells,
                                 const double* origin, double cell, const float* queries, const long long* qorder, long m, int k, float max_dist,
                                 long long* idx, float* dist, int* count, double* mean, void* stream) {
+    GridView g;
     const int rings = grid_search_rings(records, n, cell_keys, cell_start, ncells, origin, cell, m, max_dist, max_dist >= 0.0f && k >= 1,
-                                        k <= CER_KNN_MAX, queries && count);
+                                        k <= CER_KNN_MAX, queries && count, g);
     if (rings <= 0) return rings;                            // (an empty side: the caller fills idx = -1, dist = mean = +inf, count = 0)
-    const dim3 grid(grid_blocks(m, 256)), block(256);
-    hipStream_t st = (hipStream_t)stream;
-#define KNN_LAUNCH(KMAX)                                                                                                                  \
-    hipLaunchKernelGGL(grid_knn_kernel<KMAX>, grid, block, 0, st, (const uint4*)records, cell_keys, cell_start, ncells, origin[0], origin[1], \
-                       origin[2], cell, queries, qorder, m, k, max_dist, rings, idx, dist, count, mean)
-    if (k <= 8) KNN_LAUNCH(8);
-    else if (k <= 16) KNN_LAUNCH(16);
-    else KNN_LAUNCH(32);
-#undef KNN_LAUNCH
+    knn_dispatch(k, [&](auto K) {
+        hipLaunchKernelGGL(grid_knn_kernel<decltype(K)::value>, dim3(grid_blocks(m, 256)), dim3(256), 0, (hipStream_t)stream, g, queries, qorder, m,
+                           k, max_dist, idx, dist, count, mean);
+    });
     CER_RETURN_IF_LAUNCH_FAILED();
     return CER_OK;
 }
@@ -724,18 +710,14 @@ extern "C" int cer_grid_normals_f32(const void* records, long n, const long long
                                     const double* origin, double cell, const float* queries, const long long* qorder, long m, int k,
                                     float max_dist, const float* points, const float* viewpoints, float* normal, float* curvature, int* count,
                                     double* mom, void* stream) {
+    GridView g;
     const int rings = grid_search_rings(records, n, cell_keys, cell_start, ncells, origin, cell, m, max_dist, max_dist >= 0.0f && k >= 1,
-                                        k <= CER_KNN_MAX, queries && count && points);
+                                        k <= CER_KNN_MAX, queries && count && points, g);
     if (rings <= 0) return rings;                            // (an empty side: the caller fills normal = 0, curvature = NaN, count = 0, mom = 0)
-    const dim3 grid(grid_blocks(m, 256)), block(256);
-    hipStream_t st = (hipStream_t)stream;
-#define NORMALS_LAUNCH(KMAX)                                                                                                                  \
-    hipLaunchKernelGGL(grid_normals_kernel<KMAX>, grid, block, 0, st, (const uint4*)records, cell_keys, cell_start, ncells, origin[0], origin[1], \
-                       origin[2], cell, queries, qorder, m, k, max_dist, rings, points, viewpoints, normal, curvature, count, mom)
-    if (k <= 8) NORMALS_LAUNCH(8);
-    else if (k <= 16) NORMALS_LAUNCH(16);
-    else NORMALS_LAUNCH(32);
-#undef NORMALS_LAUNCH
+    knn_dispatch(k, [&](auto K) {
+        hipLaunchKernelGGL(grid_normals_kernel<decltype(K)::value>, dim3(grid_blocks(m, 256)), dim3(256), 0, (hipStream_t)stream, g, queries, qorder,
+                           m, k, max_dist, points, viewpoints, normal, curvature, count, mom);
+    });
     CER_RETURN_IF_LAUNCH_FAILED();
     return CER_OK;
 }
@@ -743,11 +725,12 @@ extern "C" int cer_grid_normals_f32(const void* records, long n, const long long
 extern "C" int cer_grid_count_within_f32(const void* records, long n, const long long* cell_keys, const long long* cell_start, long ncells,
                                          const double* origin, double cell, const float* queries, const long long* qorder, long m,
                                          float radius, int* count, void* stream) {
+    GridView g;
     const int rings = grid_search_rings(records, n, cell_keys, cell_start, ncells, origin, cell, m, radius, radius >= 0.0f, true,
-                                        queries && count);
+                                        queries && count, g);
     if (rings <= 0) return rings;                            // (an empty side: the caller fills count = 0)
-    hipLaunchKernelGGL(grid_count_within_kernel, dim3(grid_blocks(m, 256)), dim3(256), 0, (hipStream_t)stream, (const uint4*)records, cell_keys,
-                       cell_start, ncells, origin[0], origin[1], origin[2], cell, queries, qorder, m, radius, rings, count);
+    hipLaunchKernelGGL(grid_count_within_kernel, dim3(grid_blocks(m, 256)), dim3(256), 0, (hipStream_t)stream, g, queries, qorder, m, radius,
+                       count);
     CER_RETURN_IF_LAUNCH_FAILED();
     return CER_OK;
 }
@@ -755,11 +738,12 @@ extern "C" int cer_grid_count_within_f32(const void* records, long n, const long
 extern "C" int cer_grid_thin_round_f32(const void* records, long n, const long long* cell_keys, const long long* cell_start, long ncells,
                                        const double* origin, double cell, const int* active, long n_active, float radius,
                                        unsigned char* state, void* stream) {
+    GridView g;
     const int rings = grid_search_rings(records, n, cell_keys, cell_start, ncells, origin, cell, n_active, radius,
-                                        radius > 0.0f && grid_is_finite((double)radius), n_active <= n, state != nullptr);
+                                        radius > 0.0f && grid_is_finite((double)radius), n_active <= n, state != nullptr, g);
     if (rings <= 0) return rings;                            // (active may be NULL: the list 0 .. n_active-1)
-    hipLaunchKernelGGL(grid_thin_round_kernel, dim3(grid_blocks(n_active, 256)), dim3(256), 0, (hipStream_t)stream, (const uint4*)records,
-                       cell_keys, cell_start, ncells, origin[0], origin[1], origin[2], cell, active, n_active, radius, rings, state);
+    hipLaunchKernelGGL(grid_thin_round_kernel, dim3(grid_blocks(n_active, 256)), dim3(256), 0, (hipStream_t)stream, g, active, n_active, radius,
+                       state);
     CER_RETURN_IF_LAUNCH_FAILED();
     return CER_OK;
 }
