@@ -17,6 +17,12 @@ typedef float cer_f2 __attribute__((ext_vector_type(2)));
 typedef _Float16 cer_h2 __attribute__((ext_vector_type(2)));
 typedef _Float16 cer_h8 __attribute__((ext_vector_type(8)));
 #if defined(__HIPCC__)
+// one element (epilogues that hold one value per lane)
+__device__ __forceinline__ void cer_split1(float v, _Float16& hi, _Float16& lo) {
+    const float x = fminf(fmaxf(v, -65504.0f), 65504.0f);
+    hi = (_Float16)x;
+    lo = (_Float16)((x - (float)hi) * 2048.0f);
+}
 __device__ __forceinline__ void cer_split2(cer_f2 x, cer_h2& hi, cer_h2& lo) {
     x = __builtin_elementwise_min(__builtin_elementwise_max(x, (cer_f2){-65504.0f, -65504.0f}), (cer_f2){65504.0f, 65504.0f});
     hi = __builtin_convertvector(x, cer_h2);

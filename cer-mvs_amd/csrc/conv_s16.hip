@@ -30,9 +30,6 @@
 //   * the hoisted `init` term / bias is the accumulators' initial value (16-byte loads in the prologue).
 #include "conv_s16_shared.hpp"
 #include "pack.hpp"       // weight layouts: pack.cpp
-#ifndef SX_MT8
-#define SX_MT8 0
-#endif
 
 struct SxStage {                           // what to put into the NEXT activation buffer
     int kind;                              // 0 nothing, 2 tensor half-chunk, 1 literal disparity group, 3 collapsed disparity group
@@ -41,8 +38,10 @@ struct SxStage {                           // what to put into the NEXT activati
     int g;                                 // disparity group index
 };
 
+// Two blocks per CU.  (Three for the 64-channel fp8-correction kernels - 167 VGPRs, 8 spilled, 8-row tiles - measured slower: q 70.3 us against
+// 65.2 at 296 x 400; one block of eight m-tiles per wave: profiles/r06_mt8_one_block_per_cu.txt)
 template <int WM_, int WN_, int MT, int EPI, int F8>
-__global__ __launch_bounds__(256, (WM_ == 2 && F8 && SX_OCC3) ? 3 : (MT >= 8 ? 1 : 2)) void conv3x3_s16_kernel(const S16Args a) {
+__global__ __launch_bounds__(256, 2) void conv3x3_s16_kernel(const S16Args a) {
     constexpr int TH = WM_ * 2 * MT, HR = TH + 2;
     constexpr int ABUF = HR * (F8 ? SX_ROWB8 : SX_ROWB);
     constexpr int NPIX = HR * SX_HW, NITEM = NPIX * 4, ITEMS = (NITEM + 255) / 256;
@@ -119,7 +118,7 @@ __global__ __launch_bounds__(256, (WM_ == 2 && F8 && SX_OCC3) ? 3 : (MT >= 8 ? 1
     // than three blocks per CU pair the SECOND workgroup of a CU (HW_ID.TG_ID parity) of the first round of blocks sleeps for about a quarter of a chunk
     // loop before it starts: one block's memory phases then fall under the other's matrix phase.  Timing only - results cannot change.  Same-box A/B
     // (profiles/r06_stagger_ab.txt): + 1.7 % depth maps per second one at a time (four pairs, every pair), +- 0 with three in flight; longer sleeps lose.
-    if ((!SX_STAGGER_WM1 || WM_ == 1) && (int)gridDim.x > 3 * SX_STAGGER_CUS && (int)blockIdx.x < 2 * SX_STAGGER_CUS) {
+    if ((int)gridDim.x > 3 * SX_STAGGER_CUS && (int)blockIdx.x < 2 * SX_STAGGER_CUS) {
         const unsigned hw = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));    // HW_REG_HW_ID
         if ((hw >> SX_STAGGER_BIT) & 1)
             for (int i = 0; i < nsteps * SX_STAGGER; ++i) __builtin_amdgcn_s_sleep(1);      // 64 cycles each
@@ -511,8 +510,7 @@ __global__ __launch_bounds__(256, (WM_ == 2 && F8 && SX_OCC3) ? 3 : (MT >= 8 ? 1
     // than an L2 round trip: their chunk loop ran at 1.75 x its pipe floor (tools/trace_s16.py --conv q: 8.0 k cycles per chunk against
     // 4.6 k; alone on a CU 388 per 16-channel step against 128).  They request two steps ahead (ring of three; 9 taps = 3 x 3: no slot swap):
     // 6.7 k per chunk.
-    constexpr int WR = (F8 && ((WM_ == 2 && MT == 2 && SX_WRING3) || MT >= 8)) ? 3 : 2;         // (three m-tiles per wave: 229 VGPRs already, and 384 pipe cycles per step)
-    constexpr bool WSPLIT = F8 && WR == 2 && SX_WSPLIT;                           // two slots, refilled part by part (see mma8_roll)
+    constexpr int WR = (F8 && WM_ == 2 && MT == 2) ? 3 : 2;                       // (three m-tiles per wave: 229 VGPRs already, and 384 pipe cycles per step)
     W8 w8[WR];
     auto load_w8 = [&](W8& f, int cstep) {                 // (clamped: the steps past the tensors are never multiplied)
         const char* p = wlane8 + (long)min(cstep, (nsteps_t >> 1) - 1) * (2 * wstep);
@@ -523,7 +521,7 @@ __global__ __launch_bounds__(256, (WM_ == 2 && F8 && SX_OCC3) ? 3 : (MT >= 8 ? 1
     // the steps of the disparity source follow the tensors' (same bytes per 16-channel step in both forms)
     if (F8 && ngroups_t > 0) {
         load_w8(w8[0], 0);
-        if constexpr (WR == 3 || WSPLIT) load_w8(w8[1], 1);
+        if constexpr (WR == 3) load_w8(w8[1], 1);
     } else {
         load_w(fw[0], 0);
         load_w(fw[1], 1);
@@ -636,32 +634,23 @@ __global__ __launch_bounds__(256, (WM_ == 2 && F8 && SX_OCC3) ? 3 : (MT >= 8 ? 1
             if constexpr (F6) return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(w.q.v(), x.v(), c, 2, 2, 0, w.q.scale(), 0, x.scale());
             else return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(w.q.v(), x.v(), c, 0, 0, 0, 127, 0, 130);
         };
-        // `refill` (WSPLIT kernels, round 6): chunk step whose weights replace this slot's, PART BY PART, as soon as the part's last MFMA of this
-        // tap has been issued - h0 behind the first group, h1 behind the second, the 8- / 6-bit operand behind the third.  Every part then has
-        // 1 2/3 taps between its request and its use with the same two register slots (loading a whole slot at the top of the tap before its
-        // use gave the f16 hi part of half-chunk 0 ONE tap: with the FP6 form's 768-cycle taps that is less than an L2 round trip, and the
-        // chunk loop ran at 1 100 cycles per tap - 7.9 k per chunk with the weights not streamed at all, tools/trace_s16.py).  -1: no refill.
-        auto mma8_roll = [&](W8& w, int pa, int rowoff, int refill) {
-            const char* wp = wlane8 + (long)min(max(refill, 0), (nsteps_t >> 1) - 1) * (2 * wstep);
+        // (a weight slot is loaded whole, one chunk step ahead; refilling it part by part behind the MFMA group that used the part measured no
+        // faster inside the forward and spilled 16 registers: profiles/r06_wsplit_ab.txt)
+        auto mma8_roll = [&](W8& w, int pa, int rowoff) {
 #pragma unroll
             for (int m = 0; m < MT; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w.h0, fx.h[m], acc[m], 0, 0, 0);
-            if (WSPLIT && refill >= 0) w.h0 = *reinterpret_cast<const half8*>(wp);
 #pragma unroll
             for (int m = 0; m < MT; ++m) {
                 acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w.h1, fx.l[m], acc[m], 0, 0, 0);
                 fx.h[m] = *reinterpret_cast<const half8*>(sx_smem + pa + (2 * m) * SX_ROWB8 + rowoff);
                 __builtin_amdgcn_sched_barrier(0);
             }
-            if (WSPLIT && refill >= 0) w.h1 = *reinterpret_cast<const half8*>(wp + 1024);
 #pragma unroll
             for (int m = 0; m < MT; ++m) {
                 acc[m] = mma_corr(w, f8[m], acc[m]);
                 fx.l[m] = *reinterpret_cast<const half8*>(sx_smem + (pa ^ 16) + (2 * m) * SX_ROWB8 + rowoff);
                 f8[m].load(sx_smem + (pa ^ 64) + (2 * m) * SX_ROWB8 + rowoff, sx_smem + (pa ^ 80) + (2 * m) * SX_ROWB8 + rowoff);
                 __builtin_amdgcn_sched_barrier(0);
-            }
-            if (WSPLIT && refill >= 0) {
-                w.q.load(wp + 2048, wp + 3072);
             }
         };
         // the last tap of the last chunk rolls in the first operands of the disparity section (16-channel layout, f16 hi | lo)
@@ -695,12 +684,11 @@ __global__ __launch_bounds__(256, (WM_ == 2 && F8 && SX_OCC3) ? 3 : (MT >= 8 ? 1
                 // the first two slices of the disparity section instead
                 W8& wc = w8[WR == 3 ? t % 3 : (t & 1)];
                 W8& wn = w8[WR == 3 ? (t + 2) % 3 : ((t + 1) & 1)];
-                if (!WSPLIT && (WR == 3 ? (t < 7 || !last) : (t < 8 || !last))) load_w8(wn, gi * 9 + t + WR - 1);
+                if (WR == 3 ? (t < 7 || !last) : (t < 8 || !last)) load_w8(wn, gi * 9 + t + WR - 1);
                 if (t == 8 && last) { load_w(fw[0], nsteps_t); load_w(fw[1], nsteps_t + 1); }     // (the free weight slot's registers)
                 __builtin_amdgcn_sched_barrier(0);
-                const int refill = (WSPLIT && (t < 7 || !last)) ? gi * 9 + t + 2 : -1;
-                if (t < 8) mma8_roll(wc, (xa[(t + 1) % 3] ^ vary) + bufC, ((t + 1) / 3) * SX_ROWB8, refill);
-                else if (!last) mma8_roll(wc, (xa[0] ^ vary) + bufN, 0, refill);
+                if (t < 8) mma8_roll(wc, (xa[(t + 1) % 3] ^ vary) + bufC, ((t + 1) / 3) * SX_ROWB8);
+                else if (!last) mma8_roll(wc, (xa[0] ^ vary) + bufN, 0);
                 else mma8_last(wc, xh[1] + bufN, xl[1] + bufN, SX_ROWB);       // (collapsed disparity group or nothing: see the launcher)
             }
             if constexpr (WR == 2) {
@@ -1097,9 +1085,6 @@ extern "C" int cer_conv3x3_s16(const cer_conv_inputs* in, const int* log2sx, con
         }
         return best_mt;
     };
-#ifdef SX_PROBE          // probe builds (tools/archive/r05/mkprobe.sh): ONE kernel configuration - the 64-output-channel fp8-correction form - compiled in seconds
-    return sx_launch<2, 2, 2, 1>(a, epi, st);
-#else
     // the fp8-correction kernels evaluate a disparity source in the collapsed form with the rim correction only
     if (corr_fp8 && nd == 1 && !(packed_collapsed && edge_w)) return CER_ESHAPE;
 #if CER_WITH_SXPC
@@ -1114,11 +1099,6 @@ extern "C" int cer_conv3x3_s16(const cer_conv_inputs* in, const int* log2sx, con
 #endif
     if (Cout % 128 == 0) {
         int mt = tile_mt;
-#if SX_MT8
-        // experiment (round 6): ONE block per CU, eight m-tiles (16 rows) per wave - a weight slice is fetched once per CU and tap instead of twice
-        if (mt == 8 && corr_fp6) return sx_launch<1, 4, 8, 2>(a, epi, st);
-        if (mt == 8 && corr_fp8) return sx_launch<1, 4, 8, 1>(a, epi, st);
-#endif
         if (mt != 2 && mt != 4) mt = pick(2, 2, 4, Cout / 128) == 2 ? 2 : 4;
         if (corr_fp6) return mt == 2 ? sx_launch<1, 4, 2, 2>(a, epi, st) : sx_launch<1, 4, 4, 2>(a, epi, st);
         if (corr_fp8) return mt == 2 ? sx_launch<1, 4, 2, 1>(a, epi, st) : sx_launch<1, 4, 4, 1>(a, epi, st);
@@ -1134,7 +1114,6 @@ extern "C" int cer_conv3x3_s16(const cer_conv_inputs* in, const int* log2sx, con
     }
     if (mt < 2 || mt > 4) mt = pick(4, 2, 4, Cout / 64);
     return mt == 2 ? sx_launch<2, 2, 2, 0>(a, epi, st) : mt == 3 ? sx_launch<2, 2, 3, 0>(a, epi, st) : sx_launch<2, 2, 4, 0>(a, epi, st);
-#endif
 }
 
 // ---- layout conversion (model load / API boundaries / tests): plain fp32 [h*w, C] <-> the m-tile-major layouts of the s16 convs.

@@ -24,38 +24,13 @@ typedef int intx8 __attribute__((ext_vector_type(8)));
 // excluded by micro-tests then.  Round 4 found what fails on this chip - packed-fp32 instructions that take their low result from src1's
 // high half, next to f16 MFMA waves (tools/check_isa.py) - and the statement most likely only changed what hipcc emitted
 // around it; the variant is gone and cannot be re-checked.  The form that ships contains no such instruction with or without the
-// statement (-DSX_NO_STORE_WAIT: same scan result) and never failed either way.
-#ifndef SX_NO_STORE_WAIT
+// statement and never failed either way.
 #define SX_LDS_STORE_WAIT() asm volatile("s_nop 3" ::: "memory")
-#else
-#define SX_LDS_STORE_WAIT() do { } while (0)
-#endif
-#ifndef SX_OCC3
-#define SX_OCC3 0    // 1: the 64-channel fp8-correction kernels aim at three blocks per CU (167 VGPRs, 8 spilled; fits with 8-row tiles, tile_mt 2:
-                     // 52.7 KB of LDS per block).  Measured at 296 x 400: q 70.3 us against 65.2 (default, 12-row tiles, two blocks), corr2 32.1 / 32.3 - off
-#endif
-#ifndef SX_WRING3
-#define SX_WRING3 1  // the 64-output-channel fp8-correction kernels request their weight slices two chunk steps ahead (ring of three register slots)
-#endif
-#ifndef SX_WSPLIT
-#define SX_WSPLIT 0  // 1: the fp8- / FP6-correction kernels with two weight slots refill a slot part by part behind the MFMA group that used the part
-                     // (every part gets 1 2/3 taps between request and use instead of 1 .. 1 2/3).  Round 6, same-box A/B (profiles/r06_wsplit_ab.txt):
-                     // z|r stand-alone 98.4-99.4 against 101.8-102.7 us in the fp8 form but 95.6 against 92.6 in the FP6 form, delta 78.7 against
-                     // 77.0; inside the forward 95.5-96.1 against 96.2-96.4 us and the same depth maps per second - and 16 spilled registers
-                     // (outside the chunk loop) where the default has none.  Off.
-#endif
 #ifndef SX_STAGGER
 #define SX_STAGGER 4       // conv_s16.hip: delay of a CU's second workgroup in the first round of blocks, in 64-cycle units per 16-channel step of the launch (0: off)
 #endif
-#ifndef SX_STAGGER_BIT
 #define SX_STAGGER_BIT 16  // HW_ID bit that tells the two workgroups of a CU apart: 16 = thread-group id parity (0 = wave slot parity: measured equal)
-#endif
-#ifndef SX_STAGGER_WM1
-#define SX_STAGGER_WM1 0   // 1: only the 128-output-channel launches (1 x 4 wave layout: z|r gates, delta head)
-#endif
-#ifndef SX_STAGGER_CUS
-#define SX_STAGGER_CUS 256
-#endif
+#define SX_STAGGER_CUS 256 // launches of more than 3 x this many blocks are staggered, in their first 2 x this many blocks
 #ifndef SX_TRACE
 #define SX_TRACE 0   // variant builds only (tools/trace_s16.py): per wave cycle stamps + HW_ID written to `aux2` (GATES: unused there)
 #endif

@@ -164,39 +164,6 @@ __device__ __noinline__ float cl_direct(const _Float16* __restrict__ f1t, long p
     return d[0] * (wn0 * wm0) + d[1] * (wn0 * wm1) + d[2] * (wn1 * wm0) + d[3] * (wn1 * wm1);
 }
 
-// ---- cycle statistics of the one-line kernel (variant build -DCL_STATS=1: tools/archive/r05/mkvariant.sh clstats cost_lines.hip -DCL_STATS=1;
-// tools/archive/r05/stats_cost_lines1.py).  Wave 0's view of a tile's phases, summed over all tiles with atomics.
-#ifndef CL_STATS
-#define CL_STATS 0
-#endif
-
-#if CL_STATS
-#define CL_SLOTS 4096
-__device__ unsigned long long cl_stats[CL_SLOTS][16];      // hashed by block: no contention on the counters; the host sums the slots
-#define CL_CLK() __builtin_readcyclecounter()
-// (durations are collected in registers of thread 0 and added ONCE per tile, behind its last store: atomics inside the chunk loop would sit in
-// the same vmcnt queue as the fragment loads)
-#define CL_STAT(i_, v_) do { if (threadIdx.x == 0) cl_acc[i_] += (unsigned long long)(v_); } while (0)
-#define CL_FLUSH() do { if (threadIdx.x == 0) for (int q_ = 0; q_ < 16; ++q_) if (cl_acc[q_]) atomicAdd(&cl_stats[blockIdx.x & (CL_SLOTS - 1)][q_], cl_acc[q_]); } while (0)
-extern "C" int cer_cost_lines1_stats(unsigned long long* out, int reset) {
-    if (!out) return CER_EINVAL;
-    static unsigned long long hostbuf[CL_SLOTS][16];
-    hipError_t e = hipMemcpyFromSymbol(hostbuf, HIP_SYMBOL(cl_stats), sizeof(hostbuf));
-    if (e != hipSuccess) return (int)e;
-    for (int q = 0; q < 16; ++q) { out[q] = 0; for (int sl = 0; sl < CL_SLOTS; ++sl) out[q] += hostbuf[sl][q]; }
-    if (reset) {
-        memset(hostbuf, 0, sizeof(hostbuf));
-        e = hipMemcpyToSymbol(HIP_SYMBOL(cl_stats), hostbuf, sizeof(hostbuf));
-        if (e != hipSuccess) return (int)e;
-    }
-    return CER_OK;
-}
-#else
-#define CL_CLK() 0ull
-#define CL_STAT(i_, v_) do { (void)sizeof(v_); } while (0)
-#define CL_FLUSH() do { } while (0)
-#endif
-
 // The band of one (view, segment, line) tile: what cl_tile's chunk loop, projection and gather need to know about where the tile's samples
 // lie in the source map.  Round 6: computed by cost_lines_bands_kernel in a pass of its own (one WAVE per tile) instead of by wave 0 of
 // every tile block while its other three waves sat at a barrier (profiles/r05_cost_lines_phases.txt: 15.3 k of a tile's 68 k cycles).
@@ -425,10 +392,6 @@ __device__ __forceinline__ void cl_tile(const ClArgs& A, const int v, const int 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 31, kg = lane >> 5;
     const int h1 = A.h1, w1 = A.w1, h2 = A.h2, w2 = A.w2, D = A.D;
-    const unsigned long long cl_t0 = CL_CLK();
-#if CL_STATS
-    unsigned long long cl_acc[16] = {0};
-#endif
     // ---- the tile's band (cost_lines_bands_kernel): a uniform address - scalar loads, requested before anything else
     const ClBand* rec = A.bands + (long)v * A.tpv + rem;
     int smaj = rec->smaj, nchunks = rec->nchunks, R = rec->R, Wc = rec->Wc, cmin = rec->cmin, cmax = rec->cmax, dir = rec->dir;
@@ -453,8 +416,6 @@ __device__ __forceinline__ void cl_tile(const ClArgs& A, const int v, const int 
     }
     auto project = [&](int k, float& u, float& w) -> bool { return L.project(k, u, w); };
 
-    const unsigned long long cl_t1 = CL_CLK();
-    CL_STAT(0, 1); CL_STAT(3, cl_t1 - cl_t0);
     smaj = __builtin_amdgcn_readfirstlane(smaj);
     const int Wmaj = smaj ? h2 : w2, Wmin = smaj ? w2 : h2;
     const int wp = w2 + 4;
@@ -533,8 +494,6 @@ __device__ __forceinline__ void cl_tile(const ClArgs& A, const int v, const int 
     }
     if (!valid) inmask = dmask = 0u;                        // (a slot without a pixel: nothing to gather, nothing is written out)
 
-    const unsigned long long cl_t2 = CL_CLK();
-    CL_STAT(4, cl_t2 - cl_t1);
     // ---- per-lane cursor over the samples of `inmask`, lowest hypothesis first (a lane only ever reads descriptors it wrote itself)
     const int CL_NONE = 0x40000000;                         // band-linear index of "no sample left": outside every chunk (|chunk base| < 2^20)
     unsigned pk = 0u;
@@ -562,7 +521,6 @@ __device__ __forceinline__ void cl_tile(const ClArgs& A, const int v, const int 
 
     for (int n = 0; n < nchunks; ++n) {
         const int cb = cb0 + n * cstep;
-        const unsigned long long cl_ta = CL_CLK();
         // ---- dots of this wave's 32 texels with the 32 pixels: 12 MFMAs
         floatx16 acc0;
 #pragma unroll
@@ -580,9 +538,7 @@ __device__ __forceinline__ void cl_tile(const ClArgs& A, const int v, const int 
             const int row = wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * kg;
             prod[row * 32 + li] = acc0[r];
         }
-        const unsigned long long cl_tb = CL_CLK();
         __syncthreads();
-        const unsigned long long cl_tc = CL_CLK();
         // ---- gather: every lane takes its samples whose cell lies in this chunk.  Band index of (column c, row r) in the chunk =
         // (c + 4) R + r - (cb + 4) R; the cell columns of the chunk are cb .. cb + Wc - 2 and a cell's row r0 is < R - 1, so the cell
         // lies in the chunk exactly when that index is in [0, (Wc - 1) R): one unsigned comparison, whose wave-wide result ends the loop
@@ -601,11 +557,8 @@ __device__ __forceinline__ void cl_tile(const ClArgs& A, const int v, const int 
                 next_in();
             }
         }
-        const unsigned long long cl_td = CL_CLK();
         __syncthreads();
-        CL_STAT(1, 1); CL_STAT(5, cl_tb - cl_ta); CL_STAT(6, cl_tc - cl_tb); CL_STAT(7, cl_td - cl_tc); CL_STAT(8, CL_CLK() - cl_td);
     }
-    const unsigned long long cl_t3 = CL_CLK();
     // ---- what the chunks did not cover (no band, samples out of order, bands too wide): direct path, behind a single wave-uniform test
     while (__ballot(dmask != 0u) != 0ull) {
         if (dmask != 0u) {
@@ -619,8 +572,6 @@ __device__ __forceinline__ void cl_tile(const ClArgs& A, const int v, const int 
         }
     }
     __syncthreads();
-    const unsigned long long cl_t4 = CL_CLK();
-    CL_STAT(9, cl_t4 - cl_t3);
     // ---- rows out: wave w writes pixel slots w, w + 4, ...; lane = hypothesis (one coalesced D-float row per store)
     float* pv = A.part + (long)v * ((long)h1 * w1) * D;
     const int pme = pidx[li];                               // one LDS read: lane l holds the pixel of slot l & 31, readlane hands slot i's to the scalar unit
@@ -630,25 +581,13 @@ __device__ __forceinline__ void cl_tile(const ClArgs& A, const int v, const int 
         const int p = __builtin_amdgcn_readlane(pme, i);
         if (p >= 0 && lane < D) pv[(long)p * D + lane] = desc[(lane * CL_DP + i) * 4 + 3];
     }
-    CL_STAT(10, CL_CLK() - cl_t4); CL_STAT(2, CL_CLK() - cl_t0);
-    CL_FLUSH();
 }
 
 // XCD-aware order (blocks are dealt round-robin over the 8 XCDs): each XCD gets a contiguous range of (view, segment, line):
 // neighbouring lines share most of their band, which then stays in that XCD's L2
-#ifndef CL_CU_ADJ
-#define CL_CU_ADJ 0      // experiment (round 6): N > 0 - the k-th block of an XCD takes, inside groups of 3 N consecutive tiles, tile (k % N) * 3 + k / N:
-                         // if the dispatcher deals an XCD's blocks round-robin over N CUs, the three resident blocks of a CU then hold ADJACENT lines
-#endif
 __device__ __forceinline__ unsigned cl_xcd_order() {
     const unsigned nblk = gridDim.x, bid = blockIdx.x, q = nblk >> 3, r = nblk & 7, xcd = bid & 7;
-    unsigned k = bid >> 3;
-#if CL_CU_ADJ > 0
-    {
-        const unsigned len = xcd < r ? q + 1 : q, G = 3u * CL_CU_ADJ, g = k / G, j = k - g * G;
-        if ((g + 1) * G <= len) k = g * G + (j % CL_CU_ADJ) * 3u + j / CL_CU_ADJ;
-    }
-#endif
+    const unsigned k = bid >> 3;
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
 }
 

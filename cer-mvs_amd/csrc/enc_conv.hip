@@ -17,9 +17,6 @@
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
-#ifndef ES_STREAM
-#define ES_STREAM 1                    // 32 -> 32 3x3 stride-1 convolutions through the persistent streaming kernel (0: tiled kernel)
-#endif
 #define EC_AS 144                      // LDS bytes per halo pixel: 32 hi | 32 lo | 16 pad
 #define EC_EPI_RAW 0                   // out = conv + bias (raw, pre-norm), optional stats partials
 #define EC_EPI_FMAP 1                  // out = (conv + bias) * scale into a (possibly bordered) channels-last map
@@ -40,12 +37,6 @@ struct EncArgs {
     int out_border;                    // EC_EPI_FMAP: zero border of the destination map
     float out_scale;
 };
-
-__device__ __forceinline__ void ec_split(float v, _Float16& hi, _Float16& lo) {
-    const float x = fminf(fmaxf(v, -65504.0f), 65504.0f);
-    hi = (_Float16)x;
-    lo = (_Float16)((x - (float)hi) * 2048.0f);
-}
 
 template <int NB, int NWAVES>
 __device__ __forceinline__ void ec_issue_B(char* __restrict__ ldsB, const _Float16* __restrict__ slice) {
@@ -287,17 +278,6 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, MINW) void enc_conv_kernel(
 //   and NO vector memory (weights resident) -> barrier -> raw output through a wave-private transpose that overlays the tile
 //   (16-byte stores) -> barrier.
 // Same arithmetic, same tiling for the partial statistics (one record per 8 x 32 tile) as enc_conv_kernel<8,1,1,1,...>.
-#ifndef ES_ABL
-#define ES_ABL 0                        // profiling ablations: 1 no MFMA loop, 2 no commit (LDS tile not written), 4 no output stores, 8 no halo loads
-#endif
-#ifndef ES_TRACE
-#define ES_TRACE 0                      // debug build: per-wave phase cycle sums (s_memtime) written to a.out2 [blocks][4 waves][16] (u64)
-#endif
-#if ES_TRACE
-#define ES_T(k) do { const unsigned long long now_ = __builtin_readcyclecounter(); tsum[k] += now_ - tlast; tlast = now_; } while (0)
-#else
-#define ES_T(k) do { } while (0)
-#endif
 #define ES_TH 8                         // tile rows (statistics granularity); processed as two halves of ES_SH rows
 #define ES_SH 4
 #define ES_HH (ES_SH + 2)
@@ -342,10 +322,6 @@ __global__ __launch_bounds__(ES_NTHR, 2) void enc_conv32_stream_kernel(const Enc
     if (t < total_tiles) issue(2 * t);
     int cur_img = -1;
     float mu[8], rs[8];
-#if ES_TRACE
-    unsigned long long tsum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = __builtin_readcyclecounter();
-    const unsigned long long tstart = tlast;
-#endif
     for (; t < total_tiles; t += gridDim.x) {
         const int img = t / a.nblk, tile = t - img * a.nblk;
         const int tx0 = (tile % a.tiles_x) * 32;
@@ -361,15 +337,11 @@ __global__ __launch_bounds__(ES_NTHR, 2) void enc_conv32_stream_kernel(const Enc
 #pragma unroll 1
         for (int sub = 0; sub < 2; ++sub) {
             const int ty0 = (tile / a.tiles_x) * ES_TH + sub * ES_SH;
-#if ES_TRACE
-            __builtin_amdgcn_s_waitcnt(0x0F70);            // (trace build) make the halo wait its own phase
-            ES_T(6);
-#endif
             // ---- commit the prefetched halo: transform + split + LDS write
 #pragma unroll
             for (int i = 0; i < ITEMS; ++i) {
                 const int row = prow0 + RSTEP * i;
-                if (row < ES_ROWS && !(ES_ABL & 2)) {
+                if (row < ES_ROWS) {
                     const int hy = row / ES_HW, hx = row - hy * ES_HW;
                     const int gy = ty0 + hy - 1, gx = tx0 + hx - 1;
                     const bool inside = gy >= 0 && gy < a.h && gx >= 0 && gx < a.w;
@@ -387,13 +359,11 @@ __global__ __launch_bounds__(ES_NTHR, 2) void enc_conv32_stream_kernel(const Enc
                     *reinterpret_cast<half8*>(ldsA + row * EC_AS + 64 + g * 16) = lo;
                 }
             }
-            ES_T(0);                                       // commit (incl. waiting for the prefetched halo)
             __builtin_amdgcn_s_waitcnt(0x0F70);            // vmcnt(0): (first half) the weight DMAs have landed
             __syncthreads();                               // tile (and weights) visible to every wave
-            ES_T(1);                                       // vmcnt(0) + barrier
             {                                              // next half's halo travels during the MFMAs
                 const int nh = sub == 0 ? 2 * t + 1 : 2 * (t + (int)gridDim.x);
-                if (nh < 2 * total_tiles && !(ES_ABL & 8)) issue(nh);
+                if (nh < 2 * total_tiles) issue(nh);
             }
             // ---- 9 taps x 2 k16-steps, weights resident: no barrier, no vector memory.  Software pipeline in source: the
             // fragments of step i+2 are requested before the MFMAs of step i and the scheduler is fenced per step - left alone,
@@ -414,7 +384,7 @@ __global__ __launch_bounds__(ES_NTHR, 2) void enc_conv32_stream_kernel(const Enc
             load(0, 0);
             load(1, 1);
 #pragma unroll
-            for (int i = 0; i < ((ES_ABL & 1) ? 1 : 18); ++i) {
+            for (int i = 0; i < 18; ++i) {
                 if (i + 2 < 18) load((i + 2) % 3, i + 2);
                 __builtin_amdgcn_sched_barrier(0);         // the requests stay in front of this step's MFMAs
                 const int b = i % 3;
@@ -423,9 +393,7 @@ __global__ __launch_bounds__(ES_NTHR, 2) void enc_conv32_stream_kernel(const Enc
                 accl = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[b][1], fb[b][0], accl, 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
             }
-            ES_T(2);                                       // halo issue + 18 MFMA steps
             __syncthreads();                               // every wave is done reading the tile: the patches may overlay it
-            ES_T(3);                                       // barrier
             // ---- epilogue: statistics in the MFMA layout, raw output through the transpose
             const int gy = ty0 + wave;
             float* Et = reinterpret_cast<float*>(ldsA) + wave * (32 * 36);
@@ -445,7 +413,7 @@ __global__ __launch_bounds__(ES_NTHR, 2) void enc_conv32_stream_kernel(const Enc
                 const int idx = lane + 64 * j;
                 const int px = idx >> 3, g4 = idx & 7;
                 const float4 v = *reinterpret_cast<const float4*>(Et + px * 36 + 4 * g4);
-                if (gy < a.ho && tx0 + px < a.wo && !(ES_ABL & 4))
+                if (gy < a.ho && tx0 + px < a.wo)
                     *reinterpret_cast<float4*>(a.out + (((long)img * a.ho + gy) * a.wo + tx0 + px) * 32 + 4 * g4) = v;
             }
             if (a.part && sub == 1) {
@@ -455,9 +423,7 @@ __global__ __launch_bounds__(ES_NTHR, 2) void enc_conv32_stream_kernel(const Enc
                     red[(wave * 32 + li) * 2 + 1] = q2;
                 }
             }
-            ES_T(4);                                       // epilogue (transpose, stores, statistics)
             __syncthreads();                               // patches read back: the tile may be rewritten; partials visible
-            ES_T(5);                                       // barrier
         }
         if (a.part && threadIdx.x < 32) {
             float s2 = 0.f, q2 = 0.f;
@@ -471,14 +437,6 @@ __global__ __launch_bounds__(ES_NTHR, 2) void enc_conv32_stream_kernel(const Enc
             dst[1] = q2;
         }
     }
-#if ES_TRACE
-    if (lane == 0 && a.out2) {
-        unsigned long long* o = reinterpret_cast<unsigned long long*>(a.out2) + ((long)blockIdx.x * 4 + wave) * 16;
-        for (int k = 0; k < 7; ++k) o[k] = tsum[k];
-        o[8] = __builtin_readcyclecounter() - tstart;
-        o[9] = (unsigned long long)((total_tiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x);
-    }
-#endif
 }
 
 template <int WAVES_M, int WAVES_N, int WM, int WN, int NBUF, int MINW, int TH, int STRIDE, int TAPS>
@@ -539,7 +497,7 @@ extern "C" int cer_enc_conv_f16x3(const float* src, const float* tf_stats, int t
     a.out_border = out_border;
     a.out_scale = out_scale;
     hipStream_t st = (hipStream_t)stream;
-    if (stride == 1 && taps == 9 && Cin == 32 && Cout == 32 && epi == EC_EPI_RAW && ES_STREAM) {
+    if (stride == 1 && taps == 9 && Cin == 32 && Cout == 32 && epi == EC_EPI_RAW) {
         // layer-1 shape: persistent streaming kernel, two 4-wave blocks per CU
         a.tiles_x = (a.wo + 31) / 32;
         a.nblk = a.tiles_x * ((a.ho + ES_TH - 1) / ES_TH);

@@ -45,24 +45,6 @@ typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef unsigned int pc_u32x4 __attribute__((ext_vector_type(4)));
 typedef int pc_intx8 __attribute__((ext_vector_type(8)));
 
-#ifndef PC_ABL
-#define PC_ABL 0                       // profiling ablations (variant builds only): 1 no MFMAs, 2 no output stores, 4 no operand transform (halves of the raw bits),
-                                       // 8 / 16: the MATRIX TIME of an fp8- / FP6-correction form (2 of 3 / 3 of 6 MFMAs issued; results wrong) - upper bounds
-#endif
-#ifndef PC_EXP24
-#define PC_EXP24 0
-#endif
-#ifndef PC_PAD
-#define PC_PAD 0
-#endif
-#ifndef PC_TRACE
-#define PC_TRACE 0                     // debug build: per-wave phase cycle sums written to a.out2 [blocks][8 waves][8] (u64); tools/archive/trace_pc.py
-#endif
-#if PC_TRACE
-#define PC_T(k) do { const unsigned long long now_ = __builtin_readcyclecounter(); tsum[k] += now_ - tlast; tlast = now_; } while (0)
-#else
-#define PC_T(k) do { } while (0)
-#endif
 #define PC_AS 144                      // LDS bytes per halo pixel and 32-channel chunk: 32 hi | 32 lo | 16 pad (conflict-free ds_read_b128)
 #define PC_EPI_RAW 0
 #define PC_EPI_FMAP 1
@@ -125,24 +107,16 @@ __device__ __forceinline__ int pc_lds_pixel(int hy, int hx) {
 // blocks of an XCD work on 32 vertically adjacent tiles, so the two halo rows a tile shares with the tile above / below (25 % extra
 // reads with 8-row tiles) are fetched into that XCD's L2 once instead of crossing the fabric twice.  The tile's identity (statistics
 // record, output position) stays row-major.
-#ifndef PC_XCD_ORDER
-#define PC_XCD_ORDER 1
-#endif
 __device__ __forceinline__ int pc_work_offset() {
     const int G = (int)gridDim.x, b = (int)blockIdx.x;
-    return (PC_XCD_ORDER && G % 8 == 0) ? (b % 8) * (G / 8) + b / 8 : b;
+    return (G % 8 == 0) ? (b % 8) * (G / 8) + b / 8 : b;
 }
 __device__ __forceinline__ void pc_work_tile(const PcArgs& a, int widx, int& img, int& tile, int& ty, int& tx) {
     img = widx / a.nblk;
     const int c = widx - img * a.nblk;
-    if (PC_XCD_ORDER) {
-        const int tiles_y = a.nblk / a.tiles_x;
-        tx = c / tiles_y;
-        ty = c - tx * tiles_y;
-    } else {
-        ty = c / a.tiles_x;
-        tx = c - ty * a.tiles_x;
-    }
+    const int tiles_y = a.nblk / a.tiles_x;
+    tx = c / tiles_y;
+    ty = c - tx * tiles_y;
     tile = ty * a.tiles_x + tx;
 }
 
@@ -165,20 +139,7 @@ __device__ __forceinline__ void pc_split8_scaled(const float (&y)[8], half8& hi,
     lo = __builtin_bit_cast(half8, (u32x4){l[0], l[1], l[2], l[3]});
 }
 
-#if PC_ABL & 1
-__device__ __forceinline__ floatx16 pc_keep(half8 a_, half8 b_, floatx16 c_) { asm volatile("" :: "v"(a_), "v"(b_)); return c_; }
-#define PC_MFMA(a_, b_, c_) pc_keep(a_, b_, c_)
-#else
 #define PC_MFMA(a_, b_, c_) __builtin_amdgcn_mfma_f32_32x32x16_f16(a_, b_, c_, 0, 0, 0)
-#endif
-#if PC_ABL & 24
-__device__ __forceinline__ floatx16 pc_keep2(half8 a_, half8 b_, floatx16 c_) { asm volatile("" :: "v"(a_), "v"(b_)); return c_; }
-#define PC_MFMA_C3(a_, b_, c_, s_) pc_keep2(a_, b_, c_)                                        // lo x hi: never issued
-#define PC_MFMA_C2(a_, b_, c_, s_) (((PC_ABL & 16) && ((s_) & 1)) ? pc_keep2(a_, b_, c_) : PC_MFMA(a_, b_, c_))   // hi x lo: FP6 time = every other step
-#else
-#define PC_MFMA_C3(a_, b_, c_, s_) PC_MFMA(a_, b_, c_)
-#define PC_MFMA_C2(a_, b_, c_, s_) PC_MFMA(a_, b_, c_)
-#endif
 #define PC_YMAX 134152192.0f           // 65504 * 2048: what the f16 hi half can hold, in the scaled domain
 
 // FP6 form: the item's 16 values [hi (8) | lo' (8)] -> 16 e2m3 fields (three dwords) under the block's scale; `sb` = its E8M0 byte
@@ -263,18 +224,10 @@ __device__ __forceinline__ void pc_producer(const PcArgs& a, char* __restrict__ 
         const int gy = min(max(nx_y0 + hyv[i] * PS, 0), a.h - 1), gx = min(max(nx_x0 + hxv[i] * PS, 0), a.w - 1);
         const int off = nx_interior ? (nx_y0 * a.w + nx_x0) * CIN + ioff[i] : (gy * a.w + gx) * CIN + 8 * g;
         rawA[i][0] = cer_ld4(nx_pa + off);
-#if PC_EXP24       // timing experiment (WRONG results): 24 instead of 32 bytes per item in, three of four 16-byte stores out - the traffic of a 3-byte format
-        { const float2 t2 = *reinterpret_cast<const float2*>(nx_pa + off + 4); rawA[i][1] = make_float4(t2.x, t2.y, t2.x, t2.y); }
-#else
         rawA[i][1] = cer_ld4(nx_pa + off + 4);
-#endif
         if (DUAL) {
             rawB[DUAL ? i : 0][0] = cer_ld4(nx_pb + off);
-#if PC_EXP24
-            { const float2 t2 = *reinterpret_cast<const float2*>(nx_pb + off + 4); rawB[DUAL ? i : 0][1] = make_float4(t2.x, t2.y, t2.x, t2.y); }
-#else
             rawB[DUAL ? i : 0][1] = cer_ld4(nx_pb + off + 4);
-#endif
         }
     };
     float muA[8], rsA[8], muB[8], rsB[8];                                        // rs = 2048 rstd
@@ -306,20 +259,7 @@ __device__ __forceinline__ void pc_producer(const PcArgs& a, char* __restrict__ 
                     yv[e] = (BORDER && !inside) ? 0.f : y;                       // zero padding of the (normalised) activation
                 }
                 half8 hi, lo;
-                if (PC_ABL & 4) {
-                    typedef float f32x4 __attribute__((ext_vector_type(4)));
-                    hi = __builtin_bit_cast(half8, (f32x4){va[0], va[1], va[2], va[3]});
-                    lo = __builtin_bit_cast(half8, (f32x4){va[4], va[5], va[6], va[7]});
-                } else
                 pc_split8_scaled(yv, hi, lo);
-#if PC_PAD          // timing experiment: PC_PAD extra VALU instructions per 8-value item (what a narrower correction format's conversion would add)
-                {
-                    unsigned pad_ = __builtin_bit_cast(unsigned, yv[0]);
-#pragma unroll
-                    for (int q_ = 0; q_ < PC_PAD; ++q_) asm volatile("v_add_u32 %0, %0, %1" : "+v"(pad_) : "v"(q_ + 1));
-                    asm volatile("" :: "v"(pad_));
-                }
-#endif
                 *reinterpret_cast<half8*>(buf + lpix[i]) = hi;
                 if constexpr (F6) {
                     // block (pixel, kg = g & 1): dwords 0-3 at +64 + 16 kg, dwords 4-5 | scale at +96 + 16 kg; this item (k16-step g >> 1) owns
@@ -389,35 +329,18 @@ __device__ __forceinline__ void pc_producer(const PcArgs& a, char* __restrict__ 
         dst[1] = q;
     };
 
-#if PC_TRACE
-    unsigned long long tsum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = __builtin_readcyclecounter();
-    const unsigned long long tstart = tlast;
-#endif
     if (U > 0) {
         prepare(0);
 #pragma unroll
         for (int i = 0; i < C::ITEMS; ++i) issue_item(i);
     }
     for (int u = 0; u < U; ++u) {
-        PC_T(0);
         commit(u);                                                               // (per item: wait for its loads, transform, LDS, request the next unit's)
-        PC_T(1);
-        PC_T(2);
         pc_barrier();                                                            // #u: buffer u & 1 is complete
-        PC_T(3);
         if (u >= 1) finalize(u - 1);
-        PC_T(4);
     }
     pc_barrier();                                                                // #U: the consumers' last epilogue is done
     if (U >= 1) finalize(U - 1);
-#if PC_TRACE
-    if ((tid & 63) == 0 && a.out2) {
-        unsigned long long* o = reinterpret_cast<unsigned long long*>(a.out2) + ((long)blockIdx.x * 8 + (tid >> 6)) * 8;
-        for (int k = 0; k < 5; ++k) o[k] = tsum[k];
-        o[6] = __builtin_readcyclecounter() - tstart;
-        o[7] = (unsigned long long)U;
-    }
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------------------------ consumers
@@ -459,10 +382,6 @@ __device__ __forceinline__ void pc_consumer(const PcArgs& a, const char* __restr
         else pix = (m + dy) * C::HW + dx;
         return pix * PC_AS + ks * 32;
     };
-#if PC_TRACE
-    unsigned long long tsum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = __builtin_readcyclecounter();
-    const unsigned long long tstart = tlast;
-#endif
     constexpr bool ROLL = C::RPW >= 2;          // fragments rolled in place one step ahead (RPW = 1: triple-buffered two steps ahead)
     constexpr int NBUF = ROLL ? 1 : 3;
     static_assert(!F6 || ROLL || C::WRES, "FP6 form at one m-tile per wave: resident weights only");
@@ -473,12 +392,7 @@ __device__ __forceinline__ void pc_consumer(const PcArgs& a, const char* __restr
         const pc_intx8 A0 = (pc_intx8){(int)a0.x, (int)a0.y, (int)a0.z, (int)a0.w, (int)a1.x, (int)a1.y, 0, 0};
         const pc_intx8 B0 = (pc_intx8){(int)b0.x, (int)b0.y, (int)b0.z, (int)b0.w, (int)b1.x, (int)b1.y, 0, 0};
         const pc_intx8 A = __builtin_shufflevector(A0, A0, 0, 1, 2, 3, 4, 5, -1, -1), B = __builtin_shufflevector(B0, B0, 0, 1, 2, 3, 4, 5, -1, -1);
-#if PC_ABL & 1
-        asm volatile("" :: "v"(A), "v"(B));
-        return c;
-#else
         return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(A, B, c, 2, 2, 0, (int)a1.z, 0, (int)b1.z);
-#endif
     };
 
     for (int j = 0; j < ntile; ++j) {
@@ -509,9 +423,7 @@ __device__ __forceinline__ void pc_consumer(const PcArgs& a, const char* __restr
 #pragma unroll
                 for (int d = 0; d < WD; ++d) loadW(d, d);
             }
-            PC_T(0);
             pc_barrier();                                                        // #u: the producers have filled buffer u & 1
-            PC_T(1);
             if constexpr (F6 && ROLL) {
                 // a tap's MFMAs in three groups (main term of k16-step 0, of step 1, the FP6 correction of both); the four fragment sets of a
                 // row - hi of both steps, the block's two 16-byte pieces - are re-requested for the NEXT tap right behind their last use:
@@ -609,13 +521,13 @@ __device__ __forceinline__ void pc_consumer(const PcArgs& a, const char* __restr
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                     for (int m = 0; m < C::RPW; ++m) {
-                        accl[m] = PC_MFMA_C2(fa[0][m][0], bl, accl[m], s);
+                        accl[m] = PC_MFMA(fa[0][m][0], bl, accl[m]);
                         if (s + 1 < C::NS) loadA1(0, m, s + 1, 0);
                         __builtin_amdgcn_sched_barrier(0);
                     }
 #pragma unroll
                     for (int m = 0; m < C::RPW; ++m) {
-                        accl[m] = PC_MFMA_C3(fa[0][m][1], bh, accl[m], s);
+                        accl[m] = PC_MFMA(fa[0][m][1], bh, accl[m]);
                         if (s + 1 < C::NS) loadA1(0, m, s + 1, 1);
                         __builtin_amdgcn_sched_barrier(0);
                     }
@@ -638,13 +550,12 @@ __device__ __forceinline__ void pc_consumer(const PcArgs& a, const char* __restr
                     const half8 bh = C::WRES ? wres[ch * C::NS + s][0] : wst[s % WR][0];
                     const half8 bl = C::WRES ? wres[ch * C::NS + s][1] : wst[s % WR][1];
                     accm[0] = PC_MFMA(fa[b][0][0], bh, accm[0]);
-                    accl[0] = PC_MFMA_C2(fa[b][0][0], bl, accl[0], s);
-                    accl[0] = PC_MFMA_C3(fa[b][0][1], bh, accl[0], s);
+                    accl[0] = PC_MFMA(fa[b][0][0], bl, accl[0]);
+                    accl[0] = PC_MFMA(fa[b][0][1], bh, accl[0]);
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
         }
-        PC_T(2);
         // ---- epilogue: the lane holds channel co of pixels x = tx0 + (r & 3) + 8 (r >> 2) + 4 kg of each of its rows.  The values
         // leave through a wave-private LDS transpose as 16-byte stores: with one dword store per accumulator register (256 B per
         // wave instruction) the consumers issued 128 stores per tile and CU and every one of them waited ~100 cycles for a slot in
@@ -722,8 +633,7 @@ __device__ __forceinline__ void pc_consumer(const PcArgs& a, const char* __restr
                             *reinterpret_cast<half4_t*>(rowb + loff) = (half4_t){h0.x, h0.y, h1.x, h1.y};
                             *reinterpret_cast<half4_t*>(rowb + loff + 4 * (long)bt16) = (half4_t){l0.x, l0.y, l1.x, l1.y};
                         }
-                    } else if (PC_ABL & 2) asm volatile("" :: "v"(v4.x), "v"(v4.y), "v"(v4.z), "v"(v4.w));
-                    else if ((!PC_EXP24 || EPI != PC_EPI_RAW || jj != 3) && (FULL || (gy < a.ho && tx0 + (lane >> 3) + 8 * jj < a.wo))) *reinterpret_cast<float4*>(o + lane_off + 8 * jj * pstride) = v4;
+                    } else if (FULL || (gy < a.ho && tx0 + (lane >> 3) + 8 * jj < a.wo)) *reinterpret_cast<float4*>(o + lane_off + 8 * jj * pstride) = v4;
                 }
             }
         };
@@ -739,17 +649,8 @@ __device__ __forceinline__ void pc_consumer(const PcArgs& a, const char* __restr
                 r[1] = q2;
             }
         }
-        PC_T(3);
     }
     pc_barrier();                                                                // #U
-#if PC_TRACE
-    if (lane == 0 && a.out2 && EPI == PC_EPI_RAW) {
-        unsigned long long* o = reinterpret_cast<unsigned long long*>(a.out2) + ((long)blockIdx.x * 8 + 4 + cw) * 8;
-        for (int k = 0; k < 4; ++k) o[k] = tsum[k];
-        o[6] = __builtin_readcyclecounter() - tstart;
-        o[7] = (unsigned long long)ntile;
-    }
-#endif
 }
 
 template <int CIN, int COUT, int STRIDE, int TAPS, int EPI, bool DUAL, bool F6 = false>

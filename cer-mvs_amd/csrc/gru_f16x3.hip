@@ -27,25 +27,15 @@
 //   * epilogue: the wave's tile goes through a private LDS transpose, so that the hoisted `init` term, the GRU operands and
 //     the outputs move as 16-byte accesses; gate math as in the fp32 kernel; CER_EPI_DELTA instead projects the hidden tile
 //     onto the nine taps of the 256->1 conv and writes only those planes.
-// Compile-time experiment switches (default off; DESIGN.md roadmap): HX_ABL (phase ablations), HX_TRACE (cycle stamps),
-// HX_CFG / HX_TH (other tilings), HX_EPI2=0 (direct 4-byte epilogue).
 #include "common.hpp"
 #include "pack.hpp"       // weight layouts: pack.cpp
 #include <stdlib.h>
 #include <string.h>
-#ifndef HX_ABL
-#define HX_ABL 0      // profiling ablations, compile time: 1 no MFMA, 2 no barriers, 4 no staging, 8 no init/epilogue, 16 no weight DMA
-#endif
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
-#ifndef HX_EPI2
-#define HX_EPI2 1     // epilogue through LDS with 16-byte global accesses (0: the direct 4-byte form, kept for A/B runs)
-#endif
-#ifndef HX_TH
-#define HX_TH 4                        // tile rows (8: experiment, one 8-wave block of 256 px per CU)
-#endif
+#define HX_TH 4                        // tile rows
 #define HX_TW 32
 #define HX_HH (HX_TH + 2)
 #define HX_HW (HX_TW + 2)
@@ -56,18 +46,6 @@ static_assert(HX_KC == PACK_KC, "padded_channels (pack.hpp) pads to the chunk");
 #define HX_A_BYTES (HX_ROWS * HX_AS)   // 29376
 #define HX_EPI_DELTA 4                 // conv + ReLU + projection onto the 9 taps of the 256->1 delta conv (cer_mvs.h: CER_EPI_DELTA)
 #define HX_HS 272                      // LDS bytes per pixel row of the hidden tile (128 f16 + 16 pad: conflict-free b128 reads)
-
-// HX_TRACE (debug builds only, tools/archive/trace_conv.py): per (block, wave, step) cycle stamps written to `aux2`, which the traced
-// epilogue (GATES) does not use: [0] loop top, [1] after the barrier, [2] after the first k16-step, [3] end of the step; slot
-// 63 of each wave holds (kernel entry, main loop start, main loop end, kernel end) and slot 62 the HW_ID register.
-#ifndef HX_TRACE
-#define HX_TRACE 0
-#endif
-#if HX_TRACE
-#define HX_STAMP(k) do { if (HX_TRACE) trace_v[k] = __builtin_readcyclecounter(); } while (0)
-#else
-#define HX_STAMP(k) do { } while (0)
-#endif
 
 struct ConvArgsX {
     const float* src[CER_CONV_MAX_SRC];
@@ -90,12 +68,6 @@ struct ConvArgsX {
 };
 
 __device__ __forceinline__ float hx_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-__device__ __forceinline__ void hx_split(float v, _Float16& hi, _Float16& lo) {
-    const float x = fminf(fmaxf(v, -65504.0f), 65504.0f);
-    hi = (_Float16)x;
-    lo = (_Float16)((x - (float)hi) * 2048.0f);
-}
 
 #define HX_DT_H (HX_HH + 6)            // disparity tile rows (halo + 3 each side for the 7x7 unfold)
 #define HX_DT_W (HX_HW + 6)
@@ -277,11 +249,6 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, MINW) void conv3x3_f16x3_ke
     const int li = lane & 31, kg = lane >> 5;
     const int NT = a.cout / 32;
 
-#if HX_TRACE
-    unsigned long long trace_v[4];
-    unsigned long long* trace_base = (unsigned long long*)a.aux2 + ((long)(blockIdx.y * gridDim.x + blockIdx.x) * NWAVES + wave) * 64 * 4;
-    const unsigned long long trace_t0 = __builtin_readcyclecounter();
-#endif
     // ---- pipeline prologue: the weight DMA ring runs NBUF-1 steps ahead of the multiply, across chunk boundaries
     // tiles whose pixels all have their 3x3 neighbourhood inside the image take the collapsed disparity chunks
     const bool coll = a.wpk_c && ty0 >= 1 && ty0 + HX_TH <= a.h - 1 && tx0 >= 1 && tx0 + HX_TW <= a.w - 1;
@@ -290,7 +257,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, MINW) void conv3x3_f16x3_ke
     const _Float16* wbase = (coll ? a.wpk_c : a.wpk) + (long)(nb0 / 32) * 2048;      // + step * NT * 2048
 #pragma unroll
     for (int i = 0; i < NBUF - 1; ++i)
-        if (i < nsteps && !(HX_ABL & 16)) hx_issue_B<NB, NWAVES>(ldsB + i * B_BYTES, wbase + (long)i * NT * 2048);
+        if (i < nsteps) hx_issue_B<NB, NWAVES>(ldsB + i * B_BYTES, wbase + (long)i * NT * 2048);
     for (int s = 0; s < a.nsrc; ++s)
         if (a.kind[s] == 1) hx_load_disp_tile<NTHR>(ldsD, a.src[s], a.h, a.w, ty0, tx0);
 
@@ -304,9 +271,9 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, MINW) void conv3x3_f16x3_ke
             floatx16 v;
 #pragma unroll
             for (int r = 0; r < 16; ++r) v[r] = 0.f;
-            if (a.init && !(HX_ABL & 8)) {
-                // (with the LDS epilogue the hoisted term is added there, through 16-byte loads)
-                if (!HX_EPI2 || EPI == HX_EPI_DELTA) {
+            if (a.init) {
+                // (the LDS epilogue adds the hoisted term there, through 16-byte loads)
+                if (EPI == HX_EPI_DELTA) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const int gx = tx0 + (r & 3) + 8 * (r >> 2) + 4 * kg;
@@ -348,15 +315,9 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, MINW) void conv3x3_f16x3_ke
         for (int m = 0; m < WM; ++m)
 #pragma unroll
             for (int n = 0; n < WN; ++n) {
-                if (HX_ABL & 1) {
-#if defined(__HIP_DEVICE_COMPILE__)
-                    asm volatile("" ::"v"(f.ah[m]), "v"(f.al[m]), "v"(f.bh[n]), "v"(f.bl[n]));
-#endif
-                } else {
-                    accm[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.ah[m], f.bh[n], accm[m][n], 0, 0, 0);
-                    accl[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.ah[m], f.bl[n], accl[m][n], 0, 0, 0);
-                    accl[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.al[m], f.bh[n], accl[m][n], 0, 0, 0);
-                }
+                accm[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.ah[m], f.bh[n], accm[m][n], 0, 0, 0);
+                accl[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.ah[m], f.bl[n], accl[m][n], 0, 0, 0);
+                accl[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.al[m], f.bh[n], accl[m][n], 0, 0, 0);
             }
     };
     // (64-channel blocks only: with 128 channels per block the extra live fragment set does not fit 128 VGPRs.)
@@ -376,37 +337,30 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, MINW) void conv3x3_f16x3_ke
 #pragma unroll
         for (int e = 0; e < 8; ++e) { pend.bh[n][e] = (_Float16)0; pend.bl[n][e] = (_Float16)0; }
 
-#if HX_TRACE
-    const unsigned long long trace_t1 = __builtin_readcyclecounter();
-#endif
     int step = 0;                                          // chunk * 9 + tap; ring slot = step % NBUF
     for (int s = 0; s < a.nsrc; ++s) {
         const bool c9 = coll && a.kind[s] == 1;
         const int chunk_end = c9 ? 96 : a.chpad[s], ntaps = c9 ? 1 : 9;
         for (int c0 = 0; c0 < chunk_end; c0 += HX_KC) {
             __syncthreads();                               // every wave has finished reading A (previous chunk, tap 8); ldsD visible
-            if (!(HX_ABL & 4)) {
-                if (a.kind[s] != 1) {
-                    if constexpr (PS) hx_stage_presplit<NTHR>(ldsA, a, s, c0, ty0, tx0);
-                    else hx_stage_tensor<NTHR>(ldsA, a, s, c0, ty0, tx0);
-                } else if (c9) hx_stage_disp9<NTHR>(ldsA, ldsD, c0);
-                else hx_stage_disp<NTHR>(ldsA, ldsD, a, c0, ty0, tx0);
-            }
+            if (a.kind[s] != 1) {
+                if constexpr (PS) hx_stage_presplit<NTHR>(ldsA, a, s, c0, ty0, tx0);
+                else hx_stage_tensor<NTHR>(ldsA, a, s, c0, ty0, tx0);
+            } else if (c9) hx_stage_disp9<NTHR>(ldsA, ldsD, c0);
+            else hx_stage_disp<NTHR>(ldsA, ldsD, a, c0, ty0, tx0);
 #pragma unroll 1
             for (int t = 0; t < ntaps; ++t, ++step) {
                 const int tap = c9 ? 4 : t;
                 // B[step] was DMA'd NBUF-1 steps ago.  VMEM ops retire in order, so leaving the DMAs of the NBUF-2 younger
                 // steps in flight still guarantees B[step].  (Builtin waits: hipcc's own scoreboard must see them.)
-                HX_STAMP(0);
                 const int younger = min(NBUF - 2, nsteps - 1 - step);
                 if (NBUF >= 3 && younger >= 1) __builtin_amdgcn_s_waitcnt(0x0F70 | DMA_PER_WAVE);
                 else __builtin_amdgcn_s_waitcnt(0x0F70);
                 __builtin_amdgcn_s_waitcnt(0xC07F);        // lgkmcnt(0): this wave's LDS writes (A tile) are done
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");    // (the bare builtin does not order LDS accesses for the compiler)
-                if (!(HX_ABL & 2)) __builtin_amdgcn_s_barrier();   // all shares of B[step] + A visible; slot of B[step-1] free
+                __builtin_amdgcn_s_barrier();              // all shares of B[step] + A visible; slot of B[step-1] free
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-                HX_STAMP(1);
-                if (step + NBUF - 1 < nsteps && !(HX_ABL & 16))
+                if (step + NBUF - 1 < nsteps)
                     hx_issue_B<NB, NWAVES>(ldsB + ((step + NBUF - 1) % NBUF) * B_BYTES, wbase + (long)(step + NBUF - 1) * NT * 2048);
                 const char* B = ldsB + (step % NBUF) * B_BYTES;
                 const int dy = tap / 3, dx = tap - dy * 3;
@@ -439,40 +393,19 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, MINW) void conv3x3_f16x3_ke
                         for (int m = 0; m < WM; ++m)
 #pragma unroll
                             for (int n = 0; n < WN; ++n) {
-                                if (HX_ABL & 1) {
-#if defined(__HIP_DEVICE_COMPILE__)
-                                    asm volatile("" ::"v"(ah[m]), "v"(al[m]), "v"(bh[n]), "v"(bl[n]));
-#endif
-                                } else {
-                                    accm[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[m], bh[n], accm[m][n], 0, 0, 0);
-                                    accl[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[m], bl[n], accl[m][n], 0, 0, 0);
-                                    accl[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[m], bh[n], accl[m][n], 0, 0, 0);
-                                }
+                                accm[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[m], bh[n], accm[m][n], 0, 0, 0);
+                                accl[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[m], bl[n], accl[m][n], 0, 0, 0);
+                                accl[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[m], bh[n], accl[m][n], 0, 0, 0);
                             }
-                        if (ks == 0) HX_STAMP(2);
                     }
                 }
-#if HX_TRACE
-                trace_v[3] = __builtin_readcyclecounter();
-                if (lane == 0 && step < 62)
-                    for (int k = 0; k < 4; ++k) trace_base[step * 4 + k] = trace_v[k];
-#endif
             }
         }
     }
     if constexpr (SKEW) mma(pend);
-#if HX_TRACE
-    const unsigned long long trace_t2 = __builtin_readcyclecounter();
-#endif
 
     // ---- epilogue: lane holds channel co, pixels x = tx0 + (r&3) + 8*(r>>2) + 4*kg of row gy
     const int half = a.cout / 2;
-    if (HX_ABL & 8) {
-#if defined(__HIP_DEVICE_COMPILE__)
-        for (int m = 0; m < WM; ++m) for (int n = 0; n < WN; ++n) asm volatile("" ::"v"(accm[m][n]), "v"(accl[m][n]));
-#endif
-        return;
-    }
     if constexpr (EPI == HX_EPI_DELTA) {
         // delta head, fused: hid = relu(conv) never leaves the CU.  The block's 128 x 128 (pixel x channel) hidden tile is
         // split to hi|lo f16 into LDS (A-operand order) and multiplied by the 256->1 conv's weights arranged as a
@@ -490,7 +423,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, MINW) void conv3x3_f16x3_ke
                 const int prow = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * kg;
                 const float v = fmaxf(fmaf(accl[0][n][r], 1.0f / 2048.0f, accm[0][n][r]), 0.f);
                 _Float16 h, l;
-                hx_split(v, h, l);
+                cer_split1(v, h, l);
                 *reinterpret_cast<_Float16*>(Hhi + prow * HX_HS + col * 2) = h;
                 *reinterpret_cast<_Float16*>(Hlo + prow * HX_HS + col * 2) = l;
             }
@@ -529,125 +462,82 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, MINW) void conv3x3_f16x3_ke
         }
         return;
     }
-    if constexpr (HX_EPI2 != 0) {
-        // Each wave transposes its tile through a private LDS patch (the activation / weight buffers are free now): the MFMA
-        // layout gives a lane one channel of 16 pixels, i.e. 4-byte accesses 512 B apart; after the transpose a lane owns 4
-        // consecutive channels of a pixel, so `init`, `aux`, `aux2` and the outputs move as 16-byte accesses (4x fewer
-        // vector-memory instructions - the epilogue is issue-bound, not bandwidth-bound).
-        constexpr int CW = WN * 32;                        // channels of a wave
-        constexpr int PITCH = CW + 4;                      // floats per pixel row of the patch
-        static_assert((long)NWAVES * 32 * PITCH * 4 <= (long)HX_A_BYTES + (long)NBUF * B_BYTES, "epilogue patch does not fit");
-        float* Et = reinterpret_cast<float*>(hx_smem) + wave * (32 * PITCH);
-        __syncthreads();                                   // main loop finished everywhere: LDS can be reused
-#pragma unroll
-        for (int m = 0; m < WM; ++m) {
-#pragma unroll
-            for (int n = 0; n < WN; ++n)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    Et[((r & 3) + 8 * (r >> 2) + 4 * kg) * PITCH + n * 32 + li] = fmaf(accl[m][n][r], 1.0f / 2048.0f, accm[m][n][r]);
-            __builtin_amdgcn_s_waitcnt(0xC07F);            // lgkmcnt(0): the patch is wave-private
-            const int gy = ty0 + wm * WM + m;
-            constexpr int G = CW / 8;                      // 8-channel groups per pixel
-#pragma unroll 1                                           // one item at a time: four interleaved items of 32 temporaries each spill
-            for (int j = 0; j < 32 * G / 64; ++j) {
-                const int idx = lane + 64 * j;
-                const int px = idx / G, g = idx - px * G;
-                const int gx = tx0 + px;
-                const float4 va = *reinterpret_cast<const float4*>(Et + px * PITCH + 8 * g);
-                const float4 vb = *reinterpret_cast<const float4*>(Et + px * PITCH + 8 * g + 4);
-                if (gy >= a.h || gx >= a.w) continue;
-                const long pix = (long)gy * a.w + gx;
-                const int co = nb0 + wn * CW + 8 * g;
-                float v[8] = {va.x, va.y, va.z, va.w, vb.x, vb.y, vb.z, vb.w};
-                auto ld8 = [](const float* q, float (&o)[8]) {
-                    const float4 t0 = cer_ld4(q), t1 = cer_ld4(q + 4);
-                    o[0] = t0.x; o[1] = t0.y; o[2] = t0.z; o[3] = t0.w; o[4] = t1.x; o[5] = t1.y; o[6] = t1.z; o[7] = t1.w;
-                };
-                auto st8 = [](float* q, const float (&o)[8]) {
-                    *reinterpret_cast<float4*>(q) = make_float4(o[0], o[1], o[2], o[3]);
-                    *reinterpret_cast<float4*>(q + 4) = make_float4(o[4], o[5], o[6], o[7]);
-                };
-                if (a.init) {
-                    float t[8];
-                    ld8(a.init + pix * a.cout + co, t);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] += t[e];
-                }
-                if (EPI == CER_EPI_LINEAR || EPI == CER_EPI_RELU) {
-                    if (EPI == CER_EPI_RELU)
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
-                    if (a.out_split) hx_store_split8(a.out, pix, a.cout, co, v);
-                    else st8(a.out + pix * a.cout + co, v);
-                } else if (EPI == CER_EPI_GATES) {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = hx_sigmoid(v[e]);
-                    if (co < half) {
-                        st8(a.out + pix * half + co, v);                                 // z stays fp32 (blend operand of the q conv)
-                    } else {
-                        float hp[8];
-                        if (a.aux_split) hx_load_split8(a.aux, pix, half, co - half, hp);
-                        else ld8(a.aux + pix * half + (co - half), hp);
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) v[e] *= hp[e];
-                        if (a.out_split) hx_store_split8(a.out2, pix, half, co - half, v);
-                        else st8(a.out2 + pix * half + (co - half), v);
-                    }
-                } else if (EPI == CER_EPI_GRU) {
-                    float z[8], hp[8];
-                    ld8(a.aux2 + pix * a.cout + co, z);
-                    if (a.aux_split) hx_load_split8(a.aux, pix, a.cout, co, hp);
-                    else ld8(a.aux + pix * a.cout + co, hp);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = (1.0f - z[e]) * hp[e] + z[e] * tanhf(v[e]);
-                    if (a.out_split) hx_store_split8(a.out, pix, a.cout, co, v);
-                    else st8(a.out + pix * a.cout + co, v);
-                }
-            }
-        }
-        return;
-    }
+    // Each wave transposes its tile through a private LDS patch (the activation / weight buffers are free now): the MFMA
+    // layout gives a lane one channel of 16 pixels, i.e. 4-byte accesses 512 B apart; after the transpose a lane owns 4
+    // consecutive channels of a pixel, so `init`, `aux`, `aux2` and the outputs move as 16-byte accesses (4x fewer
+    // vector-memory instructions - the epilogue is issue-bound, not bandwidth-bound).
+    constexpr int CW = WN * 32;                        // channels of a wave
+    constexpr int PITCH = CW + 4;                      // floats per pixel row of the patch
+    static_assert((long)NWAVES * 32 * PITCH * 4 <= (long)HX_A_BYTES + (long)NBUF * B_BYTES, "epilogue patch does not fit");
+    float* Et = reinterpret_cast<float*>(hx_smem) + wave * (32 * PITCH);
+    __syncthreads();                                   // main loop finished everywhere: LDS can be reused
 #pragma unroll
     for (int m = 0; m < WM; ++m) {
+#pragma unroll
+        for (int n = 0; n < WN; ++n)
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                Et[((r & 3) + 8 * (r >> 2) + 4 * kg) * PITCH + n * 32 + li] = fmaf(accl[m][n][r], 1.0f / 2048.0f, accm[m][n][r]);
+        __builtin_amdgcn_s_waitcnt(0xC07F);            // lgkmcnt(0): the patch is wave-private
         const int gy = ty0 + wm * WM + m;
-        if (gy >= a.h) continue;
+        constexpr int G = CW / 8;                      // 8-channel groups per pixel
+#pragma unroll 1                                       // one item at a time: four interleaved items of 32 temporaries each spill
+        for (int j = 0; j < 32 * G / 64; ++j) {
+            const int idx = lane + 64 * j;
+            const int px = idx / G, g = idx - px * G;
+            const int gx = tx0 + px;
+            const float4 va = *reinterpret_cast<const float4*>(Et + px * PITCH + 8 * g);
+            const float4 vb = *reinterpret_cast<const float4*>(Et + px * PITCH + 8 * g + 4);
+            if (gy >= a.h || gx >= a.w) continue;
+            const long pix = (long)gy * a.w + gx;
+            const int co = nb0 + wn * CW + 8 * g;
+            float v[8] = {va.x, va.y, va.z, va.w, vb.x, vb.y, vb.z, vb.w};
+            auto ld8 = [](const float* q, float (&o)[8]) {
+                const float4 t0 = cer_ld4(q), t1 = cer_ld4(q + 4);
+                o[0] = t0.x; o[1] = t0.y; o[2] = t0.z; o[3] = t0.w; o[4] = t1.x; o[5] = t1.y; o[6] = t1.z; o[7] = t1.w;
+            };
+            auto st8 = [](float* q, const float (&o)[8]) {
+                *reinterpret_cast<float4*>(q) = make_float4(o[0], o[1], o[2], o[3]);
+                *reinterpret_cast<float4*>(q + 4) = make_float4(o[4], o[5], o[6], o[7]);
+            };
+            if (a.init) {
+                float t[8];
+                ld8(a.init + pix * a.cout + co, t);
 #pragma unroll
-        for (int n = 0; n < WN; ++n) {
-            const int co = nb0 + (wn * WN + n) * 32 + li;
+                for (int e = 0; e < 8; ++e) v[e] += t[e];
+            }
+            if (EPI == CER_EPI_LINEAR || EPI == CER_EPI_RELU) {
+                if (EPI == CER_EPI_RELU)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int gx = tx0 + (r & 3) + 8 * (r >> 2) + 4 * kg;
-                if (gx >= a.w) continue;
-                const long pix = (long)gy * a.w + gx;
-                const float v = fmaf(accl[m][n][r], 1.0f / 2048.0f, accm[m][n][r]);
-                if (EPI == CER_EPI_LINEAR) {
-                    a.out[pix * a.cout + co] = v;
-                } else if (EPI == CER_EPI_RELU) {
-                    a.out[pix * a.cout + co] = fmaxf(v, 0.f);
-                } else if (EPI == CER_EPI_GATES) {
-                    const float g = hx_sigmoid(v);
-                    if (co < half) a.out[pix * half + co] = g;
-                    else a.out2[pix * half + (co - half)] = g * a.aux[pix * half + (co - half)];
-                } else if (EPI == CER_EPI_GRU) {
-                    const float q = tanhf(v);
-                    const float z = a.aux2[pix * a.cout + co], hprev = a.aux[pix * a.cout + co];
-                    a.out[pix * a.cout + co] = (1.0f - z) * hprev + z * q;
+                    for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
+                if (a.out_split) hx_store_split8(a.out, pix, a.cout, co, v);
+                else st8(a.out + pix * a.cout + co, v);
+            } else if (EPI == CER_EPI_GATES) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) v[e] = hx_sigmoid(v[e]);
+                if (co < half) {
+                    st8(a.out + pix * half + co, v);                                 // z stays fp32 (blend operand of the q conv)
+                } else {
+                    float hp[8];
+                    if (a.aux_split) hx_load_split8(a.aux, pix, half, co - half, hp);
+                    else ld8(a.aux + pix * half + (co - half), hp);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) v[e] *= hp[e];
+                    if (a.out_split) hx_store_split8(a.out2, pix, half, co - half, v);
+                    else st8(a.out2 + pix * half + (co - half), v);
                 }
+            } else if (EPI == CER_EPI_GRU) {
+                float z[8], hp[8];
+                ld8(a.aux2 + pix * a.cout + co, z);
+                if (a.aux_split) hx_load_split8(a.aux, pix, a.cout, co, hp);
+                else ld8(a.aux + pix * a.cout + co, hp);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) v[e] = (1.0f - z[e]) * hp[e] + z[e] * tanhf(v[e]);
+                if (a.out_split) hx_store_split8(a.out, pix, a.cout, co, v);
+                else st8(a.out + pix * a.cout + co, v);
             }
         }
     }
-#if HX_TRACE
-    if (EPI == CER_EPI_GATES && lane == 0) {
-        trace_base[63 * 4 + 0] = trace_t0;
-        trace_base[63 * 4 + 1] = trace_t1;
-        trace_base[63 * 4 + 2] = trace_t2;
-        trace_base[63 * 4 + 3] = __builtin_readcyclecounter();
-        trace_base[62 * 4 + 0] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));   // HW_REG_HW_ID, all 32 bits
-        trace_base[62 * 4 + 1] = (unsigned long long)nsteps;
-        trace_base[62 * 4 + 2] = __builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11));  // HW_REG_XCC_ID
-    }
-#endif
 }
 
 // ---------------------------------------------------------------------------------------- host side
@@ -694,7 +584,7 @@ extern "C" int cer_conv3x3_f16x3(const cer_conv_inputs* in, const void* packed_w
     if (in->nsrc <= 0 || in->nsrc > CER_CONV_MAX_SRC) return CER_EINVAL;
     const int out_split = (epi & CER_EPI_OUT_SPLIT) != 0, aux_split = (epi & CER_EPI_AUX_SPLIT) != 0;
     epi &= ~(CER_EPI_OUT_SPLIT | CER_EPI_AUX_SPLIT);
-    if ((out_split || aux_split) && (epi == HX_EPI_DELTA || !HX_EPI2)) return CER_EINVAL;
+    if ((out_split || aux_split) && epi == HX_EPI_DELTA) return CER_EINVAL;
     if (epi == CER_EPI_GATES && (!out2 || !aux)) return CER_EINVAL;
     if (epi == CER_EPI_GRU && (!aux || !aux2)) return CER_EINVAL;
     if (epi == HX_EPI_DELTA && (!aux || Cout % 128 != 0)) return CER_EINVAL;
@@ -731,21 +621,8 @@ extern "C" int cer_conv3x3_f16x3(const cer_conv_inputs* in, const void* packed_w
     hipStream_t st = (hipStream_t)stream;
     // 128 output channels per block: 8 waves (4 x 2) of 32 px x 64 ch, 3-slot weight ring, 2 blocks (16 waves) per CU;
     //  64 output channels per block: 8 waves (4 x 2) of 32 px x 32 ch, 3-slot ring, 2 blocks (16 waves) per CU.
-#if HX_TH == 8                          // experiment: 8 x 32 pixel tile, 8 waves of 64 px x (64 | 32) ch, 256 registers, 1 block/CU
-    if (epi == HX_EPI_DELTA) return CER_ESHAPE;
-    if (Cout % 128 == 0) return hx_launch<4, 2, 2, 2, 3, 2>(a, epi, Cout / 128, st);
-    return hx_launch<4, 2, 2, 1, 3, 2>(a, epi, Cout / 64, st);
-#elif defined(HX_CFG) && HX_CFG == 1      // experiment: 4-wave blocks, 64 px x 64 ch per wave, 256 registers, 2 blocks/CU
-    if (Cout % 128 == 0 && epi != HX_EPI_DELTA) return hx_launch<2, 2, 2, 2, 3, 2>(a, epi, Cout / 128, st);
-#elif defined(HX_CFG) && HX_CFG == 2    // experiment: 4-wave blocks, 128 px x 32 ch per wave
-    if (Cout % 128 == 0 && epi != HX_EPI_DELTA) return hx_launch<1, 4, 4, 1, 3, 2>(a, epi, Cout / 128, st);
-#elif defined(HX_CFG) && HX_CFG == 3    // experiment: 4-wave blocks, 32 px x 128 ch per wave
-    if (Cout % 128 == 0 && epi != HX_EPI_DELTA) return hx_launch<4, 1, 1, 4, 3, 2>(a, epi, Cout / 128, st);
-#endif
-#if HX_TH == 4
     if (Cout % 128 == 0) return hx_launch<4, 2, 1, 2, 3, 4>(a, epi, Cout / 128, st);
     return hx_launch<4, 2, 1, 1, 3, 4>(a, epi, Cout / 64, st);
-#endif
 }
 
 // ---- delta head tail for the fused path ------------------------------------------------------------------

@@ -524,3 +524,29 @@ def test_encoder_fp6_weight_packing():
             best = d.min(axis=1)
             assert np.all(np.abs(np.abs(dec) - x) <= best + 1e-12)
             assert np.all((np.sign(dec) == np.sign(ref)) | (dec == 0))
+
+
+# Every macro a product source lets a -D flag override (#ifndef NAME / #define NAME), and who needs it.  A new one belongs here with
+# its user, and in DESIGN.md's table "Compile-time switches of the product sources"; an experiment's switch leaves with the experiment.
+PRODUCT_SWITCHES = {
+    "SX_TRACE": "tools/trace_s16.py reads the cycle stamps of variants/libcermvs_sxtrace.so",
+    "SX_STAGGER": "timing only, 0 (off) is a legitimate value: DESIGN.md 3q, the other side of profiles/r06_stagger_ab.txt",
+    "CER_FUZZ": "tools/fuzz_schedule.sh runs tests/test_determinism_gpu.py on variants/libcermvs_fuzz.so",
+    "CER_WITH_SXPC": "variants/libcermvs_optin.so: the producer / consumer convs behind cer_conv3x3_s16_pc (tests marked `variants`)",
+    "CER_WITH_LINES8": "variants/libcermvs_optin.so: the multi-line cost volume behind cer_cost_lines_form (tests marked `variants`)",
+}
+
+
+def test_product_sources_have_no_other_compile_time_switches():
+    csrc = os.path.join(REPO, "cer-mvs_amd", "csrc")
+    srcs = re.search(r"^SRCS\s*=\s*(.*)$", open(os.path.join(csrc, "Makefile")).read(), re.M).group(1).split()
+    assert len(srcs) >= 18
+    found = {}
+    for name in srcs + ["common.hpp", "conv_s16_shared.hpp", "compact.hpp", "pack.hpp"]:
+        text = open(os.path.join(csrc, name)).read()
+        for m in re.finditer(r"^[ \t]*#[ \t]*ifndef[ \t]+(\w+)[^\n]*\n[ \t]*#[ \t]*define[ \t]+(\w+)", text, re.M):
+            if m.group(1) == m.group(2):
+                found.setdefault(m.group(1), name)
+    extra = {k: v for k, v in found.items() if k not in PRODUCT_SWITCHES}
+    assert not extra, f"overridable switches without a listed user (name: file): {extra}"
+    assert sorted(found) == sorted(PRODUCT_SWITCHES), f"listed but gone: {sorted(set(PRODUCT_SWITCHES) - set(found))}"
