@@ -6,7 +6,6 @@ each convolution stores its RAW output plus per-block statistics partials, and t
 ``relu((x - mean) * rstd)`` while it stages its input tile.  Activations are channels-last fp32; convolutions run on
 the split-f16 MFMA path (fp32-equivalent).  Only "instance" and "none" norms (the two the reference uses) are built."""
 import ctypes
-import os
 
 import torch
 
@@ -14,8 +13,9 @@ from . import _lib as L
 
 STEM_MFMA = True          # 7x7 stem on the matrix cores (csrc/enc_stem.hip); False: the direct fp32 kernel (exact fmaf chain)
 # "pc" (round 4, default): producer / consumer convolutions with the residual merges formed on the fly (csrc/enc_pc.hip);
-# "tiled": the round-2/3 kernels (csrc/enc_conv.hip: every wave runs every phase; separate enc_merge passes) - kept for A/B runs
-ENGINE = os.environ.get("CER_ENC_ENGINE", "pc")
+# "tiled": the round-2/3 kernels (csrc/enc_conv.hip: every wave runs every phase; separate enc_merge passes) - the cross-reference of "pc"
+# (tests/test_encoder_parity_gpu.py sets it)
+ENGINE = "pc"
 
 
 class _In:

@@ -7,6 +7,20 @@ projective_ops.py:5-13,26-28, core/corr.py:87-88) runs inside the cost-build ker
 import torch
 
 
+def scaled_cameras(poses, intrinsics, scale, factor):
+    """The camera prologue of every forward (reference: core/raft.py:35-39): poses [...,4,4] with the translations multiplied
+    by ``scale`` (a float, or a tensor with one element on any device; None: left as they are), intrinsics [B,N,3,3] with the first
+    two rows divided by the encoders' ``factor`` -> (poses, intrinsics, s), float32 copies - the inputs are not mutated - and
+    ``scale`` as a Python float (None for None)."""
+    poses = poses.clone().float()
+    s = None if scale is None else float(torch.as_tensor(scale).reshape(-1)[0])
+    if s is not None:
+        poses[..., :3, 3] *= s
+    intrinsics = intrinsics.clone().float()
+    intrinsics[:, :, :2] /= factor
+    return poses, intrinsics, s
+
+
 def pij_matrices(poses, intrinsics, ii, jj):
     """poses [N,4,4] world->camera, intrinsics [N,3,3] at feature resolution, ii/jj index lists
     -> float32 CPU tensor [len(jj),4,4]."""

@@ -12,8 +12,9 @@ reference that a caller can observe, all deliberate (SURVEY.md §8(a) "quirks"):
   * computation is fp32 end to end by default (``precision="fp32"``); the reference's GPU path runs
     encoders + GRU under fp16 autocast (raft.py:9,55), selectable with ``precision="amp"`` for the
     encoders only.  ``gru_precision`` picks the arithmetic of the update block's 3x3 convolutions: "auto" (default: the first
-    AUTO_INPUTS forwards of a set of weights run in both split-f16 forms and "s16f8" is kept only if it stays within AUTO_TOL of
-    "s16" on every one of them - see __init__),
+    AUTO_INPUTS forwards of a set of weights walk the candidates of AUTO_FORMS, cheapest first - each input runs in the last form,
+    "s16", and in the current candidate; a candidate further than AUTO_TOL from "s16" is demoted to the next form, which is tested on
+    the same input, and "s16" ends the walk - see __init__),
     "s16f8" (split-f16 operands, x*w = xh*wh + (xh*wl + xl*wh) into one fp32 accumulator with the main term on the f16
     matrix instruction and the two 2^-11 correction terms on the block-scaled fp8 one - 4e-6 relative L1 from fp32 end to end,
     csrc/conv_s16.hip), "s16" (all three terms in f16: fp32-class, 2e-7), "f16x3" (round-1 kernels: two fp32 accumulators) or
@@ -30,11 +31,8 @@ from . import dist as cdist
 from . import ops
 from .corr import CorrBlock, fmaps_to_nhwc, report
 from .extractor import BasicEncoder
-from .projective import pij_matrices
+from .projective import pij_matrices, scaled_cameras
 from .update import UpdateBlock
-
-
-_SIDE_STREAMS = {}
 
 
 class SaturationError(RuntimeError):
@@ -86,18 +84,18 @@ class RAFT(nn.Module):
         # "auto" (default): the fp8-correction form keeps ~15 product bits in the correction terms; how much of that reaches the depth
         # depends on how the update block's weights condition the 32-iteration recurrence (tests/test_determinism_gpu.py: 22-38 x the
         # all-f16 form's distance from exact fp32 - 3e-6 on the golden weights, 3e-4 with the conv weights doubled and heavy-tailed).
-        # So the FIRST AUTO_INPUTS (3) test-mode forwards of a set of weights run twice - "s16f8" and "s16" (fp32-class) - each on its own
-        # input (round 5: conditioning also depends on the scene, VERDICT r4 "weak" 1c; round 4 decided on the first input alone); if on
-        # ANY of them the two disparities differ by more than AUTO_TOL relative L1 (or AUTO_MAX_TOL of the largest disparity at any
-        # single pixel) the model keeps "s16" from there on (with a warning), else "s16f8".  Three extra forwards per set of weights buy the
-        # 12 % of the fp8 form wherever it is safe, and the fp32-class margin wherever it is not.  Callers who need a decision that does
-        # not depend on which inputs come first pin gru_precision explicitly.
-        # Round 6: the calibration walks a LIST of candidates (AUTO_FORMS) from the cheapest: the current candidate is compared with "s16" on
-        # every calibration input, a miss demotes to the next form (tested on the same input), "s16" ends the walk.  A third form exists -
-        # "s16f6", the correction terms on the FP6 form of the same instruction (half its matrix-pipe passes again; one E8M0 scale per
-        # 16-channel block) - see AUTO_FORMS for why it is not a default candidate.
-        self.auto_choice = None                   # None until decided; then "s16f6", "s16f8" or "s16"
-        self.auto_error = None                    # the worst measured relative L1 between the two forms
+        # So the FIRST AUTO_INPUTS (3) test-mode forwards of a set of weights are calibration forwards, each on its own input (conditioning
+        # also depends on the scene, VERDICT r4 "weak" 1c).  They walk a LIST of candidates (_auto_forms: AUTO_FORMS, cheapest first; the last
+        # one, "s16", is the fp32-class reference): every calibration input runs in the last form and in the current candidate; if the two
+        # disparities differ by more than AUTO_TOL relative L1 (or AUTO_MAX_TOL of the largest disparity at any single pixel) the candidate
+        # is demoted to the next form (with a warning), which is tested on the same input; reaching the last form ends the walk.  The
+        # candidate that stands after the last calibration input is kept.  The extra forwards buy the cheaper forms' speed wherever they are
+        # safe, and the fp32-class margin wherever they are not.  Callers who need a decision that does not depend on which inputs come
+        # first pin gru_precision explicitly.  A further form exists - "s16f6", the correction terms on the FP6 form of the same instruction
+        # (half its matrix-pipe passes again; one E8M0 scale per 16-channel block) - see AUTO_FORMS for why it is not a default candidate.
+        self.auto_choice = None                   # None until decided; then the form that stands (one of _auto_forms())
+        self.auto_error = None                    # the worst relative L1 from the last form among the comparisons that passed (a walk
+                                                  # that ended at the last form: the last demoted candidate's)
         self._auto_sig = None
         self._auto_left = 0                       # calibration forwards still to run for the current set of weights
         self.encoder_backend = encoder_backend      # "hip": channels-last engine (csrc/enc_conv.hip); "miopen": PyTorch-ROCm convs
@@ -198,125 +196,55 @@ class RAFT(nn.Module):
         ``parts``: "all", or "src" (source features only: (None, None, None, f2)) / "ref" (context + reference features:
         (net, inp, f1, None)) - the sharded forward encodes its source views first, starts their all-gather, and encodes the
         reference view while the collective is in flight."""
-        if parts == "src":
-            if not views:
-                return None, None, None, None
-            if self.encoder_backend == "hip" and self.precision == "fp32" and self.encoder_type == "HR":
-                dev = images.device
-                self._get_engines(dev)
-                factor = 4
-                h, w = images.shape[-2] // factor, images.shape[-1] // factor
-                key = (len(views), h, w, str(dev))
-                buf = self._src_buf.get(key)
-                if buf is None:
-                    buf = torch.zeros(len(views), (h + 4) * (w + 4), self.dim_fmap, device=dev, dtype=torch.float32)
-                    self._src_buf = {key: buf}
-                _, src, _, _ = self._engines[1].features(images[0, list(views)], n_ref=0, border=2, scale=0.125, src_out=buf, raw=raw)
-                return None, None, None, src
-            x = images[0, list(views)]
-            if raw:
-                x = x.float() * (2 / 255.0) - 1
-            with torch.autocast("cuda", dtype=torch.float16, enabled=self.precision == "amp"):
-                fm = self.fnet(x).float()
-            return None, None, None, fmaps_to_nhwc(fm, border=2)
-        if parts == "ref":
-            views = []
-        idx = [0] + list(views)
+        views = [] if parts == "ref" else list(views)
+        ref = parts != "src"
+        if not ref and not views:
+            return None, None, None, None
+        idx = ([0] if ref else []) + views
         stack = images[0] if idx == list(range(images.shape[1])) else images[0, idx]      # (no gather copy when every view is local)
-        if self.encoder_backend == "hip" and self.precision == "fp32" and self.encoder_type == "HR":
+        if self._hip_encoders():
             dev = images.device
             _, eng_f, eng_c = self._get_engines(dev)
-            net, inp, h, w = eng_c.context(images[0, :1], raw=raw)
-            key = (len(views), h, w, str(dev))
-            buf = self._src_buf.get(key)
-            if views and buf is None:      # border texels are written once (zeros) and never touched again
-                buf = torch.zeros(len(views), (h + 4) * (w + 4), self.dim_fmap, device=dev, dtype=torch.float32)
-                self._src_buf = {key: buf}
-            ref, src, _, _ = eng_f.features(stack, n_ref=1, border=2, scale=0.125, src_out=buf if views else None, raw=raw)
-            return net, inp, ref[0], src
+            net, inp, h, w = None, None, images.shape[-2] // 4, images.shape[-1] // 4
+            if ref:
+                net, inp, h, w = eng_c.context(images[0, :1], raw=raw)
+            buf = self._source_buffer((len(views), h, w, str(dev)), lambda: torch.zeros(
+                len(views), (h + 4) * (w + 4), self.dim_fmap, device=dev, dtype=torch.float32)) if views else None
+            f1, src, _, _ = eng_f.features(stack, n_ref=int(ref), border=2, scale=0.125, src_out=buf, raw=raw)
+            return net, inp, f1[0] if ref else None, src
         if raw:
-            images = images.float() * (2 / 255.0) - 1
-            stack = images[0] if idx == list(range(images.shape[1])) else images[0, idx]
-        amp = self.precision == "amp"
-        with torch.autocast("cuda", dtype=torch.float16, enabled=amp):
-            ctx = self.cnet(images[:, [0]])[0, 0].float()                       # [128,h,w]
+            stack = stack.float() * (2 / 255.0) - 1
+        with torch.autocast("cuda", dtype=torch.float16, enabled=self.precision == "amp"):
+            ctx = self.cnet(stack[None, :1])[0, 0].float() if ref else None      # [128,h,w]
             fm = self.fnet(stack).float()                                      # [n,C,h,w] (instance norm is per image)
+        if not ref:
+            return None, None, None, fmaps_to_nhwc(fm, border=2)
         net = torch.tanh(ctx[: self.dim_net])
         inp = torch.relu(ctx[self.dim_net:])
         f2 = fmaps_to_nhwc(fm[1:], border=2) if views else None
         return ops.nchw_to_nhwc(net.contiguous()), ops.nchw_to_nhwc(inp.contiguous()), fmaps_to_nhwc(fm[:1])[0], f2
 
-    # ---------------------------------------------------------------- encoders with the first stage's cost volume underneath
-    import os as _os
-    # single-GPU fast path: build stage 0's per-view partial volumes on a second stream while later view batches are encoded.  OFF by
-    # default: measured at the bench workload (tools/archive/exp_pipeline.py, same process, 10 forwards each) 20.97 ms with it, 20.96 without -
-    # the tile kernel's three 50-KiB-LDS blocks per CU leave no room for encoder blocks beside them, so the two kernels take turns
-    # on the CUs instead of overlapping.  CER_PIPELINE=1 (or RAFT.PIPELINE_BUILD = True) turns it on; results are bit-identical.
-    PIPELINE_BUILD = _os.environ.get("CER_PIPELINE", "0") == "1"
+    def _hip_encoders(self):
+        """The HIP encoder engines (encoder_hip.py) serve this model; otherwise the PyTorch-ROCm modules do."""
+        return self.encoder_backend == "hip" and self.precision == "fp32" and self.encoder_type == "HR"
 
-    @staticmethod
-    def _batches(V):
-        nb = 2 if V >= 2 else 1           # (measured at 10 views: two batches 20.9 ms, three 20.95, no pipeline 21.1 - the two kernels share CUs badly)
-        base, rem = divmod(V, nb)
-        return [base + (1 if i < rem else 0) for i in range(nb)]
-
-    def _encode_pipelined(self, images, V, Pij, disp, D, incre, h, w):
-        """encode() for all V source views in batches; as soon as a batch's feature rows exist, a second HIP stream splits them to
-        f16 hi|lo and builds that batch's partial cost volumes (cer_cost_lines_views_f32) - a kernel bound by vector issue and LDS
-        latency that leaves the matrix pipe and most issue slots idle - while the main stream encodes the next batch (MFMA / HBM
-        bound).  Returns (net, inp, f1, f2, (f1s, f2s), event of the last build); the caller finishes the volume with ops.cost_lines_reduce."""
-        dev = images.device
-        _, eng_f, eng_c = self._get_engines(dev)
-        main = torch.cuda.current_stream()
-        side = _SIDE_STREAMS.get(str(dev))          # (module-level: streams / events must not end up in a deep copy of the model)
-        if side is None:
-            side = _SIDE_STREAMS[str(dev)] = torch.cuda.Stream(device=dev)
-        net, inp, _, _ = eng_c.context(images[0, :1], raw=True)
-        Pb = (h + 4) * (w + 4)
-        key = (V, h, w, str(dev))
-        buf = self._src_buf.get(key)
-        if buf is None:                        # border texels are written once (zeros) and never touched again
-            buf = torch.zeros(V, Pb, self.dim_fmap, device=dev, dtype=torch.float32)
-            self._src_buf = {key: buf}
-        lws = ops.lines_workspace(V, h, w, D, dev)           # (this stream's: both halves of the build use it)
-        f1s = torch.empty(h * w, 128, device=dev, dtype=torch.float16)
-        f2s = torch.empty(V, Pb, 128, device=dev, dtype=torch.float16)
-        f1, v0 = None, 0
-        for bi, nvb in enumerate(self._batches(V)):
-            if bi == 0:
-                ref, _, _, _ = eng_f.features(images[0, 0:1 + nvb], n_ref=1, border=2, scale=0.125, src_out=buf[0:nvb], raw=True)
-                f1 = ref[0]
-            else:
-                eng_f.features(images[0, 1 + v0:1 + v0 + nvb], n_ref=0, border=2, scale=0.125, src_out=buf[v0:v0 + nvb], raw=True)
-            ev = torch.cuda.Event()
-            ev.record(main)
-            with torch.cuda.stream(side):
-                side.wait_event(ev)
-                if bi == 0:
-                    ops.feat_split(f1, out=f1s)
-                ops.feat_split(buf[v0:v0 + nvb], out=f2s[v0:v0 + nvb])
-                ops.cost_lines_views(f1s, f2s, None, Pij, disp, V, v0, nvb, h, w, D, incre, True, ws=lws, two_term=self._cost_x2)
-            v0 += nvb
-        done = torch.cuda.Event()
-        done.record(side)                      # (the caller waits for it right before the view reduction: the hoisted convs run meanwhile)
-        return net, inp, f1, buf, (f1s, f2s), (done, lws)
-
-    DIRECT_SPLIT = _os.environ.get("CER_DIRECT_SPLIT", "1") == "1"
-    COMPACT_VOLUME = _os.environ.get("CER_COMPACT_VOLUME", "1") == "1"      # level-0-only rows of the folded volume (s16 loop; A/B switch)
+    def _source_buffer(self, key, make):
+        """The persistent buffer the feature head writes the source views into: its border texels are written once (zeros, by ``make``)
+        and never touched again.  One live entry: a new key (view count, feature grid, device, layout) replaces it."""
+        if key not in self._src_buf:
+            self._src_buf = {key: make()}
+        return self._src_buf[key]
 
     def _encode_direct_split(self, images, V, h, w):
         """encode() whose feature head writes the cost volume's split-f16 operand planes directly -> (net, inp, (f1s, f2s, slots))."""
         dev = images.device
         _, eng_f, eng_c = self._get_engines(dev)
         net, inp, _, _ = eng_c.context(images[0, :1], raw=True)
-        key = ("split", V, h, w, str(dev))
-        buf = self._src_buf.get(key)
-        if buf is None:                        # border texels are written once (zeros) and never touched again
-            buf = (torch.zeros(V, (h + 4) * (w + 4), 128, device=dev, dtype=torch.float16), torch.arange(V, device=dev, dtype=torch.int32))
-            self._src_buf = {key: buf}
+        f2s, slots = self._source_buffer(("split", V, h, w, str(dev)), lambda: (
+            torch.zeros(V, (h + 4) * (w + 4), 128, device=dev, dtype=torch.float16), torch.arange(V, device=dev, dtype=torch.int32)))
         f1s = torch.empty(h * w, 128, device=dev, dtype=torch.float16)
-        eng_f.features_split(images[0], f1s, buf[0], n_ref=1, border=2, scale=0.125, raw=True, flag=ops.overflow_flag(dev))
-        return net, inp, (f1s, buf[0], buf[1])
+        eng_f.features_split(images[0], f1s, f2s, n_ref=1, border=2, scale=0.125, raw=True, flag=ops.overflow_flag(dev))
+        return net, inp, (f1s, f2s, slots)
 
     # ---------------------------------------------------------------- forward
     def forward(self, images, poses, intrinsics, scale=None, do_report=False):
@@ -408,10 +336,13 @@ class RAFT(nn.Module):
         return True
 
     def _forward_calibrating(self, images, poses, intrinsics, scale, do_report):
-        """gru_precision="auto": this set of weights is still being calibrated - run the forward in both split-f16 forms and compare
-        (relative L1 and largest single difference; all ranks of a view_group agree on the worst rank's figures).  The fp8-correction
-        form survives only if EVERY one of the first AUTO_INPUTS inputs stays within the tolerances; the first one that does not
-        settles the model on the fp32-class form.  Returns the result of the form that stands after this input."""
+        """gru_precision="auto": this set of weights is still being calibrated - one step of the walk over ``_auto_forms()`` (AUTO_FORMS,
+        cheapest first; the last form is the fp32-class reference).  The input runs in the last form and in the current candidate (the
+        form that stood after the previous calibration input; the first form for new weights) and the two results are compared (relative
+        L1 and largest single difference; all ranks of a view_group agree on the worst rank's figures).  A candidate outside the
+        tolerances is demoted to the next form, which is tested on this same input; reaching the last form ends the walk for these
+        weights.  A candidate that passes stands, and AUTO_INPUTS inputs are tested in all.  Returns the result of the form that stands
+        after this input."""
         ub = self.update_block
         if self._auto_sig != self._params_sig():   # new weights: start over
             self._auto_left, self.auto_error, self.auto_choice = self.AUTO_INPUTS, 0.0, None
@@ -457,22 +388,14 @@ class RAFT(nn.Module):
                           f"gru_precision={cand!r} for these weights")
         return out
 
-    def _split_path(self, dev, V, D0=None):
-        """(pipelined, direct_split) of a single-GPU forward with V source views: which of the two encode forms that hand the cost volume
-        its split-f16 operand planes applies (neither: the plain ``encode``)."""
+    def _split_path(self, dev, V):
+        """A single-GPU forward with V source views takes the direct-split path: every stage builds its volume on the epipolar-line
+        tiles, so the feature head writes the cost volume's split-f16 operand planes itself (encoder_hip.features_split) - no fp32
+        feature maps, no feat_split pass.  Otherwise the plain ``encode`` applies."""
         from . import _lib as L
-        if D0 is None:
-            D0 = self.stages()[0][0]
-        pipelined = (self.PIPELINE_BUILD and self.view_group is None and V >= 2 and self.encoder_backend == "hip" and self.precision == "fp32"
-                     and self.encoder_type == "HR" and self.dim_fmap == 64 and D0 <= 64 and L.load().cer_cost_build_algo(-1) != 1)
-        # single-GPU fast path: when every stage builds its volume on the epipolar-line tiles, the feature head writes the split-f16
-        # operand planes itself (encoder_hip.features_split): no fp32 feature maps, no feat_split pass
-        direct_split = (self.DIRECT_SPLIT and not pipelined and self.view_group is None and V >= 1 and self.encoder_backend == "hip"
-                        and self.precision == "fp32" and self.encoder_type == "HR" and self.dim_fmap == 64
-                        and L.load().cer_cost_build_algo(-1) != 1 and all(D_ <= 64 for D_, _, _ in self.stages()))
-        if direct_split:
-            direct_split = self._get_engines(dev)[1].supports_split_head()
-        return bool(pipelined), bool(direct_split)
+        return bool(self.view_group is None and V >= 1 and self._hip_encoders() and self.dim_fmap == 64
+                    and L.load().cer_cost_build_algo(-1) != 1 and all(D_ <= 64 for D_, _, _ in self.stages())
+                    and self._get_engines(dev)[1].supports_split_head())
 
     def supports_cached(self, dev):
         """``forward_cached`` applies: a test-mode forward of this model takes the direct-split path (HIP "HR" encoders in fp32, every stage
@@ -481,32 +404,26 @@ class RAFT(nn.Module):
         agg = self.update_block.aggregation
         if not self.test_mode or "mean" not in agg or len(agg) != 1 or self.overflow_policy == "fallback":
             return False
-        return self._split_path(dev, 2) == (False, True) and self._split_path(dev, 1) == (False, True)
+        return self._split_path(dev, 1)              # (the number of views does not enter beyond V >= 1)
 
     def _forward_fast(self, images, poses, intrinsics, scale, do_report):
         self._validate_packs()
         dev = images.device
         batch, num, ch, ht, wd = images.shape
+        factor = 8 if self.encoder_type == "LR" else 4
         if self.view_group is not None and self.shard == "slab":
             from . import slab
             ex = getattr(self, "_slab_ex", None)           # one exchange object per (model, group): its gather / receive buffers are persistent
             if ex is None or ex.group is not self.view_group:
                 ex = self._slab_ex = slab.DistExchange(self.view_group)
-            if ex.G > 1 and slab.can_shard(ht // (8 if self.encoder_type == "LR" else 4), ex.G):
+            if ex.G > 1 and slab.can_shard(ht // factor, ex.G):
                 return slab.sharded_forward(self, images, poses, intrinsics, scale, ex)
-        poses = poses.clone().float()
-        s = float(torch.as_tensor(scale).reshape(-1)[0])
-        poses[..., :3, 3] *= s
-        factor = 8 if self.encoder_type == "LR" else 4
-        intrinsics = intrinsics.clone().float()
-        intrinsics[:, :, :2] /= factor
+        poses, intrinsics, s = scaled_cameras(poses, intrinsics, scale, factor)
         if ht % factor or wd % factor:
             raise RuntimeError(f"RAFT.forward: image size {wd}x{ht} must be a multiple of {factor} (the cost volume lives at 1/{factor} "
                                "resolution; the reference crops / rescales to such sizes, utils/data_utils.py:58-78)")
         images = images.float()                           # (normalised to [-1,1] inside the encoders' stem kernel)
         h, w = ht // factor, wd // factor
-        P = h * w
-        ub = self.update_block
 
         # ---- view sharding: this rank encodes and builds the partial view-sum over its own source views only
         V = num - 1
@@ -514,20 +431,15 @@ class RAFT(nn.Module):
         # (uploaded BEFORE the encoders are enqueued: a pageable H2D copy is stream-ordered and would block the host
         # until everything enqueued so far has finished)
         Pij = pij_matrices(poses[0], intrinsics[0], [0] * len(views), views).to(dev) if views else None
-        disp = torch.zeros(P, device=dev, dtype=torch.float32)
-        (D0, incre0, _) = self.stages()[0]
-        from . import _lib as L
-        pipelined, direct_split = self._split_path(dev, V, D0)
-        split, build_done = None, None
-        if pipelined:
-            net_l, inp_l, f1, f2, split, build_done = self._encode_pipelined(images, V, Pij, disp, D0, incre0, h, w)
-        elif direct_split:
+        disp = torch.zeros(h * w, device=dev, dtype=torch.float32)
+        if self._split_path(dev, V):
             net_l, inp_l, split = self._encode_direct_split(images, V, h, w)
             f1, f2 = split[0], None                       # (cost_build takes the device from its first argument; the rows are never read)
         else:
             net_l, inp_l, f1, f2 = self.encode(images, views, raw=True)
+            split = None
         del images
-        return self._run_stages(dev, net_l, inp_l, f1, f2, split, views, V, Pij, disp, h, w, s, do_report, pipelined, build_done)
+        return self._run_stages(net_l, inp_l, f1, f2, split, Pij, disp, views, V, h, w, do_report) * s
 
     def forward_cached(self, ref_image, f1s, store, slots, poses, intrinsics, scale):
         """A test-mode forward whose fnet features already exist (scan.ScanSession): ``ref_image`` [1,3,H,W] (or [3,H,W]) raw 0..255, the
@@ -551,11 +463,7 @@ class RAFT(nn.Module):
         if ref_image.dim() == 3:
             ref_image = ref_image[None]
         ht, wd = ref_image.shape[-2:]
-        poses = poses.clone().float()
-        s = float(torch.as_tensor(scale).reshape(-1)[0])
-        poses[..., :3, 3] *= s
-        intrinsics = intrinsics.clone().float()
-        intrinsics[:, :, :2] /= 4
+        poses, intrinsics, s = scaled_cameras(poses, intrinsics, scale, 4)
         if ht % 4 or wd % 4:
             raise RuntimeError(f"RAFT.forward_cached: image size {wd}x{ht} must be a multiple of 4")
         h, w = ht // 4, wd // 4
@@ -568,14 +476,17 @@ class RAFT(nn.Module):
         Pij = pij_matrices(poses[0], intrinsics[0], [0] * V, views).to(dev)
         disp = torch.zeros(h * w, device=dev, dtype=torch.float32)
         net_l, inp_l, _, _ = self._get_engines(dev)[2].context(ref_image.float(), raw=True)
-        return self._run_stages(dev, net_l, inp_l, f1s, None, (f1s, store, slots), views, V, Pij, disp, h, w, s, False, False, None)
+        return self._run_stages(net_l, inp_l, f1s, None, (f1s, store, slots), Pij, disp, views, V, h, w) * s
 
-    def _run_stages(self, dev, net_l, inp_l, f1, f2, split, views, V, Pij, disp, h, w, s, do_report, pipelined, build_done):
+    def _run_stages(self, net_l, inp_l, f1, f2, split, Pij, disp, views, V, h, w, do_report=False):
         """What follows the encoders in a single-GPU or view-sharded forward: the update block's loop objects, the hoisted convolutions,
-        per stage the cost volume and the GRU iterations, the overflow policy's end-of-forward step -> disparity * scale [1,1,h,w]."""
+        per stage the cost volume and the GRU iterations, the overflow policy's end-of-forward step -> disparity [1,1,h,w] (unscaled).
+        What the encoders produced: ``net_l``, ``inp_l`` (context), ``f1`` / ``f2`` (fp32 reference / bordered source rows of this rank's
+        ``views``) or ``split`` (the same as split-f16 operand planes with a view -> block map; None: formed here when a stage needs them).
+        The geometry: ``Pij`` of ``views`` (this rank's, of V in all), the zeroed ``disp`` [h*w] that the stages update in place."""
         from . import _lib as L
         ub = self.update_block
-        P = h * w
+        dev = disp.device
         if ub.conv_mode == "s16":
             try:
                 for st_ in range(len(self.cascade)):
@@ -599,23 +510,18 @@ class RAFT(nn.Module):
             single = self.view_group is None   # no cross-rank sum between the build and the pooling: fuse them
             # round 5: the folded volume keeps LEVEL 0 ONLY (rows of D instead of 1.75 D floats); the lookup kernel forms the pooled levels
             # on the fly, bit-identically (csrc/lookup.hip lk_elem) - less to write, to all-reduce (shard="views") and to read 32 times
-            compact = self.COMPACT_VOLUME
-            if pipelined and stage == 0:          # the partial volumes were built under the encoders: only the view reduction is left
-                torch.cuda.current_stream().wait_event(build_done[0])
-                vol, origin = ops.cost_lines_reduce(disp, V, h, w, D, incre, True, ub.num_levels, pyramid_scale=1.0 / V, ws=build_done[1],
-                                                    compact=compact)
-            elif views:
+            if views:
                 vol, origin = ops.cost_build(f1, f2, Pij, disp, D, incre, stage == 0, h, w, ub.num_levels, fold=True,
                                              pyramid_scale=(1.0 / V) if (single and D <= 64) else None, split=split,
-                                             src_hw=(h, w) if f2 is None else None, compact=compact, two_term=self._cost_x2)
+                                             src_hw=(h, w) if f2 is None else None, compact=True, two_term=self._cost_x2)
             else:                      # more ranks than views: contribute zeros
-                _, _, rs = ops.row_layout(D, ub.num_levels, compact)
-                vol = torch.zeros(P, rs, device=dev)
-                vol.level0_only = bool(compact)
+                _, _, rs = ops.row_layout(D, ub.num_levels, True)
+                vol = torch.zeros(h * w, rs, device=dev)
+                vol.level0_only = True
                 origin = cdist.stage_origin(disp, D, incre, stage == 0)
             if not (single and views and D <= 64):
                 cdist.reduce_volume(vol, self.view_group)
-                ops.pyramid(vol, D, 1 if compact else ub.num_levels, scale=1.0 / V)
+                ops.pyramid(vol, D, 1, scale=1.0 / V)
             if do_report and stage > 0:
                 report()
             ub.run(T, vol, origin, net_l, disp, hoisted, stage, h, w, D, incre, ws)
@@ -627,20 +533,14 @@ class RAFT(nn.Module):
             bits = cdist.max_int(int(ops.check_overflow(dev)), self.view_group, dev)
             if bits:
                 self._raise_overflow(bits)
-        return disp.view(1, 1, h, w) * s
+        return disp.view(1, 1, h, w)
 
     def _forward_literal(self, images, poses, intrinsics, scale, do_report):
         """Reference control flow call for call (CorrBlock per stage, per-view lookup, UpdateBlock.forward):
         used for non-"mean" aggregations and by the parity tests of the literal API."""
         dev = images.device
-        poses = poses.clone().float()
-        s = None
-        if scale is not None:
-            s = float(torch.as_tensor(scale).reshape(-1)[0])
-            poses[..., :3, 3] *= s
         factor = 8 if self.encoder_type == "LR" else 4
-        intrinsics = intrinsics.clone().float()
-        intrinsics[:, :, :2] /= factor
+        poses, intrinsics, s = scaled_cameras(poses, intrinsics, scale, factor)
         batch, num, ch, ht, wd = images.shape
         images = images.float() * (2 / 255.0) - 1
         h, w = ht // factor, wd // factor

@@ -312,18 +312,14 @@ def sharded_forward(model, images, poses, intrinsics, scale, ex):
     Returns the full-resolution disparity [1,1,h,w] * scale (identical on every rank)."""
     from . import _lib as L, ops, update
     from .dist import local_views_for
-    from .projective import pij_matrices
+    from .projective import pij_matrices, scaled_cameras
     dev = images.device
     G = ex.G
     if getattr(model, "overflow_policy", "lazy") == "fallback":
         raise NotImplementedError("RAFT.overflow_policy='fallback' is not available on the sharded forward (every rank would have to "
                                   "repeat the forward together): use 'lazy' or 'raise'")
-    s = float(torch.as_tensor(scale).reshape(-1)[0])
-    poses = poses.clone().float()
-    poses[..., :3, 3] *= s
     factor = 8 if model.encoder_type == "LR" else 4
-    intr = intrinsics.clone().float()
-    intr[:, :, :2] /= factor
+    poses, intr, s = scaled_cameras(poses, intrinsics, scale, factor)
     _, num, _, ht, wd = images.shape
     if ht % factor or wd % factor:
         raise RuntimeError(f"sharded_forward: image size {wd}x{ht} must be a multiple of {factor}")
@@ -398,9 +394,9 @@ def sharded_forward(model, images, poses, intrinsics, scale, ex):
             d = st[g]
             vol, origin = ops.cost_build(d["f1s"], d["f2"], Pij, d["disp"], D, incre, stage == 0, d["hs"], w, ub.num_levels,
                                          fold=True, src_hw=(h, w), y0=d["e0"], pyramid_scale=(1.0 / V) if D <= 64 else None,
-                                         split=d["split"], compact=model.COMPACT_VOLUME, two_term=model._cost_x2)
+                                         split=d["split"], compact=True, two_term=model._cost_x2)
             if D > 64:
-                ops.pyramid(vol, D, 1 if model.COMPACT_VOLUME else ub.num_levels, scale=1.0 / V)
+                ops.pyramid(vol, D, 1, scale=1.0 / V)        # (level-0-only rows, as in RAFT._run_stages)
             d["vol"], d["origin"] = vol, origin
         loop = ub.loop(stage, dev)             # host-side weight packing stays out of the recorded plans
         for it in range(T):

@@ -16,7 +16,7 @@ import torch.nn.functional as F
 
 from . import ops
 from .corr import DirectCorr
-from .projective import pij_matrices
+from .projective import pij_matrices, scaled_cameras
 
 BACKENDS = ("torch", "hip")
 
@@ -155,12 +155,8 @@ def forward_train(model, images, poses, intrinsics, scale=None, backend=None):
     if batch != 1:
         raise RuntimeError("forward_train: batch must be 1")
     dev = images.device
-    poses = poses.clone().float()
-    if scale is not None:
-        poses[..., :3, 3] *= float(torch.as_tensor(scale).reshape(-1)[0])
     factor = 8 if model.encoder_type == "LR" else 4
-    intr = intrinsics.clone().float()
-    intr[:, :, :2] /= factor
+    poses, intr, _ = scaled_cameras(poses, intrinsics, scale, factor)
     imgs = images.float() * (2 / 255.0) - 1
     h, w = ht // factor, wd // factor
     V = num - 1

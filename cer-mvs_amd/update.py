@@ -21,7 +21,7 @@ from . import ops
 
 
 USE_PLANS = True         # replay recorded launches for GRU iterations 2..T (False: every iteration through the checked wrappers)
-ALIAS_RN_C1 = __import__("os").environ.get("CER_ALIAS_RN_C1", "1") == "1"      # (A/B switch, see _S16Loop.workspace)
+ALIAS_RN_C1 = True       # r*h shares c1's buffer (see _S16Loop.workspace; False: two independent buffers)
 
 
 class ConvGRU(nn.Module):
@@ -86,7 +86,7 @@ class _S16Loop:
     # the disparity update of iteration i (the 18-tap gather of the fused delta head's tap planes, ``ops.delta_sum``) rides on the lookup launch of
     # iteration i + 1 (csrc/lookup.hip, round 5): one launch less per iteration; the last iteration of a stage ends with the stand-alone kernel.
     # Off where something reads ``disp`` between two iterations (the row-slab exchange: ``run(after=...)``).
-    FUSE_DELTA = __import__("os").environ.get("CER_FUSE_DELTA", "1") == "1"      # (A/B switch)
+    FUSE_DELTA = True
 
     def __init__(self, ub, stage, device, corr_fp8):
         g = _stage_weights(ub, stage, device)
@@ -123,7 +123,7 @@ class _S16Loop:
             # working set - 283 MB at 296 x 400 - sits just above the 256 MB Infinity Cache).  Legal because nothing reads c1 behind the z|r
             # launch of an iteration.  (The padding slots of these tensors need NOT stay zero: the epilogues store whole m-tiles, and every
             # consumer masks pixels outside the image while it stages; tests/test_conv_s16_gpu.py::test_rn_may_share_c1s_buffer runs a forward
-            # on a garbage-filled workspace.)  Tools that want two independent buffers set CER_ALIAS_RN_C1=0.
+            # on a garbage-filled workspace.)  Tools that want two independent buffers set update.ALIAS_RN_C1 = False.
             cache[key]["rn"] = cache[key]["c1"] if ALIAS_RN_C1 else z(64)
         return cache[key]
 

@@ -271,6 +271,39 @@ def test_pij_matches_oracle():
     assert torch.equal(a, b)
 
 
+def test_camera_prologue_matches_the_hand_written_expression():
+    """projective.scaled_cameras, the one camera prologue of every forward: float32 copies with the translations times ``scale`` and the
+    intrinsics' first two rows over ``factor`` - bit for bit what each forward used to spell out; the inputs stay as they were."""
+    from cer_mvs_amd.projective import pij_matrices, scaled_cameras
+    from cer_mvs_amd.synthetic import synthetic_scene
+    _, poses, intr, _ = synthetic_scene(8, 8, 5, seed=2)
+    poses, intr = poses.double(), intr.double()                 # (not float32: the copies must be)
+    poses0, intr0 = poses.clone(), intr.clone()
+    views = [1, 2, 3, 4, 5]
+    for factor in (4, 8):
+        for scale in (0.37, torch.tensor(0.37), torch.tensor([0.37]), torch.tensor([[0.37]], dtype=torch.float64)):
+            s_want = float(torch.as_tensor(scale).reshape(-1)[0])
+            p_want = poses0.clone().float()
+            p_want[..., :3, 3] *= s_want
+            k_want = intr0.clone().float()
+            k_want[:, :, :2] /= factor
+            p, k, s = scaled_cameras(poses, intr, scale, factor)
+            assert isinstance(s, float) and s == s_want
+            assert p.dtype == k.dtype == torch.float32 and torch.equal(p, p_want) and torch.equal(k, k_want)
+            assert not torch.equal(p, poses0.float()) and not torch.equal(k, intr0.float())
+            assert torch.equal(poses, poses0) and torch.equal(intr, intr0)
+            assert torch.equal(pij_matrices(p[0], k[0], [0] * 5, views), pij_matrices(p_want[0], k_want[0], [0] * 5, views))
+        # scale=None (training row, literal path): the poses are only copied
+        p, k, s = scaled_cameras(poses, intr, None, factor)
+        assert s is None and torch.equal(p, poses0.float()) and torch.equal(k, k_want)
+        assert torch.equal(poses, poses0) and torch.equal(intr, intr0)
+    # float32 inputs are copied too, never aliased
+    pf, kf = poses0.float(), intr0.float()
+    p, k, _ = scaled_cameras(pf, kf, 2.0, 4)
+    assert p.data_ptr() != pf.data_ptr() and k.data_ptr() != kf.data_ptr()
+    assert torch.equal(pf, poses0.float()) and torch.equal(kf, intr0.float())
+
+
 def test_row_layout():
     from cer_mvs_amd.ops import row_layout
     assert row_layout(64, 3) == ([0, 64, 96], [64, 32, 16], 112)
@@ -550,3 +583,20 @@ def test_product_sources_have_no_other_compile_time_switches():
     extra = {k: v for k, v in found.items() if k not in PRODUCT_SWITCHES}
     assert not extra, f"overridable switches without a listed user (name: file): {extra}"
     assert sorted(found) == sorted(PRODUCT_SWITCHES), f"listed but gone: {sorted(set(PRODUCT_SWITCHES) - set(found))}"
+
+
+def test_product_package_reads_one_environment_variable():
+    """The A/B switches of the Python layer are settled and folded: the package reads CER_MVS_LIB (which library to load)
+    and nothing else from the environment.  A read this test cannot name (a computed key, os.environ passed on whole) fails it as well."""
+    import glob
+    names, unnamed = set(), []
+    for path in sorted(glob.glob(os.path.join(REPO, "cer-mvs_amd", "*.py"))):
+        text = open(path).read()
+        reads = list(re.finditer(r"environ|getenv", text))
+        named = list(re.finditer(r"(?:environ\s*\.\s*(?:get|pop|setdefault)\s*\(|environ\s*\[|getenv\s*\()\s*[\"'](\w+)[\"']", text))
+        names.update(m.group(1) for m in named)
+        if len(named) != len(reads):
+            unnamed.append(os.path.basename(path))
+    assert len(glob.glob(os.path.join(REPO, "cer-mvs_amd", "*.py"))) >= 20
+    assert not unnamed, f"environment reads without a literal name in {unnamed}"
+    assert names == {"CER_MVS_LIB"}, f"environment variables read by the product package: {sorted(names)}"
