@@ -19,7 +19,12 @@ Clouds in slightly different frames are registered first (csrc/cloud_align.hip, 
     T = register(pred, gt, stages=((4 * tau, 8 * tau, 30), (None, 3 * tau, 30)))["T"]      # coarse to fine; or icp(pred, gt, max_dist)
     fscore(pred, gt, tau, align=T)
 
-with ``rigid_transform`` and ``pair_moments`` as its two kernels and ``rigid_from_moments`` (Kabsch, numpy fp64) as its solve.
+with ``rigid_transform`` and ``pair_moments`` as its two kernels and ``rigid_from_moments`` (Kabsch, numpy fp64) as its solve.  On a surface,
+point-to-plane ICP needs a fraction of the iterations - the target's normals let a match slide along the surface:
+
+    icp(pred, gt, max_dist, method="plane")                       # normals of gt estimated once (or dst_normals=...); register(...) likewise
+
+with ``plane_moments`` (the 6x6 normal equations, 30 fp64 sums in the same tree) and ``rigid_from_plane_moments`` as kernel and solve.
 
 The same index answers two more queries: ``CloudIndex.knn`` / ``knn_mean_distance`` - the k <= 32 nearest points of every query
 in ascending (d2, index) order, or only their mean distance - and ``CloudIndex.count_within``, the number of points within a radius; same
@@ -63,7 +68,9 @@ KNN_CELL_DIVISOR = DEFAULT_CELL_DIVISOR
 MOMENT_TILE = 2048                                           # cer_mvs.h CER_MOMENT_TILE
 MOMENT_COUNT = 17                                            # cer_mvs.h CER_MOMENT_COUNT
 COLLINEAR_RATIO = 1e-12                                      # rigid_from_moments: second singular value / first at or below this -> no rotation
-NORMAL_DEGENERATE = COLLINEAR_RATIO                          # cloud_eval.hip NORMAL_DEGENERATE: second eigenvalue / largest at or below this -> no normal
+PLANE_MOMENT_COUNT = 30                                      # cer_mvs.h CER_PLANE_MOMENT_COUNT
+PLANE_DEGENERATE = 1e-10                                     # rigid_from_plane_moments: smallest eigenvalue of the scaled normal matrix at or below this -> no step
+NORMAL_DEGENERATE = COLLINEAR_RATIO                       # cloud_eval.hip NORMAL_DEGENERATE: second eigenvalue / largest at or below this -> no normal
 
 
 def _cloud(t, name):
@@ -674,6 +681,111 @@ def rigid_from_moments(mom, pivot=(0.0, 0.0, 0.0)):
     return T
 
 
+# ---------------------------------------------------------------- point-to-plane
+def _normals_of(normals, cloud, name):
+    """``normals`` as a contiguous float32 [len(cloud), 3] on ``cloud``'s device, or the error that says what it is not"""
+    if not isinstance(normals, torch.Tensor) or not normals.is_cuda:
+        raise RuntimeError(f"{name} must be a CUDA tensor (no CPU fallback)")
+    if normals.dtype != torch.float32:
+        raise RuntimeError(f"{name} must be float32")
+    if tuple(normals.shape) != (int(cloud.shape[0]), 3) or normals.device != cloud.device:
+        raise ValueError(f"{name}: float32 [{int(cloud.shape[0])}, 3] on the cloud's device expected, got {tuple(normals.shape)} on {normals.device}")
+    return normals.contiguous()
+
+
+def _plane_moments(a, b, nrm, idx, pivot):                   # checked clouds and normals, idx int64 [len(a)] on their device, pivot: 3 doubles
+    m, dev = int(a.shape[0]), a.device
+    if m == 0:
+        return np.zeros(PLANE_MOMENT_COUNT)
+    lib = L.load()
+    partials = torch.empty(PLANE_MOMENT_COUNT * int(lib.cer_cloud_plane_moment_partials(m)), device=dev, dtype=torch.float64)
+    out = torch.empty(PLANE_MOMENT_COUNT, device=dev, dtype=torch.float64)
+    L.check(lib.cer_cloud_plane_moments_f64(L.dev_ptr(a, "a"), L.dev_ptr(b, "b"), L.dev_ptr(nrm, "normals"), L.dev_ptr(idx, "idx", torch.int64), m,
+                                            (ctypes.c_double * 3)(*[float(v) for v in pivot]), L.dev_ptr(partials, "partials", torch.float64),
+                                            L.dev_ptr(out, "out", torch.float64), L.cur_stream()), "cloud_plane_moments")
+    return out.cpu().numpy()
+
+
+def plane_moments(a, b, normals, idx, pivot=None):
+    """numpy float64 [30]: the normal equations of one point-to-plane step over the pairs (a[i], b[q], n = normals[q]), q = idx[i] >= 0, a[i]
+    finite, n finite and not (0, 0, 0) (``estimate_normals``' "no plane": such a match makes no pair).  ``normals``: float32 [len(b), 3] on
+    the clouds' device, used as given, not normalised.  With A = double(a) - pivot, D = double(a) - double(b), r = (Dx*nx + Dy*ny) + Dz*nz
+    (the plane residual), c = A x n and J = (c0, c1, c2, n0, n1, n2): [0] k, the number of pairs; [1:22] the upper triangle of sum J_i J_j,
+    row-major; [22:28] sum J_i r; [28] sum r^2; [29] sum |a - b|^2 as ``nearest`` forms d2.  fp64, no fused multiply-add, ``pair_moments``'
+    summation tree: the same bits on every run.  Returning them is the one host read.  ``idx`` as ``pair_moments`` takes it."""
+    pivot = _pivot(pivot)
+    a, b = _cloud(a, "a"), _cloud(b, "b")
+    normals = _normals_of(normals, b, "normals")
+    if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int64 or tuple(idx.shape) != (a.shape[0],):
+        raise ValueError("idx: an int64 tensor with one entry per point of a expected")
+    idx = idx.to(a.device).contiguous()
+    if len(idx) and (int(idx.max()) >= int(b.shape[0]) or int(idx.min()) < -1):
+        raise ValueError(f"idx: entries in -1 .. {int(b.shape[0]) - 1} expected")
+    return _plane_moments(a, b, normals, idx, pivot)
+
+
+def rigid_from_plane_moments(mom, pivot=(0.0, 0.0, 0.0)):
+    """The point-to-plane step of the pairs behind ``mom`` (``plane_moments`` taken about ``pivot``) as a 4x4 float64: x = (w, t) minimises
+    sum (r + J x)^2, the residual after a small rotation w about the pivot and a translation t - M x = -g with M the symmetric 6x6 of
+    [1:22] and g = [22:28].  Solved with the diagonal scaled to 1 (s_i = 1 / sqrt(M_ii), Ms = s s^T * M, x = s * solve(Ms, -(s * g))), which
+    makes the degeneracy test independent of the units and of the pivot's distance.  The step is p -> pivot + R (p - pivot) + t with R =
+    exp([w]x) by Rodrigues' formula (the series I + K + K^2 / 2 below |w| = 1e-8): an exact rotation of the linearised solution, not the
+    Euler-angle composition Open3D's TransformationEstimationPointToPlane builds from the same x.  Pure numpy.  ValueError for fewer than 6
+    pairs, for an M_ii <= 0 (a degree of freedom nothing constrains) and for a smallest eigenvalue of Ms <= 1e-10: a plane, a sphere with
+    radial normals, a cylinder - some motion slides the target on itself and the step is not determined."""
+    mom = np.array(mom, dtype=np.float64).reshape(-1)
+    if mom.shape != (PLANE_MOMENT_COUNT,):
+        raise ValueError(f"mom: {PLANE_MOMENT_COUNT} sums expected")
+    pivot = _pivot(pivot)
+    if not mom[0] >= 6:
+        raise ValueError(f"rigid_from_plane_moments: at least 6 pairs expected, got {mom[0]:g}")
+    M = np.zeros((6, 6))
+    M[np.triu_indices(6)] = mom[1:22]
+    M = M + np.triu(M, 1).T
+    g = mom[22:28].copy()
+    diag = np.diag(M)
+    if not (diag > 0.0).all():
+        raise ValueError("rigid_from_plane_moments: a diagonal entry of the normal matrix is not positive; the pairs do not constrain the motion")
+    s = 1.0 / np.sqrt(diag)
+    Ms = np.outer(s, s) * M
+    if not np.linalg.eigvalsh(Ms)[0] > PLANE_DEGENERATE:
+        raise ValueError("rigid_from_plane_moments: the pairs are degenerate (a plane, a sphere, a cylinder: some motion slides the target on "
+                         "itself); the step is not determined")
+    x = s * np.linalg.solve(Ms, -(s * g))
+    w = x[:3]
+    K = np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+    th = math.sqrt((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2])
+    if th < 1e-8:
+        R = np.eye(3) + K + 0.5 * (K @ K)
+    else:
+        R = np.eye(3) + (math.sin(th) / th) * K + ((1.0 - math.cos(th)) / (th * th)) * (K @ K)
+    T = np.eye(4)
+    T[:3, :3] = R
+    T[:3, 3] = (pivot - R @ pivot) + x[3:]
+    return T
+
+
+def _is_plane(method, dst_normals, normals):
+    """``method`` and what may go with it, checked before anything else is looked at -> True for "plane" """
+    if method not in ("point", "plane"):
+        raise ValueError(f'method: "point" or "plane" expected, got {method!r}')
+    if method == "point" and (dst_normals is not None or normals is not None):
+        raise ValueError('dst_normals / normals go with method="plane"; method="point" uses no normals')
+    return method == "plane"
+
+
+def _target_normals(plane, dst, dst_normals, normals):
+    """None unless ``plane``; else the normals of the checked cloud ``dst``: ``dst_normals``, or estimated (once) with ``normals``' options"""
+    if not plane:
+        return None
+    if dst_normals is not None:
+        if normals is not None:
+            raise ValueError("normals: options of the estimation; dst_normals were given, nothing is estimated")
+        return _normals_of(dst_normals, dst, "dst_normals")
+    options = normals_options(normals or True)
+    return estimate_normals(dst, **options)[0] if int(dst.shape[0]) else dst.new_zeros(0, 3)
+
+
 def _icp_args(max_dist, init, max_iter, tol_fitness, tol_rmse):
     max_dist = float(np.float32(max_dist))
     if not (max_dist > 0.0 and math.isfinite(max_dist)):
@@ -687,8 +799,10 @@ def _icp_args(max_dist, init, max_iter, tol_fitness, tol_rmse):
     return max_dist, (np.eye(4) if init is None else _rigid(init, "init")), max_iter, tol_fitness, tol_rmse
 
 
-def icp(src, dst, max_dist, init=None, max_iter=50, tol_fitness=1e-6, tol_rmse=1e-6, cell=None, index=None):
-    """Point-to-point ICP of ``src`` onto ``dst`` (CUDA float32 [n, 3] each), from ``init`` (4x4, default the identity).  ``dst`` is indexed
+def icp(src, dst, max_dist, init=None, max_iter=50, tol_fitness=1e-6, tol_rmse=1e-6, cell=None, index=None, method="point", dst_normals=None,
+        normals=None):
+    """ICP of ``src`` onto ``dst`` (CUDA float32 [n, 3] each), from ``init`` (4x4, default the identity); point-to-point unless
+    ``method="plane"`` (below).  ``dst`` is indexed
     once (``CloudIndex(dst, cell)``, ``cell`` default ``max_dist / 4``; or the caller's ``index``, which must be over ``dst``).  An iteration:
     cur = rigid_transform(src, T) - always from the original ``src`` with the accumulated fp64 T: one rounding, no drift; index.nearest(cur,
     max_dist); the moments of the pairs about the index's origin; fitness = pairs / len(src), rmse = sqrt(mean d2 of the pairs); stop when
@@ -697,40 +811,60 @@ def icp(src, dst, max_dist, init=None, max_iter=50, tol_fitness=1e-6, tol_rmse=1
 
     -> {"T": 4x4 float64 numpy, src -> dst's frame; "iterations": evaluations made; "converged"; "fitness", "rmse", "n_pairs": of the last
     evaluation (when ``max_iter`` ends the loop: the one before the last update of T); "history": [(fitness, rmse), ...]}.  Fewer than 3
-    pairs (empty clouds included) stop the loop with converged = False and T as it stands; collinear pairs raise ValueError."""
+    pairs (empty clouds included) stop the loop with converged = False and T as it stands; collinear pairs raise ValueError.
+
+    ``method="plane"``: point-to-plane ICP (Chen & Medioni; Open3D's TransformationEstimationPointToPlane) - the same loop with
+    ``plane_moments`` about the index's origin and ``rigid_from_plane_moments`` as the step.  A match whose target normal is (0, 0, 0) or
+    not finite makes no pair; fitness = pairs / len(src); rmse = sqrt(mean r^2), the PLANE residual (Open3D's definition for this
+    estimator); the dict gains "rmse_point" = sqrt(mean d2 of the pairs) and every history entry carries it as a third element.  The loop
+    stops below 6 pairs; a degenerate target (a plane, a sphere, a cylinder) raises ValueError.  ``dst_normals``: float32 [len(dst), 3] on
+    the device, used as given; None: ``estimate_normals(dst, **normals_options(normals or True))``, once (``normals``: a dict with any of
+    "k", "max_dist", "cell").  Either of them with ``method="point"`` is a ValueError, as is any other method."""
+    plane = _is_plane(method, dst_normals, normals)
     max_dist, T, max_iter, tol_fitness, tol_rmse = _icp_args(max_dist, init, max_iter, tol_fitness, tol_rmse)
     src, dst = _cloud(src, "src"), _cloud(dst, "dst")
+    nrm = _target_normals(plane, dst, dst_normals, normals)
     if index is None:
         index = CloudIndex(dst, float(max_dist) / DEFAULT_CELL_DIVISOR if cell is None else cell)
     elif not isinstance(index, CloudIndex) or index.points.shape != dst.shape or index.points.device != dst.device:
         raise ValueError("index: a CloudIndex over dst expected")
     n = int(src.shape[0])
     out = {"T": T, "iterations": 0, "converged": False, "fitness": 0.0, "rmse": 0.0, "n_pairs": 0, "history": []}
+    if plane:
+        out["rmse_point"] = 0.0
     if n == 0 or index.n == 0:
         return out
     pivot = np.array([float(v) for v in index.origin])
     for _ in range(max_iter):
         cur = _transform(src, T)
-        mom = _moments(cur, index.points, index.nearest(cur, max_dist)[1], pivot)      # (the one host read)
+        idx = index.nearest(cur, max_dist)[1]
+        mom = _plane_moments(cur, index.points, nrm, idx, pivot) if plane else _moments(cur, index.points, idx, pivot)      # (the one host read)
         k = int(mom[0])
-        fitness, rmse = k / n, (math.sqrt(mom[16] / k) if k else 0.0)
+        fitness, rmse = k / n, (math.sqrt(mom[28 if plane else 16] / k) if k else 0.0)
         moved = (abs(fitness - out["fitness"]), abs(rmse - out["rmse"])) if out["iterations"] else None
-        out["history"].append((fitness, rmse))
         out.update(iterations=out["iterations"] + 1, fitness=fitness, rmse=rmse, n_pairs=k)
-        if k < 3:
+        if plane:
+            out["rmse_point"] = math.sqrt(mom[29] / k) if k else 0.0
+            out["history"].append((fitness, rmse, out["rmse_point"]))
+        else:
+            out["history"].append((fitness, rmse))
+        if k < (6 if plane else 3):
             break
         if moved is not None and moved[0] < tol_fitness and moved[1] < tol_rmse:
             out["converged"] = True
             break
-        T = rigid_from_moments(mom, pivot) @ T
+        T = (rigid_from_plane_moments(mom, pivot) if plane else rigid_from_moments(mom, pivot)) @ T
         out["T"] = T
     return out
 
 
-def register(src, dst, stages, init=None):
+def register(src, dst, stages, init=None, method="point", dst_normals=None, normals=None):
     """Coarse-to-fine ICP: ``stages`` is a sequence of (voxel, max_dist, max_iter); every stage runs ``icp`` on ``voxel_downsample`` of both
     clouds with that edge (voxel None: the clouds as they are) from the stage before's T (the first from ``init``).  -> the last stage's dict
-    plus "stages", the list of every stage's dict."""
+    plus "stages", the list of every stage's dict.  ``method`` / ``dst_normals`` / ``normals``: as ``icp`` takes them; with ``"plane"`` the
+    normals are those of the FULL ``dst`` (given, or estimated once - not per stage: a thinned cloud has another surface scale), and a
+    stage's voxel selection of ``dst`` selects their rows with it."""
+    plane = _is_plane(method, dst_normals, normals)
     try:
         stages = [(None if v is None else _cell(v), float(d), int(it)) for v, d, it in stages]
     except (TypeError, ValueError) as e:
@@ -741,11 +875,13 @@ def register(src, dst, stages, init=None):
         _icp_args(d, None, it, 0.0, 0.0)
     T = np.eye(4) if init is None else _rigid(init, "init")
     src, dst = _cloud(src, "src"), _cloud(dst, "dst")
+    nrm = _target_normals(plane, dst, dst_normals, normals)
     done = []
     for voxel, max_dist, max_iter in stages:
         s = src if voxel is None else src.index_select(0, voxel_downsample(src, voxel))
-        d = dst if voxel is None else dst.index_select(0, voxel_downsample(dst, voxel))
-        done.append(icp(s, d, max_dist, init=T, max_iter=max_iter))
+        sel = None if voxel is None else voxel_downsample(dst, voxel)
+        d, n = (dst, nrm) if sel is None else (dst.index_select(0, sel), nrm.index_select(0, sel) if plane else None)
+        done.append(icp(s, d, max_dist, init=T, max_iter=max_iter, **({"method": "plane", "dst_normals": n} if plane else {})))
         T = done[-1]["T"]
     return {**done[-1], "stages": done}
 

@@ -692,6 +692,22 @@ long cer_cloud_moment_partials(long m);
 int cer_cloud_pair_moments_f64(const float* a, const float* b, const long long* idx, long m, const double* pivot, double* partials,
                                double* out, void* stream);
 
+/* Point-to-plane registration (ABI 1160; csrc/cloud_align.hip, cer-mvs_amd/cloud_eval.py plane_moments / rigid_from_plane_moments /
+ * icp(method="plane")): the normal equations of the linearised point-to-plane step.  Sizes, errors, their order and the
+ * summation shape are cer_cloud_pair_moments_f64's; fp64, every association fixed, no fused multiply-add, no atomics.
+ *
+ *   cer_cloud_plane_moment_partials: HOST function: ceil(m / CER_MOMENT_TILE); `partials` holds CER_PLANE_MOMENT_COUNT * that many doubles.
+ *   cer_cloud_plane_moments_f64: a pair is (a[i], b[q], n = nrm[q]) for every i < m with q = idx[i] >= 0 (a valid row of b and of nrm), a
+ *     finite a[i], and n finite and not (0, 0, 0) (cer_grid_normals_f32's "no plane").  nrm: [rows of b, 3] floats, used as given (not
+ *     normalised).  pivot: 3 HOST doubles.  With A = double(a) - pivot, D = double(a) - double(b), r = (Dx*nx + Dy*ny) + Dz*nz,
+ *     c = (A1*n2 - A2*n1, A2*n0 - A0*n2, A0*n1 - A1*n0) and J = (c0, c1, c2, n0, n1, n2), out (CER_PLANE_MOMENT_COUNT DEVICE doubles, written
+ *     whole) = [k, the number of pairs | sum J_i * J_j for i <= j, row-major (21) | sum J_i * r (6) | sum r * r | sum (Dx*Dx + Dy*Dy) +
+ *     Dz*Dz, the d2 of cer_grid_nearest_f32]. */
+#define CER_PLANE_MOMENT_COUNT 30
+long cer_cloud_plane_moment_partials(long m);
+int cer_cloud_plane_moments_f64(const float* a, const float* b, const float* nrm, const long long* idx, long m, const double* pivot,
+                                double* partials, double* out, void* stream);
+
 /* Multi-GPU row-slab exchange (cer-mvs_amd/slab.py): up to CER_COPY_MAX_SEG contiguous fp32 ranges copied by ONE launch -
  * the pack of a rank's (net, disp) border strips into its send buffer, and the refresh of its halo rows from the gathered
  * strips.  n[i] floats from src[i] to dst[i]; n[i] == 0 skips a segment.  Device pointers; ranges must not overlap. */

@@ -2,7 +2,7 @@
 prediction) against B (the ground truth), on the device (cer-mvs_amd/cloud_eval.py).
 
     python tools/compare_clouds.py A.ply B.ply [--max-dist 20.0] [--tau 2.0] [--thin 0.2] [--thin-method voxel|greedy] [--thin-seed 0]
-                                   [--align none|icp] [--align-max-dist D] [--align-voxel V [V ...]] [--init T.txt]
+                                   [--align none|icp|icp-plane] [--align-max-dist D] [--align-voxel V [V ...]] [--align-normals-k K] [--init T.txt]
 
 Binary little-endian PLY files (what `reconstruct_scan` / `fusion` write).  --thin: thin A first - --thin-method voxel (the default): one point
 per cell of that edge; greedy: the DTU script's own reduction, `radius_thin` with that radius, visiting the points in the random order of
@@ -10,7 +10,9 @@ per cell of that edge; greedy: the DTU script's own reduction, `radius_thin` wit
 --align-voxel edge on the voxel-thinned clouds, coarse to fine, then one on the clouds as they are, every stage matching within
 --align-max-dist (default --max-dist), from the 4x4 of --init (a text file `numpy.loadtxt` reads; default the identity) - and moved by the
 result before anything is measured; the JSON line gains "T", "align_iterations" (all stages), "align_converged", "align_fitness" and "align_rmse" (the last
-stage's).  With --align none (the default) --init alone moves A.  Crop volumes, observability masks and ground planes of the benchmarks are the
+stage's).  --align icp-plane: the same stages with point-to-plane ICP (`register(method="plane")`) on B's normals, estimated once
+on the whole of B from --align-normals-k neighbours (default 20); the line then also carries "align_method": "plane" and "align_rmse_point", and
+"align_rmse" is the plane residual's.  With --align none (the default) --init alone moves A.  Crop volumes, observability masks and ground planes of the benchmarks are the
 caller's business.  Needs a GPU."""
 import argparse
 import json
@@ -30,9 +32,10 @@ def main():
     ap.add_argument("--thin", type=float, default=None, help="voxel edge / radius for thinning A")
     ap.add_argument("--thin-method", choices=("voxel", "greedy"), default="voxel", help="voxel_downsample or radius_thin (the DTU script's)")
     ap.add_argument("--thin-seed", type=int, default=0, help="seed of the greedy thinning's visiting order")
-    ap.add_argument("--align", choices=("none", "icp"), default="none", help="register A onto B first (point-to-point ICP)")
+    ap.add_argument("--align", choices=("none", "icp", "icp-plane"), default="none", help="register A onto B first (point-to-point / point-to-plane ICP)")
     ap.add_argument("--align-max-dist", type=float, default=None, help="matching distance of the registration (default: --max-dist)")
     ap.add_argument("--align-voxel", type=float, nargs="+", default=[], help="voxel edges of the coarse stages, coarse to fine")
+    ap.add_argument("--align-normals-k", type=int, default=20, help="neighbours behind B's normals (--align icp-plane)")
     ap.add_argument("--init", default=None, help="text file with the 4x4 initial motion of A (numpy.loadtxt)")
     args = ap.parse_args()
     import numpy as np
@@ -45,12 +48,15 @@ def main():
     b = torch.from_numpy(CE.read_ply(args.b)[0]).cuda()
     out = {"a": args.a, "b": args.b, "max_dist": args.max_dist, "thin": args.thin, "thin_method": args.thin_method, "thin_seed": args.thin_seed}
     T = None if args.init is None else np.loadtxt(args.init, dtype=np.float64)
-    if args.align == "icp":
+    if args.align != "none":
         reach = args.max_dist if args.align_max_dist is None else args.align_max_dist
-        reg = CE.register(a, b, [(v, reach, 50) for v in args.align_voxel] + [(None, reach, 50)], init=T)
+        plane = {"method": "plane", "normals": {"k": args.align_normals_k}} if args.align == "icp-plane" else {}
+        reg = CE.register(a, b, [(v, reach, 50) for v in args.align_voxel] + [(None, reach, 50)], init=T, **plane)
         T = reg["T"]
         out.update(T=T.tolist(), align_iterations=sum(st["iterations"] for st in reg["stages"]), align_converged=reg["converged"],
                    align_fitness=reg["fitness"], align_rmse=reg["rmse"])
+        if plane:
+            out.update(align_method="plane", align_rmse_point=reg["rmse_point"])
     if T is not None:
         a = CE.rigid_transform(a, T)
     out.update(CE.accuracy_completeness(a, b, max_dist=args.max_dist, thin=args.thin, thin_method=args.thin_method, thin_seed=args.thin_seed))
