@@ -8,7 +8,7 @@ Mirrors the reference's interface:
     depth and the mask area leave the kernel;
   * ``fuse_depth_maps(depths, Ks, Es, pairs, glb)`` - the ten-round bisection of fusion.py:199-262 on device tensors;
   * ``fusion(data_loader, output_folder, suffix, glb, rescale)`` - the reference's driver: reads the ``depths/*.pfm`` that
-    ``inference`` wrote, runs the loop, writes ``mask/<view>.png`` and ``result.ply``.
+    ``inference`` wrote, runs the loop, writes ``mask/<view>.png`` (``write_masks``, which ``scan.reconstruct_scan`` calls too) and ``result.ply``.
   * ``point_cloud(masks, depth_est, Ks, Es, colors, order)`` / ``color_grid(prepared, h, w)`` - the driver's tail on the device
     (csrc/cloud.hip): masked pixels -> world points and colours, in the driver's order; ``scan.reconstruct_scan`` chains them behind
     ``ScanSession.depths`` and ``fuse_depth_maps`` without a trip through files or the host.
@@ -16,8 +16,8 @@ The camera algebra (3x3 / 4x4 inverses and products, a few hundred flops per vie
 in the reference's order; everything per pixel is in the kernel.  No CPU fallback: tensors must be CUDA tensors."""
 import ctypes
 import math
-import os
 import re
+from pathlib import Path
 
 import numpy as np
 import torch
@@ -240,6 +240,18 @@ def write_ply(path, xyz, rgb, normals=None):
         f.write(v.tobytes())
 
 
+def write_masks(folder, masks_np, refs, suffix=""):
+    """``mask/<index><suffix>.png`` under ``folder`` (a Path) for every view of ``refs``, as the reference's driver writes them."""
+    (folder / "mask").mkdir(exist_ok=True, parents=True)
+    try:
+        from PIL import Image
+        for ref in refs:
+            Image.fromarray(masks_np[ref].astype(np.uint8) * 255).save(str(folder / "mask" / f"{ref}{suffix}.png"))
+    except ImportError:                                      # no PNG encoder in this Python: keep the arrays
+        for ref in refs:
+            np.save(str(folder / "mask" / f"{ref}{suffix}.npy"), masks_np[ref])
+
+
 def _resize(img, h, w):
     """cv2.resize(..., INTER_LINEAR) of the reference (fusion.py:144,151): half-pixel-centre bilinear."""
     t = torch.from_numpy(np.ascontiguousarray(img)).float()
@@ -275,7 +287,7 @@ def fusion(data_loader, output_folder, suffix="", glb=0.25, rescale=1, device="c
     intrinsics [1,n,3,3], image_names, _) per reference view; the estimated depth of view <name> is read from
     ``output_folder/depths/<name><suffix>.pfm``.  Writes ``mask/<index><suffix>.png`` and ``result.ply`` (``write``), returns
     {"masks", "depth_est", "xyz", "rgb", "threshold", "history"}."""
-    output_folder = output_folder if hasattr(output_folder, "__truediv__") else __import__("pathlib").Path(output_folder)
+    output_folder = Path(output_folder)
     imgs, deps, Ks, Es, index_of, pair_names = [], [], [], [], {}, []
     for i, (images, extrinsics, intrinsics, image_names, _) in enumerate(data_loader):
         images = images.squeeze(0)
@@ -315,13 +327,6 @@ def fusion(data_loader, output_folder, suffix="", glb=0.25, rescale=1, device="c
         rgb.append((imgs[ref][masks_np[ref]] * 255).astype(np.uint8))
     xyz, rgb = np.concatenate(xyz, 0), np.concatenate(rgb, 0)
     if write:
-        os.makedirs(os.path.join(output_folder, "mask"), exist_ok=True)
-        try:
-            from PIL import Image
-            for ref, _ in pairs:
-                Image.fromarray(masks_np[ref].astype(np.uint8) * 255).save(str(output_folder / "mask" / f"{ref}{suffix}.png"))
-        except ImportError:                                  # no PNG encoder in this Python: keep the arrays
-            for ref, _ in pairs:
-                np.save(str(output_folder / "mask" / f"{ref}{suffix}.npy"), masks_np[ref])
-        write_ply(os.path.join(output_folder, "result.ply"), xyz.astype(np.float32), rgb)
+        write_masks(output_folder, masks_np, [ref for ref, _ in pairs], suffix)
+        write_ply(output_folder / "result.ply", xyz.astype(np.float32), rgb)
     return {"masks": masks_np, "depth_est": est_np, "xyz": xyz, "rgb": rgb, "threshold": thre, "history": hist}

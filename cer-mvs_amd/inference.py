@@ -2,8 +2,10 @@
 utils/data_utils.py:58-78, utils/frame_utils.py:138-163): scale/crop of images + intrinsics,
 model call, disparity -> depth, PFM writer.  Dataset readers are out of scope:
 ``inference`` takes any iterable yielding the reference's loader tuple
-(images [1,N,3,H,W], poses [1,N,4,4], intrinsics [1,N,3,3], image_names, scale)."""
-import os
+(images [1,N,3,H,W], poses [1,N,4,4], intrinsics [1,N,3,3], image_names, scale).
+
+The file drivers (``inference`` here, ``scan.inference_scan``) are a job generator each over one loop, ``run_jobs``: the forwards in flight and the overflow
+protocol are pipeline.py's (``checked``), a finished disparity becomes files in ``write_depth``, the clean-up after a ``SaturationError`` is written once."""
 import time
 from pathlib import Path
 
@@ -11,7 +13,8 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from .raft import RAFT, SaturationError
+from .pipeline import DepthMapPipeline, checked, running_model, stream_count
+from .raft import SaturationError
 
 
 def scale_operation(images, intrinsics, s):
@@ -50,57 +53,60 @@ def write_pfm(file, image, scale=1):
     Path(file).write_bytes(head + rows.tobytes())
 
 
+def depth_file(folder, name, rescale, nf):
+    """Where the depth map of view ``name`` goes (reference: inference.py:60)."""
+    return Path(folder) / "depths" / f"{name}_scale{rescale}_nf{nf}.pfm"
+
+
+def write_depth(disp, folder, name, rescale, nf, write_min_depth=None):
+    """A finished disparity [1,1,h,w] becomes files: the depth as PFM and, with ``write_min_depth`` (a folder), half the 10 % quantile
+    of the valid depths as ``{name}.txt``.  Returns the PFM's path."""
+    im = disp_to_depth(disp.cpu().numpy()[0, 0])
+    path = depth_file(folder, name, rescale, nf)
+    write_pfm(path, im)
+    if write_min_depth is not None:
+        wm = Path(write_min_depth)
+        wm.mkdir(exist_ok=True)
+        with open(wm / f"{name}.txt", "w") as f:
+            f.write(f"{np.quantile(im[im > 0], 0.1) / 2}\n")
+    return str(path)
+
+
+def run_jobs(pipe, core, jobs, folder, rescale, write_min_depth=None, report=None):
+    """The file drivers' loop.  ``jobs`` yields (handle, name, nf) and submits a forward each time it is pulled; ``pipe`` (a
+    DepthMapPipeline, a ScanSession, a test's fake: ``__len__``, ``result``, ``poll_overflow``, ``check_overflow``) keeps ``len(pipe)`` of them
+    in flight under ``pipeline.checked``; each result is written by ``write_depth`` (``report``: called first, for ``do_report``).  Returns the
+    list of files written."""
+    written = []
+    try:
+        for (_, name, nf), disp in checked(pipe, core, jobs, lambda job: pipe.result(job[0])):
+            if report is not None:
+                report()
+            written.append(write_depth(disp, folder, name, rescale, nf, write_min_depth))
+    except SaturationError:
+        # (ADVICE r4: ONE clean-up for both raise sites - the poll after a wait and the final check; ADVICE r5: for THIS error only -
+        # an out-of-memory or loader error must not delete depth maps that were written correctly.)  The files of the last
+        # `streams` forwards were written before their flags could be read: remove them rather than leave saturated depth maps next to
+        # good ones
+        for path in written[-len(pipe):]:
+            try:
+                Path(path).unlink()
+            except OSError:
+                pass
+        raise
+    return written
+
+
 def inference(test_loader, ckpt, output_folder, rescale=1, crop=None, do_report=False, write_min_depth=None,
               model=None, num_frames=None, streams=3):
     """Reference signature (inference.py:19-27) plus ``model`` (pre-built RAFT), ``num_frames`` (the reference reads
     test_loader.dataset.num_frames for the file name) and ``streams``: reference views kept in flight on the GPU
     (pipeline.DepthMapPipeline: 3 = +12-16 % depth maps per second at DTU size; 1 = the reference's one-at-a-time loop;
     ``do_report`` forces 1 so that the per-view time it prints means what it says).  Same files either way."""
-    if model is None:
-        model = RAFT(test_mode=True).cuda()
-        if ckpt is not None:
-            model.load_state_dict(torch.load(ckpt, map_location="cpu"), strict=True)
-    # the reference wraps its model in nn.DataParallel (inference.py:28-35): the pipeline works on the RAFT module itself
-    core = model.module if hasattr(model, "module") and isinstance(getattr(model, "module"), RAFT) else model
-    was_training = core.training
-    core.eval()
     output_folder = Path(output_folder)
-    (output_folder / "depths").mkdir(exist_ok=True, parents=True)
-    written = []
-    from .pipeline import DepthMapPipeline
-    # Depth maps in flight: each extra stream is a REPLICA of the model (weights, packed weights, feature buffers, workspaces: ~3.7 GB
-    # per replica at DTU size, ~32 GB at 3840x2160 x 15 views).  A sharded model (view_group) runs collectives inside its forward:
-    # replicas issuing them from several streams in rank-dependent order could deadlock, and a process group is not deep-copyable - one
-    # depth map at a time there (bench.py does the same).
-    n_streams = 1 if (do_report or getattr(core, "view_group", None) is not None) else max(1, int(streams))
-    pipe = DepthMapPipeline(core, streams=n_streams)
-    pending = []
-
-    def finish(entry):
-        handle, name, nf = entry
-        disp_est = pipe.result(handle)
-        # saturation of a split-f16 operand is an error, not a silent clamp: under the lazy policy the flag of forward k is polled when
-        # forward k + streams starts; nothing is written for a forward whose flag is already known to be set
-        bits = pipe.poll_overflow()
-        if bits:
-            core._raise_overflow(bits)
-        if do_report:
-            torch.cuda.synchronize()
-            print(f"per view time: {time.time() - tic[0]}")
-        im = disp_to_depth(disp_est.cpu().numpy()[0, 0])
-        path = output_folder / "depths" / f"{name}_scale{rescale}_nf{nf}.pfm"
-        write_pfm(path, im)
-        written.append(str(path))
-        if write_min_depth is not None:
-            wm = Path(write_min_depth)
-            wm.mkdir(exist_ok=True)
-            with open(wm / f"{name}.txt", "w") as f:
-                f.write(f"{np.quantile(im[im > 0], 0.1) / 2}\n")
-
     tic = [0.0]
-    n_flight = len(pipe)
-    try:
-      with torch.no_grad():
+
+    def jobs(pipe):
         for images, poses, intrinsics, image_names, scale in test_loader:
             poses = poses.cuda()
             images, intrinsics = scale_operation(images.squeeze(0), intrinsics.squeeze(0), rescale)
@@ -113,24 +119,14 @@ def inference(test_loader, ckpt, output_folder, rescale=1, crop=None, do_report=
                 tic[0] = time.time()
             name = image_names[0][0] if isinstance(image_names[0], (list, tuple)) else image_names[0]
             nf = num_frames if num_frames is not None else getattr(getattr(test_loader, "dataset", None), "num_frames", images.shape[1])
-            pending.append((pipe.submit(images, poses, intrinsics, scale, do_report=do_report), name, nf))
-            if len(pending) >= n_flight:
-                finish(pending.pop(0))
-        while pending:
-            finish(pending.pop(0))
-      pipe.check_overflow()                                 # (reads the flag: covers the last forwards, whose snapshots nobody polled)
-    except SaturationError:
-        # (ONE clean-up for both raise sites - the poll inside finish() and the final check; ADVICE r5: for THIS error only -
-        # an out-of-memory or loader error must not delete depth maps that were written correctly.)  The files of the last
-        # `streams` forwards were written before their flags could be read: remove them rather than leave saturated depth maps next to
-        # good ones
-        for path in written[-n_flight:]:
-            try:
-                Path(path).unlink()
-            except OSError:
-                pass
-        raise
-    finally:
-        if was_training:
-            core.train()
-    return written
+            yield pipe.submit(images, poses, intrinsics, scale, do_report=do_report), name, nf
+
+    def report():                                           # (behind the result and the poll, before the read-back and the PFM write)
+        torch.cuda.synchronize()
+        print(f"per view time: {time.time() - tic[0]}")
+
+    with running_model(model if model is not None else ckpt) as core, torch.no_grad():
+        (output_folder / "depths").mkdir(exist_ok=True, parents=True)
+        pipe = DepthMapPipeline(core, streams=1 if do_report else stream_count(core, streams))
+        return run_jobs(pipe, core, jobs(pipe), output_folder, rescale, write_min_depth, report if do_report else None)
+

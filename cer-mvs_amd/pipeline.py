@@ -8,11 +8,79 @@ three streams: 18.0), outputs bit-identical.  Default three: with the fp8-correc
 17.1, six: 16.7 - an even number of forwards tends to run in phase; tools/archive/exp_streams2.py).  ``DepthMapPipeline`` keeps ``streams`` forwards in flight: one replica of the model
 per stream (a deep copy - the packed weights, feature buffers and workspaces of a forward are per replica, the library itself is
 stateless; ``refresh_weights`` re-synchronises the replicas after the original's parameters changed), round-robin submission from
-one host thread."""
+one host thread.
+
+The drivers above a forward (``inference``, ``scan.inference_scan``, ``ScanSession.depths``, ``map``) share what this module owns: the window of
+forwards in flight (``in_flight``), the overflow protocol around it (``checked``), the replica rule and the launch (``DepthMapPipeline.pick`` /
+``launch``), and the way from a model or a checkpoint to the RAFT that runs (``running_model``, ``unwrap``, ``stream_count``)."""
 import collections
+import contextlib
 import copy
 
 import torch
+
+from .raft import RAFT
+
+
+def in_flight(entries, n):
+    """The window: ``entries`` submits a forward each time it is pulled; yields the oldest entry once ``n`` are pending, then drains."""
+    pending = collections.deque()
+    for entry in entries:
+        pending.append(entry)
+        if len(pending) >= n:
+            yield pending.popleft()
+    while pending:
+        yield pending.popleft()
+
+
+def checked(pipe, core, entries, wait):
+    """``in_flight`` with the overflow protocol, written once: yields (entry, ``wait(entry)``) for every entry, ``len(pipe)`` in flight.
+    Saturation of a split-f16 operand is an error, not a silent clamp: under the lazy policy the flag of forward k is polled when forward
+    k + streams starts, after the wait and before the caller's work on that result - nothing is written for a forward whose flag is
+    already known to be set.  After the last entry ``check_overflow()`` reads the flag: that covers the last forwards, whose snapshots
+    nobody polled.  ``pipe``: anything with ``__len__``, ``poll_overflow`` and ``check_overflow``; ``core``: the RAFT that raises."""
+    for entry in in_flight(entries, len(pipe)):
+        got = wait(entry)
+        bits = pipe.poll_overflow()
+        if bits:
+            core._raise_overflow(bits)
+        yield entry, got
+    pipe.check_overflow()
+
+
+def unwrap(model):
+    """The reference wraps its model in nn.DataParallel (inference.py:28-35): the drivers work on the RAFT module itself."""
+    return model.module if isinstance(getattr(model, "module", None), RAFT) else model
+
+
+@contextlib.contextmanager
+def running_model(model_or_ckpt):
+    """A model, a checkpoint path or None (untrained weights) -> the RAFT that runs, in eval mode: built on the GPU and loaded if it
+    is not a module, unwrapped; its ``training`` state is restored behind the block, also on an error."""
+    model = model_or_ckpt
+    if not isinstance(model, torch.nn.Module):
+        model = RAFT(test_mode=True).cuda()
+        if model_or_ckpt is not None:
+            model.load_state_dict(torch.load(model_or_ckpt, map_location="cpu"), strict=True)
+    core = unwrap(model)
+    was_training = core.training
+    core.eval()
+    try:
+        yield core
+    finally:
+        core.train(was_training)
+
+
+def stream_count(model, streams):
+    """Depth maps in flight: each extra stream is a REPLICA of the model (weights, packed weights, feature buffers, workspaces: ~3.7 GB
+    per replica at DTU size, ~32 GB at 3840x2160 x 15 views).  A sharded model (view_group) runs collectives inside its forward:
+    replicas issuing them from several streams in rank-dependent order could deadlock, and a process group is not deep-copyable - one
+    depth map at a time there (bench.py does the same)."""
+    return 1 if getattr(model, "view_group", None) is not None else max(1, int(streams))
+
+
+def calibrating(m):
+    return getattr(m, "gru_precision", None) == "auto" and m._auto_pending()
 
 
 class DepthMapPipeline:
@@ -69,30 +137,38 @@ class DepthMapPipeline:
         for m in self.models[1:]:
             m.load_state_dict(sd)
 
+    def pick(self):
+        """The replica of the next submission, round robin -> (k, model, stream)."""
+        k = self._next % len(self.streams)
+        self._next += 1
+        m = self.models[k]
+        if k and calibrating(m):
+            # one arithmetic form for all replicas: the first model's calibration decides.  If that model has not calibrated these weights
+            # yet (first submission, or right after refresh_weights), this submission goes to it
+            if not m.adopt_precision(self.models[0]) and calibrating(self.models[0]):
+                k = 0
+        return k, self.models[k], self.streams[k]
+
+    def launch(self, st, fn, *args, **kw):
+        """``fn(*args, **kw)`` on stream ``st``, behind what the caller's stream has enqueued, without autograd -> the handle for ``result``."""
+        st.wait_stream(torch.cuda.current_stream(self.device))       # inputs produced on the caller's stream
+        with torch.cuda.stream(st), torch.no_grad():
+            out = fn(*args, **kw)
+            done = torch.cuda.Event()
+            done.record(st)
+        return out, done, st
+
     def submit(self, images, poses, intrinsics, scale, **kw):
         """Enqueue one test-mode forward on the next stream; returns a handle for ``result``.  The inputs must stay alive and
         unmodified until the result has been taken."""
         if self._closed:
             raise RuntimeError("DepthMapPipeline: submit() after close()")
-        k = self._next % len(self.streams)
-        self._next += 1
-        st = self.streams[k]
-        m = self.models[k]
-        if k and getattr(m, "gru_precision", None) == "auto" and m._auto_pending():
-            # one arithmetic form for all replicas: the first model's calibration decides.  If that model has not calibrated these weights
-            # yet (first submission, or right after refresh_weights), this submission goes to it
-            if not m.adopt_precision(self.models[0]) and self.models[0]._auto_pending():
-                k = 0
-                st = self.streams[0]
-        st.wait_stream(torch.cuda.current_stream(self.device))       # inputs produced on the caller's stream
-        with torch.cuda.stream(st), torch.no_grad():
-            out = self.models[k](images, poses, intrinsics, scale=scale, **kw)
-            done = torch.cuda.Event()
-            done.record(st)
+        _, m, st = self.pick()
+        handle = self.launch(st, m, images, poses, intrinsics, scale=scale, **kw)
         for t in (images, poses, intrinsics):
             if isinstance(t, torch.Tensor) and t.is_cuda:
                 t.record_stream(st)
-        return out, done, st
+        return handle
 
     @staticmethod
     def result(handle, wait_on_host=True):
@@ -108,13 +184,8 @@ class DepthMapPipeline:
 
     def map(self, items, **kw):
         """items: iterable of (images, poses, intrinsics, scale) -> yields the disparities in order, ``len(self)`` forwards in flight."""
-        pending = collections.deque()
-        for it in items:
-            pending.append(self.submit(*it, **kw))
-            if len(pending) >= len(self.streams):
-                yield self.result(pending.popleft())
-        while pending:
-            yield self.result(pending.popleft())
+        for handle in in_flight((self.submit(*it, **kw) for it in items), len(self.streams)):
+            yield self.result(handle)
 
     def synchronize(self):
         for st in self.streams:

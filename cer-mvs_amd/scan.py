@@ -16,15 +16,20 @@ same bits as ``RAFT.forward`` on the stack of those images, so the same disparit
 Where the cached path cannot apply - whenever the model's forward would not take its direct-split path (``RAFT.supports_cached``: "LR"
 encoders, ``precision="amp"``, MIOpen encoders, a view_group, a stage with D > 64, the fp32 cost-volume walk, overflow_policy
 "fallback") - the session hands stacks gathered from the prepared images to the ordinary forward (``cached == False``): the single
-upload and the device-side preparation still apply."""
+upload and the device-side preparation still apply.
+
+The drivers are short callers of pipeline.py and inference.py: ``submit`` is the pipeline's ``pick`` and ``launch`` around the choice between store and
+stack, ``depths`` and ``inference_scan`` run ``pipeline.checked`` (the latter through ``inference.run_jobs``, which writes the files), and
+``reconstruct_scan`` reads as its steps: ``_depth_stacks``, ``_merged`` and the vote loop, ``_cloud_tail``, then the files."""
 import time
 from pathlib import Path
 
-import numpy as np
 import torch
 
+from . import fusion as FU
 from . import ops
-from .raft import RAFT, SaturationError
+from .inference import depth_file, run_jobs, write_pfm
+from .pipeline import DepthMapPipeline, calibrating, checked, running_model, stream_count, unwrap
 
 
 def scan_intrinsics(intrinsics, H0, W0, rescale=1, crop=None):
@@ -68,8 +73,7 @@ class ScanSession:
 
     def __init__(self, model, images, poses, intrinsics, rescale=1, crop=None, streams=3, encode_batch=4, max_bytes=None, bgr=False,
                  force_uncached=False):
-        from .pipeline import DepthMapPipeline
-        core = model.module if hasattr(model, "module") and isinstance(getattr(model, "module"), RAFT) else model
+        core = unwrap(model)
         if not core.test_mode:
             raise RuntimeError("ScanSession: the model must be built with test_mode=True")
         dev = next(core.parameters()).device
@@ -119,8 +123,7 @@ class ScanSession:
         self._store_key = None
         self._store_ready = None
         self._slots = {}
-        self._next = 0
-        if self.cached and not self._calibrating(core):
+        if self.cached and not calibrating(core):
             self._ensure_store()
 
     def __len__(self):
@@ -131,10 +134,6 @@ class ScanSession:
     def cached(self):
         """True: depth maps run ``RAFT.forward_cached`` on the feature store; False: the ordinary forward on gathered stacks."""
         return not self.force_uncached and self.model.supports_cached(self.device)
-
-    @staticmethod
-    def _calibrating(m):
-        return m.gru_precision == "auto" and m._auto_pending()
 
     def _key(self):
         m = self.model
@@ -188,32 +187,22 @@ class ScanSession:
         if not 0 <= ref < self.M:
             raise IndexError(f"ScanSession: reference view {ref} outside the scan of {self.M} images")
         srcs = [int(j) for j in srcs]
-        k = self._next % len(pipe.streams)
-        self._next += 1
-        m = pipe.models[k]
-        if k and self._calibrating(m):
-            # one arithmetic form for all replicas: the first model's calibration decides (pipeline.DepthMapPipeline.submit)
-            if not m.adopt_precision(pipe.models[0]) and self._calibrating(pipe.models[0]):
-                k, m = 0, pipe.models[0]
-        use_cached = self.cached and not self._calibrating(m)
+        _, m, st = pipe.pick()                          # (a replica still calibrating adopted the first model's form, or m is the first model)
+        use_cached = self.cached and not calibrating(m)
         idx = [ref] + srcs
         poses, intr = self.poses[idx][None], self.intrinsics[idx][None]
         if use_cached:
             self._ensure_store()
             slots = self._slot_tensor(srcs)
-        st = pipe.streams[k]
-        st.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(st), torch.no_grad():
+
+        def forward():
             if use_cached:
                 st.wait_event(self._store_ready)
                 f1s = ops.feat_ref_rows(self.store[ref], self.h, self.w, border=2)
-                out = m.forward_cached(self.prepared[ref:ref + 1], f1s, self.store, slots, poses, intr, scale)
-            else:
-                # calibration pending, or a model whose forward does not take the direct-split path: the ordinary forward on a gathered stack
-                out = m(self.stack(ref, srcs), poses, intr, scale=scale)
-            done = torch.cuda.Event()
-            done.record(st)
-        return out, done, st
+                return m.forward_cached(self.prepared[ref:ref + 1], f1s, self.store, slots, poses, intr, scale)
+            # calibration pending, or a model whose forward does not take the direct-split path: the ordinary forward on a gathered stack
+            return m(self.stack(ref, srcs), poses, intr, scale=scale)
+        return pipe.launch(st, forward)
 
     def result(self, handle, wait_on_host=True):
         return self.pipe.result(handle, wait_on_host=wait_on_host)
@@ -225,33 +214,25 @@ class ScanSession:
     def depths(self, pairs, scales, num_frames=10):
         """One depth map per image i against ``pairs[i][:num_frames]`` with ``scales[i]`` -> float32 [M,h,w] on the device, ``len(self)`` depth maps
         in flight.  Each disparity is inverted on the stream that produced it (``ops.disp_to_depth``: ``inference.disp_to_depth``'s bits)
-        straight into its slice.  The overflow flag is polled as ``inference_scan`` polls it; a ``SaturationError`` leaves nothing behind."""
+        straight into its slice.  The overflow protocol is the file drivers' (``pipeline.checked``); a ``SaturationError`` leaves nothing behind."""
         M = self.M
         if len(pairs) != M or len(scales) != M:
             raise ValueError(f"ScanSession.depths: pairs and scales need one entry per image ({M})")
         stack = torch.empty(M, self.h, self.w, device=self.device, dtype=torch.float32)
-        pending, n_flight = [], len(self)
         cur = torch.cuda.current_stream(self.device)
 
-        def finish(done):
-            done.synchronize()
-            bits = self.poll_overflow()
-            if bits:
-                self.model._raise_overflow(bits)
-
-        try:
+        def inverted():
             for i in range(M):
                 disp, _, st = self.submit(i, [int(j) for j in pairs[i]][:num_frames], scales[i])
                 with torch.cuda.stream(st):
                     ops.disp_to_depth(disp, out=stack[i])
                     done = torch.cuda.Event()
                     done.record(st)
-                pending.append(done)
-                if len(pending) >= n_flight:
-                    finish(pending.pop(0))
-            while pending:
-                finish(pending.pop(0))
-            self.check_overflow()                           # (reads the flag: covers the last forwards, whose snapshots nobody polled)
+                yield done
+
+        try:
+            for _ in checked(self, self.model, inverted(), torch.cuda.Event.synchronize):
+                pass
         finally:
             for st in self.pipe.streams:                    # (also on an error: no forward still writes into a stack that is let go)
                 stack.record_stream(st)
@@ -281,81 +262,88 @@ def inference_scan(model_or_ckpt, images, poses, intrinsics, names, pairs, scale
     the reference's load_pair orders them) and the loader's per-view ``scales[i]``; same files (``depths/{name}_scale{rescale}_nf{num_frames}.pfm``,
     the optional min-depth text), same overflow handling.  ``model_or_ckpt``: a RAFT, or a checkpoint path (None: untrained weights).
     ``timings``: a dict that receives the session's host-side figures.  Returns the list of files written."""
-    from .inference import disp_to_depth, write_pfm
-    if isinstance(model_or_ckpt, torch.nn.Module):
-        model = model_or_ckpt
-    else:
-        model = RAFT(test_mode=True).cuda()
-        if model_or_ckpt is not None:
-            model.load_state_dict(torch.load(model_or_ckpt, map_location="cpu"), strict=True)
-    core = model.module if hasattr(model, "module") and isinstance(getattr(model, "module"), RAFT) else model
-    was_training = core.training
     output_folder = Path(output_folder)
-    (output_folder / "depths").mkdir(exist_ok=True, parents=True)
-    n_streams = 1 if getattr(core, "view_group", None) is not None else max(1, int(streams))
-    sess = ScanSession(core, images, poses, intrinsics, rescale=rescale, crop=crop, streams=n_streams, encode_batch=encode_batch,
-                       max_bytes=max_bytes, bgr=bgr, force_uncached=force_uncached)
-    M = sess.M
-    if len(names) != M or len(pairs) != M or len(scales) != M:
-        raise ValueError(f"inference_scan: names, pairs and scales need one entry per image ({M})")
-    written, pending = [], []
-    n_flight = len(sess)
-
-    def finish(entry):
-        handle, name = entry
-        disp_est = sess.result(handle)
-        # (as inference(): under the lazy policy the flag of forward k is polled when forward k + streams starts; nothing is written for a
-        # forward whose flag is already known to be set)
-        bits = sess.poll_overflow()
-        if bits:
-            core._raise_overflow(bits)
-        im = disp_to_depth(disp_est.cpu().numpy()[0, 0])
-        path = output_folder / "depths" / f"{name}_scale{rescale}_nf{num_frames}.pfm"
-        write_pfm(path, im)
-        written.append(str(path))
-        if write_min_depth is not None:
-            wm = Path(write_min_depth)
-            wm.mkdir(exist_ok=True)
-            with open(wm / f"{name}.txt", "w") as f:
-                f.write(f"{np.quantile(im[im > 0], 0.1) / 2}\n")
-
-    try:
-        for i in range(M):
-            srcs = [int(j) for j in pairs[i]][:num_frames]
-            pending.append((sess.submit(i, srcs, scales[i]), names[i]))
-            if len(pending) >= n_flight:
-                finish(pending.pop(0))
-        while pending:
-            finish(pending.pop(0))
-        sess.check_overflow()                               # (reads the flag: covers the last forwards, whose snapshots nobody polled)
-    except SaturationError:
-        # the files of the last `streams` forwards were written before their flags could be read (inference())
-        for path in written[-n_flight:]:
-            try:
-                Path(path).unlink()
-            except OSError:
-                pass
-        raise
-    finally:
-        if timings is not None:
-            timings.update(sess.timings)
-            timings["cached"] = bool(sess.cached)
-        sess.close()
-        if was_training:
-            core.train()
-    return written
+    with running_model(model_or_ckpt) as core:
+        (output_folder / "depths").mkdir(exist_ok=True, parents=True)
+        sess = ScanSession(core, images, poses, intrinsics, rescale=rescale, crop=crop, streams=stream_count(core, streams),
+                           encode_batch=encode_batch, max_bytes=max_bytes, bgr=bgr, force_uncached=force_uncached)
+        try:
+            M = sess.M
+            if len(names) != M or len(pairs) != M or len(scales) != M:
+                raise ValueError(f"inference_scan: names, pairs and scales need one entry per image ({M})")
+            jobs = ((sess.submit(i, [int(j) for j in pairs[i]][:num_frames], scales[i]), names[i], num_frames) for i in range(M))
+            return run_jobs(sess, core, jobs, output_folder, rescale, write_min_depth)
+        finally:
+            if timings is not None:
+                timings.update(sess.timings)
+                timings["cached"] = bool(sess.cached)
+            sess.close()
 
 
-def _write_masks(folder, masks_np, refs, suffix=""):
-    """``mask/<index><suffix>.png`` as ``fusion.fusion`` writes them."""
-    (folder / "mask").mkdir(exist_ok=True, parents=True)
-    try:
-        from PIL import Image
-        for ref in refs:
-            Image.fromarray(masks_np[ref].astype(np.uint8) * 255).save(str(folder / "mask" / f"{ref}{suffix}.png"))
-    except ImportError:                                      # no PNG encoder in this Python: keep the arrays
-        for ref in refs:
-            np.save(str(folder / "mask" / f"{ref}{suffix}.npy"), masks_np[ref])
+def _depth_stacks(core, images, poses, intrinsics, pairs, scales, passes, num_frames, timings, **session_kw):
+    """Step 1 of ``reconstruct_scan``: one session per pass, one after the other -> the depth stack [M,h,w] of every pass, and the colours
+    and cameras of the first pass's images at the grid that is fused (the finer one in the two-pass form)."""
+    stacks, colors, Ks, Es = [], None, None, None
+    for k, s in enumerate(passes):
+        sess = ScanSession(core, images, poses, intrinsics, rescale=s, **session_kw)
+        try:
+            stacks.append(sess.depths(pairs, scales, num_frames=num_frames))
+            if k == 0:
+                # colours and cameras as fusion() derives them from the prepared images and their intrinsics, at the grid that is fused
+                gh, gw = (sess.h * 2, sess.w * 2) if len(passes) == 2 else (sess.h, sess.w)
+                colors = FU.color_grid(sess.prepared, gh, gw)
+                scale, flag, _, _, index = FU.depth_grid_geometry(sess.H, sess.W, gh, gw)
+                Ks = torch.stack([FU.modify_camera_parameters(sess.intrinsics[i].clone().float(), scale, index, flag) for i in range(sess.M)])
+                Es = sess.poses.clone().float()
+                torch.cuda.current_stream(sess.device).synchronize()     # (the session's images go away with it)
+            if timings is not None:
+                timings.update(sess.timings)
+                timings["cached"] = bool(sess.cached)
+        finally:
+            sess.close()
+    return stacks, colors, Ks, Es
+
+
+def _merged(stacks, colors, th, keep):
+    """Step 2 of ``reconstruct_scan``, up to the vote loop: the stack that is fused (two passes: ``multires.merge`` per view, at the finer
+    grid) and, with ``keep``, every pass's stack on the host for the PFMs."""
+    if len(stacks) == 2:
+        from .multires import merge
+        if tuple(stacks[1].shape[1:]) != (colors.shape[2], colors.shape[3]):
+            raise ValueError("reconstruct_scan: the second pass's depth grid is not twice the first's")
+        depths = torch.stack([merge(stacks[0][i], stacks[1][i], th=th) for i in range(stacks[0].shape[0])])
+    else:
+        depths = stacks[0]
+    torch.cuda.current_stream(depths.device).synchronize()
+    return depths, ([st.cpu().numpy() for st in stacks] if keep else [])
+
+
+def _cloud_tail(masks, est, Ks, Es, colors, refs, clean, normals):
+    """Step 3 of ``reconstruct_scan``: masked pixels -> points and colours, the optional ``clean`` filter and ``normals`` (already checked
+    options, or None) on the device, then the one copy to the host -> the result's arrays and the bytes that copy moved."""
+    dev = masks.device
+    if normals is None:
+        xyz, rgb = FU.point_cloud(masks, est, Ks, Es, colors, refs)
+    else:
+        xyz, rgb, view_base = FU.point_cloud(masks, est, Ks, Es, colors, refs, view_base=True)
+    out, kept = {}, None
+    if clean is not None:
+        from .cloud_eval import clean_cloud
+        kept, cleaned = clean_cloud(xyz, clean)
+        out["clean"] = {"n_in": int(xyz.shape[0]), **cleaned}
+        xyz, rgb = xyz.index_select(0, kept), rgb.index_select(0, kept)
+    if normals is not None:
+        from .cloud_eval import estimate_normals
+        # the view of a fused row: the last k with view_base[k] <= row (views without a point share their base with the next one)
+        rows = kept if kept is not None else torch.arange(int(xyz.shape[0]), device=dev)
+        slot = torch.searchsorted(view_base, rows, right=True) - 1
+        centres = FU.cloud_cams(Ks, Es)[:, [12, 16, 20]].float()[refs].to(dev)      # inv(E)[:3, 3] of every emitted view
+        out["normal_info"] = {}
+        nrm, _ = estimate_normals(xyz, viewpoints=centres.index_select(0, slot), info=out["normal_info"], **normals)
+        out["normals"] = nrm.cpu().numpy()
+    out.update(xyz=xyz.cpu().numpy(), rgb=rgb.cpu().numpy(), masks=masks.cpu().numpy().astype(bool), depth_est=est.cpu().numpy())
+    nbytes = int(xyz.numel() * 4 + rgb.numel() + masks.numel() + est.numel() * 4)
+    return out, nbytes + (int(out["normals"].nbytes) if normals is not None else 0)
 
 
 def reconstruct_scan(model_or_ckpt, images, poses, intrinsics, names, pairs, scales, output_folder=None, rescale=1, crop=None, num_frames=10,
@@ -381,8 +369,6 @@ def reconstruct_scan(model_or_ckpt, images, poses, intrinsics, names, pairs, sca
     produced the point - the one piece of information that orients a normal without guessing.  The result gains "normals" (float32 [n, 3];
     zeros where the neighbourhood has no plane) and "normal_info" ({"n_valid", "max_dist", "cell", "k"}), and ``result.ply`` carries nx ny nz.
     None (the default): no normals, no such keys, the file as before."""
-    from . import fusion as FU
-    from .inference import write_pfm
     two_pass = isinstance(rescale, (tuple, list))
     passes = [r for r in rescale] if two_pass else [rescale]
     if two_pass and (len(passes) != 2 or passes[1] != 2 * passes[0]):
@@ -397,96 +383,35 @@ def reconstruct_scan(model_or_ckpt, images, poses, intrinsics, names, pairs, sca
     if normals is not None:
         from .cloud_eval import normals_options
         normals = normals_options(normals)
-    if isinstance(model_or_ckpt, torch.nn.Module):
-        model = model_or_ckpt
-    else:
-        model = RAFT(test_mode=True).cuda()
-        if model_or_ckpt is not None:
-            model.load_state_dict(torch.load(model_or_ckpt, map_location="cpu"), strict=True)
-    core = model.module if hasattr(model, "module") and isinstance(getattr(model, "module"), RAFT) else model
-    was_training = core.training
-    n_streams = 1 if getattr(core, "view_group", None) is not None else max(1, int(streams))
     t = {} if timings is None else timings
-    stacks, colors, Ks, Es = [], None, None, None
+    # ---- 1. depth stacks, 2. merge and fuse
     tic = time.perf_counter()
-    try:
-        for k, s in enumerate(passes):
-            sess = ScanSession(core, images, poses, intrinsics, rescale=s, crop=crop, streams=n_streams, encode_batch=encode_batch, max_bytes=max_bytes, bgr=bgr, force_uncached=force_uncached)
-            try:
-                stacks.append(sess.depths(pairs, scales, num_frames=num_frames))
-                if k == 0:
-                    # colours and cameras as fusion() derives them from the prepared images and their intrinsics, at the grid that is fused
-                    gh, gw = (sess.h * 2, sess.w * 2) if two_pass else (sess.h, sess.w)
-                    colors = FU.color_grid(sess.prepared, gh, gw)
-                    scale, flag, _, _, index = FU.depth_grid_geometry(sess.H, sess.W, gh, gw)
-                    Ks = torch.stack([FU.modify_camera_parameters(sess.intrinsics[i].clone().float(), scale, index, flag) for i in range(sess.M)])
-                    Es = sess.poses.clone().float()
-                    torch.cuda.current_stream(sess.device).synchronize()     # (the session's images go away with it)
-                if timings is not None:
-                    timings.update(sess.timings)
-                    timings["cached"] = bool(sess.cached)
-            finally:
-                sess.close()
-    finally:
-        if was_training:
-            core.train()
-    if two_pass:
-        from .multires import merge
-        if tuple(stacks[1].shape[1:]) != (colors.shape[2], colors.shape[3]):
-            raise ValueError("reconstruct_scan: the second pass's depth grid is not twice the first's")
-        depths = torch.stack([merge(stacks[0][i], stacks[1][i], th=th) for i in range(stacks[0].shape[0])])
-    else:
-        depths = stacks[0]
-    dev = depths.device
-    torch.cuda.current_stream(dev).synchronize()
-    stacks_np = [st.cpu().numpy() for st in stacks] if write_depths else []
+    with running_model(model_or_ckpt) as core:
+        stacks, colors, Ks, Es = _depth_stacks(core, images, poses, intrinsics, pairs, scales, passes, num_frames, timings, crop=crop,
+                                               streams=stream_count(core, streams), encode_batch=encode_batch, max_bytes=max_bytes, bgr=bgr,
+                                               force_uncached=force_uncached)
+    depths, stacks_np = _merged(stacks, colors, th, keep=write_depths)
     del stacks                                              # (two-pass: the coarse and the fine stack are not needed behind the merge)
     t["depths_s"] = time.perf_counter() - tic
     tic = time.perf_counter()
     fpairs = [(i, [int(j) for j in pairs[i]][:num_frames]) for i in range(M)]
     masks, est, thre, hist = FU.fuse_depth_maps(depths, Ks, Es, fpairs, glb=glb)
     t["fuse_s"] = time.perf_counter() - tic
+    # ---- 3. cloud tail
     tic = time.perf_counter()
     refs = [ref for ref, _ in fpairs]
-    if normals is None:
-        xyz, rgb = FU.point_cloud(masks, est, Ks, Es, colors, refs)
-    else:
-        xyz, rgb, view_base = FU.point_cloud(masks, est, Ks, Es, colors, refs, view_base=True)
-    cleaned, kept = None, None
-    if clean is not None:
-        from .cloud_eval import clean_cloud
-        kept, cleaned = clean_cloud(xyz, clean)
-        cleaned = {"n_in": int(xyz.shape[0]), **cleaned}
-        xyz, rgb = xyz.index_select(0, kept), rgb.index_select(0, kept)
-    nrm_np, normal_info = None, None
-    if normals is not None:
-        from .cloud_eval import estimate_normals
-        # the view of a fused row: the last k with view_base[k] <= row (views without a point share their base with the next one)
-        rows = kept if kept is not None else torch.arange(int(xyz.shape[0]), device=dev)
-        slot = torch.searchsorted(view_base, rows, right=True) - 1
-        centres = FU.cloud_cams(Ks, Es)[:, [12, 16, 20]].float()[refs].to(dev)      # inv(E)[:3, 3] of every emitted view
-        normal_info = {}
-        nrm, _ = estimate_normals(xyz, viewpoints=centres.index_select(0, slot), info=normal_info, **normals)
-        nrm_np = nrm.cpu().numpy()
-    xyz_np, rgb_np, masks_np, est_np = xyz.cpu().numpy(), rgb.cpu().numpy(), masks.cpu().numpy().astype(bool), est.cpu().numpy()
-    t["d2h_bytes"] = int(xyz.numel() * 4 + rgb.numel() + masks.numel() + est.numel() * 4) + sum(int(a.nbytes) for a in stacks_np)
-    if nrm_np is not None:
-        t["d2h_bytes"] += int(nrm_np.nbytes)
-    if write or write_depths:
-        output_folder = Path(output_folder)
-        output_folder.mkdir(exist_ok=True, parents=True)
+    cloud, nbytes = _cloud_tail(masks, est, Ks, Es, colors, refs, clean, normals)
+    t["d2h_bytes"] = nbytes + sum(int(a.nbytes) for a in stacks_np)
+    # ---- 4. write
     if write_depths:
-        (output_folder / "depths").mkdir(exist_ok=True, parents=True)
+        (Path(output_folder) / "depths").mkdir(exist_ok=True, parents=True)
         for k, s in enumerate(passes):
             for i in range(M):
-                write_pfm(output_folder / "depths" / f"{names[i]}_scale{s}_nf{num_frames}.pfm", stacks_np[k][i])
+                write_pfm(depth_file(output_folder, names[i], s, num_frames), stacks_np[k][i])
     if write:
-        _write_masks(output_folder, masks_np, refs)
-        FU.write_ply(str(output_folder / "result.ply"), xyz_np, rgb_np, normals=nrm_np)
+        FU.write_masks(Path(output_folder), cloud["masks"], refs)
+        FU.write_ply(str(Path(output_folder) / "result.ply"), cloud["xyz"], cloud["rgb"], normals=cloud.get("normals"))
     t["tail_s"] = time.perf_counter() - tic
-    out = {"masks": masks_np, "depth_est": est_np, "xyz": xyz_np, "rgb": rgb_np, "threshold": thre, "history": hist}
-    if cleaned is not None:
-        out["clean"] = cleaned
-    if nrm_np is not None:
-        out["normals"], out["normal_info"] = nrm_np, normal_info
+    out = {"masks": cloud["masks"], "depth_est": cloud["depth_est"], "xyz": cloud["xyz"], "rgb": cloud["rgb"], "threshold": thre, "history": hist}
+    out.update({k: cloud[k] for k in ("clean", "normals", "normal_info") if k in cloud})
     return out
