@@ -1,6 +1,7 @@
 """Python faces of the HIP kernels: shape bookkeeping + output allocation around include/cer_mvs.h.
 All tensors are CUDA float32; every call enqueues on torch's current stream."""
 import ctypes
+import math
 
 import torch
 
@@ -51,23 +52,22 @@ def alt_corr_forward(fmap1, fmap2, coords, radius):
     return corr
 
 
-DETERMINISTIC_BACKWARD = True      # fmap2 gradient by a sorted segmented reduction (False: float atomics, like the reference)
-
-
-def alt_corr_backward(fmap1, fmap2, coords, corr_grad, radius, deterministic=None):
-    """-> (fmap1_grad, fmap2_grad, coords_grad = 0) (correlation.cpp:36-48).  ``deterministic`` (default
-    ``DETERMINISTIC_BACKWARD``): fmap2_grad without atomics - tuples kernel, stable sort of the texel keys (torch), segmented
-    reduction kernel: bit-identical from run to run."""
+def alt_corr_backward(fmap1, fmap2, coords, corr_grad, radius, deterministic=True):
+    """-> (fmap1_grad, fmap2_grad, coords_grad = 0) (correlation.cpp:36-48).  ``deterministic``: fmap2_grad without atomics - tuples
+    kernel, stable sort of the texel keys (torch), segmented reduction kernel: bit-identical from run to run.  False: the one-call
+    form with float atomics, like the reference (the cross-reference of tests/test_train_gpu.py)."""
     B, H1, W1, C = fmap1.shape
     _, H2, W2, _ = fmap2.shape
     N = coords.shape[1]
-    if DETERMINISTIC_BACKWARD if deterministic is None else deterministic:
-        lib, dev = L.load(), fmap1.device
-        g1 = torch.empty_like(fmap1)
-        gc = torch.zeros_like(coords)
-        L.check(lib.cer_alt_corr_backward_f32(L.dev_ptr(fmap1, "fmap1"), L.dev_ptr(fmap2, "fmap2"), L.dev_ptr(coords, "coords"),
-                                              L.dev_ptr(corr_grad, "corr_grad"), L.dev_ptr(g1, "g1"), None, None, B, N, H1, W1, H2, W2, C,
-                                              radius, L.cur_stream()), "alt_corr_backward[f1]")
+    lib, dev = L.load(), fmap1.device
+    g1, g2 = torch.empty_like(fmap1), torch.empty_like(fmap2)
+    gc = torch.zeros_like(coords) if deterministic else torch.empty_like(coords)
+    # (null g2 / gc: the kernel writes fmap1_grad only)
+    L.check(lib.cer_alt_corr_backward_f32(L.dev_ptr(fmap1, "fmap1"), L.dev_ptr(fmap2, "fmap2"), L.dev_ptr(coords, "coords"),
+                                          L.dev_ptr(corr_grad, "corr_grad"), L.dev_ptr(g1, "g1"), L.dev_ptr(None if deterministic else g2, "g2"),
+                                          L.dev_ptr(None if deterministic else gc, "gc"), B, N, H1, W1, H2, W2, C, radius, L.cur_stream()),
+            "alt_corr_backward")
+    if deterministic:
         # one batch element (= one source view under DirectCorr) at a time: its tuples (key, coefficient, source pixel: ~32 B each with
         # the sort's temporaries) are N*H1*W1*(2r+2)^2 - 1/B of the transient memory of sorting all views at once (~1.7 GB per stage
         # at 10 views x 64 hypotheses x 128x160), and B small sorts instead of one large one; keys are partitioned by b anyway
@@ -77,7 +77,6 @@ def alt_corr_backward(fmap1, fmap2, coords, corr_grad, radius, deterministic=Non
         src = torch.empty(n, device=dev, dtype=torch.int32)
         T = H2 * W2
         bounds = torch.arange(T + 1, device=dev, dtype=torch.int64)
-        g2 = torch.empty_like(fmap2)
         for b in range(B):
             L.check(lib.cer_alt_corr_bwd_tuples_f32(L.dev_ptr(coords[b:b + 1], "coords"), L.dev_ptr(corr_grad[b:b + 1], "corr_grad"),
                                                     L.dev_ptr(keys, "keys", torch.int64), L.dev_ptr(coef, "coef"), L.dev_ptr(src, "src", torch.int32),
@@ -87,14 +86,6 @@ def alt_corr_backward(fmap1, fmap2, coords, corr_grad, radius, deterministic=Non
             L.check(lib.cer_alt_corr_bwd_reduce_f32(L.dev_ptr(fmap1[b:b + 1], "fmap1"), L.dev_ptr(order.contiguous(), "order", torch.int64),
                                                     L.dev_ptr(coef, "coef"), L.dev_ptr(src, "src", torch.int32), L.dev_ptr(seg, "seg", torch.int64),
                                                     L.dev_ptr(g2[b:b + 1], "g2"), T, C, L.cur_stream()), "alt_corr_bwd_reduce")
-        return g1, g2, gc
-    g1 = torch.empty_like(fmap1)
-    g2 = torch.empty_like(fmap2)
-    gc = torch.empty_like(coords)
-    L.check(L.load().cer_alt_corr_backward_f32(L.dev_ptr(fmap1, "fmap1"), L.dev_ptr(fmap2, "fmap2"), L.dev_ptr(coords, "coords"),
-                                               L.dev_ptr(corr_grad, "corr_grad"), L.dev_ptr(g1, "g1"), L.dev_ptr(g2, "g2"),
-                                               L.dev_ptr(gc, "gc"), B, N, H1, W1, H2, W2, C, radius, L.cur_stream()),
-            "alt_corr_backward")
     return g1, g2, gc
 
 
@@ -159,16 +150,23 @@ def overflow_poll(device):
     return bits
 
 
+def _given_or_new(out, shape, dtype, device, what, exact=False):
+    """A caller-supplied output (``out=``, ``origin=``: a slice of a larger buffer): None -> a new tensor of ``shape``; else it must
+    lie on ``device`` and hold as many elements (``exact``: have that shape), or ``what`` says what it must be."""
+    if out is None:
+        return torch.empty(shape, device=device, dtype=dtype)
+    if out.device != device or (tuple(out.shape) != tuple(shape) if exact else out.numel() != math.prod(shape)):
+        raise RuntimeError(f"{what} on {device}")
+    return out
+
+
 def feat_split(x, out=None):
     """fp32 rows [texels, 64] (one block: the reference map) or [blocks, texels, 64] (source views) -> the split-f16 operand
     planes of ``cost_build(..., split=...)`` / cer_cost_lines_f32 (cer_mvs.h: per block 8 planes [texels][16], same bytes)."""
     if x.shape[-1] != 64 or x.dim() not in (2, 3):
         raise RuntimeError("feat_split: [texels, 64] or [blocks, texels, 64]")
     blocks, texels = (1, x.shape[0]) if x.dim() == 2 else (x.shape[0], x.shape[1])
-    if out is None:
-        out = torch.empty(x.shape[:-1] + (128,), device=x.device, dtype=torch.float16)
-    elif out.numel() != 2 * x.numel() or out.device != x.device:
-        raise RuntimeError(f"feat_split: out must hold {2 * x.numel()} halves on {x.device} (got {out.numel()} on {out.device})")
+    out = _given_or_new(out, x.shape[:-1] + (128,), torch.float16, x.device, f"feat_split: out must hold {2 * x.numel()} halves")
     L.check(L.load().cer_feat_split_f16(L.dev_ptr(x, "x"), L.dev_ptr(out, "out", torch.float16), blocks, texels, 64,
                                         L.dev_ptr(overflow_flag(x.device), "flag", torch.int32), L.cur_stream()), "feat_split")
     return out
@@ -187,10 +185,6 @@ def release_lines_workspace(device, stream=None):
 
 def lines_workspace(V, h1, w1, D, device):
     """The (persistent, per device and stream) workspace of the epipolar-line-tile cost volume: partial volumes + tile parameters."""
-    return _lines_workspace(V, h1, w1, D, device)
-
-
-def _lines_workspace(V, h1, w1, D, device):
     need = int(L.load().cer_cost_lines_workspace(V, h1, w1, D))
     key = (str(device), torch.cuda.current_stream(device).cuda_stream)       # per stream: forwards on different streams overlap
     ws = _LINES_WS.get(key)
@@ -198,6 +192,27 @@ def _lines_workspace(V, h1, w1, D, device):
         ws = torch.empty(need, device=device, dtype=torch.uint8)
         _LINES_WS[key] = ws
     return ws
+
+
+def on_line_tiles(C, D, can_walk=True):
+    """A folded volume of D hypotheses over C-channel maps is built on the epipolar-line-tile kernel (cer_cost_lines_f32): C = 64,
+    D <= 64, and the process has not selected the fp32 walk (``cer_cost_build_algo(1)``, read here and nowhere else) - which a
+    caller that holds no fp32 source maps (``can_walk`` False) cannot follow."""
+    return C == 64 and D <= 64 and not (can_walk and L.load().cer_cost_build_algo(-1) == 1)
+
+
+def _new_volume(lead, D, num_levels, compact, written, device):
+    """A volume [*lead, row stride] for a builder.  ``written``: the kernel's epilogue writes every level of every row (the fused
+    pyramid, the forward's hot path) - no 50 MB zero fill, only the alignment pad of a row (<= 3 floats) is cleared; else zeros:
+    the pooled levels stay 0 until ``pyramid`` runs."""
+    offs, lens, rs = row_layout(D, num_levels, compact)
+    if not written:
+        return torch.zeros(*lead, rs, device=device, dtype=torch.float32)
+    vol = torch.empty(*lead, rs, device=device, dtype=torch.float32)
+    used = D if compact else offs[-1] + lens[-1]
+    if used < rs:
+        vol[..., used:] = 0
+    return vol
 
 
 def cost_build(fmap1, fmap2, Pij, disp_in, D, incre, shift, h1, w1, num_levels, fold, vol=None, accumulate=False, src_hw=None, y0=0,
@@ -230,24 +245,11 @@ def cost_build(fmap1, fmap2, Pij, disp_in, D, incre, shift, h1, w1, num_levels, 
     if fuse and (not fold or accumulate or D > 64):
         raise ValueError("cost_build: the fused pyramid needs fold=True, accumulate=False and D <= 64")
     lib = L.load()
-    on_lines = fold and C == 64 and D <= 64 and (fmap2 is None or lib.cer_cost_build_algo(-1) != 1)
+    on_lines = fold and on_line_tiles(C, D, can_walk=fmap2 is not None)
     fuse_levels = 0 if not fuse else (1 if compact else num_levels)      # (1 = scale only, in both builders since ABI 1060)
     if vol is None:
-        shape = (P, rs) if fold else (V, P, rs)
-        if fuse:
-            # fused pyramid (the forward's hot path): the kernel writes every level of every row - no 50 MB zero fill; only the
-            # alignment pad of a row (rs - used, <= 3 floats) is cleared
-            vol = torch.empty(shape, device=fmap1.device, dtype=torch.float32)
-            offs, lens, _ = row_layout(D, num_levels)
-            used = D if compact else offs[-1] + lens[-1]
-            if used < rs:
-                vol[..., used:] = 0
-        else:
-            vol = torch.zeros(shape, device=fmap1.device, dtype=torch.float32)     # pooled levels stay 0 until ``pyramid`` runs
-    if origin is None:
-        origin = torch.empty(P, device=fmap1.device, dtype=torch.float32)
-    elif origin.numel() != P or origin.device != fmap1.device:
-        raise RuntimeError(f"cost_build: origin must hold {P} floats on {fmap1.device}")
+        vol = _new_volume((P,) if fold else (V, P), D, num_levels, compact, fuse, fmap1.device)
+    origin = _given_or_new(origin, (P,), torch.float32, fmap1.device, f"cost_build: origin must hold {P} floats")
     mode = (2 if accumulate else 1) if fold else 0
     slots = split[2] if (split is not None and len(split) > 2) else None
     if on_lines:
@@ -256,7 +258,7 @@ def cost_build(fmap1, fmap2, Pij, disp_in, D, incre, shift, h1, w1, num_levels, 
             f1s = feat_split(fmap1)
         if f2s is None:
             f2s = feat_split(fmap2)
-        ws = _lines_workspace(V, h1, w1, D, fmap1.device)
+        ws = lines_workspace(V, h1, w1, D, fmap1.device)
         L.check(lib.cer_cost_lines_f32(L.dev_ptr(f1s, "fmap1_split", torch.float16), L.dev_ptr(f2s, "fmap2_split", torch.float16),
                                        L.dev_ptr(slots, "view_slot", torch.int32), L.dev_ptr(Pij, "Pij"), L.dev_ptr(disp_in, "disp_in"), L.dev_ptr(vol, "vol"),
                                        L.dev_ptr(origin, "origin"), L.dev_ptr(ws, "workspace", torch.uint8), V, h1, w1, h2, w2, C, D, rs,
@@ -279,7 +281,7 @@ def cost_lines_views(f1s, f2s, slots, Pij, disp_in, V, v0, nv, h1, w1, D, incre,
     lines workspace (cer_cost_lines_views_f32).  ``cost_lines_reduce`` finishes the volume once every view has been built."""
     h2, w2 = src_hw if src_hw is not None else (h1, w1)
     if ws is None:                                           # (callers that split the two halves over streams pass one workspace to both)
-        ws = _lines_workspace(V, h1, w1, D, f1s.device)
+        ws = lines_workspace(V, h1, w1, D, f1s.device)
     L.check(L.load().cer_cost_lines_views_f32(L.dev_ptr(f1s, "fmap1_split", torch.float16), L.dev_ptr(f2s, "fmap2_split", torch.float16),
                                               L.dev_ptr(slots, "view_slot", torch.int32), L.dev_ptr(Pij, "Pij"), L.dev_ptr(disp_in, "disp_in"),
                                               L.dev_ptr(ws, "workspace", torch.uint8), V, int(v0), int(nv), h1, w1, h2, w2, 64, D, float(incre),
@@ -294,15 +296,10 @@ def cost_lines_reduce(disp_in, V, h1, w1, D, incre, shift, num_levels, pyramid_s
     fuse = pyramid_scale is not None and (num_levels > 1 or compact) and not accumulate
     dev = disp_in.device
     if vol is None:
-        vol = torch.empty(P, rs, device=dev, dtype=torch.float32) if fuse else torch.zeros(P, rs, device=dev, dtype=torch.float32)
-        if fuse:
-            offs, lens, _ = row_layout(D, num_levels)
-            used = D if compact else offs[-1] + lens[-1]
-            if used < rs:
-                vol[..., used:] = 0
+        vol = _new_volume((P,), D, num_levels, compact, fuse, dev)
     origin = torch.empty(P, device=dev, dtype=torch.float32)
     if ws is None:
-        ws = _lines_workspace(V, h1, w1, D, dev)
+        ws = lines_workspace(V, h1, w1, D, dev)
     L.check(L.load().cer_cost_lines_reduce_f32(L.dev_ptr(ws, "workspace", torch.uint8), L.dev_ptr(disp_in, "disp_in"), L.dev_ptr(vol, "vol"),
                                                L.dev_ptr(origin, "origin"), V, h1, w1, D, rs, float(incre), int(bool(shift)),
                                                2 if accumulate else 1, (1 if compact else num_levels) if fuse else 0,
@@ -364,6 +361,16 @@ def lookup_encode(vol, origin, disp, w_t, b, D, incre, num_levels, radius, out=N
     return out
 
 
+def pack_host(size, dtype, fill, what, device):
+    """The one sequence of every host weight packer: ``size`` elements as the library reports them (<= 0: a shape it does not
+    build, refused with ``what``), a host tensor of ``dtype``, ``fill(pointer) -> return code``, the upload to ``device``."""
+    if size <= 0:
+        raise RuntimeError(what)
+    t = torch.empty(size, dtype=dtype)
+    L.check(fill(ctypes.c_void_p(t.data_ptr())), what.partition(":")[0])
+    return t.to(device)
+
+
 class PackedConv3x3:
     """A 3x3 conv's weights packed for the MFMA kernels, for a given K-source list.
     ``sources``: list of (channels, kind) with kind 0 = tensor, 1 = disparity encoder (49).
@@ -380,55 +387,49 @@ class PackedConv3x3:
         ch = (ctypes.c_int * n)(*[c for c, _ in sources])
         kind = (ctypes.c_int * n)(*[k for _, k in sources])
         kpad = sum(64 if k == 1 else (c + 31) // 32 * 32 for c, k in sources)
-        size = lib.cer_conv3x3_packed_size(Cout, kpad)
-        if size <= 0:
-            raise RuntimeError(f"conv3x3 pack: unsupported shape Cout={Cout} Kpad={kpad}")
-        packed = torch.empty(size, dtype=torch.float32)
-        L.check(lib.cer_conv3x3_pack_f32(ctypes.c_void_p(w.data_ptr()), ctypes.c_void_p(packed.data_ptr()), Cout, Cin, ch, kind, n),
-                "conv3x3_pack")
-        self.packed = packed.to(device)
-        size_x = lib.cer_conv3x3_f16x3_packed_size(Cout, kpad)
-        if size_x <= 0:
-            raise RuntimeError(f"conv3x3 f16x3 pack: unsupported shape Cout={Cout} Kpad={kpad}")
-        packed_x = torch.empty(size_x, dtype=torch.float16)
-        L.check(lib.cer_conv3x3_f16x3_pack(ctypes.c_void_p(w.data_ptr()), ctypes.c_void_p(packed_x.data_ptr()), Cout, Cin, ch, kind, n),
-                "conv3x3_f16x3_pack")
-        self.packed_x = packed_x.to(device)
+        wp, shape = ctypes.c_void_p(w.data_ptr()), (Cout, Cin, ch, kind, n)
+        self.packed = pack_host(lib.cer_conv3x3_packed_size(Cout, kpad), torch.float32, lambda p: lib.cer_conv3x3_pack_f32(wp, p, *shape),
+                                f"conv3x3 pack: unsupported shape Cout={Cout} Kpad={kpad}", device)
+        self.packed_x = pack_host(lib.cer_conv3x3_f16x3_packed_size(Cout, kpad), torch.float16, lambda p: lib.cer_conv3x3_f16x3_pack(wp, p, *shape),
+                                  f"conv3x3 f16x3 pack: unsupported shape Cout={Cout} Kpad={kpad}", device)
         self.packed_c = None                 # collapsed-disparity packing (interior tiles), only with a kind-1 source
         if any(k == 1 for _, k in sources):
-            size_c = lib.cer_conv3x3_f16x3_collapsed_size(Cout, ch, kind, n)
-            if size_c <= 0:
-                raise RuntimeError(f"conv3x3 collapsed pack: unsupported shape Cout={Cout}")
-            packed_c = torch.empty(size_c, dtype=torch.float16)
-            L.check(lib.cer_conv3x3_f16x3_pack_collapsed(ctypes.c_void_p(w.data_ptr()), ctypes.c_void_p(packed_c.data_ptr()), Cout, Cin,
-                                                         ch, kind, n), "conv3x3_f16x3_pack_collapsed")
-            self.packed_c = packed_c.to(device)
+            self.packed_c = pack_host(lib.cer_conv3x3_f16x3_collapsed_size(Cout, ch, kind, n), torch.float16,
+                                      lambda p: lib.cer_conv3x3_f16x3_pack_collapsed(wp, p, *shape),
+                                      f"conv3x3 collapsed pack: unsupported shape Cout={Cout}", device)
         self.bias = None if bias is None else bias.detach().to(device, torch.float32).contiguous()
         self.cout = Cout
-
-
-CONV_MODE = "f16x3"      # default arithmetic of ops.conv3x3: "f16x3" (split-f16 MFMA, fp32-equivalent) or "fp32" (exact fp32 MFMA)
 
 
 COLLAPSE_DISP = True     # interior tiles of a conv with a disparity source use the 81-tap collapsed form (cer_mvs.h)
 
 
-def conv3x3(pc, srcs, h, w, epi, out=None, out2=None, aux=None, aux2=None, init=None, use_bias=True, mode=None, out_split=False,
+def _conv_inputs(srcs, sources, kinds=None):
+    """The ConvInputs record of a launch: ``srcs`` checked (dense device fp32) against ``sources`` = [(channels, kind, ...)]."""
+    ci = L.ConvInputs()
+    ci.nsrc = len(srcs)
+    for i, (t, src) in enumerate(zip(srcs, sources)):
+        L.dev_ptr(t, f"src{i}")
+        ci.src[i] = t.data_ptr()
+        ci.ch[i] = src[0]
+        ci.kind[i] = src[1] if kinds is None else kinds[i]
+    return ci
+
+
+def conv3x3(pc, srcs, h, w, epi, out=None, out2=None, aux=None, aux2=None, init=None, use_bias=True, mode="f16x3", out_split=False,
             aux_split=False, kinds=None):
-    """srcs: list of tensors matching ``pc.sources`` ([P,ch] for kind 0, disp [P] for kind 1).
+    """srcs: list of tensors matching ``pc.sources`` ([P,ch] for kind 0, disp [P] for kind 1).  ``mode``: "f16x3" (split-f16 MFMA,
+    fp32-equivalent) or "fp32" (exact fp32 MFMA).
     f16x3 mode only: ``kinds`` overrides the source kinds of this call (3 = the tensor is in the split32 layout, see
     ``split32``); ``out_split`` writes the (RELU/LINEAR out, GATES out2, GRU out) result in that layout, ``aux_split`` reads
     the previous hidden state ``aux`` from it."""
-    mode = mode or CONV_MODE
+    if mode not in ("f16x3", "fp32"):
+        raise ValueError(f"conv3x3: unknown mode {mode!r}")
+    if mode == "fp32" and (out_split or aux_split or (kinds is not None and 3 in kinds)):
+        raise ValueError("the split32 layout exists only for the f16x3 kernels")
     dev = srcs[0].device
     P = h * w
-    ci = L.ConvInputs()
-    ci.nsrc = len(srcs)
-    for i, (t, (c, k)) in enumerate(zip(srcs, pc.sources)):
-        ci.src[i] = t.data_ptr()
-        L.dev_ptr(t, f"src{i}")
-        ci.ch[i] = c
-        ci.kind[i] = k if kinds is None else kinds[i]
+    ci = _conv_inputs(srcs, pc.sources, kinds)
     oc = pc.cout // 2 if epi == L.EPI_GATES else pc.cout
     if epi == L.EPI_DELTA:
         if mode != "f16x3":
@@ -441,19 +442,14 @@ def conv3x3(pc, srcs, h, w, epi, out=None, out2=None, aux=None, aux2=None, init=
         out2 = torch.empty(P, oc, device=dev, dtype=torch.float32)
     bias = pc.bias if (use_bias and init is None) else None
     aux_p = L.dev_ptr(aux, "aux", torch.float16) if epi == L.EPI_DELTA else L.dev_ptr(aux, "aux")
+    flags = (L.EPI_OUT_SPLIT if out_split else 0) | (L.EPI_AUX_SPLIT if aux_split else 0)      # (none in fp32 mode: refused above)
     tail = (L.dev_ptr(bias, "bias"), L.dev_ptr(init, "init"), L.dev_ptr(out, "out"), L.dev_ptr(out2, "out2"), aux_p,
-            L.dev_ptr(aux2, "aux2"), h, w, pc.cout, epi, L.cur_stream())
+            L.dev_ptr(aux2, "aux2"), h, w, pc.cout, epi | flags, L.cur_stream())
     if mode == "f16x3":
         coll = L.dev_ptr(pc.packed_c, "packed_collapsed", torch.float16) if (COLLAPSE_DISP and pc.packed_c is not None) else None
-        flags = (L.EPI_OUT_SPLIT if out_split else 0) | (L.EPI_AUX_SPLIT if aux_split else 0)
-        tail = tail[:9] + (epi | flags,) + tail[10:]
         rc = L.load().cer_conv3x3_f16x3(ctypes.byref(ci), L.dev_ptr(pc.packed_x, "packed_w", torch.float16), coll, *tail)
-    elif mode == "fp32":
-        if out_split or aux_split or (kinds is not None and 3 in kinds):
-            raise ValueError("the split32 layout exists only for the f16x3 kernels")
-        rc = L.load().cer_conv3x3_f32(ctypes.byref(ci), L.dev_ptr(pc.packed, "packed_w"), *tail)
     else:
-        raise ValueError(f"conv3x3: unknown mode {mode!r}")
+        rc = L.load().cer_conv3x3_f32(ctypes.byref(ci), L.dev_ptr(pc.packed, "packed_w"), *tail)
     L.check(rc, f"conv3x3[{mode}]")
     return (out, out2) if epi == L.EPI_GATES else out
 
@@ -463,20 +459,20 @@ def delta_proj_pack(w2, device):
     lib = L.load()
     w = w2.detach().to("cpu", torch.float32).contiguous()
     C = w.shape[1]
-    size = lib.cer_delta_proj_packed_size(C)
-    if size <= 0:
-        raise RuntimeError(f"delta projection pack: unsupported C={C}")
-    packed = torch.empty(size, dtype=torch.float16)
-    L.check(lib.cer_delta_proj_pack(ctypes.c_void_p(w.data_ptr()), ctypes.c_void_p(packed.data_ptr()), C), "delta_proj_pack")
-    return packed.to(device)
+    return pack_host(lib.cer_delta_proj_packed_size(C), torch.float16, lambda p: lib.cer_delta_proj_pack(ctypes.c_void_p(w.data_ptr()), p, C),
+                     f"delta projection pack: unsupported C={C}", device)
+
+
+def _delta_outputs(P, device, disp_out, want_delta):
+    """(disp_out - the caller's, or new - , delta [P] or None) of the two delta-head tails."""
+    new = lambda: torch.empty(P, device=device, dtype=torch.float32)
+    return (new() if disp_out is None else disp_out), (new() if want_delta else None)
 
 
 def delta_sum(T, bias, disp_in, h, w, disp_out=None, want_delta=True):
     """T [nhalf,9,P] tap planes -> (disp_out [P], delta [P] or None)."""
     nhalf, _, P = T.shape
-    if disp_out is None:
-        disp_out = torch.empty(P, device=T.device, dtype=torch.float32)
-    delta = torch.empty(P, device=T.device, dtype=torch.float32) if want_delta else None
+    disp_out, delta = _delta_outputs(P, T.device, disp_out, want_delta)
     L.check(L.load().cer_delta_sum_f32(L.dev_ptr(T, "T"), nhalf, float(bias), L.dev_ptr(disp_in, "disp_in"), L.dev_ptr(disp_out, "disp_out"),
                                        L.dev_ptr(delta, "delta"), h, w, L.cur_stream()), "delta_sum")
     return disp_out, delta
@@ -485,9 +481,7 @@ def delta_sum(T, bias, disp_in, h, w, disp_out=None, want_delta=True):
 def delta_tail(hid, w_tap_c, bias, disp_in, h, w, disp_out=None, want_delta=True):
     """hid [P,C]; w_tap_c [9,C]; returns (disp_out [P], delta [P] or None)."""
     P, C = hid.shape
-    if disp_out is None:
-        disp_out = torch.empty(P, device=hid.device, dtype=torch.float32)
-    delta = torch.empty(P, device=hid.device, dtype=torch.float32) if want_delta else None
+    disp_out, delta = _delta_outputs(P, hid.device, disp_out, want_delta)
     L.check(L.load().cer_delta_tail_f32(L.dev_ptr(hid, "hid"), L.dev_ptr(w_tap_c, "w"), float(bias), L.dev_ptr(disp_in, "disp_in"),
                                         L.dev_ptr(disp_out, "disp_out"), L.dev_ptr(delta, "delta"), h, w, C, L.cur_stream()),
             "delta_tail")
@@ -615,22 +609,19 @@ class PackedConvS16:
             raise RuntimeError("conv3x3_s16: cannot scale these weights / sources (one source's weights are too small next to another's "
                                "for a shared split-f16 scale); use gru_precision='f16x3'")
 
+        shape = (Cout, Cin, self.ch, self.kind, self.log2sx, n)
+        form = 4 if self.corr_fp8 == 6 else 2 if self.corr_fp8 else 0
+
         def pack(collapsed):
-            size = lib.cer_conv3x3_s16_packed_size(Cout, self.ch, self.kind, n, collapsed)
-            if size <= 0:
-                raise RuntimeError(f"conv3x3_s16 pack: unsupported shape Cout={Cout} sources={sources}")
-            t = torch.empty(size, dtype=torch.float16)
-            L.check(lib.cer_conv3x3_s16_pack(wp, ctypes.c_void_p(t.data_ptr()), Cout, Cin, self.ch, self.kind, self.log2sx, n,
-                                             collapsed | (4 if self.corr_fp8 == 6 else 2 if self.corr_fp8 else 0), self.log2S), "conv3x3_s16_pack")
-            return t.to(device)
+            return pack_host(lib.cer_conv3x3_s16_packed_size(Cout, self.ch, self.kind, n, collapsed), torch.float16,
+                             lambda p: lib.cer_conv3x3_s16_pack(wp, p, *shape, collapsed | form, self.log2S),
+                             f"conv3x3_s16 pack: unsupported shape Cout={Cout} sources={sources}", device)
         self.packed = pack(0)
         self.packed_c, self.edge = None, None
         if any(k == 1 for _, k, _ in sources):
             self.packed_c = pack(1)
-            edge = torch.empty(lib.cer_conv3x3_s16_edge_size(Cout), dtype=torch.float16)
-            L.check(lib.cer_conv3x3_s16_edge_pack(wp, ctypes.c_void_p(edge.data_ptr()), Cout, Cin, self.ch, self.kind, self.log2sx, n, self.log2S),
-                    "conv3x3_s16_edge_pack")
-            self.edge = edge.to(device)
+            self.edge = pack_host(lib.cer_conv3x3_s16_edge_size(Cout), torch.float16, lambda p: lib.cer_conv3x3_s16_edge_pack(wp, p, *shape, self.log2S),
+                                  f"conv3x3_s16 edge pack: unsupported Cout={Cout}", device)
         self.bias = None if bias is None else bias.detach().to(device, torch.float32).contiguous()
         self.cout = Cout
 
@@ -640,13 +631,11 @@ def delta_proj_pack_s16(w2, device):
     lib = L.load()
     w = w2.detach().to("cpu", torch.float32).contiguous()
     C = w.shape[1]
-    size = lib.cer_delta_proj_s16_packed_size(C)
-    if size <= 0:
-        raise RuntimeError(f"delta projection pack: unsupported C={C}")
-    packed = torch.empty(size, dtype=torch.float16)
     log2s = ctypes.c_int(0)
-    L.check(lib.cer_delta_proj_s16_pack(ctypes.c_void_p(w.data_ptr()), ctypes.c_void_p(packed.data_ptr()), C, ctypes.byref(log2s)), "delta_proj_s16_pack")
-    return packed.to(device), log2s.value
+    packed = pack_host(lib.cer_delta_proj_s16_packed_size(C), torch.float16,
+                       lambda p: lib.cer_delta_proj_s16_pack(ctypes.c_void_p(w.data_ptr()), p, C, ctypes.byref(log2s)),
+                       f"delta projection pack: unsupported C={C}", device)
+    return packed, log2s.value
 
 
 TILE_MT = 0              # 0: let the library choose the tile height; tests force 3 / 4 / 5
@@ -662,15 +651,10 @@ def conv3x3_s16(pc, srcs, h, w, epi, out=None, out2=None, aux=None, aux2=None, i
     aux = (packed projection, log2 scale); ``init``: acc32."""
     dev = srcs[0].device
     P, PP = h * w, s16_pixels(h, w)
-    ci = L.ConvInputs()
-    ci.nsrc = len(srcs)
     for i, (t, (c, k, _)) in enumerate(zip(srcs, pc.sources)):
         if t.numel() != (P if k == 1 else PP * c):
             raise ValueError(f"conv3x3_s16: source {i} has {t.numel()} elements, expected {(P if k == 1 else PP * c)}")
-        ci.src[i] = t.data_ptr()
-        L.dev_ptr(t, f"src{i}")
-        ci.ch[i] = c
-        ci.kind[i] = k
+    ci = _conv_inputs(srcs, pc.sources)
     oc = pc.cout // 2 if epi == L.EPI_GATES else pc.cout
     if epi == L.EPI_DELTA:
         aux, log2s_aux = aux
@@ -795,10 +779,7 @@ def image_prep(img, rescale=1, crop=None, out=None, bgr=False):
             raise ValueError("image_prep: bgr is for the uint8 form")
         H0, W0 = int(img.shape[1]), int(img.shape[2])
     H2, W2, y0, x0, H, W = prep_geometry(H0, W0, rescale, crop)
-    if out is None:
-        out = torch.empty(3, H, W, device=img.device, dtype=torch.float32)
-    elif tuple(out.shape) != (3, H, W) or out.device != img.device:
-        raise RuntimeError(f"image_prep: out must be [3,{H},{W}] on {img.device}")
+    out = _given_or_new(out, (3, H, W), torch.float32, img.device, f"image_prep: out must be [3,{H},{W}]", exact=True)
     lib = L.load()
     if u8:
         L.check(lib.cer_image_prep_u8(L.dev_ptr(img, "img", torch.uint8), L.dev_ptr(out, "out"), H0, W0, H2, W2, y0, x0, H, W, int(bool(bgr)),
@@ -815,10 +796,7 @@ def feat_ref_rows(slot, h, w, border=2, out=None):
     Pb = (h + 2 * border) * (w + 2 * border)
     if slot.numel() != Pb * 128:
         raise RuntimeError(f"feat_ref_rows: the block must hold {Pb} x 128 halves")
-    if out is None:
-        out = torch.empty(h * w, 128, device=slot.device, dtype=torch.float16)
-    elif out.numel() != h * w * 128 or out.device != slot.device:
-        raise RuntimeError(f"feat_ref_rows: out must hold {h * w} x 128 halves on {slot.device}")
+    out = _given_or_new(out, (h * w, 128), torch.float16, slot.device, f"feat_ref_rows: out must hold {h * w} x 128 halves")
     L.check(L.load().cer_feat_ref_rows_f16(L.dev_ptr(slot, "slot", torch.float16), L.dev_ptr(out, "out", torch.float16), h, w, border,
                                            L.cur_stream()), "feat_ref_rows")
     return out
@@ -827,9 +805,6 @@ def feat_ref_rows(slot, h, w, border=2, out=None):
 def disp_to_depth(disp, out=None):
     """``inference.disp_to_depth`` on the device: float32 disparity (any shape, dense) -> depth, 0 where the disparity is 0, else the correctly
     rounded 1 / d - the host function's bits.  ``out``: where to write (a slice of a depth stack), same number of elements."""
-    if out is None:
-        out = torch.empty_like(disp)
-    elif out.numel() != disp.numel() or out.device != disp.device:
-        raise RuntimeError(f"disp_to_depth: out must hold {disp.numel()} floats on {disp.device}")
+    out = _given_or_new(out, disp.shape, torch.float32, disp.device, f"disp_to_depth: out must hold {disp.numel()} floats")
     L.check(L.load().cer_disp_to_depth_f32(L.dev_ptr(disp, "disp"), L.dev_ptr(out, "out"), disp.numel(), L.cur_stream()), "disp_to_depth")
     return out

@@ -392,9 +392,8 @@ class RAFT(nn.Module):
         """A single-GPU forward with V source views takes the direct-split path: every stage builds its volume on the epipolar-line
         tiles, so the feature head writes the cost volume's split-f16 operand planes itself (encoder_hip.features_split) - no fp32
         feature maps, no feat_split pass.  Otherwise the plain ``encode`` applies."""
-        from . import _lib as L
-        return bool(self.view_group is None and V >= 1 and self._hip_encoders() and self.dim_fmap == 64
-                    and L.load().cer_cost_build_algo(-1) != 1 and all(D_ <= 64 for D_, _, _ in self.stages())
+        return bool(self.view_group is None and V >= 1 and self._hip_encoders()
+                    and all(ops.on_line_tiles(self.dim_fmap, D_) for D_, _, _ in self.stages())
                     and self._get_engines(dev)[1].supports_split_head())
 
     def supports_cached(self, dev):
@@ -484,7 +483,6 @@ class RAFT(nn.Module):
         What the encoders produced: ``net_l``, ``inp_l`` (context), ``f1`` / ``f2`` (fp32 reference / bordered source rows of this rank's
         ``views``) or ``split`` (the same as split-f16 operand planes with a view -> block map; None: formed here when a stage needs them).
         The geometry: ``Pij`` of ``views`` (this rank's, of V in all), the zeroed ``disp`` [h*w] that the stages update in place."""
-        from . import _lib as L
         ub = self.update_block
         dev = disp.device
         if ub.conv_mode == "s16":
@@ -500,7 +498,7 @@ class RAFT(nn.Module):
         # (only when the epipolar-line-tile kernel will run for some stage: cer_feat_split_f16 is what raises overflow bit 1, and a
         # forward on the fp32 walk - cer_cost_build_algo(1), the remedy the overflow error names - must not be able to raise it)
         if split is None:
-            lines = (views and self.dim_fmap == 64 and L.load().cer_cost_build_algo(-1) != 1 and any(D_ <= 64 for D_, _, _ in self.stages()))
+            lines = views and any(ops.on_line_tiles(self.dim_fmap, D_) for D_, _, _ in self.stages())
             split = (ops.feat_split(f1), ops.feat_split(f2)) if lines else None
 
         hoisted_all = ub.hoist_all(inp_l, h, w, len(self.cascade))

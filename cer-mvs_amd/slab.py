@@ -338,11 +338,10 @@ def sharded_forward(model, images, poses, intrinsics, scale, ex):
     # step of the cost volume) is in flight while the rank encodes the reference view and the context map
     st = {}
     send = []
-    lib = L.load()
     # cost volume on the epipolar-line-tile kernel (C = 64, D <= 64): every rank splits ITS views' rows to f16 hi|lo (same bytes)
     # and the all-gather lands them in one persistent [G, vmax, Pb, 128] buffer that the kernel reads through a view -> block map -
     # no per-view reassembly copies, no fresh 333 MB buffer per forward.  Otherwise (fp32 walk): gather fp32 rows and reorder.
-    lines = C == 64 and all(D <= 64 for D, _, _ in model.stages()) and lib.cer_cost_build_algo(-1) != 1
+    lines = all(ops.on_line_tiles(C, D) for D, _, _ in model.stages())
     pads = getattr(model, "_slab_pads", None)
     if pads is None:
         pads = model._slab_pads = {}

@@ -82,7 +82,6 @@ class _S16Loop:
     whole m-tiles (ops.s16_pixels).  PackedConvS16 raises when the weights of one conv do not fit a shared scale (cer_conv3x3_s16_scale): RAFT
     sees that error when it builds the loops and switches ``conv_mode`` to "f16x3" (with a warning)."""
 
-    CHECK_OVERFLOW = True       # scan the ReLU-class activation tensors for saturation once per stage (ops.check_overflow reads the flag)
     # the disparity update of iteration i (the 18-tap gather of the fused delta head's tap planes, ``ops.delta_sum``) rides on the lookup launch of
     # iteration i + 1 (csrc/lookup.hip, round 5): one launch less per iteration; the last iteration of a stage ends with the stand-alone kernel.
     # Off where something reads ``disp`` between two iterations (the row-slab exchange: ``run(after=...)``).
@@ -102,8 +101,7 @@ class _S16Loop:
 
     def hoist(self, inp_l, h, w):         # (the results are in the acc32 layout: they seed the accumulators of the loop's convs)
         inp_s = ops.to_frag16(inp_l, h, w, L.S16_RELU)
-        if self.CHECK_OVERFLOW:
-            ops.scan_overflow(inp_s)
+        ops.scan_overflow(inp_s)              # (a ReLU-class tensor: saturation must not be silent, see ``finish``)
         return (ops.conv3x3_s16(self.zr_inp, [inp_s], h, w, L.EPI_LINEAR), ops.conv3x3_s16(self.q_inp, [inp_s], h, w, L.EPI_LINEAR))
 
     def prepare_net(self, net_l, h, w):
@@ -144,8 +142,7 @@ class _S16Loop:
     def finish(self, ws):       # after a stage's last iteration
         # the s16 layouts clamp ReLU-class activations beyond 4094 (65504 / 2^4): saturation must not be silent - scan what the last
         # iteration left in memory (~8 us; the delta head's hidden map is checked inside its kernel, c1 by the lookup kernel since round 5)
-        if self.CHECK_OVERFLOW:
-            ops.scan_overflow(ws["c2"])
+        ops.scan_overflow(ws["c2"])
 
     def rows(self, h, w):       # row mover of the m-tile-major hidden state for the slab exchange
         return lambda t, flat, y0, nr, to_t: ops.s16_rows(t, flat, h, w, y0, nr, to_t)
@@ -193,23 +190,27 @@ class _WideLoop:
 
     def step(self, vol, origin, net_l, disp, hoisted, h, w, D, incre, ws, delta="now"):
         hzr, hq = hoisted
-        if self.mode == "fp32":
-            # corr2, z|r and q on the f16x3 kernel: what this form has always launched; the hoisted term and the delta head in exact fp32
-            ops.lookup_encode(vol, origin, disp, self.w0t, self.b0, D, incre, self.num_levels, self.radius, out=ws["c1"])
-            ops.conv3x3(self.corr2, [ws["c1"]], h, w, L.EPI_RELU, mode="f16x3", out=ws["c2"])
-            ops.conv3x3(self.zr, [net_l, disp, ws["c2"]], h, w, L.EPI_GATES, mode="f16x3", out=ws["z"], out2=ws["rn"], aux=net_l, init=hzr)
-            ops.conv3x3(self.q, [ws["rn"], disp, ws["c2"]], h, w, L.EPI_GRU, mode="f16x3", out=net_l, aux=net_l, aux2=ws["z"], init=hq)
-            ops.conv3x3(self.d1, [net_l], h, w, L.EPI_RELU, mode="fp32", out=ws["hid"])
-            ops.delta_tail(ws["hid"], self.d2w, self.d2b, disp, h, w, disp_out=disp, want_delta=False)
-            return
-        ops.lookup_encode(vol, origin, disp, self.w0t, self.b0, D, incre, self.num_levels, self.radius, out=ws["c1"], out_split=True)
-        ops.conv3x3(self.corr2, [ws["c1"]], h, w, L.EPI_RELU, mode="f16x3", out=ws["c2"], kinds=[3], out_split=True)
+        # corr2, z|r and q run on the f16x3 kernel in both modes: what the "fp32" form has always launched (its hoisted term and its delta
+        # head are the exact fp32 ones).  f16x3: the loop's tensors are in the split32 layout (kind 3 sources, split results)
+        split = self.mode == "f16x3"
+        one, three = ([3], [3, 1, 3]) if split else (None, None)      # source kinds of the one- and the three-source convs
+        ops.lookup_encode(vol, origin, disp, self.w0t, self.b0, D, incre, self.num_levels, self.radius, out=ws["c1"], out_split=split)
+        ops.conv3x3(self.corr2, [ws["c1"]], h, w, L.EPI_RELU, mode="f16x3", out=ws["c2"], kinds=one, out_split=split)
         ops.conv3x3(self.zr, [net_l, disp, ws["c2"]], h, w, L.EPI_GATES, mode="f16x3", out=ws["z"], out2=ws["rn"], aux=net_l, init=hzr,
-                    kinds=[3, 1, 3], out_split=True, aux_split=True)
+                    kinds=three, out_split=split, aux_split=split)
         ops.conv3x3(self.q, [ws["rn"], disp, ws["c2"]], h, w, L.EPI_GRU, mode="f16x3", out=net_l, aux=net_l, aux2=ws["z"], init=hq,
-                    kinds=[3, 1, 3], out_split=True, aux_split=True)
-        ops.conv3x3(self.d1, [net_l], h, w, L.EPI_DELTA, mode="f16x3", out=ws["T"], aux=self.d2proj, kinds=[3])
-        ops.delta_sum(ws["T"], self.d2b, disp, h, w, disp_out=disp, want_delta=False)
+                    kinds=three, out_split=split, aux_split=split)
+        self.delta_head(net_l, disp, h, w, buf=ws["T" if split else "hid"], kinds=one, disp_out=disp, want_delta=False)
+
+    def delta_head(self, net_l, disp, h, w, buf=None, kinds=None, disp_out=None, want_delta=True):
+        """delta 3x3 64 -> 256 ReLU, 3x3 256 -> 1, disparity update -> (disp_out, delta or None).  f16x3: the projection rides in the first
+        conv's epilogue (EPI_DELTA: tap planes, summed by ``delta_sum``); fp32: the hidden map, then ``delta_tail``.  ``buf``: where the tap
+        planes / the hidden map go (the loop's workspace; None: a new tensor); ``kinds``: [3] when ``net_l`` is in the split32 layout."""
+        if self.mode == "f16x3":
+            T = ops.conv3x3(self.d1, [net_l], h, w, L.EPI_DELTA, mode="f16x3", out=buf, aux=self.d2proj, kinds=kinds)
+            return ops.delta_sum(T, self.d2b, disp, h, w, disp_out=disp_out, want_delta=want_delta)
+        hid = ops.conv3x3(self.d1, [net_l], h, w, L.EPI_RELU, mode="fp32", out=buf)
+        return ops.delta_tail(hid, self.d2w, self.d2b, disp, h, w, disp_out=disp_out, want_delta=want_delta)
 
     def finish(self, ws):       # (no clamping layouts)
         pass
@@ -369,11 +370,6 @@ class UpdateBlock(nn.Module):
         c2 = ops.conv3x3(p.corr2, [c1], ht, wd, L.EPI_RELU, mode=p.mode)
         z, rn = ops.conv3x3(p.zr, [net_l, inp_l, disp_l, c2], ht, wd, L.EPI_GATES, mode=p.mode, aux=net_l)
         new = ops.conv3x3(p.q, [rn, inp_l, disp_l, c2], ht, wd, L.EPI_GRU, mode=p.mode, aux=net_l, aux2=z)
-        if p.mode == "f16x3":
-            T = ops.conv3x3(p.d1, [new], ht, wd, L.EPI_DELTA, mode="f16x3", aux=p.d2proj)
-            _, delta = ops.delta_sum(T, p.d2b, disp_l, ht, wd)
-        else:
-            hid = ops.conv3x3(p.d1, [new], ht, wd, L.EPI_RELU, mode=p.mode)
-            _, delta = ops.delta_tail(hid, p.d2w, p.d2b, disp_l, ht, wd)
+        _, delta = p.delta_head(new, disp_l, ht, wd)
         net_out = ops.nhwc_to_nchw(new).view(batch, num, ch, ht, wd)
         return net_out, delta.view(batch, num, ht, wd)

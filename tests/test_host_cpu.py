@@ -585,6 +585,39 @@ def test_product_sources_have_no_other_compile_time_switches():
     assert sorted(found) == sorted(PRODUCT_SWITCHES), f"listed but gone: {sorted(set(PRODUCT_SWITCHES) - set(found))}"
 
 
+# Every run-time switch of the kernel faces - a module-level ALL-CAPS name of ops.py, encoder_hip.py or update.py that is assigned a
+# bool, an int or a string and read by the module's code - and the file under tests/, tools/ (not tools/archive) or bench.py that sets
+# it.  A switch that nothing sets guards a branch that ships and never runs: it is folded, not listed ("Run-time switches").
+FACE_SWITCHES = {
+    ("ops.py", "COLLAPSE_DISP"): "tests/test_hip_parity.py",
+    ("ops.py", "EDGE_CORRECT"): "tests/test_conv_s16_gpu.py",
+    ("ops.py", "TILE_MT"): "tests/test_conv_s16_gpu.py",
+    ("encoder_hip.py", "ENGINE"): "tests/test_encoder_parity_gpu.py",
+    ("update.py", "USE_PLANS"): "bench.py",
+    ("update.py", "ALIAS_RN_C1"): "tests/test_conv_s16_gpu.py",
+}
+
+
+def test_every_switch_of_the_kernel_faces_has_a_writer():
+    import ast
+    found = set()
+    for module in ("ops.py", "encoder_hip.py", "update.py"):
+        tree = ast.parse(open(os.path.join(REPO, "cer-mvs_amd", module)).read())
+        read = {n.id for n in ast.walk(tree) if isinstance(n, ast.Name) and isinstance(n.ctx, ast.Load)}
+        for node in tree.body:
+            if (isinstance(node, ast.Assign) and len(node.targets) == 1 and isinstance(node.targets[0], ast.Name)
+                    and isinstance(node.value, ast.Constant) and isinstance(node.value.value, (bool, int, str))):
+                name = node.targets[0].id
+                if re.fullmatch(r"[A-Z][A-Z0-9_]*", name) and name in read:
+                    found.add((module, name))
+    assert found == set(FACE_SWITCHES), (f"switches without a listed writer: {sorted(found - set(FACE_SWITCHES))}; "
+                                         f"listed but gone: {sorted(set(FACE_SWITCHES) - found)}")
+    for (module, name), writer in FACE_SWITCHES.items():
+        assert writer == "bench.py" or (writer.split("/")[0] in ("tests", "tools") and not writer.startswith("tools/archive")), writer
+        text = open(os.path.join(REPO, writer)).read()
+        assert re.search(r"\.%s\b[^=\n]*=[^=]|setattr\(\w+, \"%s\"" % (name, name), text), f"{writer} does not set {module[:-3]}.{name}"
+
+
 def test_product_package_reads_one_environment_variable():
     """The A/B switches of the Python layer are settled and folded: the package reads CER_MVS_LIB (which library to load)
     and nothing else from the environment.  A read this test cannot name (a computed key, os.environ passed on whole) fails it as well."""

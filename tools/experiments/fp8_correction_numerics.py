@@ -122,7 +122,7 @@ def conv_mode(x, w, b, MODE, **kw):
 
 
 MODES = ("fp32", "f16x3", "fp8c", "fp6c", "fp6j")
-PER_CONV_MODES = ()
+PER_CONV_FORMS = ()
 PER_CONV_OTHERS = ("fp8c",)
 
 
@@ -155,7 +155,7 @@ def main():
     O.F.conv2d = conv_emul
     try:
         for others in PER_CONV_OTHERS:
-            for mode in PER_CONV_MODES:
+            for mode in PER_CONV_FORMS:
                 for shape in ((64, 64), (64, 241), (256, 64), (1, 256)):
                     ONLY, MODE, OTHERS = shape, mode, others
                     with torch.no_grad():

@@ -21,7 +21,8 @@ forward (no untraced forward: it would be the first calibration input); c e2e_cf
 walk); e encoder_backend="miopen"; f encoder_type="LR" on e2e_lr; g aggregation=("mean", "max"), the literal path; h forward_cached
 on a three-image store, equal to the ordinary forward of the same stack (recorded as well); i slab.sharded_forward on
 slab.LocalExchange(2) at e2e_cfg1's size; j overflow_policy="raise"; k forward_train, train_backend "torch" and "hip" (digest over the
-concatenated predictions)."""
+concatenated predictions); l ``encoder_hip.ENGINE = "tiled"`` around a default forward and around ``HipEncoder.forward_nchw`` of fnet
+and cnet (digest over the three results); m gru_precision="f16x3"; n gru_precision="fp32" (l - n on e2e_tiny)."""
 import argparse
 import ctypes
 import hashlib
@@ -69,7 +70,7 @@ def digest(out):
 def configurations(golden_dir, only):
     """name -> (build, inputs, warm): ``build()`` returns run(input) -> tensor(s); ``inputs``: what the forwards are run on"""
     import torch
-    from cer_mvs_amd import RAFT, ops, slab
+    from cer_mvs_amd import RAFT, encoder_hip, ops, slab
     from cer_mvs_amd.synthetic import fill_state_dict, synthetic_scene
     from cer_mvs_amd.update import UpdateBlock
     dev = torch.device("cuda", 0)
@@ -131,6 +132,22 @@ def configurations(golden_dir, only):
             return lambda s: slab.sharded_forward(m, s[0], s[1], s[2], s[3], ex)
         return build, g
 
+    def tiled():
+        g, cascade = fixture("e2e_tiny")
+
+        def build():
+            m = model(g, cascade, gru_precision="s16f8")
+
+            def run(s):
+                prev, encoder_hip.ENGINE = encoder_hip.ENGINE, "tiled"
+                try:
+                    x = s[0][0].float() * (2 / 255.0) - 1
+                    return [m(*s[:3], scale=s[3])] + [encoder_hip.HipEncoder(net, dev).forward_nchw(x) for net in (m.fnet, m.cnet)]
+                finally:
+                    encoder_hip.ENGINE = prev
+            return run
+        return build, g
+
     def train(backend):
         g, cascade = fixture("train_tiny")
 
@@ -152,6 +169,9 @@ def configurations(golden_dir, only):
         "j": (*plain("e2e_tiny", gru_precision="s16f8", policy="raise"), None, True),
         "k_torch": (*train("torch"), None, True),
         "k_hip": (*train("hip"), None, True),
+        "l": (*tiled(), None, True),
+        "m": (*plain("e2e_tiny", gru_precision="f16x3"), None, True),
+        "n": (*plain("e2e_tiny", gru_precision="fp32"), None, True),
     }
     for name, (build, g, seeds, warm) in table.items():
         if only and name.split("_")[0] not in only:
