@@ -8,7 +8,9 @@ bound, decided equal or provably undecidable; the image preparation from torch's
 comparison of the multires kernels - ``bits_equal``), and by tests/test_wide_parity_{cpu,gpu}.py (the wide-range loop: the float64 pieces
 of one GRU iteration, which tests/test_fullsize_parity_gpu.py shares, the ``wide_*`` references and bounds, the split32 layout in numpy).
 The last section - the cost volume from restated fp32 coordinates (``fma32``, ``cost_coords32``, ``cost_samples_ref64``, ``cost_rows_ref64``,
-``cost_bound``) - serves tests/test_cost_geometry_{cpu,gpu}.py.
+``cost_bound``) - serves tests/test_cost_geometry_{cpu,gpu}.py.  ``loop_ref64`` chains the update-loop pieces into T whole iterations
+(hidden state and disparity after each): the float64 anchor of tests/test_update_run_gpu.py, which holds the three execution protocols
+of ``UpdateBlock.run`` to identical bits; tests/test_update_run_cpu.py checks it against the oracle evaluated in float64.
 Plain module, no fixtures.
 
 Conventions: an image tensor is pixel-major, ``[h*w, C]`` or ``[h*w]``; a *tile* is a (rows, columns) block of pixels - 8 x 16 by
@@ -1183,6 +1185,35 @@ def lookup_ref(vol, origin, disp, w0t, b0, D, incre, L=3, r=5):
         step = (row[:, 1:] - row[:, :-1]).abs().max(1).values                     # largest |v[i+1] - v[i]| of the row, zero border included
         idx += (dt / 2 ** l * step)[:, None] * w0t[l * (2 * r + 1):(l + 1) * (2 * r + 1)].abs().sum(0)[None]
     return ref, mag, idx
+
+
+def loop_ref64(iters, vol, origin, net, disp, inp, g, D, incre, h, w, L=3, r=5):
+    """``iters`` iterations of the update step (``_S16Loop.step`` / ``_WideLoop.step`` with delta="now"; core/update.py:87-120, 17-25) in
+    float64, from the values the device holds at the start: vol [P, >= D] level-0 rows, origin, disp [P], net, inp [P, 64] (the hidden state
+    read back through its layout's inverse), all float64; ``g``: ``update._stage_weights(ub, stage, "cpu")``.  One iteration is
+    ``lookup_ref`` -> relu(corr2) -> sigmoid(z | r) over net | inp | ``disp_feature_parts`` | corr -> tanh(q) over r*net | ... -> the GRU
+    blend -> relu(delta1) projected per channel half and tap, summed by ``delta_sum64``.  -> [(net, disp) after iteration 0, 1, ...]."""
+    d = lambda t: t.detach().cpu().double()
+    w0t, b0 = d(g.w0t), d(g.b0)
+    wc, bc = d(g.corr2.weight), d(g.corr2.bias)
+    wzr, bzr, wq, bq = d(g.wzr), d(g.bzr), d(g.wq), d(g.bq)
+    w1, b1 = d(g.delta1.weight), d(g.delta1.bias)
+    proj = d(g.delta2.weight)[0].reshape(-1, 128, 9)                               # [half, channel, tap]
+    net, disp, inp, vol, origin = net.double(), disp.double(), inp.double(), vol.double(), origin.double()
+    out = []
+    for _ in range(iters):
+        c1 = lookup_ref(vol, origin, disp, w0t, b0, D, incre, L, r)[0]
+        c2 = torch.relu(conv64(c1, wc, h, w) + bc)
+        feat = disp_feature_parts(disp, h, w)[0]
+        zr = torch.sigmoid(conv64(torch.cat([net, inp, feat, c2], 1), wzr, h, w) + bzr)
+        z, rr = zr[:, :64], zr[:, 64:]
+        q = torch.tanh(conv64(torch.cat([rr * net, inp, feat, c2], 1), wq, h, w) + bq)
+        net = (1 - z) * net + z * q
+        hid = torch.relu(conv64(net, w1, h, w) + b1)
+        T = torch.stack([(hid[:, hf * 128:(hf + 1) * 128] @ proj[hf]).t() for hf in range(proj.shape[0])], 0)      # [nhalf, 9, P]
+        disp = delta_sum64(T, g.d2b, disp, h, w)[0]
+        out.append((net, disp))
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ the wide-range loop (_WideLoop)
