@@ -9,7 +9,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CER_MVS_LIB") or os.path.join(_HERE, "csrc", "libcermvs.so")
-ABI_VERSION = 1160
+ABI_VERSION = 1170
 CONV_MAX_SRC = 4
 EPI_LINEAR, EPI_RELU, EPI_GATES, EPI_GRU, EPI_DELTA = 0, 1, 2, 3, 4
 EPI_OUT_SPLIT, EPI_AUX_SPLIT = 0x100, 0x200       # cer_mvs.h: split32 activation layout flags, or-ed into `epi`
@@ -142,6 +142,11 @@ _SIGNATURES = {
     "cer_cloud_pair_moments_f64": (_I, [_P, _P, _P, _L, _c.POINTER(_D), _P, _P, _P]),
     "cer_cloud_plane_moment_partials": (_L, [_L]),
     "cer_cloud_plane_moments_f64": (_I, [_P, _P, _P, _P, _L, _c.POINTER(_D), _P, _P, _P]),
+    "cer_mesh_partials": (_L, [_I, _I, _I]),
+    "cer_tsdf_integrate_f32": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _c.POINTER(_D), _D, _I, _I, _I, _D, _P, _P, _P]),
+    "cer_mesh_cells_u16": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    "cer_mesh_count": (_I, [_P, _I, _I, _I, _P, _P, _P, _P]),
+    "cer_mesh_emit_f32": (_I, [_P, _P, _c.POINTER(_D), _D, _I, _I, _I, _P, _LL, _LL, _LL, _LL, _P, _P, _P, _P]),
 }
 
 # include/cer_mvs_variants.h: exported by csrc/variants/libcermvs_optin.so only (round 4's opt-in kernel forms; CER_MVS_LIB selects the library)

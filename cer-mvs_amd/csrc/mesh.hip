@@ -1,0 +1,363 @@
+// Surface mesh of a fused scan on the device (cer-mvs_amd/mesh.py, scan.py reconstruct_scan(mesh=...)): the fused depth maps
+// integrated into a dense volume of truncated signed distances (one value and one count per NODE of a regular grid), and marching tetrahedra
+// on that volume - the Kuhn split of every cell into the six tetrahedra around its 0-7 diagonal.
+//
+// Order: a vertex lives on a lattice edge (node a, d = 1..7 as a bit vector, from a to a + d) and has the slot node_index * 8 + d; a face has
+// the slot (cell_index * 6 + tet) * 2 + s.  Every slot is a 0/1 flag at a fixed position: vertices and faces leave in slot order through
+// compact.hpp's count / scan / emit, twice.  No atomics, no output cursor: the same bytes on every run, whatever the schedule.
+//
+// All coordinate arithmetic is fp64 with every association written out and no fused multiply-add (-ffp-contract=off): tests/mesh_reference.py
+// restates it in numpy and the GPU tests compare bits.
+#include "common.hpp"
+#include "compact.hpp"
+
+#define MESH_TILE CER_MESH_TILE                      // slots per block of the count and emit passes
+#define MESH_ITER (MESH_TILE / 256)
+
+// ---- the case table, derived (not copied): for tet t and the 4-bit mask of its inside corners in listing order, the number of triangles and
+// up to six lattice edges, 6 bits each: (lower corner << 3) | d.  Triangle s takes edges 3 s .. 3 s + 2.
+struct MeshTable {
+    unsigned long long tri[6][16];                   // bits 0-35: six edge codes; bits 36-37: the number of triangles
+    unsigned short corners[6];                       // the tet's four corners in listing order, 3 bits each
+};
+
+constexpr int MESH_TETS[6][4] = {{0, 1, 3, 7}, {0, 3, 2, 7}, {0, 2, 6, 7}, {0, 6, 4, 7}, {0, 4, 5, 7}, {0, 5, 1, 7}};
+
+constexpr int mesh_axis(int corner, int a) { return (corner >> a) & 1; }
+// the integer determinant of [B - A, C - A, D - A] on corner offsets
+constexpr int mesh_det(int A, int B, int C, int D) {
+    const int u[3] = {mesh_axis(B, 0) - mesh_axis(A, 0), mesh_axis(B, 1) - mesh_axis(A, 1), mesh_axis(B, 2) - mesh_axis(A, 2)};
+    const int v[3] = {mesh_axis(C, 0) - mesh_axis(A, 0), mesh_axis(C, 1) - mesh_axis(A, 1), mesh_axis(C, 2) - mesh_axis(A, 2)};
+    const int w[3] = {mesh_axis(D, 0) - mesh_axis(A, 0), mesh_axis(D, 1) - mesh_axis(A, 1), mesh_axis(D, 2) - mesh_axis(A, 2)};
+    return u[0] * (v[1] * w[2] - v[2] * w[1]) - u[1] * (v[0] * w[2] - v[2] * w[0]) + u[2] * (v[0] * w[1] - v[1] * w[0]);
+}
+// the lattice edge between corners X and Y of a Kuhn tet: one is the other plus a bit vector
+constexpr unsigned long long mesh_edge(int X, int Y) { return (unsigned long long)(((X & Y) << 3) | (X ^ Y)); }
+constexpr unsigned long long mesh_pack3(unsigned long long e0, unsigned long long e1, unsigned long long e2, bool swap) {
+    return swap ? (e0 | e2 << 6 | e1 << 12) : (e0 | e1 << 6 | e2 << 12);
+}
+constexpr MeshTable mesh_make_table() {
+    MeshTable T = {};
+    for (int t = 0; t < 6; ++t) {
+        T.corners[t] = (unsigned short)(MESH_TETS[t][0] | MESH_TETS[t][1] << 3 | MESH_TETS[t][2] << 6 | MESH_TETS[t][3] << 9);
+        for (int m = 0; m < 16; ++m) {
+            int ins[4] = {}, out[4] = {}, ni = 0, no = 0;
+            for (int l = 0; l < 4; ++l) {
+                if ((m >> l) & 1) ins[ni++] = MESH_TETS[t][l];
+                else out[no++] = MESH_TETS[t][l];
+            }
+            unsigned long long code = 0;
+            if (ni == 1) {
+                const int A = ins[0], B = out[0], C = out[1], D = out[2];
+                code = mesh_pack3(mesh_edge(A, B), mesh_edge(A, C), mesh_edge(A, D), mesh_det(A, B, C, D) < 0) | 1ull << 36;
+            } else if (ni == 3) {
+                const int A = out[0], B = ins[0], C = ins[1], D = ins[2];
+                code = mesh_pack3(mesh_edge(A, B), mesh_edge(A, C), mesh_edge(A, D), mesh_det(A, B, C, D) > 0) | 1ull << 36;
+            } else if (ni == 2) {
+                const int A = ins[0], B = ins[1], C = out[0], D = out[1];
+                const bool swap = mesh_det(A, B, C, D) < 0;
+                const unsigned long long q0 = mesh_edge(A, C), q1 = mesh_edge(A, D), q2 = mesh_edge(B, D), q3 = mesh_edge(B, C);
+                code = mesh_pack3(q0, q1, q2, swap) | mesh_pack3(q0, q2, q3, swap) << 18 | 2ull << 36;
+            }
+            T.tri[t][m] = code;
+        }
+    }
+    return T;
+}
+__constant__ MeshTable mesh_table = mesh_make_table();
+
+struct MeshGrid {
+    double ox, oy, oz, voxel;
+    int nx, ny, nz;
+};
+
+// ---- integration: one thread owns a node for the whole view loop, x along the lanes.  cams: per view CER_CLOUD_CAM_DOUBLES doubles =
+// K [9] | rows 0-2 of E [12] (the float32 matrices promoted on the host): wave-uniform, scalar loads.  views: n_views DEVICE ints.
+__global__ __launch_bounds__(256) void tsdf_integrate_kernel(const float* __restrict__ depths, const unsigned char* __restrict__ masks,
+                                                             const double* __restrict__ cams, int N, int h, int w,
+                                                             const int* __restrict__ views, int n_views, MeshGrid g, double trunc,
+                                                             unsigned nodes, float* __restrict__ tsdf, int* __restrict__ weight) {
+    const unsigned n = blockIdx.x * 256u + threadIdx.x;
+    if (n >= nodes) return;
+    const unsigned row = n / (unsigned)g.nx, i = n - row * (unsigned)g.nx;
+    const unsigned k = row / (unsigned)g.ny, j = row - k * (unsigned)g.ny;
+    const double px = g.ox + (double)i * g.voxel, py = g.oy + (double)j * g.voxel, pz = g.oz + (double)k * g.voxel;
+    const long P = (long)h * w;
+    const double dw = (double)w, dh = (double)h;
+    double sum = 0.0;
+    int cnt = 0;
+    for (int v = 0; v < n_views; ++v) {
+        const int view = views[v];
+        if (view < 0 || view >= N) continue;                             // (uniform; the caller has checked the list: never taken)
+        const double* c = cams + (long)view * CER_CLOUD_CAM_DOUBLES;
+        const double cx = ((c[9] * px + c[10] * py) + c[11] * pz) + c[12];
+        const double cy = ((c[13] * px + c[14] * py) + c[15] * pz) + c[16];
+        const double cz = ((c[17] * px + c[18] * py) + c[19] * pz) + c[20];
+        const double ux = (c[0] * cx + c[1] * cy) + c[2] * cz;
+        const double uy = (c[3] * cx + c[4] * cy) + c[5] * cz;
+        const double uz = (c[6] * cx + c[7] * cy) + c[8] * cz;
+        const double a = ux / uz + 0.5, b = uy / uz + 0.5;
+        if (!(uz > 0.0 && a >= 0.0 && a < dw && b >= 0.0 && b < dh)) continue;       // (NaN fails every comparison)
+        const long p = (long)view * P + (long)(int)floor(b) * w + (int)floor(a);
+        if (masks && masks[p] == 0) continue;
+        const double d = (double)depths[p];
+        if (!(d > 0.0 && d - d == 0.0)) continue;                        // finite and positive
+        const double sdf = d - uz;
+        if (!(sdf >= -trunc)) continue;
+        sum += sdf >= trunc ? 1.0 : sdf / trunc;
+        ++cnt;
+    }
+    weight[n] = cnt;
+    tsdf[n] = cnt ? (float)(sum / (double)cnt) : 1.0f;
+}
+
+// ---- cell pass: cells[cell] = the 8-bit mask of the corners with tsdf < 0 | 0x100 iff all eight corners are valid (weight >= min_weight and
+// a finite tsdf).  Cells are [nz - 1, ny - 1, nx - 1], x fastest.
+__global__ __launch_bounds__(256) void mesh_cells_kernel(const float* __restrict__ tsdf, const int* __restrict__ weight, int nx, int ny,
+                                                         int min_weight, unsigned ncells, unsigned short* __restrict__ cells) {
+    const unsigned c = blockIdx.x * 256u + threadIdx.x;
+    if (c >= ncells) return;
+    const unsigned cx = (unsigned)nx - 1, cy = (unsigned)ny - 1;
+    const unsigned row = c / cx, i = c - row * cx;
+    const unsigned k = row / cy, j = row - k * cy;
+    const long base = ((long)k * ny + j) * nx + i;
+    unsigned m = 0, ok = 1;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const long n = base + (q & 1) + (long)((q >> 1) & 1) * nx + (long)((q >> 2) & 1) * nx * ny;
+        const float f = tsdf[n];
+        ok &= (unsigned)(weight[n] >= min_weight && f - f == 0.0f);
+        m |= (unsigned)(f < 0.0f) << q;
+    }
+    cells[c] = (unsigned short)(m | ok << 8);
+}
+
+struct MeshDims {
+    int nx, ny, nz;
+    long vslots, fslots;                             // nodes * 8, cells * 12
+};
+
+// vertex slot p = node * 8 + d: set iff the endpoints' signs differ and a valid cell contains the edge.  The candidates are the cells that
+// have node a as corner o with o & d == 0 (4 / 2 / 1 of them); in such a cell the other endpoint is corner o | d.
+__device__ __forceinline__ bool mesh_vertex_set(const unsigned short* __restrict__ cells, const MeshDims& D, long p) {
+    if (p >= D.vslots) return false;
+    const unsigned d = (unsigned)p & 7u, n = (unsigned)(p >> 3);
+    if (d == 0) return false;
+    const unsigned row = n / (unsigned)D.nx, i = n - row * (unsigned)D.nx;
+    const unsigned k = row / (unsigned)D.ny, j = row - k * (unsigned)D.ny;
+    bool set = false;
+#pragma unroll
+    for (unsigned o = 0; o < 8; ++o) {
+        if (o & d) continue;
+        const int ci = (int)i - (int)(o & 1), cj = (int)j - (int)((o >> 1) & 1), ck = (int)k - (int)(o >> 2);
+        if (ci < 0 || cj < 0 || ck < 0 || ci > D.nx - 2 || cj > D.ny - 2 || ck > D.nz - 2) continue;
+        const unsigned m = cells[((long)ck * (D.ny - 1) + cj) * (D.nx - 1) + ci];
+        set |= (m >> 8) && (((m >> o) ^ (m >> (o | d))) & 1u);
+    }
+    return set;
+}
+
+// the inside mask of tet t of a cell, in listing order
+__device__ __forceinline__ unsigned mesh_tet_mask(unsigned m, unsigned t) {
+    const unsigned c = mesh_table.corners[t];
+    return ((m >> (c & 7)) & 1u) | ((m >> ((c >> 3) & 7)) & 1u) << 1 | ((m >> ((c >> 6) & 7)) & 1u) << 2 | ((m >> ((c >> 9) & 7)) & 1u) << 3;
+}
+
+// face slot q = (cell * 6 + tet) * 2 + s: set iff the cell is valid and its tet has more than s triangles
+__device__ __forceinline__ bool mesh_face_set(const unsigned short* __restrict__ cells, const MeshDims& D, long q) {
+    if (q >= D.fslots) return false;
+    const long cell = q / 12;
+    const unsigned r = (unsigned)(q - cell * 12);
+    const unsigned m = cells[cell];
+    if (!(m >> 8)) return false;
+    return (r & 1u) < (unsigned)(mesh_table.tri[r >> 1][mesh_tet_mask(m, r >> 1)] >> 36);
+}
+
+// ---- count: grid = vertex blocks then face blocks, one partial each
+__global__ __launch_bounds__(256) void mesh_count_kernel(const unsigned short* __restrict__ cells, MeshDims D, unsigned vblocks,
+                                                         unsigned* __restrict__ partials) {
+    unsigned long long bal[MESH_ITER];
+    const bool faces = blockIdx.x >= vblocks;                            // (uniform)
+    const long seg = compact_seg<MESH_TILE, long>() - (faces ? (long)vblocks * MESH_TILE : 0);
+    const unsigned wave = faces ? compact_ballots(seg, [&](long q) { return mesh_face_set(cells, D, q); }, bal)
+                                : compact_ballots(seg, [&](long p) { return mesh_vertex_set(cells, D, p); }, bal);
+    const unsigned tot = compact_block_total(wave);
+    if (threadIdx.x == 0) partials[blockIdx.x] = tot;
+}
+
+// ---- scan: block 0 the vertex partials -> offsets[0 .. vblocks], totals[0] = nv; block 1 the face partials -> offsets[vblocks + 1 ..],
+// totals[1] = nf
+__global__ __launch_bounds__(1024) void mesh_scan_kernel(const unsigned* __restrict__ partials, long vblocks, long fblocks,
+                                                         long long* __restrict__ offsets, long long* __restrict__ totals) {
+    const bool faces = blockIdx.x != 0;
+    const long long t = compact_scan(partials + (faces ? vblocks : 0), faces ? fblocks : vblocks, offsets + (faces ? vblocks + 1 : 0));
+    if (threadIdx.x == 0) totals[blockIdx.x] = t;
+}
+
+// ---- vertex emit: vmap[slot] = the vertex's output index (written for every set slot: the faces read it), and the position if it is below
+// the caller's capacity: origin + (idx + (d_a ? t : 0)) * voxel per axis with t = f0 / (f0 - f1), rounded ONCE to float32
+__global__ __launch_bounds__(256) void mesh_vertex_emit_kernel(const float* __restrict__ tsdf, const unsigned short* __restrict__ cells,
+                                                               MeshDims D, MeshGrid g, const long long* __restrict__ offsets,
+                                                               long long capacity, int* __restrict__ vmap, float* __restrict__ vertices) {
+    const int lane = threadIdx.x & 63;
+    const long seg = compact_seg<MESH_TILE, long>();
+    unsigned long long bal[MESH_ITER];
+    const unsigned tot = compact_ballots(seg, [&](long p) { return mesh_vertex_set(cells, D, p); }, bal);
+    long long base = compact_wave_base(tot, offsets, blockIdx.x);
+#pragma unroll
+    for (int jj = 0; jj < MESH_ITER; ++jj) {
+        const long p = seg + 64 * jj;
+        const long long idx = base + compact_rank(bal[jj]);
+        base += __popcll(bal[jj]);
+        if (!((bal[jj] >> lane) & 1ull)) continue;
+        vmap[p] = (int)idx;
+        if (idx >= capacity) continue;                                   // (never past what the caller allocated)
+        const unsigned d = (unsigned)p & 7u, n = (unsigned)(p >> 3);
+        const unsigned row = n / (unsigned)D.nx, i = n - row * (unsigned)D.nx;
+        const unsigned k = row / (unsigned)D.ny, j = row - k * (unsigned)D.ny;
+        const long n1 = (long)n + (d & 1) + (long)((d >> 1) & 1) * D.nx + (long)(d >> 2) * D.nx * D.ny;
+        const double f0 = (double)tsdf[n], f1 = (double)tsdf[n1];
+        const double t = f0 / (f0 - f1);
+        float* o = vertices + idx * 3;
+        o[0] = (float)(g.ox + ((double)i + ((d & 1) ? t : 0.0)) * g.voxel);
+        o[1] = (float)(g.oy + ((double)j + ((d & 2) ? t : 0.0)) * g.voxel);
+        o[2] = (float)(g.oz + ((double)k + ((d & 4) ? t : 0.0)) * g.voxel);
+    }
+}
+
+// ---- face emit: the three lattice edges of triangle s of the tet -> their vertex slots -> vmap
+__global__ __launch_bounds__(256) void mesh_face_emit_kernel(const unsigned short* __restrict__ cells, MeshDims D,
+                                                             const long long* __restrict__ offsets, long long capacity,
+                                                             const int* __restrict__ vmap, int* __restrict__ faces) {
+    const int lane = threadIdx.x & 63;
+    const long seg = compact_seg<MESH_TILE, long>();
+    unsigned long long bal[MESH_ITER];
+    const unsigned tot = compact_ballots(seg, [&](long q) { return mesh_face_set(cells, D, q); }, bal);
+    long long base = compact_wave_base(tot, offsets, blockIdx.x);
+#pragma unroll
+    for (int jj = 0; jj < MESH_ITER; ++jj) {
+        const long q = seg + 64 * jj;
+        const long long idx = base + compact_rank(bal[jj]);
+        base += __popcll(bal[jj]);
+        if (!((bal[jj] >> lane) & 1ull) || idx >= capacity) continue;    // (never past what the caller allocated)
+        const long cell = q / 12;
+        const unsigned r = (unsigned)(q - cell * 12);
+        const unsigned cx = (unsigned)D.nx - 1, cy = (unsigned)D.ny - 1;
+        const unsigned row = (unsigned)cell / cx, i = (unsigned)cell - row * cx;
+        const unsigned k = row / cy, j = row - k * cy;
+        const long node = ((long)k * D.ny + j) * D.nx + i;
+        const unsigned long long code = mesh_table.tri[r >> 1][mesh_tet_mask(cells[cell], r >> 1)] >> (18 * (r & 1u));
+        int* o = faces + idx * 3;
+#pragma unroll
+        for (int e = 0; e < 3; ++e) {
+            const unsigned c6 = (unsigned)(code >> (6 * e)) & 63u, a = c6 >> 3;
+            const long na = node + (a & 1) + (long)((a >> 1) & 1) * D.nx + (long)(a >> 2) * D.nx * D.ny;
+            o[e] = vmap[na * 8 + (c6 & 7u)];
+        }
+    }
+}
+
+// ---- host side.  The order of the checks is the documented one (cer_mvs.h): negative sizes, too large, the frame, nothing to do, pointers.
+static bool mesh_is_finite(double v) { return v - v == 0.0; }
+static bool mesh_frame_ok(const double* origin, double voxel) {
+    return origin && mesh_is_finite(origin[0]) && mesh_is_finite(origin[1]) && mesh_is_finite(origin[2]) && mesh_is_finite(voxel) && voxel > 0.0;
+}
+// CER_OK and the node count, or the error of a negative or too large grid
+static int mesh_nodes(int nx, int ny, int nz, long* nodes) {
+    if (nx < 0 || ny < 0 || nz < 0) return CER_EINVAL;
+    *nodes = 0;
+    if (nx == 0 || ny == 0 || nz == 0) return CER_OK;
+    const long lim = 0x7fffffffL - MESH_TILE;                            // nodes < 2^31 - tile
+    if ((long)nx * ny >= lim || (long)nx * ny * nz >= lim) return CER_ESHAPE;
+    *nodes = (long)nx * ny * nz;
+    return CER_OK;
+}
+static MeshDims mesh_dims(int nx, int ny, int nz) {
+    MeshDims D = {nx, ny, nz, (long)nx * ny * nz * 8, (long)(nx - 1) * (ny - 1) * (nz - 1) * 12};
+    return D;
+}
+static long mesh_blocks(long slots) { return (slots + MESH_TILE - 1) / MESH_TILE; }
+
+extern "C" long cer_mesh_partials(int nx, int ny, int nz) {
+    long nodes = 0;
+    const int rc = mesh_nodes(nx, ny, nz, &nodes);
+    if (rc != CER_OK) return rc;
+    if (nodes == 0 || nx == 1 || ny == 1 || nz == 1) return 0;
+    const MeshDims D = mesh_dims(nx, ny, nz);
+    return mesh_blocks(D.vslots) + mesh_blocks(D.fslots);
+}
+
+extern "C" int cer_tsdf_integrate_f32(const float* depths, const unsigned char* masks, const double* cams, int N, int h, int w,
+                                      const int* views, int n_views, const double* origin, double voxel, int nx, int ny, int nz,
+                                      double trunc, float* tsdf, int* weight, void* stream) {
+    long nodes = 0;
+    if (N < 0 || h < 0 || w < 0 || n_views < 0) return CER_EINVAL;
+    const int rc = mesh_nodes(nx, ny, nz, &nodes);
+    if (rc != CER_OK) return rc;
+    if ((long)h * w > 0x7fffffffL) return CER_ESHAPE;
+    if (!mesh_frame_ok(origin, voxel) || !(mesh_is_finite(trunc) && trunc > 0.0)) return CER_EINVAL;
+    if (nodes == 0 || n_views == 0) return CER_OK;                       // (no views: weight 0 and tsdf 1 are the caller's to fill)
+    if (!depths || !cams || !views || !tsdf || !weight || N == 0 || h == 0 || w == 0) return CER_EINVAL;
+    const MeshGrid g = {origin[0], origin[1], origin[2], voxel, nx, ny, nz};
+    hipLaunchKernelGGL(tsdf_integrate_kernel, dim3((unsigned)((nodes + 255) / 256)), dim3(256), 0, (hipStream_t)stream, depths, masks, cams, N,
+                       h, w, views, n_views, g, trunc, (unsigned)nodes, tsdf, weight);
+    CER_RETURN_IF_LAUNCH_FAILED();
+    return CER_OK;
+}
+
+extern "C" int cer_mesh_cells_u16(const float* tsdf, const int* weight, int nx, int ny, int nz, int min_weight, unsigned short* cells,
+                                  void* stream) {
+    long nodes = 0;
+    const int rc = mesh_nodes(nx, ny, nz, &nodes);
+    if (rc != CER_OK) return rc;
+    if (nodes == 0 || nx == 1 || ny == 1 || nz == 1) return CER_OK;
+    if (!tsdf || !weight || !cells) return CER_EINVAL;
+    const long ncells = (long)(nx - 1) * (ny - 1) * (nz - 1);
+    hipLaunchKernelGGL(mesh_cells_kernel, dim3((unsigned)((ncells + 255) / 256)), dim3(256), 0, (hipStream_t)stream, tsdf, weight, nx, ny,
+                       min_weight, (unsigned)ncells, cells);
+    CER_RETURN_IF_LAUNCH_FAILED();
+    return CER_OK;
+}
+
+extern "C" int cer_mesh_count(const unsigned short* cells, int nx, int ny, int nz, unsigned int* partials, long long* offsets,
+                              long long* totals, void* stream) {
+    long nodes = 0;
+    const int rc = mesh_nodes(nx, ny, nz, &nodes);
+    if (rc != CER_OK) return rc;
+    if (nodes == 0 || nx == 1 || ny == 1 || nz == 1) return CER_OK;      // (no cell: totals are the caller's to zero)
+    if (!cells || !partials || !offsets || !totals) return CER_EINVAL;
+    const MeshDims D = mesh_dims(nx, ny, nz);
+    const long vb = mesh_blocks(D.vslots), fb = mesh_blocks(D.fslots);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(mesh_count_kernel, dim3((unsigned)(vb + fb)), dim3(256), 0, st, cells, D, (unsigned)vb, partials);
+    CER_RETURN_IF_LAUNCH_FAILED();
+    hipLaunchKernelGGL(mesh_scan_kernel, dim3(2), dim3(1024), 0, st, partials, vb, fb, offsets, totals);
+    CER_RETURN_IF_LAUNCH_FAILED();
+    return CER_OK;
+}
+
+extern "C" int cer_mesh_emit_f32(const float* tsdf, const unsigned short* cells, const double* origin, double voxel, int nx, int ny, int nz,
+                                 const long long* offsets, long long nv, long long nf, long long vcap, long long fcap, int* vmap,
+                                 float* vertices, int* faces, void* stream) {
+    long nodes = 0;
+    if (nv < 0 || nf < 0 || vcap < 0 || fcap < 0) return CER_EINVAL;
+    const int rc = mesh_nodes(nx, ny, nz, &nodes);
+    if (rc != CER_OK) return rc;
+    if (nv > 0x7fffffffLL || nf > 0x7fffffffLL) return CER_ESHAPE;       // indices are int32
+    if (!mesh_frame_ok(origin, voxel)) return CER_EINVAL;
+    if (nodes == 0 || nx == 1 || ny == 1 || nz == 1 || (nv == 0 && nf == 0) || (vcap == 0 && fcap == 0)) return CER_OK;
+    if (!tsdf || !cells || !offsets || !vmap || (vcap && !vertices) || (fcap && !faces)) return CER_EINVAL;
+    const MeshDims D = mesh_dims(nx, ny, nz);
+    const MeshGrid g = {origin[0], origin[1], origin[2], voxel, nx, ny, nz};
+    const long vb = mesh_blocks(D.vslots), fb = mesh_blocks(D.fslots);
+    hipStream_t st = (hipStream_t)stream;
+    if (nv) {
+        hipLaunchKernelGGL(mesh_vertex_emit_kernel, dim3((unsigned)vb), dim3(256), 0, st, tsdf, cells, D, g, offsets, vcap, vmap, vertices);
+        CER_RETURN_IF_LAUNCH_FAILED();
+    }
+    if (nf && fcap) {
+        hipLaunchKernelGGL(mesh_face_emit_kernel, dim3((unsigned)fb), dim3(256), 0, st, cells, D, offsets + vb + 1, fcap, vmap, faces);
+        CER_RETURN_IF_LAUNCH_FAILED();
+    }
+    return CER_OK;
+}

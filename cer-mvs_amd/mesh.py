@@ -1,0 +1,315 @@
+"""Surface mesh of a fused scan on the device (csrc/mesh.hip, C ABI 1170): the fused depth maps of ``fusion.fuse_depth_maps``
+integrated into a dense volume of truncated signed distances (``tsdf_volume``), and marching tetrahedra on that volume (``extract_mesh``).
+Vertex and face order are a pure function of the volume - every output slot is a flag at a fixed position, compacted without atomics - and
+all coordinate arithmetic is fp64 with fixed associations: tests/mesh_reference.py restates it in numpy, bit for bit.
+
+Every argument check that needs no device runs before the library is loaded."""
+import ctypes
+import math
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+from . import _lib as L
+
+CAM_DOUBLES = 24                                             # cer_mvs.h CER_CLOUD_CAM_DOUBLES
+MESH_TILE = 2048                                             # cer_mvs.h CER_MESH_TILE
+NODE_LIMIT = 2 ** 31 - MESH_TILE
+
+Grid = namedtuple("Grid", "origin voxel dims")
+Grid.__doc__ = """origin (3 floats), voxel (> 0), dims = (nx, ny, nz): node (i, j, k) sits at origin + (i, j, k) * voxel; volumes are [nz, ny, nx]"""
+
+
+def _grid(grid, who):
+    """the checked grid: (origin as a ctypes double[3], voxel, (nx, ny, nz))"""
+    try:
+        origin, voxel, dims = grid
+        origin = [float(v) for v in origin]
+        voxel = float(voxel)
+        dims = tuple(int(v) for v in dims)
+        same = all(int(v) == v for v in grid[2])
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"{who}: grid = (origin [3], voxel, (nx, ny, nz)) expected") from e
+    if len(origin) != 3 or len(dims) != 3 or not same:
+        raise ValueError(f"{who}: grid = (origin [3], voxel, (nx, ny, nz)) expected")
+    if not all(math.isfinite(v) for v in origin):
+        raise ValueError(f"{who}: the grid's origin must be finite")
+    if not (math.isfinite(voxel) and voxel > 0.0):
+        raise ValueError(f"{who}: the grid's voxel must be a positive finite number")
+    if min(dims) < 0:
+        raise ValueError(f"{who}: the grid's dims must not be negative")
+    if dims[0] * dims[1] * dims[2] >= NODE_LIMIT:
+        raise ValueError(f"{who}: {dims[0]} x {dims[1]} x {dims[2]} nodes is beyond 2^31 - {MESH_TILE}")
+    return (ctypes.c_double * 3)(*origin), voxel, dims
+
+
+def grid_for(points, voxel=None, resolution=256, margin=None, max_nodes=2 ** 28, trunc=None):
+    """The grid around a cloud: points float32 [n, 3] (a device cloud costs one host read of its bounding box).  ``voxel``, or the longest
+    side of the box divided by ``resolution``; ``margin`` (world units, default ``trunc``, whose default is 3 voxels) is added on every side;
+    the origin is snapped down to a multiple of ``voxel``, and the dims are the fewest nodes that reach the far corner.  fp64 on the host.
+    ValueError: no finite point, a grid beyond ``max_nodes`` nodes."""
+    if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError("grid_for: points [n, 3] expected")
+    if voxel is not None and not (math.isfinite(float(voxel)) and float(voxel) > 0.0):
+        raise ValueError("grid_for: voxel must be a positive finite number")
+    if voxel is None and not (isinstance(resolution, int) and resolution >= 1):
+        raise ValueError("grid_for: resolution must be a positive integer")
+    for name, v in (("margin", margin), ("trunc", trunc)):
+        if v is not None and not (math.isfinite(float(v)) and float(v) >= 0.0):
+            raise ValueError(f"grid_for: {name} must be a finite number >= 0")
+    if points.shape[0] == 0:
+        raise ValueError("grid_for: an empty cloud has no bounding box")
+    finite = torch.isfinite(points).all(1)
+    p = points[finite]
+    if p.shape[0] == 0:
+        raise ValueError("grid_for: no finite point")
+    box = torch.stack([p.min(0).values, p.max(0).values]).double().cpu().numpy()         # the one host read
+    lo, hi = box[0], box[1]
+    if voxel is None:
+        side = float((hi - lo).max())
+        if not side > 0.0:
+            raise ValueError("grid_for: the cloud's bounding box is a point; give a voxel")
+        voxel = side / resolution
+    voxel = float(voxel)
+    if margin is None:
+        margin = 3.0 * voxel if trunc is None else float(trunc)
+    margin = float(margin)
+    i0 = np.floor((lo - margin) / voxel)
+    origin = i0 * voxel
+    dims = np.ceil((hi + margin - origin) / voxel).astype(np.int64) + 1
+    nodes = int(dims[0]) * int(dims[1]) * int(dims[2])
+    if nodes > int(max_nodes):
+        raise ValueError(f"grid_for: {int(dims[0])} x {int(dims[1])} x {int(dims[2])} = {nodes} nodes is beyond max_nodes = {int(max_nodes)}; "
+                         "take a larger voxel or a lower resolution")
+    return Grid(tuple(float(v) for v in origin), voxel, tuple(int(v) for v in dims))
+
+
+def forward_cams(Ks, Es):
+    """Per view K [9] | rows 0-2 of E [12] | padding, float64 [N, 24] (CPU): the float32 FORWARD matrices as given, promoted (the packing of
+    ``fusion.cloud_cams``, which carries the inverses)."""
+    Ks = torch.as_tensor(Ks).detach().to("cpu", torch.float32).numpy()
+    Es = torch.as_tensor(Es).detach().to("cpu", torch.float32).numpy()
+    if Ks.ndim != 3 or Ks.shape[1:] != (3, 3) or Es.shape != (Ks.shape[0], 4, 4):
+        raise ValueError("forward_cams: Ks [N,3,3] and Es [N,4,4] expected")
+    cams = np.zeros((Ks.shape[0], CAM_DOUBLES), dtype=np.float64)
+    cams[:, :9] = Ks.reshape(-1, 9)
+    cams[:, 9:21] = Es[:, :3].reshape(-1, 12)
+    return torch.from_numpy(cams)
+
+
+def _check_maps(depths, masks, who):
+    if not isinstance(depths, torch.Tensor) or depths.dim() != 3 or depths.dtype != torch.float32:
+        raise ValueError(f"{who}: depths float32 [N,h,w] expected")
+    if masks is not None and (not isinstance(masks, torch.Tensor) or masks.dtype != torch.uint8 or masks.shape != depths.shape):
+        raise ValueError(f"{who}: masks uint8 {list(depths.shape)} (or None) expected")
+    if masks is not None and masks.device != depths.device:
+        raise ValueError(f"{who}: depths and masks must be on one device")
+
+
+def _check_views(views, N, who):
+    views = list(range(N)) if views is None else [int(v) for v in views]
+    if views and (min(views) < 0 or max(views) >= N):
+        raise ValueError(f"{who}: views must list views in 0..{N - 1}")
+    return views
+
+
+def _check_trunc(trunc, who):
+    trunc = float(trunc)
+    if not (math.isfinite(trunc) and trunc > 0.0):
+        raise ValueError(f"{who}: trunc must be a positive finite number")
+    return trunc
+
+
+def tsdf_volume(depths, masks, Ks, Es, grid, trunc, views=None):
+    """The depth maps integrated into the grid's nodes: depths float32 [N,h,w] and masks uint8 [N,h,w] (or None: every pixel) on the device,
+    Ks [N,3,3] / Es [N,4,4] float32 forward matrices, ``trunc`` in world units, ``views``: the views to integrate, in this order (None: all).
+    Returns (tsdf float32 [nz,ny,nx], weight int32 [nz,ny,nx]) on the device: weight = the number of contributing views, tsdf = the mean of
+    their clamped sdf / trunc (1 where no view contributes) - the contract is cer_mvs.h's, cer_tsdf_integrate_f32."""
+    _check_maps(depths, masks, "tsdf_volume")
+    origin, voxel, dims = _grid(grid, "tsdf_volume")
+    trunc = _check_trunc(trunc, "tsdf_volume")
+    N, h, w = (int(v) for v in depths.shape)
+    cams = forward_cams(Ks, Es)
+    if cams.shape[0] != N:
+        raise ValueError(f"tsdf_volume: {N} cameras expected")
+    views = _check_views(views, N, "tsdf_volume")
+    if not depths.is_cuda:
+        raise RuntimeError("tsdf_volume: depths must be a CUDA tensor (no CPU fallback)")
+    dev = depths.device
+    nx, ny, nz = dims
+    tsdf = torch.ones(nz, ny, nx, device=dev, dtype=torch.float32)
+    weight = torch.zeros(nz, ny, nx, device=dev, dtype=torch.int32)
+    if not views or tsdf.numel() == 0:
+        return tsdf, weight
+    if h * w == 0:
+        raise ValueError("tsdf_volume: empty depth maps")
+    cams = cams.to(dev)
+    vlist = torch.tensor(views, dtype=torch.int32).to(dev)
+    L.check(L.load().cer_tsdf_integrate_f32(L.dev_ptr(depths.contiguous(), "depths"),
+                                            L.dev_ptr(masks.contiguous(), "masks", torch.uint8) if masks is not None else None,
+                                            L.dev_ptr(cams, "cams", torch.float64), N, h, w, L.dev_ptr(vlist, "views", torch.int32), len(views),
+                                            origin, voxel, nx, ny, nz, trunc, L.dev_ptr(tsdf, "tsdf"), L.dev_ptr(weight, "weight", torch.int32),
+                                            L.cur_stream()), "tsdf_integrate")
+    return tsdf, weight
+
+
+def _check_volumes(tsdf, weight, dims, who):
+    nx, ny, nz = dims
+    if not isinstance(tsdf, torch.Tensor) or tsdf.dtype != torch.float32 or tuple(tsdf.shape) != (nz, ny, nx):
+        raise ValueError(f"{who}: tsdf float32 [{nz},{ny},{nx}] expected")
+    if not isinstance(weight, torch.Tensor) or weight.dtype != torch.int32 or tuple(weight.shape) != (nz, ny, nx):
+        raise ValueError(f"{who}: weight int32 [{nz},{ny},{nx}] expected")
+    if tsdf.device != weight.device:
+        raise ValueError(f"{who}: tsdf and weight must be on one device")
+
+
+def mesh_counts(tsdf, weight, grid, min_weight=1):
+    """The first half of ``extract_mesh``: (nv, nf, workspace) - the one synchronisation reads the two totals."""
+    origin, voxel, dims = _grid(grid, "extract_mesh")
+    _check_volumes(tsdf, weight, dims, "extract_mesh")
+    min_weight = int(min_weight)
+    if not tsdf.is_cuda:
+        raise RuntimeError("extract_mesh: the volumes must be CUDA tensors (no CPU fallback)")
+    nx, ny, nz = dims
+    if min(dims) < 2:
+        return 0, 0, None
+    lib, dev = L.load(), tsdf.device
+    tsdf, weight = tsdf.contiguous(), weight.contiguous()
+    P = int(lib.cer_mesh_partials(nx, ny, nz))
+    if P < 0:
+        L.check(P, "mesh_partials")
+    cells = torch.empty((nz - 1, ny - 1, nx - 1), device=dev, dtype=torch.int16)
+    partials = torch.empty(P, device=dev, dtype=torch.int32)
+    offsets = torch.empty(P + 2, device=dev, dtype=torch.int64)
+    totals = torch.zeros(2, device=dev, dtype=torch.int64)
+    pc = L.dev_ptr(cells, "cells", torch.int16)
+    L.check(lib.cer_mesh_cells_u16(L.dev_ptr(tsdf, "tsdf"), L.dev_ptr(weight, "weight", torch.int32), nx, ny, nz, min_weight, pc,
+                                   L.cur_stream()), "mesh_cells")
+    L.check(lib.cer_mesh_count(pc, nx, ny, nz, L.dev_ptr(partials, "partials", torch.int32), L.dev_ptr(offsets, "offsets", torch.int64),
+                               L.dev_ptr(totals, "totals", torch.int64), L.cur_stream()), "mesh_count")
+    nv, nf = (int(v) for v in totals.cpu())                  # the one synchronisation: the outputs are allocated exactly
+    if nv >= 2 ** 31 or nf >= 2 ** 31:
+        raise ValueError(f"extract_mesh: {nv} vertices / {nf} faces is beyond int32 indices; take a larger voxel")
+    return nv, nf, (tsdf, cells, offsets)
+
+
+def mesh_emit(grid, nv, nf, workspace, vertex_capacity=None, face_capacity=None, vertices=None, faces=None):
+    """The second half: the vertices and faces of ``mesh_counts``'s workspace.  With capacities below the totals the leading rows are written
+    and nothing behind them (``vertices`` / ``faces``: the caller's arrays, at least that large)."""
+    origin, voxel, dims = _grid(grid, "extract_mesh")
+    vcap = nv if vertex_capacity is None else int(vertex_capacity)
+    fcap = nf if face_capacity is None else int(face_capacity)
+    if vcap < 0 or fcap < 0:
+        raise ValueError("extract_mesh: capacities must not be negative")
+    tsdf, cells, offsets = workspace
+    dev = tsdf.device
+    vertices = torch.empty(vcap, 3, device=dev, dtype=torch.float32) if vertices is None else vertices
+    faces = torch.empty(fcap, 3, device=dev, dtype=torch.int32) if faces is None else faces
+    if vertices.shape[0] < vcap or faces.shape[0] < fcap:
+        raise ValueError("extract_mesh: the output arrays are smaller than the capacities")
+    nx, ny, nz = dims
+    vmap = torch.empty(nz * ny * nx * 8, device=dev, dtype=torch.int32)
+    L.check(L.load().cer_mesh_emit_f32(L.dev_ptr(tsdf, "tsdf"), L.dev_ptr(cells, "cells", torch.int16), origin, voxel, nx, ny, nz,
+                                       L.dev_ptr(offsets, "offsets", torch.int64), nv, nf, vcap, fcap, L.dev_ptr(vmap, "vmap", torch.int32),
+                                       L.dev_ptr(vertices, "vertices") if vcap else None,
+                                       L.dev_ptr(faces, "faces", torch.int32) if fcap else None, L.cur_stream()), "mesh_emit")
+    return vertices, faces
+
+
+def extract_mesh(tsdf, weight, grid, min_weight=1):
+    """Marching tetrahedra on a volume: tsdf float32 / weight int32 [nz,ny,nx] on the device -> (vertices float32 [nv,3], faces int32 [nf,3])
+    on the device.  A node is valid iff weight >= min_weight and tsdf is finite, inside iff tsdf < 0; a cell is meshed iff its eight corners
+    are valid.  Every face normal points from inside to outside; every vertex is referenced; the order is the slot order of cer_mvs.h
+    (cer_mesh_count).  The mesh is open where nodes are unobserved.  Workspace: 2 bytes per cell and 32 bytes per node."""
+    nv, nf, ws = mesh_counts(tsdf, weight, grid, min_weight)
+    if ws is None or (nv == 0 and nf == 0):
+        dev = tsdf.device
+        return torch.empty(0, 3, device=dev, dtype=torch.float32), torch.empty(0, 3, device=dev, dtype=torch.int32)
+    return mesh_emit(grid, nv, nf, ws)
+
+
+def mesh_from_depth_maps(depths, masks, Ks, Es, grid, trunc=None, views=None, min_weight=1, info=None):
+    """``tsdf_volume`` then ``extract_mesh``.  ``trunc`` defaults to 3 voxels.  ``info`` (a dict) gains the grid, trunc, nv, nf and the number
+    of observed nodes (weight >= min_weight)."""
+    _, voxel, _ = _grid(grid, "mesh_from_depth_maps")
+    trunc = 3.0 * voxel if trunc is None else _check_trunc(trunc, "mesh_from_depth_maps")
+    tsdf, weight = tsdf_volume(depths, masks, Ks, Es, grid, trunc, views)
+    vertices, faces = extract_mesh(tsdf, weight, grid, min_weight)
+    if info is not None:
+        info.update(grid=Grid(tuple(float(v) for v in grid[0]), float(grid[1]), tuple(int(v) for v in grid[2])), trunc=trunc,
+                    nv=int(vertices.shape[0]), nf=int(faces.shape[0]), observed=int((weight >= int(min_weight)).sum()))
+    return vertices, faces
+
+
+MESH_OPTION_KEYS = ("voxel", "resolution", "trunc", "min_weight", "margin")
+
+
+def mesh_options(mesh):
+    """``reconstruct_scan``'s ``mesh`` argument, checked: True or a dict with keys of MESH_OPTION_KEYS -> a dict"""
+    if mesh is True:
+        return {}
+    if not isinstance(mesh, dict):
+        raise ValueError("mesh: True or a dictionary of options expected")
+    extra = sorted(set(mesh) - set(MESH_OPTION_KEYS))
+    if extra:
+        raise ValueError(f"mesh: unknown option(s) {extra}; known: {list(MESH_OPTION_KEYS)}")
+    if "voxel" in mesh and "resolution" in mesh:
+        raise ValueError("mesh: give voxel or resolution, not both")
+    return dict(mesh)
+
+
+def mesh_of_scan(xyz, est, masks, Ks, Es, refs, options):
+    """``reconstruct_scan``'s mesh step: the grid around the fused cloud, then ``mesh_from_depth_maps`` over the emitted views"""
+    opt = dict(options)
+    min_weight = opt.pop("min_weight", 1)
+    trunc = opt.pop("trunc", None)
+    grid = grid_for(xyz, trunc=trunc, **opt)
+    info = {}
+    v, f = mesh_from_depth_maps(est, masks, Ks, Es, grid, trunc=trunc, views=refs, min_weight=min_weight, info=info)
+    return v, f, info
+
+
+_PLY_HEAD = ("ply\nformat binary_little_endian 1.0\nelement vertex {nv}\nproperty float x\nproperty float y\nproperty float z\n"
+             "element face {nf}\nproperty list uchar int vertex_indices\nend_header\n")
+_PLY_FACE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
+
+
+def _host(a):
+    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def write_mesh_ply(path, vertices, faces):
+    """Binary little-endian PLY: float x, y, z per vertex, and per face a uchar count of 3 and three int32 ``vertex_indices``."""
+    v, f = _host(vertices), _host(faces)
+    if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
+        raise ValueError("write_mesh_ply: vertices [nv, 3] and faces [nf, 3] expected")
+    if f.size and (not np.issubdtype(f.dtype, np.integer) or f.min() < 0 or f.max() >= len(v)):
+        raise ValueError("write_mesh_ply: faces must hold integer indices into vertices")
+    rec = np.empty(len(f), dtype=_PLY_FACE)
+    rec["n"], rec["v"] = 3, f
+    with open(path, "wb") as fh:
+        fh.write(_PLY_HEAD.format(nv=len(v), nf=len(f)).encode("ascii"))
+        fh.write(np.ascontiguousarray(v, dtype="<f4").tobytes())
+        fh.write(rec.tobytes())
+
+
+def read_mesh_ply(path):
+    """What ``write_mesh_ply`` wrote: (vertices float32 [nv, 3], faces int32 [nf, 3])"""
+    raw = open(path, "rb").read()
+    head, sep, body = raw.partition(b"end_header\n")
+    lines = head.decode("ascii", "replace").split("\n")
+    try:
+        nv = int(next(ln for ln in lines if ln.startswith("element vertex ")).split()[2])
+        nf = int(next(ln for ln in lines if ln.startswith("element face ")).split()[2])
+    except StopIteration:
+        nv = nf = -1
+    if not sep or head.decode("ascii", "replace") + "end_header\n" != _PLY_HEAD.format(nv=nv, nf=nf):
+        raise ValueError(f"{path}: not a mesh PLY of write_mesh_ply's form")
+    if len(body) != nv * 12 + nf * _PLY_FACE.itemsize:
+        raise ValueError(f"{path}: {len(body)} bytes of data for {nv} vertices and {nf} faces")
+    v = np.frombuffer(body, dtype="<f4", count=nv * 3).reshape(nv, 3).astype(np.float32)
+    rec = np.frombuffer(body, dtype=_PLY_FACE, offset=nv * 12, count=nf)
+    if nf and not (rec["n"] == 3).all():
+        raise ValueError(f"{path}: a face that is not a triangle")
+    return v, rec["v"].astype(np.int32)

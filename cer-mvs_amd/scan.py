@@ -318,7 +318,7 @@ def _merged(stacks, colors, th, keep):
     return depths, ([st.cpu().numpy() for st in stacks] if keep else [])
 
 
-def _cloud_tail(masks, est, Ks, Es, colors, refs, clean, normals):
+def _cloud_tail(masks, est, Ks, Es, colors, refs, clean, normals, mesh=None):
     """Step 3 of ``reconstruct_scan``: masked pixels -> points and colours, the optional ``clean`` filter and ``normals`` (already checked
     options, or None) on the device, then the one copy to the host -> the result's arrays and the bytes that copy moved."""
     dev = masks.device
@@ -327,6 +327,10 @@ def _cloud_tail(masks, est, Ks, Es, colors, refs, clean, normals):
     else:
         xyz, rgb, view_base = FU.point_cloud(masks, est, Ks, Es, colors, refs, view_base=True)
     out, kept = {}, None
+    if mesh is not None:                                    # the grid is the fused cloud's, before ``clean`` thins it
+        from .mesh import mesh_of_scan
+        mv, mf, out["mesh_info"] = mesh_of_scan(xyz, est, masks, Ks, Es, refs, mesh)
+        out["mesh_vertices"], out["mesh_faces"] = mv.cpu().numpy(), mf.cpu().numpy()
     if clean is not None:
         from .cloud_eval import clean_cloud
         kept, cleaned = clean_cloud(xyz, clean)
@@ -343,12 +347,13 @@ def _cloud_tail(masks, est, Ks, Es, colors, refs, clean, normals):
         out["normals"] = nrm.cpu().numpy()
     out.update(xyz=xyz.cpu().numpy(), rgb=rgb.cpu().numpy(), masks=masks.cpu().numpy().astype(bool), depth_est=est.cpu().numpy())
     nbytes = int(xyz.numel() * 4 + rgb.numel() + masks.numel() + est.numel() * 4)
+    nbytes += int(out["mesh_vertices"].nbytes + out["mesh_faces"].nbytes) if mesh is not None else 0
     return out, nbytes + (int(out["normals"].nbytes) if normals is not None else 0)
 
 
 def reconstruct_scan(model_or_ckpt, images, poses, intrinsics, names, pairs, scales, output_folder=None, rescale=1, crop=None, num_frames=10,
                      glb=0.25, streams=3, write_depths=False, write=True, th=0.02, bgr=False, encode_batch=4, max_bytes=None,
-                     force_uncached=False, timings=None, clean=None, normals=None):
+                     force_uncached=False, timings=None, clean=None, normals=None, mesh=None):
     """A scan to its fused point cloud without leaving the device between the stages: ``ScanSession.depths`` -> ``fusion.fuse_depth_maps`` (view i
     against ``pairs[i][:num_frames]``) -> ``fusion.point_cloud`` with the colours of ``fusion.color_grid``.  What ``inference_scan`` followed by
     ``fusion.fusion`` on the session's prepared images computes, without the PFM round trip, the host resize and the float64 numpy tail: same
@@ -368,7 +373,13 @@ def reconstruct_scan(model_or_ckpt, images, poses, intrinsics, names, pairs, sca
     normal for every point of the cloud as it leaves (after ``clean``), still on the device, turned towards the centre of the camera that
     produced the point - the one piece of information that orients a normal without guessing.  The result gains "normals" (float32 [n, 3];
     zeros where the neighbourhood has no plane) and "normal_info" ({"n_valid", "max_dist", "cell", "k"}), and ``result.ply`` carries nx ny nz.
-    None (the default): no normals, no such keys, the file as before."""
+    None (the default): no normals, no such keys, the file as before.
+
+    ``mesh``: True, or {"voxel" | "resolution", "trunc", "min_weight", "margin"} (ValueError for another key): a surface through
+    the fused depth maps, still on the device - ``mesh.grid_for`` around the fused cloud (before ``clean``), then ``mesh.mesh_from_depth_maps``
+    over ``depth_est`` and the masks of the emitted views.  The result gains "mesh_vertices" (float32 [nv, 3]), "mesh_faces" (int32 [nf, 3])
+    and "mesh_info" ({"grid", "trunc", "nv", "nf", "observed"}), and ``write`` puts ``result_mesh.ply`` beside ``result.ply``.  None (the
+    default): no mesh, no such keys, no such file."""
     two_pass = isinstance(rescale, (tuple, list))
     passes = [r for r in rescale] if two_pass else [rescale]
     if two_pass and (len(passes) != 2 or passes[1] != 2 * passes[0]):
@@ -383,6 +394,9 @@ def reconstruct_scan(model_or_ckpt, images, poses, intrinsics, names, pairs, sca
     if normals is not None:
         from .cloud_eval import normals_options
         normals = normals_options(normals)
+    if mesh is not None:
+        from .mesh import mesh_options
+        mesh = mesh_options(mesh)
     t = {} if timings is None else timings
     # ---- 1. depth stacks, 2. merge and fuse
     tic = time.perf_counter()
@@ -400,7 +414,7 @@ def reconstruct_scan(model_or_ckpt, images, poses, intrinsics, names, pairs, sca
     # ---- 3. cloud tail
     tic = time.perf_counter()
     refs = [ref for ref, _ in fpairs]
-    cloud, nbytes = _cloud_tail(masks, est, Ks, Es, colors, refs, clean, normals)
+    cloud, nbytes = _cloud_tail(masks, est, Ks, Es, colors, refs, clean, normals, mesh)
     t["d2h_bytes"] = nbytes + sum(int(a.nbytes) for a in stacks_np)
     # ---- 4. write
     if write_depths:
@@ -411,7 +425,10 @@ def reconstruct_scan(model_or_ckpt, images, poses, intrinsics, names, pairs, sca
     if write:
         FU.write_masks(Path(output_folder), cloud["masks"], refs)
         FU.write_ply(str(Path(output_folder) / "result.ply"), cloud["xyz"], cloud["rgb"], normals=cloud.get("normals"))
+        if mesh is not None:
+            from .mesh import write_mesh_ply
+            write_mesh_ply(str(Path(output_folder) / "result_mesh.ply"), cloud["mesh_vertices"], cloud["mesh_faces"])
     t["tail_s"] = time.perf_counter() - tic
     out = {"masks": cloud["masks"], "depth_est": cloud["depth_est"], "xyz": cloud["xyz"], "rgb": cloud["rgb"], "threshold": thre, "history": hist}
-    out.update({k: cloud[k] for k in ("clean", "normals", "normal_info") if k in cloud})
+    out.update({k: cloud[k] for k in ("clean", "normals", "normal_info", "mesh_vertices", "mesh_faces", "mesh_info") if k in cloud})
     return out

@@ -708,6 +708,53 @@ long cer_cloud_plane_moment_partials(long m);
 int cer_cloud_plane_moments_f64(const float* a, const float* b, const float* nrm, const long long* idx, long m, const double* pivot,
                                 double* partials, double* out, void* stream);
 
+/* Surface mesh of a fused scan (ABI 1170; csrc/mesh.hip, cer-mvs_amd/mesh.py): the fused depth maps integrated into a dense
+ * volume of truncated signed distances, and marching tetrahedra on it.  A grid is origin (3 HOST doubles), voxel and (nx, ny, nz): node
+ * (i, j, k) sits at origin + (i, j, k) * voxel (one product and one sum per axis); volumes are [nz, ny, nx], x fastest.  fp64 arithmetic with
+ * every association as written, no fused multiply-add, IEEE divisions; no atomics; the same bytes on every run.
+ *
+ * Checks, in this order, all before any launch: (1) a negative size -> CER_EINVAL; (2) too large -> CER_ESHAPE (nx ny nz >= 2^31 -
+ * CER_MESH_TILE; h w >= 2^31; nv or nf >= 2^31); (3) origin null or non-finite, voxel (and trunc) not a positive finite number ->
+ * CER_EINVAL; (4) nothing to do -> CER_OK with nothing launched (no nodes; no views for the integration; an axis of 1 - no cell - for the
+ * three extraction calls; no vertex and no face, or no capacity, for the emit); (5) a null pointer -> CER_EINVAL (with views listed: also
+ * N, h or w of 0).
+ *
+ *   cer_tsdf_integrate_f32: depths float32 [N, h, w]; masks uint8 [N, h, w] or NULL (every pixel); cams [N, CER_CLOUD_CAM_DOUBLES] doubles
+ *     per view: K row-major [9] | rows 0-2 of E [12] | padding (the float32 FORWARD matrices, promoted); views: n_views DEVICE ints, each in
+ *     0 .. N-1 (the caller checks them; a kernel skips one that is not).  For every node p and each listed view in list order:
+ *       cx = ((E00 px + E01 py) + E02 pz) + E03, cy, cz likewise; ux = (K00 cx + K01 cy) + K02 cz, uy, uz likewise;
+ *       a = ux / uz + 0.5, b = uy / uz + 0.5.  The view contributes iff uz > 0, 0 <= a < w, 0 <= b < h (in fp64; NaN fails), the mask at
+ *       (xi, yi) = (floor(a), floor(b)) is set, d = double(depth[yi, xi]) is finite and > 0, and sdf = d - uz >= -trunc.  It adds
+ *       (sdf >= trunc ? 1.0 : sdf / trunc) to an fp64 sum that starts at 0, and 1 to the count.
+ *     weight (int32) = the count; tsdf (float32) = float(sum / count), 1.0f where the count is 0.  One thread owns a node.
+ *   cer_mesh_partials: HOST function: the partial counts of the extraction, ceil(8 nodes / CER_MESH_TILE) + ceil(12 cells /
+ *     CER_MESH_TILE) (0 without a cell): partials [that many] unsigned, offsets [that many + 2] 64-bit.
+ *   cer_mesh_cells_u16: cells [nz-1, ny-1, nx-1] unsigned shorts: bit c (c = 0..7) set iff corner c - node (i + (c & 1), j + ((c >> 1) & 1),
+ *     k + ((c >> 2) & 1)) - has tsdf < 0 (so 0.0 and -0.0 are outside); bit 8 set iff the cell is valid: every corner has weight >=
+ *     min_weight and a finite tsdf.
+ *   cer_mesh_count: the per-block counts of set vertex slots and set face slots and their scans; totals[0] = nv, totals[1] = nf (2 DEVICE
+ *     64-bit integers).  Tets in corner-listing order: (0,1,3,7) (0,3,2,7) (0,2,6,7) (0,6,4,7) (0,4,5,7) (0,5,1,7).  With ins / out the
+ *     inside / outside corners of a tet in listing order, XY the vertex on the lattice edge between corners X and Y, and det the integer
+ *     determinant of [B-A, C-A, D-A] on corner offsets: one inside, A = ins[0], (B, C, D) = out: (AB, AC, AD), the last two swapped if det <
+ *     0; three inside, A = out[0], (B, C, D) = ins: (AB, AC, AD), swapped if det > 0; two inside, (A, B) = ins, (C, D) = out, q = (AC, AD,
+ *     BD, BC): (q0, q1, q2) and (q0, q2, q3), both swapped if det < 0.  Face slot (cell * 6 + tet) * 2 + s; a lattice edge is (node a, d =
+ *     1..7 as a bit vector), vertex slot node * 8 + d, set iff the endpoints' signs differ and a valid cell contains the edge.
+ *   cer_mesh_emit_f32: vertices float32 [vcap, 3] and faces int32 [fcap, 3] in slot order: the first min(nv, vcap) vertices and min(nf,
+ *     fcap) faces, never a byte beyond.  nv, nf: what cer_mesh_count found.  A vertex: t = f0 / (f0 - f1) on the endpoint values promoted
+ *     to fp64, per axis origin + (double(idx) + (d_a ? t : 0.0)) * voxel, rounded once to float32.  vmap: [nodes * 8] ints of workspace -
+ *     the output index of every set vertex slot, which the faces read (32 bytes per node). */
+#define CER_MESH_TILE 2048
+long cer_mesh_partials(int nx, int ny, int nz);
+int cer_tsdf_integrate_f32(const float* depths, const unsigned char* masks, const double* cams, int N, int h, int w, const int* views,
+                           int n_views, const double* origin, double voxel, int nx, int ny, int nz, double trunc, float* tsdf, int* weight,
+                           void* stream);
+int cer_mesh_cells_u16(const float* tsdf, const int* weight, int nx, int ny, int nz, int min_weight, unsigned short* cells, void* stream);
+int cer_mesh_count(const unsigned short* cells, int nx, int ny, int nz, unsigned int* partials, long long* offsets, long long* totals,
+                   void* stream);
+int cer_mesh_emit_f32(const float* tsdf, const unsigned short* cells, const double* origin, double voxel, int nx, int ny, int nz,
+                      const long long* offsets, long long nv, long long nf, long long vcap, long long fcap, int* vmap, float* vertices,
+                      int* faces, void* stream);
+
 /* Multi-GPU row-slab exchange (cer-mvs_amd/slab.py): up to CER_COPY_MAX_SEG contiguous fp32 ranges copied by ONE launch -
  * the pack of a rank's (net, disp) border strips into its send buffer, and the refresh of its halo rows from the gathered
  * strips.  n[i] floats from src[i] to dst[i]; n[i] == 0 skips a segment.  Device pointers; ranges must not overlap. */
