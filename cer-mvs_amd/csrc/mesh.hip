@@ -8,6 +8,9 @@
 //
 // All coordinate arithmetic is fp64 with every association written out and no fused multiply-add (-ffp-contract=off): tests/mesh_reference.py
 // restates it in numpy and the GPU tests compare bits.
+//
+// Per-vertex attributes (ABI 1180; tests/mesh_attr_reference.py): colours gathered from the views that see a vertex, and
+// area-weighted normals from the faces of any indexed triangle mesh, under the same arithmetic rules.
 #include "common.hpp"
 #include "compact.hpp"
 
@@ -257,6 +260,104 @@ __global__ __launch_bounds__(256) void mesh_face_emit_kernel(const unsigned shor
     }
 }
 
+// ---- vertex colours from the views: one thread owns a vertex for the whole view loop, laid out as tsdf_integrate_kernel is - the view's 21
+// camera doubles and its list entry are wave-uniform (scalar loads), depth, mask and colour are gathered per pixel.  The projection is the
+// integration's, association for association; a view colours the vertex iff it projects inside, the pixel is masked in, its depth is finite
+// and positive and |d - uz| <= tol (the occlusion test).  The sample is bilinear over pixel centres at integer coordinates, taps clamped.
+__device__ __forceinline__ double mesh_bilinear(const float* __restrict__ plane, long r0, long r1, int x0, int x1, double fx, double fy) {
+    const double c00 = (double)plane[r0 + x0], c01 = (double)plane[r0 + x1], c10 = (double)plane[r1 + x0], c11 = (double)plane[r1 + x1];
+    const double top = (1.0 - fx) * c00 + fx * c01;
+    const double bot = (1.0 - fx) * c10 + fx * c11;
+    return (1.0 - fy) * top + fy * bot;
+}
+__device__ __forceinline__ unsigned char mesh_byte(double sum, double cnt) {
+    const double q = (sum / cnt) * 255.0;
+    return q >= 255.0 ? (unsigned char)255 : (q > 0.0 ? (unsigned char)q : (unsigned char)0);       // (truncation; NaN fails both: 0)
+}
+__global__ __launch_bounds__(256) void mesh_vertex_color_kernel(const float* __restrict__ vertices, unsigned nv,
+                                                                const float* __restrict__ depths, const unsigned char* __restrict__ masks,
+                                                                const float* __restrict__ colors, const double* __restrict__ cams, int N,
+                                                                int h, int w, const int* __restrict__ views, int n_views, double tol,
+                                                                unsigned char* __restrict__ rgb, int* __restrict__ seen) {
+    const unsigned n = blockIdx.x * 256u + threadIdx.x;
+    if (n >= nv) return;
+    const double px = (double)vertices[3l * n], py = (double)vertices[3l * n + 1], pz = (double)vertices[3l * n + 2];
+    const long P = (long)h * w;
+    const double dw = (double)w, dh = (double)h;
+    double sr = 0.0, sg = 0.0, sb = 0.0;
+    int cnt = 0;
+    for (int v = 0; v < n_views; ++v) {
+        const int view = views[v];
+        if (view < 0 || view >= N) continue;                             // (uniform; the caller has checked the list: never taken)
+        const double* c = cams + (long)view * CER_CLOUD_CAM_DOUBLES;
+        const double cx = ((c[9] * px + c[10] * py) + c[11] * pz) + c[12];
+        const double cy = ((c[13] * px + c[14] * py) + c[15] * pz) + c[16];
+        const double cz = ((c[17] * px + c[18] * py) + c[19] * pz) + c[20];
+        const double ux = (c[0] * cx + c[1] * cy) + c[2] * cz;
+        const double uy = (c[3] * cx + c[4] * cy) + c[5] * cz;
+        const double uz = (c[6] * cx + c[7] * cy) + c[8] * cz;
+        const double x = ux / uz, y = uy / uz;
+        const double a = x + 0.5, b = y + 0.5;
+        if (!(uz > 0.0 && a >= 0.0 && a < dw && b >= 0.0 && b < dh)) continue;       // (NaN fails every comparison)
+        const long p = (long)view * P + (long)(int)floor(b) * w + (int)floor(a);
+        if (masks && masks[p] == 0) continue;
+        const double d = (double)depths[p];
+        if (!(d > 0.0 && d - d == 0.0)) continue;                        // finite and positive
+        if (!(fabs(d - uz) <= tol)) continue;                            // the occlusion test, inclusive
+        const double xf = floor(x), yf = floor(y);                       // x in [-0.5, w - 0.5): xf in -1 .. w - 1
+        const double fx = x - xf, fy = y - yf;
+        const int xi = (int)xf, yi = (int)yf;
+        const int x0 = xi < 0 ? 0 : xi, x1 = xi + 1 > w - 1 ? w - 1 : xi + 1;
+        const int y0 = yi < 0 ? 0 : yi, y1 = yi + 1 > h - 1 ? h - 1 : yi + 1;
+        const long r0 = (long)y0 * w, r1 = (long)y1 * w;
+        const float* plane = colors + (long)view * 3 * P;
+        sr += mesh_bilinear(plane, r0, r1, x0, x1, fx, fy);
+        sg += mesh_bilinear(plane + P, r0, r1, x0, x1, fx, fy);
+        sb += mesh_bilinear(plane + 2 * P, r0, r1, x0, x1, fx, fy);
+        ++cnt;
+    }
+    seen[n] = cnt;
+    unsigned char* o = rgb + 3l * n;
+    const double k = (double)cnt;
+    o[0] = cnt ? mesh_byte(sr, k) : (unsigned char)0;
+    o[1] = cnt ? mesh_byte(sg, k) : (unsigned char)0;
+    o[2] = cnt ? mesh_byte(sb, k) : (unsigned char)0;
+}
+
+// ---- vertex normals from the faces: one thread per vertex walks its corners order[starts[v] .. starts[v + 1] - 1] (a stable sort of the
+// corner entries: corner ids 3 * face + corner ascend within a vertex) and adds the faces' (B - A) x (C - A) - twice the area, so the sum is
+// area-weighted - in that order.  No atomics.  A corner id or a face index out of range is skipped, never read through.
+__global__ __launch_bounds__(256) void mesh_vertex_normals_kernel(const float* __restrict__ vertices, unsigned nv, const int* __restrict__ faces,
+                                                                  int corners, const int* __restrict__ starts, const int* __restrict__ order,
+                                                                  float* __restrict__ normals) {
+    const unsigned v = blockIdx.x * 256u + threadIdx.x;
+    if (v >= nv) return;
+    int e0 = starts[v], e1 = starts[v + 1];
+    e0 = e0 < 0 ? 0 : e0;
+    e1 = e1 > corners ? corners : e1;
+    double sx = 0.0, sy = 0.0, sz = 0.0;
+    for (int e = e0; e < e1; ++e) {
+        const int corner = order[e];
+        if (corner < 0 || corner >= corners) continue;
+        const int* f = faces + (long)(corner / 3) * 3;
+        const int ia = f[0], ib = f[1], ic = f[2];
+        if ((unsigned)ia >= nv || (unsigned)ib >= nv || (unsigned)ic >= nv) continue;
+        const float *A = vertices + 3l * ia, *B = vertices + 3l * ib, *C = vertices + 3l * ic;
+        const double ax = (double)A[0], ay = (double)A[1], az = (double)A[2];
+        const double ux = (double)B[0] - ax, uy = (double)B[1] - ay, uz = (double)B[2] - az;
+        const double wx = (double)C[0] - ax, wy = (double)C[1] - ay, wz = (double)C[2] - az;
+        sx += uy * wz - uz * wy;
+        sy += uz * wx - ux * wz;
+        sz += ux * wy - uy * wx;
+    }
+    const double len = sqrt((sx * sx + sy * sy) + sz * sz);
+    const bool ok = len > 0.0 && len - len == 0.0;                       // (an unreferenced vertex, cancelling faces, NaN, overflow: zeros)
+    float* o = normals + 3l * v;
+    o[0] = ok ? (float)(sx / len) : 0.0f;
+    o[1] = ok ? (float)(sy / len) : 0.0f;
+    o[2] = ok ? (float)(sz / len) : 0.0f;
+}
+
 // ---- host side.  The order of the checks is the documented one (cer_mvs.h): negative sizes, too large, the frame, nothing to do, pointers.
 static bool mesh_is_finite(double v) { return v - v == 0.0; }
 static bool mesh_frame_ok(const double* origin, double voxel) {
@@ -359,5 +460,31 @@ extern "C" int cer_mesh_emit_f32(const float* tsdf, const unsigned short* cells,
         hipLaunchKernelGGL(mesh_face_emit_kernel, dim3((unsigned)fb), dim3(256), 0, st, cells, D, offsets + vb + 1, fcap, vmap, faces);
         CER_RETURN_IF_LAUNCH_FAILED();
     }
+    return CER_OK;
+}
+
+extern "C" int cer_mesh_vertex_colors_u8(const float* vertices, long long nv, const float* depths, const unsigned char* masks,
+                                         const float* colors, const double* cams, int N, int h, int w, const int* views, int n_views,
+                                         double tol, unsigned char* rgb, int* seen, void* stream) {
+    if (nv < 0 || N < 0 || h < 0 || w < 0 || n_views < 0) return CER_EINVAL;
+    if (nv > 0x7fffffffLL || (long)h * w > 0x7fffffffL) return CER_ESHAPE;
+    if (!(mesh_is_finite(tol) && tol > 0.0)) return CER_EINVAL;
+    if (nv == 0 || n_views == 0) return CER_OK;                          // (no views: rgb 0 and seen 0 are the caller's to fill)
+    if (!vertices || !depths || !colors || !cams || !views || !rgb || !seen || N == 0 || h == 0 || w == 0) return CER_EINVAL;
+    hipLaunchKernelGGL(mesh_vertex_color_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, (hipStream_t)stream, vertices, (unsigned)nv,
+                       depths, masks, colors, cams, N, h, w, views, n_views, tol, rgb, seen);
+    CER_RETURN_IF_LAUNCH_FAILED();
+    return CER_OK;
+}
+
+extern "C" int cer_mesh_vertex_normals_f32(const float* vertices, long long nv, const int* faces, long long nf, const int* starts,
+                                           const int* order, float* normals, void* stream) {
+    if (nv < 0 || nf < 0) return CER_EINVAL;
+    if (nv > 0x7fffffffLL || nf > 0x7fffffffLL / 3) return CER_ESHAPE;   // corner ids 0 .. 3 nf - 1 are int32
+    if (nv == 0) return CER_OK;
+    if (!vertices || !starts || !normals || (nf && (!faces || !order))) return CER_EINVAL;
+    hipLaunchKernelGGL(mesh_vertex_normals_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, (hipStream_t)stream, vertices, (unsigned)nv,
+                       faces, (int)(3 * nf), starts, order, normals);
+    CER_RETURN_IF_LAUNCH_FAILED();
     return CER_OK;
 }

@@ -1,7 +1,9 @@
 """Surface mesh of a fused scan on the device (csrc/mesh.hip, C ABI 1170): the fused depth maps of ``fusion.fuse_depth_maps``
 integrated into a dense volume of truncated signed distances (``tsdf_volume``), and marching tetrahedra on that volume (``extract_mesh``).
 Vertex and face order are a pure function of the volume - every output slot is a flag at a fixed position, compacted without atomics - and
-all coordinate arithmetic is fp64 with fixed associations: tests/mesh_reference.py restates it in numpy, bit for bit.
+all coordinate arithmetic is fp64 with fixed associations: tests/mesh_reference.py restates it in numpy, bit for bit.  Per-vertex attributes
+(C ABI 1180; tests/mesh_attr_reference.py): ``vertex_colors`` from the views that see a vertex, ``vertex_normals`` from the
+faces of any indexed triangle mesh, and both through the PLY writer and reader.
 
 Every argument check that needs no device runs before the library is loaded."""
 import ctypes
@@ -242,11 +244,102 @@ def mesh_from_depth_maps(depths, masks, Ks, Es, grid, trunc=None, views=None, mi
     return vertices, faces
 
 
-MESH_OPTION_KEYS = ("voxel", "resolution", "trunc", "min_weight", "margin")
+# ---------------------------------------------------------------- per-vertex attributes (C ABI 1180)
+def _check_vertices(vertices, who):
+    if not isinstance(vertices, torch.Tensor) or vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32:
+        raise ValueError(f"{who}: vertices float32 [nv, 3] expected")
+    if vertices.shape[0] >= 2 ** 31:
+        raise ValueError(f"{who}: {vertices.shape[0]} vertices is beyond int32 indices")
+
+
+def vertex_colors(vertices, depths, masks, colors, Ks, Es, tol, views=None):
+    """A colour per vertex from the views that see it: vertices float32 [nv,3], depths float32 [N,h,w], masks uint8 [N,h,w] (or None: every
+    pixel) and colors float32 [N,3,h,w] (the planes ``fusion.point_cloud`` takes) on the device, Ks / Es the float32 forward matrices,
+    ``views``: the views to ask, in this order (None: all).  A view sees a vertex iff it projects inside the image (``tsdf_volume``'s
+    projection), the pixel is masked in, its depth d is finite and positive and ``|d - uz| <= tol`` (world units): the depth maps' own
+    occlusion reasoning.  Each such view adds its bilinear sample.  Returns (rgb uint8 [nv,3], seen int32 [nv]) on the device: the mean
+    colour times 255, truncated and clamped ((0, 0, 0) where ``seen`` is 0), and the number of views - the contract is cer_mvs.h's,
+    cer_mesh_vertex_colors_u8."""
+    who = "vertex_colors"
+    _check_vertices(vertices, who)
+    _check_maps(depths, masks, who)
+    N, h, w = (int(v) for v in depths.shape)
+    if not isinstance(colors, torch.Tensor) or colors.dtype != torch.float32 or tuple(colors.shape) != (N, 3, h, w):
+        raise ValueError(f"{who}: colors float32 [{N},3,{h},{w}] expected")
+    if colors.device != depths.device or vertices.device != depths.device:
+        raise ValueError(f"{who}: vertices, depths and colors must be on one device")
+    tol = float(tol)
+    if not (math.isfinite(tol) and tol > 0.0):
+        raise ValueError(f"{who}: tol must be a positive finite number")
+    cams = forward_cams(Ks, Es)
+    if cams.shape[0] != N:
+        raise ValueError(f"{who}: {N} cameras expected")
+    views = _check_views(views, N, who)
+    if not vertices.is_cuda:
+        raise RuntimeError(f"{who}: vertices must be a CUDA tensor (no CPU fallback)")
+    dev, nv = vertices.device, int(vertices.shape[0])
+    rgb = torch.zeros(nv, 3, device=dev, dtype=torch.uint8)
+    seen = torch.zeros(nv, device=dev, dtype=torch.int32)
+    if not views or nv == 0:
+        return rgb, seen
+    if h * w == 0:
+        raise ValueError(f"{who}: empty depth maps")
+    cams = cams.to(dev)
+    vlist = torch.tensor(views, dtype=torch.int32).to(dev)
+    L.check(L.load().cer_mesh_vertex_colors_u8(L.dev_ptr(vertices.contiguous(), "vertices"), nv, L.dev_ptr(depths.contiguous(), "depths"),
+                                               L.dev_ptr(masks.contiguous(), "masks", torch.uint8) if masks is not None else None,
+                                               L.dev_ptr(colors.contiguous(), "colors"), L.dev_ptr(cams, "cams", torch.float64), N, h, w,
+                                               L.dev_ptr(vlist, "views", torch.int32), len(views), tol, L.dev_ptr(rgb, "rgb", torch.uint8),
+                                               L.dev_ptr(seen, "seen", torch.int32), L.cur_stream()), "mesh_vertex_colors")
+    return rgb, seen
+
+
+def vertex_faces(faces, nv):
+    """The faces around every vertex as a CSR list over the 3 nf corner entries ``faces.reshape(-1)`` (corner id = 3 * face + corner):
+    faces int32 [nf,3] with indices in 0 .. nv-1 (ValueError otherwise) -> (starts int32 [nv + 1], order int32 [3 nf]) on the faces'
+    device: ``order[starts[v] : starts[v + 1]]`` are the corner ids that name vertex v, ascending (a stable sort).  Torch ops only."""
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
+        raise ValueError("vertex_faces: faces int32 [nf, 3] expected")
+    nv = int(nv)
+    if nv < 0 or nv >= 2 ** 31 or 3 * faces.shape[0] >= 2 ** 31:
+        raise ValueError("vertex_faces: nv and 3 nf must be in 0 .. 2^31 - 1")
+    keys = faces.reshape(-1)
+    if keys.numel() and (int(keys.min()) < 0 or int(keys.max()) >= nv):
+        raise ValueError(f"vertex_faces: faces must hold indices in 0 .. {nv - 1}")
+    ordered, order = torch.sort(keys, stable=True)
+    starts = torch.searchsorted(ordered, torch.arange(nv + 1, device=faces.device, dtype=torch.int32))
+    return starts.to(torch.int32), order.to(torch.int32)
+
+
+def vertex_normals(vertices, faces):
+    """Area-weighted vertex normals of any indexed triangle mesh (Open3D's ``compute_vertex_normals``): vertices float32 [nv,3] and faces
+    int32 [nf,3] on the device -> float32 [nv,3] on the device: the sum of (B - A) x (C - A) over the corners that name the vertex, in
+    corner order, normalised; (0, 0, 0) for an unreferenced vertex, cancelling faces and NaN - cer_mvs.h, cer_mesh_vertex_normals_f32."""
+    _check_vertices(vertices, "vertex_normals")
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
+        raise ValueError("vertex_normals: faces int32 [nf, 3] expected")
+    if faces.device != vertices.device:
+        raise ValueError("vertex_normals: vertices and faces must be on one device")
+    nv, nf = int(vertices.shape[0]), int(faces.shape[0])
+    starts, order = vertex_faces(faces, nv)
+    if not vertices.is_cuda:
+        raise RuntimeError("vertex_normals: vertices must be a CUDA tensor (no CPU fallback)")
+    normals = torch.zeros(nv, 3, device=vertices.device, dtype=torch.float32)
+    if nv == 0:
+        return normals
+    L.check(L.load().cer_mesh_vertex_normals_f32(L.dev_ptr(vertices.contiguous(), "vertices"), nv,
+                                                 L.dev_ptr(faces.contiguous(), "faces", torch.int32) if nf else None, nf,
+                                                 L.dev_ptr(starts, "starts", torch.int32), L.dev_ptr(order, "order", torch.int32) if nf else None,
+                                                 L.dev_ptr(normals, "normals"), L.cur_stream()), "mesh_vertex_normals")
+    return normals
+
+
+MESH_OPTION_KEYS = ("voxel", "resolution", "trunc", "min_weight", "margin", "colors", "normals")
 
 
 def mesh_options(mesh):
-    """``reconstruct_scan``'s ``mesh`` argument, checked: True or a dict with keys of MESH_OPTION_KEYS -> a dict"""
+    """``reconstruct_scan``'s ``mesh`` argument, checked: True or a dict with keys of MESH_OPTION_KEYS -> a dict.  "colors": True or
+    {"tol": a positive finite number} (default: the mesh's trunc); "normals": True."""
     if mesh is True:
         return {}
     if not isinstance(mesh, dict):
@@ -256,60 +349,111 @@ def mesh_options(mesh):
         raise ValueError(f"mesh: unknown option(s) {extra}; known: {list(MESH_OPTION_KEYS)}")
     if "voxel" in mesh and "resolution" in mesh:
         raise ValueError("mesh: give voxel or resolution, not both")
+    if "colors" in mesh and mesh["colors"] is not True:
+        col = mesh["colors"]
+        if not isinstance(col, dict) or set(col) - {"tol"}:
+            raise ValueError("mesh: colors must be True or {\"tol\": a positive finite number}")
+        if "tol" in col and not (isinstance(col["tol"], (int, float)) and not isinstance(col["tol"], bool) and math.isfinite(col["tol"]) and col["tol"] > 0):
+            raise ValueError("mesh: colors: tol must be a positive finite number")
+    if "normals" in mesh and mesh["normals"] is not True:
+        raise ValueError("mesh: normals must be True")
     return dict(mesh)
 
 
-def mesh_of_scan(xyz, est, masks, Ks, Es, refs, options):
-    """``reconstruct_scan``'s mesh step: the grid around the fused cloud, then ``mesh_from_depth_maps`` over the emitted views"""
+def mesh_of_scan(xyz, est, masks, Ks, Es, refs, options, colors=None):
+    """``reconstruct_scan``'s mesh step: the grid around the fused cloud, then ``mesh_from_depth_maps`` over the emitted views -> (vertices,
+    faces, info, attributes).  With the options "colors" / "normals": ``vertex_colors`` over the same views from the ``colors`` planes
+    [N,3,h,w] (tol: the option's, or the mesh's trunc) / ``vertex_normals``; ``attributes`` then holds "mesh_colors" / "mesh_normals" (device
+    tensors) and ``info`` gains "coloured", the number of vertices that a view sees."""
     opt = dict(options)
     min_weight = opt.pop("min_weight", 1)
     trunc = opt.pop("trunc", None)
+    want_colors, want_normals = opt.pop("colors", None), opt.pop("normals", None)
     grid = grid_for(xyz, trunc=trunc, **opt)
-    info = {}
+    info, attributes = {}, {}
     v, f = mesh_from_depth_maps(est, masks, Ks, Es, grid, trunc=trunc, views=refs, min_weight=min_weight, info=info)
-    return v, f, info
+    if want_colors is not None:
+        if colors is None:
+            raise ValueError("mesh: colors asked for without colour planes")
+        tol = info["trunc"] if want_colors is True else float(want_colors.get("tol", info["trunc"]))
+        attributes["mesh_colors"], seen = vertex_colors(v, est, masks, colors, Ks, Es, tol, views=refs)
+        info["coloured"] = int((seen > 0).sum())
+    if want_normals is not None:
+        attributes["mesh_normals"] = vertex_normals(v, f)
+    return v, f, info, attributes
 
 
-_PLY_HEAD = ("ply\nformat binary_little_endian 1.0\nelement vertex {nv}\nproperty float x\nproperty float y\nproperty float z\n"
-             "element face {nf}\nproperty list uchar int vertex_indices\nend_header\n")
+_PLY_NORMALS = "property float nx\nproperty float ny\nproperty float nz\n"
+_PLY_COLORS = "property uchar red\nproperty uchar green\nproperty uchar blue\n"
 _PLY_FACE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
+
+
+def _ply_head(nv, nf, normals, colors):
+    """the header of one of the four forms: x y z [nx ny nz] [red green blue] per vertex, ``fusion.write_ply``'s order"""
+    return ("ply\nformat binary_little_endian 1.0\n" f"element vertex {nv}\nproperty float x\nproperty float y\nproperty float z\n"
+            + (_PLY_NORMALS if normals else "") + (_PLY_COLORS if colors else "")
+            + f"element face {nf}\nproperty list uchar int vertex_indices\nend_header\n")
+
+
+def _ply_vertex(normals, colors):
+    return np.dtype([("p", "<f4", (3,))] + ([("n", "<f4", (3,))] if normals else []) + ([("c", "u1", (3,))] if colors else []))
 
 
 def _host(a):
     return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
 
 
-def write_mesh_ply(path, vertices, faces):
-    """Binary little-endian PLY: float x, y, z per vertex, and per face a uchar count of 3 and three int32 ``vertex_indices``."""
+def write_mesh_ply(path, vertices, faces, normals=None, colors=None):
+    """Binary little-endian PLY: float x, y, z per vertex, then float nx, ny, nz with ``normals`` ([nv, 3]) and uchar red, green, blue with
+    ``colors`` (uint8 [nv, 3]), and per face a uchar count of 3 and three int32 ``vertex_indices``."""
     v, f = _host(vertices), _host(faces)
     if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
         raise ValueError("write_mesh_ply: vertices [nv, 3] and faces [nf, 3] expected")
     if f.size and (not np.issubdtype(f.dtype, np.integer) or f.min() < 0 or f.max() >= len(v)):
         raise ValueError("write_mesh_ply: faces must hold integer indices into vertices")
+    nrm, col = (None if a is None else _host(a) for a in (normals, colors))
+    if nrm is not None and nrm.shape != v.shape:
+        raise ValueError(f"write_mesh_ply: normals [{len(v)}, 3] expected")
+    if col is not None and (col.shape != v.shape or col.dtype != np.uint8):
+        raise ValueError(f"write_mesh_ply: colors uint8 [{len(v)}, 3] expected")
     rec = np.empty(len(f), dtype=_PLY_FACE)
     rec["n"], rec["v"] = 3, f
+    ver = np.empty(len(v), dtype=_ply_vertex(nrm is not None, col is not None))
+    ver["p"] = v
+    if nrm is not None:
+        ver["n"] = nrm
+    if col is not None:
+        ver["c"] = col
     with open(path, "wb") as fh:
-        fh.write(_PLY_HEAD.format(nv=len(v), nf=len(f)).encode("ascii"))
-        fh.write(np.ascontiguousarray(v, dtype="<f4").tobytes())
+        fh.write(_ply_head(len(v), len(f), nrm is not None, col is not None).encode("ascii"))
+        fh.write(ver.tobytes())
         fh.write(rec.tobytes())
 
 
-def read_mesh_ply(path):
-    """What ``write_mesh_ply`` wrote: (vertices float32 [nv, 3], faces int32 [nf, 3])"""
+def read_mesh_ply(path, attributes=False):
+    """What ``write_mesh_ply`` wrote, in any of its four forms: (vertices float32 [nv, 3], faces int32 [nf, 3]), or with ``attributes``
+    (vertices, faces, normals float32 [nv, 3] | None, colors uint8 [nv, 3] | None)"""
     raw = open(path, "rb").read()
     head, sep, body = raw.partition(b"end_header\n")
-    lines = head.decode("ascii", "replace").split("\n")
+    text = head.decode("ascii", "replace")
+    lines = text.split("\n")
     try:
         nv = int(next(ln for ln in lines if ln.startswith("element vertex ")).split()[2])
         nf = int(next(ln for ln in lines if ln.startswith("element face ")).split()[2])
     except StopIteration:
         nv = nf = -1
-    if not sep or head.decode("ascii", "replace") + "end_header\n" != _PLY_HEAD.format(nv=nv, nf=nf):
+    has_n, has_c = "property float nx" in lines, "property uchar red" in lines
+    if not sep or text + "end_header\n" != _ply_head(nv, nf, has_n, has_c):
         raise ValueError(f"{path}: not a mesh PLY of write_mesh_ply's form")
-    if len(body) != nv * 12 + nf * _PLY_FACE.itemsize:
+    vdt = _ply_vertex(has_n, has_c)
+    if len(body) != nv * vdt.itemsize + nf * _PLY_FACE.itemsize:
         raise ValueError(f"{path}: {len(body)} bytes of data for {nv} vertices and {nf} faces")
-    v = np.frombuffer(body, dtype="<f4", count=nv * 3).reshape(nv, 3).astype(np.float32)
-    rec = np.frombuffer(body, dtype=_PLY_FACE, offset=nv * 12, count=nf)
+    ver = np.frombuffer(body, dtype=vdt, count=nv)
+    v = ver["p"].astype(np.float32)
+    rec = np.frombuffer(body, dtype=_PLY_FACE, offset=nv * vdt.itemsize, count=nf)
     if nf and not (rec["n"] == 3).all():
         raise ValueError(f"{path}: a face that is not a triangle")
-    return v, rec["v"].astype(np.int32)
+    f = rec["v"].astype(np.int32)
+    if not attributes:
+        return v, f
+    return v, f, (ver["n"].astype(np.float32) if has_n else None), (ver["c"].copy() if has_c else None)

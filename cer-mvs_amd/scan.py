@@ -329,8 +329,9 @@ def _cloud_tail(masks, est, Ks, Es, colors, refs, clean, normals, mesh=None):
     out, kept = {}, None
     if mesh is not None:                                    # the grid is the fused cloud's, before ``clean`` thins it
         from .mesh import mesh_of_scan
-        mv, mf, out["mesh_info"] = mesh_of_scan(xyz, est, masks, Ks, Es, refs, mesh)
+        mv, mf, out["mesh_info"], attributes = mesh_of_scan(xyz, est, masks, Ks, Es, refs, mesh, colors=colors)
         out["mesh_vertices"], out["mesh_faces"] = mv.cpu().numpy(), mf.cpu().numpy()
+        out.update({k: a.cpu().numpy() for k, a in attributes.items()})          # "mesh_colors" / "mesh_normals", if asked for
     if clean is not None:
         from .cloud_eval import clean_cloud
         kept, cleaned = clean_cloud(xyz, clean)
@@ -347,7 +348,7 @@ def _cloud_tail(masks, est, Ks, Es, colors, refs, clean, normals, mesh=None):
         out["normals"] = nrm.cpu().numpy()
     out.update(xyz=xyz.cpu().numpy(), rgb=rgb.cpu().numpy(), masks=masks.cpu().numpy().astype(bool), depth_est=est.cpu().numpy())
     nbytes = int(xyz.numel() * 4 + rgb.numel() + masks.numel() + est.numel() * 4)
-    nbytes += int(out["mesh_vertices"].nbytes + out["mesh_faces"].nbytes) if mesh is not None else 0
+    nbytes += sum(int(out[k].nbytes) for k in ("mesh_vertices", "mesh_faces", "mesh_colors", "mesh_normals") if k in out)
     return out, nbytes + (int(out["normals"].nbytes) if normals is not None else 0)
 
 
@@ -379,7 +380,11 @@ def reconstruct_scan(model_or_ckpt, images, poses, intrinsics, names, pairs, sca
     the fused depth maps, still on the device - ``mesh.grid_for`` around the fused cloud (before ``clean``), then ``mesh.mesh_from_depth_maps``
     over ``depth_est`` and the masks of the emitted views.  The result gains "mesh_vertices" (float32 [nv, 3]), "mesh_faces" (int32 [nf, 3])
     and "mesh_info" ({"grid", "trunc", "nv", "nf", "observed"}), and ``write`` puts ``result_mesh.ply`` beside ``result.ply``.  None (the
-    default): no mesh, no such keys, no such file."""
+    default): no mesh, no such keys, no such file.  Two further keys of ``mesh``: "colors": True or {"tol": float} - a colour
+    per vertex from the views that see it (``mesh.vertex_colors`` over the colour planes of the cloud; ``tol``, default the mesh's trunc, is
+    the occlusion bound on |depth - uz|): the result gains "mesh_colors" (uint8 [nv, 3]) and ``mesh_info`` "coloured", the number of vertices
+    some view sees; "normals": True - area-weighted vertex normals (``mesh.vertex_normals``): "mesh_normals" (float32 [nv, 3]).
+    ``result_mesh.ply`` carries what was asked for.  Without these keys nothing changes."""
     two_pass = isinstance(rescale, (tuple, list))
     passes = [r for r in rescale] if two_pass else [rescale]
     if two_pass and (len(passes) != 2 or passes[1] != 2 * passes[0]):
@@ -427,8 +432,10 @@ def reconstruct_scan(model_or_ckpt, images, poses, intrinsics, names, pairs, sca
         FU.write_ply(str(Path(output_folder) / "result.ply"), cloud["xyz"], cloud["rgb"], normals=cloud.get("normals"))
         if mesh is not None:
             from .mesh import write_mesh_ply
-            write_mesh_ply(str(Path(output_folder) / "result_mesh.ply"), cloud["mesh_vertices"], cloud["mesh_faces"])
+            write_mesh_ply(str(Path(output_folder) / "result_mesh.ply"), cloud["mesh_vertices"], cloud["mesh_faces"],
+                           normals=cloud.get("mesh_normals"), colors=cloud.get("mesh_colors"))
     t["tail_s"] = time.perf_counter() - tic
     out = {"masks": cloud["masks"], "depth_est": cloud["depth_est"], "xyz": cloud["xyz"], "rgb": cloud["rgb"], "threshold": thre, "history": hist}
-    out.update({k: cloud[k] for k in ("clean", "normals", "normal_info", "mesh_vertices", "mesh_faces", "mesh_info") if k in cloud})
+    out.update({k: cloud[k] for k in ("clean", "normals", "normal_info", "mesh_vertices", "mesh_faces", "mesh_info", "mesh_colors", "mesh_normals")
+                if k in cloud})
     return out

@@ -755,6 +755,41 @@ int cer_mesh_emit_f32(const float* tsdf, const unsigned short* cells, const doub
                       const long long* offsets, long long nv, long long nf, long long vcap, long long fcap, int* vmap, float* vertices,
                       int* faces, void* stream);
 
+/* Per-vertex attributes of a triangle mesh (ABI 1180; csrc/mesh.hip, cer-mvs_amd/mesh.py), under the rules of the section
+ * above: fp64 with every association as written, no fused multiply-add, IEEE division and square root, no atomics, the same bytes on every
+ * run.  Checks in the section's order, all before any launch: (1) a negative size -> CER_EINVAL; (2) nv, 3 nf or h w >= 2^31 -> CER_ESHAPE;
+ * (3) tol not a positive finite number -> CER_EINVAL; (4) nothing to do -> CER_OK with nothing launched (nv == 0; for the colours also
+ * n_views == 0: rgb and seen are the caller's to zero; the normals with nf == 0 and nv > 0 DO launch and write zeros); (5) a null pointer
+ * -> CER_EINVAL (the colours: also N, h or w of 0; the normals: faces and order may be null iff nf == 0).
+ *
+ *   cer_mesh_vertex_colors_u8: vertices float32 [nv, 3], promoted to double; depths, masks (or NULL: every pixel), cams and views as
+ *     cer_tsdf_integrate_f32 takes them; colors float32 [N, 3, h, w], planar.  One thread owns a vertex p; for each listed view in list order:
+ *       cx = ((E00 px + E01 py) + E02 pz) + E03, cy, cz likewise; ux = (K00 cx + K01 cy) + K02 cz, uy, uz likewise (the integration's);
+ *       x = ux / uz, y = uy / uz, a = x + 0.5, b = y + 0.5.  The view SEES the vertex iff uz > 0, 0 <= a < w, 0 <= b < h (in fp64, before
+ *       any conversion; NaN fails), the mask at (floor(a), floor(b)) is set (or masks is NULL), d = double(depth) at that pixel is finite
+ *       and > 0, and fabs(d - uz) <= tol (inclusive; world units) - the occlusion test: a vertex more than tol behind or in front of the
+ *       surface the view recorded at that pixel takes no colour from that view.
+ *       The sample is bilinear over pixel centres at integer coordinates: x0 = floor(x), fx = x - x0, y0 = floor(y), fy = y - y0; taps x0,
+ *       x0 + 1 clamped to [0, w-1] and y0, y0 + 1 clamped to [0, h-1], all four used whatever their masks; per channel, with cYX the tap
+ *       at row Y, column X promoted to double: top = (1 - fx) * c00 + fx * c01, bot = (1 - fx) * c10 + fx * c11, val = (1 - fy) * top +
+ *       fy * bot.  val is added to an fp64 sum per channel (starting at 0) and 1 to the count.
+ *     seen int32 [nv] = the count.  rgb uint8 [nv, 3]: with m = sum / double(count) and q = m * 255.0 the byte is q >= 255 ? 255 : (q > 0 ?
+ *     (uint8) q : 0) - truncation, as the cloud's (uint8)(c * 255); NaN gives 0; (0, 0, 0) where the count is 0.
+ *   cer_mesh_vertex_normals_f32: any indexed triangle mesh: vertices float32 [nv, 3], faces int32 [nf, 3].  The incidence is a CSR list
+ *     over the 3 nf corner entries faces.reshape(-1), corner id = 3 * face + corner: order int32 [3 nf] = the corner ids stably sorted by
+ *     their vertex (within one vertex the ids ascend), starts int32 [nv + 1] = the first position of every vertex in that order.  One
+ *     thread per vertex v walks e = starts[v] .. starts[v + 1] - 1: for face order[e] / 3 with indices (ia, ib, ic) and A, B, C their
+ *     positions promoted to double, U = B - A, W = C - A, n = (Uy Wz - Uz Wy, Uz Wx - Ux Wz, Ux Wy - Uy Wx) - twice the area long, so the
+ *     sum is area-weighted - added per component to an fp64 sum that starts at 0.  A face that lists v twice is visited twice.  A corner id
+ *     or a face index outside its range is skipped (the Python layer refuses such faces).  len = sqrt((sx sx + sy sy) + sz sz); normals
+ *     float32 [nv, 3] = float(s / len) per component where len > 0 and finite, else (0, 0, 0) (an unreferenced vertex, cancelling faces,
+ *     NaN). */
+int cer_mesh_vertex_colors_u8(const float* vertices, long long nv, const float* depths, const unsigned char* masks, const float* colors,
+                              const double* cams, int N, int h, int w, const int* views, int n_views, double tol, unsigned char* rgb,
+                              int* seen, void* stream);
+int cer_mesh_vertex_normals_f32(const float* vertices, long long nv, const int* faces, long long nf, const int* starts, const int* order,
+                                float* normals, void* stream);
+
 /* Multi-GPU row-slab exchange (cer-mvs_amd/slab.py): up to CER_COPY_MAX_SEG contiguous fp32 ranges copied by ONE launch -
  * the pack of a rank's (net, disp) border strips into its send buffer, and the refresh of its halo rows from the gathered
  * strips.  n[i] floats from src[i] to dst[i]; n[i] == 0 skips a segment.  Device pointers; ranges must not overlap. */
