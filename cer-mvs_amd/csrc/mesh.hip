@@ -11,6 +11,9 @@
 //
 // Per-vertex attributes (ABI 1180; tests/mesh_attr_reference.py): colours gathered from the views that see a vertex, and
 // area-weighted normals from the faces of any indexed triangle mesh, under the same arithmetic rules.
+//
+// Cleaning (ABI 1190; tests/mesh_clean_reference.py): the connected components of any indexed triangle mesh by min-label
+// sweeps without atomics or data-dependent waiting, and the sub-mesh of a face mask through the same ordered compaction.
 #include "common.hpp"
 #include "compact.hpp"
 
@@ -358,6 +361,140 @@ __global__ __launch_bounds__(256) void mesh_vertex_normals_kernel(const float* _
     o[2] = ok ? (float)(sz / len) : 0.0f;
 }
 
+// ---- connected components (ABI 1190; tests/mesh_clean_reference.py): labels[v] starts as v and falls to the smallest vertex
+// index of v's component.  One sweep: the thread that owns v - the only writer of labels[v] - takes the minimum of labels[labels[u]] over v
+// itself and every index u of the faces around v (the CSR list of the normals kernel) and stores it if it is smaller.  In place, no atomics:
+// a label read from another vertex is this sweep's or the previous one's, either way the index of a vertex of the same component, so labels
+// only fall and the only fixed point is labels[v] = the root.  Every loop below runs over the INPUT's corner list: no trip count depends on
+// another thread's stores (no find-root walk, no spin, no grid barrier).  The flag word is the one address several threads store to, all of
+// them the same 1.  A label, corner id or face index outside its range is never read through.
+__device__ __forceinline__ int mesh_label2(const int* labels, unsigned nv, int u) {
+    const int a = labels[u];
+    if ((unsigned)a >= nv) return 0x7fffffff;
+    const int b = labels[a];
+    return (unsigned)b < nv ? b : 0x7fffffff;
+}
+__global__ __launch_bounds__(256) void mesh_label_sweep_kernel(const int* __restrict__ faces, int corners, const int* __restrict__ starts,
+                                                               const int* __restrict__ order, unsigned nv, int* labels, int* flag) {
+    const unsigned v = blockIdx.x * 256u + threadIdx.x;
+    if (v >= nv) return;
+    int e0 = starts[v], e1 = starts[v + 1];
+    e0 = e0 < 0 ? 0 : e0;
+    e1 = e1 > corners ? corners : e1;
+    const int own = labels[v];
+    int m = mesh_label2(labels, nv, (int)v);
+    for (int e = e0; e < e1; ++e) {
+        const int corner = order[e];
+        if (corner < 0 || corner >= corners) continue;
+        const int* f = faces + (long)(corner / 3) * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const int u = f[c];
+            if ((unsigned)u >= nv) continue;
+            const int l = mesh_label2(labels, nv, u);
+            m = l < m ? l : m;
+        }
+    }
+    if (m < own) {
+        labels[v] = m;
+        *flag = 1;
+    }
+}
+
+// ---- face selection (ABI 1190): the kept faces in their order, the vertices they name in theirs, indices renumbered.  Both are
+// flags at fixed positions - face q: keep[q] and three indices in range; vertex p: a kept face among the faces around it, GATHERED through the
+// CSR list (no scatter) - and leave through compact.hpp's count / scan / emit as the extraction's slots do: one count launch over the vertex
+// tiles then the face tiles, mesh_scan_kernel, a vertex emit that writes position, old index and vmap[p], a face emit that reads vmap.
+__device__ __forceinline__ bool mesh_face_kept(const int* __restrict__ faces, const unsigned char* __restrict__ keep, unsigned nv, long nf,
+                                               long q) {
+    if (q >= nf || keep[q] == 0) return false;
+    const int* f = faces + q * 3;
+    return (unsigned)f[0] < nv && (unsigned)f[1] < nv && (unsigned)f[2] < nv;
+}
+__device__ __forceinline__ bool mesh_vertex_used(const int* __restrict__ faces, const unsigned char* __restrict__ keep,
+                                                 const int* __restrict__ starts, const int* __restrict__ order, unsigned nv, long nf, long p) {
+    if (p >= (long)nv) return false;
+    const int corners = (int)(3 * nf);
+    int e0 = starts[p], e1 = starts[p + 1];
+    e0 = e0 < 0 ? 0 : e0;
+    e1 = e1 > corners ? corners : e1;
+    bool used = false;
+    for (int e = e0; e < e1; ++e) {
+        const int corner = order[e];
+        if (corner < 0 || corner >= corners) continue;
+        used |= mesh_face_kept(faces, keep, nv, nf, (long)(corner / 3));
+    }
+    return used;
+}
+
+// count: grid = vertex blocks then face blocks, one partial each; used[p] is stored for the emit, which does not walk the list again
+__global__ __launch_bounds__(256) void mesh_select_count_kernel(const int* __restrict__ faces, const unsigned char* __restrict__ keep,
+                                                                const int* __restrict__ starts, const int* __restrict__ order, unsigned nv,
+                                                                long nf, unsigned vblocks, unsigned char* __restrict__ used,
+                                                                unsigned* __restrict__ partials) {
+    unsigned long long bal[MESH_ITER];
+    const bool fpart = blockIdx.x >= vblocks;                            // (uniform)
+    const long seg = compact_seg<MESH_TILE, long>() - (fpart ? (long)vblocks * MESH_TILE : 0);
+    const unsigned wave = fpart ? compact_ballots(seg, [&](long q) { return mesh_face_kept(faces, keep, nv, nf, q); }, bal)
+                                : compact_ballots(seg, [&](long p) {
+                                      const bool u = mesh_vertex_used(faces, keep, starts, order, nv, nf, p);
+                                      if (p < (long)nv) used[p] = (unsigned char)u;
+                                      return u;
+                                  }, bal);
+    const unsigned tot = compact_block_total(wave);
+    if (threadIdx.x == 0) partials[blockIdx.x] = tot;
+}
+
+// vertex emit: vmap[p] = the vertex's new index (for every used vertex: the faces read it); below the caller's capacity the position's bits
+// and the old index
+__global__ __launch_bounds__(256) void mesh_select_vertex_emit_kernel(const float* __restrict__ vertices, unsigned nv,
+                                                                      const unsigned char* __restrict__ used,
+                                                                      const long long* __restrict__ offsets, long long capacity,
+                                                                      int* __restrict__ vmap, float* __restrict__ out, int* __restrict__ index) {
+    const int lane = threadIdx.x & 63;
+    const long seg = compact_seg<MESH_TILE, long>();
+    unsigned long long bal[MESH_ITER];
+    const unsigned tot = compact_ballots(seg, [&](long p) { return p < (long)nv && used[p] != 0; }, bal);
+    long long base = compact_wave_base(tot, offsets, blockIdx.x);
+#pragma unroll
+    for (int jj = 0; jj < MESH_ITER; ++jj) {
+        const long p = seg + 64 * jj;
+        const long long idx = base + compact_rank(bal[jj]);
+        base += __popcll(bal[jj]);
+        if (!((bal[jj] >> lane) & 1ull)) continue;
+        vmap[p] = (int)idx;
+        if (idx >= capacity) continue;                                   // (never past what the caller allocated)
+        const float* s = vertices + 3 * p;
+        float* o = out + idx * 3;
+        o[0] = s[0];
+        o[1] = s[1];
+        o[2] = s[2];
+        index[idx] = (int)p;
+    }
+}
+
+__global__ __launch_bounds__(256) void mesh_select_face_emit_kernel(const int* __restrict__ faces, const unsigned char* __restrict__ keep,
+                                                                    unsigned nv, long nf, const long long* __restrict__ offsets,
+                                                                    long long capacity, const int* __restrict__ vmap, int* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const long seg = compact_seg<MESH_TILE, long>();
+    unsigned long long bal[MESH_ITER];
+    const unsigned tot = compact_ballots(seg, [&](long q) { return mesh_face_kept(faces, keep, nv, nf, q); }, bal);
+    long long base = compact_wave_base(tot, offsets, blockIdx.x);
+#pragma unroll
+    for (int jj = 0; jj < MESH_ITER; ++jj) {
+        const long q = seg + 64 * jj;
+        const long long idx = base + compact_rank(bal[jj]);
+        base += __popcll(bal[jj]);
+        if (!((bal[jj] >> lane) & 1ull) || idx >= capacity) continue;    // (never past what the caller allocated)
+        const int* f = faces + q * 3;
+        int* o = out + idx * 3;
+        o[0] = vmap[f[0]];
+        o[1] = vmap[f[1]];
+        o[2] = vmap[f[2]];
+    }
+}
+
 // ---- host side.  The order of the checks is the documented one (cer_mvs.h): negative sizes, too large, the frame, nothing to do, pointers.
 static bool mesh_is_finite(double v) { return v - v == 0.0; }
 static bool mesh_frame_ok(const double* origin, double voxel) {
@@ -486,5 +623,73 @@ extern "C" int cer_mesh_vertex_normals_f32(const float* vertices, long long nv, 
     hipLaunchKernelGGL(mesh_vertex_normals_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, (hipStream_t)stream, vertices, (unsigned)nv,
                        faces, (int)(3 * nf), starts, order, normals);
     CER_RETURN_IF_LAUNCH_FAILED();
+    return CER_OK;
+}
+
+// ---- components and selection (ABI 1190).  Checks: a negative size, nv or 3 nf >= 2^31, nothing to do, pointers.
+static int mesh_index_sizes(long long nv, long long nf) {
+    if (nv < 0 || nf < 0) return CER_EINVAL;
+    if (nv > 0x7fffffffLL || nf > 0x7fffffffLL / 3) return CER_ESHAPE;   // vertex indices and corner ids 0 .. 3 nf - 1 are int32
+    return CER_OK;
+}
+
+extern "C" int cer_mesh_label_sweeps_i32(const int* faces, long long nf, const int* starts, const int* order, long long nv, int* labels,
+                                         int* flags, int n_sweeps, void* stream) {
+    if (n_sweeps < 0) return CER_EINVAL;
+    const int rc = mesh_index_sizes(nv, nf);
+    if (rc != CER_OK) return rc;
+    if (nv == 0 || n_sweeps == 0) return CER_OK;
+    if (!starts || !labels || !flags || (nf && (!faces || !order))) return CER_EINVAL;
+    for (int i = 0; i < n_sweeps; ++i) {
+        hipLaunchKernelGGL(mesh_label_sweep_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, (hipStream_t)stream, faces, (int)(3 * nf),
+                           starts, order, (unsigned)nv, labels, flags + i);
+        CER_RETURN_IF_LAUNCH_FAILED();
+    }
+    return CER_OK;
+}
+
+extern "C" long cer_mesh_select_partials(long long nv, long long nf) {
+    const int rc = mesh_index_sizes(nv, nf);
+    if (rc != CER_OK) return rc;
+    if (nv == 0 || nf == 0) return 0;
+    return mesh_blocks((long)nv) + mesh_blocks((long)nf);
+}
+
+extern "C" int cer_mesh_select_count(const int* faces, long long nf, const int* starts, const int* order, long long nv,
+                                     const unsigned char* keep, unsigned char* used, unsigned int* partials, long long* offsets,
+                                     long long* totals, void* stream) {
+    const int rc = mesh_index_sizes(nv, nf);
+    if (rc != CER_OK) return rc;
+    if (nv == 0 || nf == 0) return CER_OK;                               // (no face, no vertex survives: totals are the caller's to zero)
+    if (!faces || !starts || !order || !keep || !used || !partials || !offsets || !totals) return CER_EINVAL;
+    const long vb = mesh_blocks((long)nv), fb = mesh_blocks((long)nf);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(mesh_select_count_kernel, dim3((unsigned)(vb + fb)), dim3(256), 0, st, faces, keep, starts, order, (unsigned)nv, (long)nf,
+                       (unsigned)vb, used, partials);
+    CER_RETURN_IF_LAUNCH_FAILED();
+    hipLaunchKernelGGL(mesh_scan_kernel, dim3(2), dim3(1024), 0, st, partials, vb, fb, offsets, totals);
+    CER_RETURN_IF_LAUNCH_FAILED();
+    return CER_OK;
+}
+
+extern "C" int cer_mesh_select_emit_f32(const float* vertices, long long nv, const int* faces, long long nf, const unsigned char* keep,
+                                        const unsigned char* used, const long long* offsets, long long nv_out, long long nf_out, int* vmap,
+                                        float* out_vertices, int* index, int* out_faces, void* stream) {
+    if (nv_out < 0 || nf_out < 0) return CER_EINVAL;
+    const int rc = mesh_index_sizes(nv, nf);
+    if (rc != CER_OK) return rc;
+    if (nv == 0 || nf == 0 || (nv_out == 0 && nf_out == 0)) return CER_OK;
+    if (!vertices || !faces || !keep || !used || !offsets || !vmap || (nv_out && (!out_vertices || !index)) || (nf_out && !out_faces))
+        return CER_EINVAL;
+    const long vb = mesh_blocks((long)nv), fb = mesh_blocks((long)nf);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(mesh_select_vertex_emit_kernel, dim3((unsigned)vb), dim3(256), 0, st, vertices, (unsigned)nv, used, offsets, nv_out, vmap,
+                       out_vertices, index);
+    CER_RETURN_IF_LAUNCH_FAILED();
+    if (nf_out) {
+        hipLaunchKernelGGL(mesh_select_face_emit_kernel, dim3((unsigned)fb), dim3(256), 0, st, faces, keep, (unsigned)nv, (long)nf,
+                           offsets + vb + 1, nf_out, vmap, out_faces);
+        CER_RETURN_IF_LAUNCH_FAILED();
+    }
     return CER_OK;
 }

@@ -3,7 +3,8 @@ integrated into a dense volume of truncated signed distances (``tsdf_volume``), 
 Vertex and face order are a pure function of the volume - every output slot is a flag at a fixed position, compacted without atomics - and
 all coordinate arithmetic is fp64 with fixed associations: tests/mesh_reference.py restates it in numpy, bit for bit.  Per-vertex attributes
 (C ABI 1180; tests/mesh_attr_reference.py): ``vertex_colors`` from the views that see a vertex, ``vertex_normals`` from the
-faces of any indexed triangle mesh, and both through the PLY writer and reader.
+faces of any indexed triangle mesh, and both through the PLY writer and reader.  Cleaning (C ABI 1190, DESIGN.md 3zc;
+tests/mesh_clean_reference.py): ``mesh_components``, ``select_faces`` and ``remove_small_components`` for any indexed triangle mesh.
 
 Every argument check that needs no device runs before the library is loaded."""
 import ctypes
@@ -334,12 +335,186 @@ def vertex_normals(vertices, faces):
     return normals
 
 
-MESH_OPTION_KEYS = ("voxel", "resolution", "trunc", "min_weight", "margin", "colors", "normals")
+# ---------------------------------------------------------------- components and small-piece removal (C ABI 1190)
+SWEEP_BATCH = 8                                              # sweeps per host read of the flags: a read costs less than a sweep of a large mesh
+
+
+def _check_faces(faces, who):
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
+        raise ValueError(f"{who}: faces int32 [nf, 3] expected")
+
+
+def _count_option(value, name, who):
+    """an int >= 1 (bool, float, 0 and negative values refused), or None"""
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, int) or value < 1:
+        raise ValueError(f"{who}: {name} must be an integer >= 1")
+    return value
+
+
+def _label_roots(faces, nv, starts, order):
+    """labels int32 [nv]: every vertex's root (the smallest index of its component), and the number of sweeps run up to and including the
+    first that changed nothing"""
+    dev, nf = faces.device, int(faces.shape[0])
+    labels = torch.arange(nv, device=dev, dtype=torch.int32)
+    if nv == 0 or nf == 0:
+        return labels, 0
+    lib, done = L.load(), 0
+    pf, ps, po = L.dev_ptr(faces, "faces", torch.int32), L.dev_ptr(starts, "starts", torch.int32), L.dev_ptr(order, "order", torch.int32)
+    while done < nv + 1:
+        n = min(SWEEP_BATCH, nv + 1 - done)
+        flags = torch.zeros(n, device=dev, dtype=torch.int32)
+        L.check(lib.cer_mesh_label_sweeps_i32(pf, nf, ps, po, nv, L.dev_ptr(labels, "labels", torch.int32), L.dev_ptr(flags, "flags", torch.int32),
+                                              n, L.cur_stream()), "mesh_label_sweeps")
+        changed = flags.cpu().tolist()                       # the batch's one host read
+        if 0 in changed:
+            return labels, done + changed.index(0) + 1
+        done += n
+    raise RuntimeError(f"mesh_components: the labels of {nv} vertices still changed in sweep {done}")
+
+
+def _components(faces, nv, starts, order):
+    """(vertex_component, face_component, n_faces, n_vertices, sweeps) of checked, contiguous device faces and their corner list"""
+    dev = faces.device
+    labels, sweeps = _label_roots(faces, nv, starts, order)
+    roots = torch.nonzero(labels == torch.arange(nv, device=dev, dtype=torch.int32)).reshape(-1).to(torch.int32)      # ascending
+    nc = int(roots.shape[0])
+    vertex_component = torch.searchsorted(roots, labels).to(torch.int32)
+    face_component = vertex_component[faces[:, 0].long()]
+    n_faces = torch.bincount(face_component, minlength=nc)
+    n_vertices = torch.bincount(vertex_component, minlength=nc)
+    return vertex_component, face_component, n_faces, n_vertices, sweeps
+
+
+def mesh_components(faces, nv, info=None):
+    """The connected components of any indexed triangle mesh: faces int32 [nf,3] with indices in 0 .. nv-1 (ValueError otherwise) on the
+    device -> (vertex_component int32 [nv], face_component int32 [nf], n_faces int64 [nc], n_vertices int64 [nc]) on the device.  Two
+    vertices are connected iff a chain of faces links them through shared vertex indices - vertex connectivity, not Open3D's shared-edge
+    adjacency of ``cluster_connected_triangles``: two pieces that touch in one vertex are ONE component.  Components are numbered by their
+    smallest vertex index, ascending; an unreferenced vertex is a component with no face; a face belongs to its first index's component.
+    ``info`` (a dict) gains "components" and "sweeps", the label sweeps run up to and including the first that changed nothing - the
+    contract is cer_mvs.h's, cer_mesh_label_sweeps_i32."""
+    _check_faces(faces, "mesh_components")
+    starts, order = vertex_faces(faces, nv)
+    nv = int(nv)
+    if not faces.is_cuda:
+        raise RuntimeError("mesh_components: faces must be a CUDA tensor (no CPU fallback)")
+    vc, fc, n_faces, n_vertices, sweeps = _components(faces.contiguous(), nv, starts, order)
+    if info is not None:
+        info.update(components=int(n_faces.shape[0]), sweeps=sweeps)
+    return vc, fc, n_faces, n_vertices
+
+
+def _check_attribute(a, nv, name, dtype, who):
+    if a is not None and (not isinstance(a, torch.Tensor) or a.dtype != dtype or tuple(a.shape) != (nv, 3)):
+        raise ValueError(f"{who}: {name} {str(dtype).replace('torch.', '')} [{nv}, 3] (or None) expected")
+
+
+def _check_mesh(vertices, faces, normals, colors, who):
+    _check_vertices(vertices, who)
+    _check_faces(faces, who)
+    nv = int(vertices.shape[0])
+    _check_attribute(normals, nv, "normals", torch.float32, who)
+    _check_attribute(colors, nv, "colors", torch.uint8, who)
+    for name, a in (("faces", faces), ("normals", normals), ("colors", colors)):
+        if a is not None and a.device != vertices.device:
+            raise ValueError(f"{who}: vertices and {name} must be on one device")
+
+
+def _select(vertices, faces, keep, starts, order, normals, colors):
+    """``select_faces`` on checked device arrays (vertices and faces contiguous, keep uint8 [nf]) and the faces' corner list"""
+    dev, nv, nf = vertices.device, int(vertices.shape[0]), int(faces.shape[0])
+    lib = L.load()
+    P = int(lib.cer_mesh_select_partials(nv, nf))
+    if P < 0:
+        L.check(P, "mesh_select_partials")
+    nvo = nfo = 0
+    if P:
+        used = torch.empty(nv, device=dev, dtype=torch.uint8)
+        partials = torch.empty(P, device=dev, dtype=torch.int32)
+        offsets = torch.empty(P + 2, device=dev, dtype=torch.int64)
+        totals = torch.zeros(2, device=dev, dtype=torch.int64)
+        pf, pk, pu = L.dev_ptr(faces, "faces", torch.int32), L.dev_ptr(keep, "keep", torch.uint8), L.dev_ptr(used, "used", torch.uint8)
+        L.check(lib.cer_mesh_select_count(pf, nf, L.dev_ptr(starts, "starts", torch.int32), L.dev_ptr(order, "order", torch.int32), nv, pk, pu,
+                                          L.dev_ptr(partials, "partials", torch.int32), L.dev_ptr(offsets, "offsets", torch.int64),
+                                          L.dev_ptr(totals, "totals", torch.int64), L.cur_stream()), "mesh_select_count")
+        nvo, nfo = (int(v) for v in totals.cpu())            # the one synchronisation: the outputs are allocated exactly
+    out_v = torch.empty(nvo, 3, device=dev, dtype=torch.float32)
+    out_f = torch.empty(nfo, 3, device=dev, dtype=torch.int32)
+    index = torch.empty(nvo, device=dev, dtype=torch.int32)
+    if nvo or nfo:
+        vmap = torch.empty(nv, device=dev, dtype=torch.int32)
+        L.check(lib.cer_mesh_select_emit_f32(L.dev_ptr(vertices, "vertices"), nv, pf, nf, pk, pu, L.dev_ptr(offsets, "offsets", torch.int64), nvo, nfo,
+                                             L.dev_ptr(vmap, "vmap", torch.int32), L.dev_ptr(out_v, "vertices") if nvo else None,
+                                             L.dev_ptr(index, "index", torch.int32) if nvo else None,
+                                             L.dev_ptr(out_f, "faces", torch.int32) if nfo else None, L.cur_stream()), "mesh_select_emit")
+    gather = index.long()
+    return (out_v, out_f, index, None if normals is None else normals.index_select(0, gather),
+            None if colors is None else colors.index_select(0, gather))
+
+
+def select_faces(vertices, faces, keep, normals=None, colors=None):
+    """The sub-mesh of a face mask (Open3D's ``remove_triangles_by_mask`` then ``remove_unreferenced_vertices``): vertices float32 [nv,3],
+    faces int32 [nf,3] with indices in 0 .. nv-1 (ValueError otherwise) and keep bool / uint8 [nf] on the device, ``normals`` float32 [nv,3]
+    and ``colors`` uint8 [nv,3] optional -> (vertices', faces', index int32 [nv'], normals' | None, colors' | None) on the device.  Kept
+    faces keep their order, with indices renumbered; a vertex survives iff a kept face names it, and survivors keep their order; ``index``
+    holds the old index of every surviving vertex and the attributes are gathered with it - cer_mvs.h, cer_mesh_select_count."""
+    who = "select_faces"
+    _check_mesh(vertices, faces, normals, colors, who)
+    nf = int(faces.shape[0])
+    if not isinstance(keep, torch.Tensor) or keep.dtype not in (torch.bool, torch.uint8) or tuple(keep.shape) != (nf,):
+        raise ValueError(f"{who}: keep bool or uint8 [{nf}] expected")
+    if keep.device != vertices.device:
+        raise ValueError(f"{who}: vertices and keep must be on one device")
+    starts, order = vertex_faces(faces, vertices.shape[0])
+    if not vertices.is_cuda:
+        raise RuntimeError(f"{who}: vertices must be a CUDA tensor (no CPU fallback)")
+    return _select(vertices.contiguous(), faces.contiguous(), keep.to(torch.uint8).contiguous(), starts, order, normals, colors)
+
+
+def remove_small_components(vertices, faces, min_faces=None, keep_largest=None, normals=None, colors=None, info=None):
+    """The mesh without its small pieces: component c of ``mesh_components`` is kept iff n_faces[c] >= ``min_faces`` (where given) and c is
+    among the first ``keep_largest`` components sorted by (n_faces descending, id ascending) (where given); at least one of the two must be
+    given, each an int >= 1 (ValueError otherwise).  Then ``select_faces`` on the kept components' faces, and its five results.  ``info`` (a
+    dict) gains "components", "removed_components" (those not kept, faceless ones included), "removed_faces", "removed_vertices" and
+    "sweeps"."""
+    who = "remove_small_components"
+    min_faces = _count_option(min_faces, "min_faces", who)
+    keep_largest = _count_option(keep_largest, "keep_largest", who)
+    if min_faces is None and keep_largest is None:
+        raise ValueError(f"{who}: give min_faces or keep_largest (or both)")
+    _check_mesh(vertices, faces, normals, colors, who)
+    nv, nf = int(vertices.shape[0]), int(faces.shape[0])
+    starts, order = vertex_faces(faces, nv)
+    if not vertices.is_cuda:
+        raise RuntimeError(f"{who}: vertices must be a CUDA tensor (no CPU fallback)")
+    vertices, faces = vertices.contiguous(), faces.contiguous()
+    _, face_component, n_faces, _, sweeps = _components(faces, nv, starts, order)
+    nc = int(n_faces.shape[0])
+    kept = torch.ones(nc, device=faces.device, dtype=torch.bool)
+    if min_faces is not None:
+        kept &= n_faces >= min_faces
+    if keep_largest is not None:
+        by_size = torch.sort(n_faces, descending=True, stable=True).indices                  # ties: the smaller id first
+        first = torch.zeros(nc, device=faces.device, dtype=torch.bool)
+        first[by_size[:keep_largest]] = True
+        kept &= first
+    keep = kept[face_component.long()].to(torch.uint8)
+    out = _select(vertices, faces, keep, starts, order, normals, colors)
+    if info is not None:
+        info.update(components=nc, removed_components=nc - int(kept.sum()), removed_faces=nf - int(out[1].shape[0]),
+                    removed_vertices=nv - int(out[0].shape[0]), sweeps=sweeps)
+    return out
+
+
+MESH_OPTION_KEYS = ("voxel", "resolution", "trunc", "min_weight", "margin", "colors", "normals", "min_component", "keep_largest")
 
 
 def mesh_options(mesh):
     """``reconstruct_scan``'s ``mesh`` argument, checked: True or a dict with keys of MESH_OPTION_KEYS -> a dict.  "colors": True or
-    {"tol": a positive finite number} (default: the mesh's trunc); "normals": True."""
+    {"tol": a positive finite number} (default: the mesh's trunc); "normals": True; "min_component" (``remove_small_components``'s
+    ``min_faces``) and "keep_largest": an int >= 1 each."""
     if mesh is True:
         return {}
     if not isinstance(mesh, dict):
@@ -357,6 +532,9 @@ def mesh_options(mesh):
             raise ValueError("mesh: colors: tol must be a positive finite number")
     if "normals" in mesh and mesh["normals"] is not True:
         raise ValueError("mesh: normals must be True")
+    for key in ("min_component", "keep_largest"):
+        if key in mesh and _count_option(mesh[key], key, "mesh") is None:
+            raise ValueError(f"mesh: {key} must be an integer >= 1")
     return dict(mesh)
 
 
@@ -364,14 +542,21 @@ def mesh_of_scan(xyz, est, masks, Ks, Es, refs, options, colors=None):
     """``reconstruct_scan``'s mesh step: the grid around the fused cloud, then ``mesh_from_depth_maps`` over the emitted views -> (vertices,
     faces, info, attributes).  With the options "colors" / "normals": ``vertex_colors`` over the same views from the ``colors`` planes
     [N,3,h,w] (tol: the option's, or the mesh's trunc) / ``vertex_normals``; ``attributes`` then holds "mesh_colors" / "mesh_normals" (device
-    tensors) and ``info`` gains "coloured", the number of vertices that a view sees."""
+    tensors) and ``info`` gains "coloured", the number of vertices that a view sees.  With "min_component" / "keep_largest":
+    ``remove_small_components`` right after the extraction, before the attributes; ``info``'s "nv" and "nf" then describe the returned mesh
+    and it gains "extracted": (nv, nf) of the extraction, and the removal's figures."""
     opt = dict(options)
     min_weight = opt.pop("min_weight", 1)
     trunc = opt.pop("trunc", None)
     want_colors, want_normals = opt.pop("colors", None), opt.pop("normals", None)
+    min_component, keep_largest = opt.pop("min_component", None), opt.pop("keep_largest", None)
     grid = grid_for(xyz, trunc=trunc, **opt)
     info, attributes = {}, {}
     v, f = mesh_from_depth_maps(est, masks, Ks, Es, grid, trunc=trunc, views=refs, min_weight=min_weight, info=info)
+    if min_component is not None or keep_largest is not None:            # before the attributes: they are computed on what is returned
+        info["extracted"] = (info["nv"], info["nf"])
+        v, f, _, _, _ = remove_small_components(v, f, min_faces=min_component, keep_largest=keep_largest, info=info)
+        info.update(nv=int(v.shape[0]), nf=int(f.shape[0]))
     if want_colors is not None:
         if colors is None:
             raise ValueError("mesh: colors asked for without colour planes")

@@ -384,7 +384,10 @@ def reconstruct_scan(model_or_ckpt, images, poses, intrinsics, names, pairs, sca
     per vertex from the views that see it (``mesh.vertex_colors`` over the colour planes of the cloud; ``tol``, default the mesh's trunc, is
     the occlusion bound on |depth - uz|): the result gains "mesh_colors" (uint8 [nv, 3]) and ``mesh_info`` "coloured", the number of vertices
     some view sees; "normals": True - area-weighted vertex normals (``mesh.vertex_normals``): "mesh_normals" (float32 [nv, 3]).
-    ``result_mesh.ply`` carries what was asked for.  Without these keys nothing changes."""
+    ``result_mesh.ply`` carries what was asked for.  Without these keys nothing changes.  And two: "min_component": n and
+    "keep_largest": k, an int >= 1 each - ``mesh.remove_small_components`` right after the extraction: a connected piece stays iff it has at
+    least n faces and is among the k largest; colours and normals are those of the returned mesh; ``mesh_info`` "nv" / "nf" describe it and
+    it gains "extracted" (nv, nf before), "components", "removed_components", "removed_faces", "removed_vertices" and "sweeps"."""
     two_pass = isinstance(rescale, (tuple, list))
     passes = [r for r in rescale] if two_pass else [rescale]
     if two_pass and (len(passes) != 2 or passes[1] != 2 * passes[0]):

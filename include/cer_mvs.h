@@ -790,6 +790,51 @@ int cer_mesh_vertex_colors_u8(const float* vertices, long long nv, const float* 
 int cer_mesh_vertex_normals_f32(const float* vertices, long long nv, const int* faces, long long nf, const int* starts, const int* order,
                                 float* normals, void* stream);
 
+/* Connected components and sub-meshes of any indexed triangle mesh (ABI 1190; csrc/mesh.hip, cer-mvs_amd/mesh.py mesh_components /
+ * select_faces / remove_small_components): integers only, no atomics, the same bytes on every run.  faces int32 [nf, 3];
+ * starts int32 [nv + 1] and order int32 [3 nf]: the CSR corner list of cer_mesh_vertex_normals_f32.  Checks in this order, all before any
+ * launch: (1) a negative size (nv, nf, n_sweeps, nv_out, nf_out) -> CER_EINVAL; (2) nv or 3 nf >= 2^31 -> CER_ESHAPE; (3) nothing to do ->
+ * CER_OK with nothing launched (the sweeps: nv == 0 or n_sweeps == 0; the selection: nv == 0 or nf == 0 - no face is kept and no vertex
+ * survives, totals are the caller's to zero - and for the emit also nv_out == 0 and nf_out == 0); (4) a null pointer -> CER_EINVAL (the
+ * sweeps: faces and order may be null iff nf == 0; the emit: out_vertices and index may be null iff nv_out == 0, out_faces iff nf_out == 0).
+ * A face index outside 0 .. nv-1, a corner id outside 0 .. 3 nf - 1 and a label outside 0 .. nv-1 are skipped, never read through (the
+ * Python layer refuses such faces).
+ *
+ * Components.  Two vertices are connected iff a chain of faces links them through shared vertex INDICES: a face links its three indices (one
+ *   with repeated indices is still a face).  This is vertex connectivity, not shared-edge adjacency: two pieces that touch in one vertex
+ *   are one component.  The root of a component is its smallest vertex index; components are numbered 0 .. nc-1 by ascending root; an
+ *   unreferenced vertex is a component of its own with no face; a face's component is that of its first index.
+ *   cer_mesh_label_sweeps_i32: labels int32 [nv], which the caller initialises to 0, 1, .., nv-1; flags: n_sweeps ints, which the caller
+ *     zeroes.  Launches n_sweeps sweeps in stream order; sweep i owns flags[i].  In a sweep one thread owns vertex v and is the only writer
+ *     of labels[v]: m = labels[labels[v]]; for every corner e in starts[v] .. starts[v + 1] - 1 and every index u of face order[e] / 3,
+ *     m = min(m, labels[labels[u]]); if m < labels[v], it stores m and stores 1 into the sweep's flag.  In place: a label read from another
+ *     vertex is this sweep's or the previous one's, either way the index of a vertex of the same component; labels only fall; the only
+ *     fixed point is labels[v] = the root, so the final bytes are unique although the intermediate ones are not.  The flag store is the
+ *     only store several threads make to one address, all of them the same value.  No loop's trip count depends on another thread's
+ *     stores: no find-root walk, no spin, no grid-wide barrier - a sweep is two dependent loads per neighbour and ends.  The component's
+ *     minimum advances at least one hop per sweep, so a sweep that changes nothing comes within nv + 1 sweeps; sweeps past it change
+ *     nothing and leave their flags 0.
+ * Selection.  Face q is kept iff keep[q] != 0 (keep: nf bytes) and its three indices are in range; vertex p survives iff a kept face is
+ *   among the faces around it, gathered through the CSR list (no scatter).  Kept faces and surviving vertices keep their order; the indices
+ *   are renumbered.  Both leave through the ordered compaction of cer_mesh_count, CER_MESH_TILE positions per block, the vertex tiles
+ *   followed by the face tiles.
+ *   cer_mesh_select_partials: HOST function: ceil(nv / CER_MESH_TILE) + ceil(nf / CER_MESH_TILE) (0 if nv or nf is 0): partials [that
+ *     many] unsigned, offsets [that many + 2] 64-bit.
+ *   cer_mesh_select_count: ONE count launch over both kinds of tile, which also stores used [nv] bytes (1 iff the vertex survives), then the
+ *     two-block scan; totals[0] = nv_out, totals[1] = nf_out (2 DEVICE 64-bit integers).
+ *   cer_mesh_select_emit_f32: nv_out, nf_out: what the count found, and the rows of the outputs - never a byte beyond them.  A vertex emit
+ *     writes out_vertices float32 [nv_out, 3] (the position's bits), index int32 [nv_out] (the old index of every surviving vertex) and
+ *     vmap int32 [nv] (workspace: the new index of every surviving vertex); a face emit writes out_faces int32 [nf_out, 3] = vmap of the
+ *     old indices.  Workspace: 5 bytes per vertex (used, vmap) and 12 bytes per CER_MESH_TILE positions. */
+int cer_mesh_label_sweeps_i32(const int* faces, long long nf, const int* starts, const int* order, long long nv, int* labels, int* flags,
+                              int n_sweeps, void* stream);
+long cer_mesh_select_partials(long long nv, long long nf);
+int cer_mesh_select_count(const int* faces, long long nf, const int* starts, const int* order, long long nv, const unsigned char* keep,
+                          unsigned char* used, unsigned int* partials, long long* offsets, long long* totals, void* stream);
+int cer_mesh_select_emit_f32(const float* vertices, long long nv, const int* faces, long long nf, const unsigned char* keep,
+                             const unsigned char* used, const long long* offsets, long long nv_out, long long nf_out, int* vmap,
+                             float* out_vertices, int* index, int* out_faces, void* stream);
+
 /* Multi-GPU row-slab exchange (cer-mvs_amd/slab.py): up to CER_COPY_MAX_SEG contiguous fp32 ranges copied by ONE launch -
  * the pack of a rank's (net, disp) border strips into its send buffer, and the refresh of its halo rows from the gathered
  * strips.  n[i] floats from src[i] to dst[i]; n[i] == 0 skips a segment.  Device pointers; ranges must not overlap. */
