@@ -14,6 +14,10 @@
 //
 // Cleaning (ABI 1190; tests/mesh_clean_reference.py): the connected components of any indexed triangle mesh by min-label
 // sweeps without atomics or data-dependent waiting, and the sub-mesh of a face mask through the same ordered compaction.
+//
+// Simplification (ABI 1200; tests/mesh_simplify_reference.py): vertex clustering on the cells of cloud_eval.py's CloudIndex -
+// one thread per cluster sums its members (and their faces' plane quadrics) in member order, faces are remapped, rotated and deduplicated
+// through two stable sorts, and what survives leaves through the selection above.
 #include "common.hpp"
 #include "compact.hpp"
 
@@ -691,5 +695,257 @@ extern "C" int cer_mesh_select_emit_f32(const float* vertices, long long nv, con
                            offsets + vb + 1, nf_out, vmap, out_faces);
         CER_RETURN_IF_LAUNCH_FAILED();
     }
+    return CER_OK;
+}
+
+// ---- simplification by vertex clustering (ABI 1200; tests/mesh_simplify_reference.py).  The clusters are the occupied cells of
+// cloud_eval.py's CloudIndex over the vertices: order (int64 [nv], the stable sort of the cell keys), cell_start (int64 [ncells + 1]) and
+// cell_keys (int64 [ncells]) are that class's arrays as they are.  Every kernel below has one writer per address and no atomics.
+#define MESH_KEY_B (CER_GRID_COORD_LIMIT - 1)
+#define MESH_KEY_MASK 0x1fffffLL
+
+// cluster[order[p]] = the cell r with cell_start[r] <= p < cell_start[r + 1]; -1 at and beyond cell_start[ncells] (the non-finite vertices)
+__global__ __launch_bounds__(256) void mesh_cluster_map_kernel(const long long* __restrict__ order, const long long* __restrict__ cell_start,
+                                                               long nv, long ncells, int* __restrict__ cluster) {
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= nv) return;
+    const long long v = order[p];
+    if ((unsigned long long)v >= (unsigned long long)nv) return;         // (never written through)
+    int r = -1;
+    if (p < cell_start[ncells]) {
+        long lo = 0, hi = ncells;                                        // the last r in [0, ncells) with cell_start[r] <= p
+        while (hi - lo > 1) {
+            const long mid = lo + (hi - lo) / 2;
+            if (cell_start[mid] <= p) lo = mid; else hi = mid;
+        }
+        r = (int)lo;
+    }
+    cluster[v] = r;
+}
+
+// ---- representatives: ONE thread owns a cluster for its whole member walk - the sums are added in member order, which a wave-wide reduction
+// would change.  Members are gathered by index; in the quadric form the faces around a member are the CSR corners of the normals kernel.  An
+// index, corner id or face index outside its range is skipped, never read through.
+template <bool QUADRIC>
+__global__ __launch_bounds__(256) void mesh_cluster_reps_kernel(const float* __restrict__ vertices, long nv, const int* __restrict__ faces,
+                                                                int corners, const int* __restrict__ starts, const int* __restrict__ corner_order,
+                                                                const long long* __restrict__ order, const long long* __restrict__ cell_start,
+                                                                const long long* __restrict__ cell_keys, long ncells, double ox, double oy,
+                                                                double oz, double cell, double regularisation,
+                                                                const unsigned char* __restrict__ colors, float* __restrict__ reps,
+                                                                unsigned char* __restrict__ rep_colors, unsigned char* __restrict__ took) {
+    const long r = (long)blockIdx.x * 256 + threadIdx.x;
+    if (r >= ncells) return;
+    long p0 = cell_start[r], p1 = cell_start[r + 1];
+    p0 = p0 < 0 ? 0 : p0;
+    p1 = p1 > nv ? nv : p1;
+    const long long key = cell_keys[r];
+    const double bx = ox + ((double)((int)(key & MESH_KEY_MASK) - MESH_KEY_B) + 0.5) * cell;
+    const double by = oy + ((double)((int)((key >> 21) & MESH_KEY_MASK) - MESH_KEY_B) + 0.5) * cell;
+    const double bz = oz + ((double)((int)((key >> 42) & MESH_KEY_MASK) - MESH_KEY_B) + 0.5) * cell;
+    double sx = 0.0, sy = 0.0, sz = 0.0;
+    double mxx = 0.0, mxy = 0.0, mxz = 0.0, myy = 0.0, myz = 0.0, mzz = 0.0, qx = 0.0, qy = 0.0, qz = 0.0;
+    unsigned long long cr = 0, cg = 0, cb = 0;
+    long count = 0;
+    for (long p = p0; p < p1; ++p) {
+        const long long v = order[p];
+        if ((unsigned long long)v >= (unsigned long long)nv) continue;
+        const float* P = vertices + 3 * v;
+        sx += (double)P[0];
+        sy += (double)P[1];
+        sz += (double)P[2];
+        ++count;
+        if (colors) {
+            const unsigned char* c = colors + 3 * v;
+            cr += c[0];
+            cg += c[1];
+            cb += c[2];
+        }
+        if (!QUADRIC) continue;
+        int e0 = starts[v], e1 = starts[v + 1];
+        e0 = e0 < 0 ? 0 : e0;
+        e1 = e1 > corners ? corners : e1;
+        for (int e = e0; e < e1; ++e) {
+            const int corner = corner_order[e];
+            if (corner < 0 || corner >= corners) continue;
+            const int* f = faces + (long)(corner / 3) * 3;
+            const int ia = f[0], ib = f[1], ic = f[2];
+            if ((unsigned)ia >= (unsigned long)nv || (unsigned)ib >= (unsigned long)nv || (unsigned)ic >= (unsigned long)nv) continue;
+            const float *A = vertices + 3l * ia, *B = vertices + 3l * ib, *C = vertices + 3l * ic;
+            const double ax = (double)A[0], ay = (double)A[1], az = (double)A[2];
+            const double ux = (double)B[0] - ax, uy = (double)B[1] - ay, uz = (double)B[2] - az;
+            const double wx = (double)C[0] - ax, wy = (double)C[1] - ay, wz = (double)C[2] - az;
+            const double nx = uy * wz - uz * wy;
+            const double ny = uz * wx - ux * wz;
+            const double nz = ux * wy - uy * wx;
+            const double d = (nx * (ax - bx) + ny * (ay - by)) + nz * (az - bz);
+            mxx += nx * nx;
+            mxy += nx * ny;
+            mxz += nx * nz;
+            myy += ny * ny;
+            myz += ny * nz;
+            mzz += nz * nz;
+            qx += nx * d;
+            qy += ny * d;
+            qz += nz * d;
+        }
+    }
+    const double k = (double)count;
+    const double mx = sx / k, my = sy / k, mz = sz / k;
+    double rx = mx, ry = my, rz = mz;
+    bool minimiser = false;
+    if (QUADRIC) {
+        const double lam = (regularisation * ((mxx + myy) + mzz)) / 3.0;
+        const double a = mxx + lam, dd = myy + lam, ff = mzz + lam;
+        const double tx = qx + lam * (mx - bx), ty = qy + lam * (my - by), tz = qz + lam * (mz - bz);
+        const double c00 = dd * ff - myz * myz;
+        const double c01 = mxz * myz - mxy * ff;
+        const double c02 = mxy * myz - mxz * dd;
+        const double c11 = a * ff - mxz * mxz;
+        const double c12 = mxy * mxz - a * myz;
+        const double c22 = a * dd - mxy * mxy;
+        const double det = (a * c00 + mxy * c01) + mxz * c02;
+        const double x = ((c00 * tx + c01 * ty) + c02 * tz) / det;
+        const double y = ((c01 * tx + c11 * ty) + c12 * tz) / det;
+        const double z = ((c02 * tx + c12 * ty) + c22 * tz) / det;
+        const double half = cell / 2.0;
+        minimiser = lam > 0.0 && det > 0.0 && det - det == 0.0 && x - x == 0.0 && y - y == 0.0 && z - z == 0.0 && fabs(x) <= half
+                    && fabs(y) <= half && fabs(z) <= half;
+        if (minimiser) {
+            rx = bx + x;
+            ry = by + y;
+            rz = bz + z;
+        }
+    }
+    float* o = reps + 3 * r;
+    o[0] = (float)rx;
+    o[1] = (float)ry;
+    o[2] = (float)rz;
+    took[r] = (unsigned char)minimiser;
+    if (colors) {
+        unsigned char* oc = rep_colors + 3 * r;
+        const unsigned long long n = count > 0 ? (unsigned long long)count : 1ull;
+        oc[0] = (unsigned char)(cr / n);
+        oc[1] = (unsigned char)(cg / n);
+        oc[2] = (unsigned char)(cb / n);
+    }
+}
+
+// ---- faces: the cluster triple of every face, rotated so that its smallest id comes first (orientation kept), and a valid byte: the three
+// indices in range, every one with a cluster, the three clusters distinct.  An invalid face gets (-1, -1, -1).
+__global__ __launch_bounds__(256) void mesh_cluster_faces_kernel(const int* __restrict__ faces, long nf, const int* __restrict__ cluster, long nv,
+                                                                 int* __restrict__ triples, unsigned char* __restrict__ valid) {
+    const long q = (long)blockIdx.x * 256 + threadIdx.x;
+    if (q >= nf) return;
+    const int* f = faces + 3 * q;
+    const int ia = f[0], ib = f[1], ic = f[2];
+    int a = -1, b = -1, c = -1;
+    if (ia >= 0 && ib >= 0 && ic >= 0 && ia < nv && ib < nv && ic < nv) {
+        a = cluster[ia];
+        b = cluster[ib];
+        c = cluster[ic];
+    }
+    const bool ok = a >= 0 && b >= 0 && c >= 0 && a != b && b != c && a != c;
+    int t0 = -1, t1 = -1, t2 = -1;
+    if (ok) {
+        if (a < b && a < c) {
+            t0 = a, t1 = b, t2 = c;
+        } else if (b < a && b < c) {
+            t0 = b, t1 = c, t2 = a;
+        } else {
+            t0 = c, t1 = a, t2 = b;
+        }
+    }
+    int* o = triples + 3 * q;
+    o[0] = t0;
+    o[1] = t1;
+    o[2] = t2;
+    valid[q] = (unsigned char)ok;
+}
+
+// ---- heads of the lexicographically sorted triples: perm[p] is the face at sorted position p (two stable sorts: equal triples keep ascending
+// face index), keep[perm[p]] = valid && (p == 0 || triple[perm[p]] != triple[perm[p - 1]]) - the lowest face index of every distinct triple
+__global__ __launch_bounds__(256) void mesh_face_heads_kernel(const int* __restrict__ triples, const unsigned char* __restrict__ valid,
+                                                              const long long* __restrict__ perm, long nf, unsigned char* __restrict__ keep) {
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= nf) return;
+    const long long q = perm[p];
+    if ((unsigned long long)q >= (unsigned long long)nf) return;         // (never written through)
+    bool head = valid[q] != 0;
+    if (head && p > 0) {
+        const long long w = perm[p - 1];
+        if ((unsigned long long)w < (unsigned long long)nf) {
+            const int *s = triples + 3 * q, *t = triples + 3 * w;
+            head = s[0] != t[0] || s[1] != t[1] || s[2] != t[2];
+        }
+    }
+    keep[q] = (unsigned char)head;
+}
+
+// Checks, in the order of the section "Surface mesh": a negative size, too large, the frame, nothing to do, pointers.
+static int mesh_cluster_sizes(long long nv, long long nf, long long ncells) {
+    if (nv < 0 || nf < 0 || ncells < 0) return CER_EINVAL;
+    if (nv > 0x7fffffffLL || nf > 0x7fffffffLL / 3 || ncells > 0x7fffffffLL || ncells > nv) return CER_ESHAPE;
+    return CER_OK;
+}
+
+extern "C" int cer_mesh_cluster_map_i32(const long long* order, const long long* cell_start, long long nv, long long ncells, int* cluster,
+                                        void* stream) {
+    const int rc = mesh_cluster_sizes(nv, 0, ncells);
+    if (rc != CER_OK) return rc;
+    if (nv == 0) return CER_OK;
+    if (!order || !cell_start || !cluster) return CER_EINVAL;
+    hipLaunchKernelGGL(mesh_cluster_map_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, (hipStream_t)stream, order, cell_start, (long)nv,
+                       (long)ncells, cluster);
+    CER_RETURN_IF_LAUNCH_FAILED();
+    return CER_OK;
+}
+
+extern "C" int cer_mesh_cluster_reps_f32(const float* vertices, long long nv, const int* faces, long long nf, const int* starts,
+                                         const int* corner_order, const long long* order, const long long* cell_start,
+                                         const long long* cell_keys, long long ncells, const double* origin, double cell, int quadric,
+                                         double regularisation, const unsigned char* colors, float* reps, unsigned char* rep_colors,
+                                         unsigned char* took, void* stream) {
+    const int rc = mesh_cluster_sizes(nv, nf, ncells);
+    if (rc != CER_OK) return rc;
+    if (!mesh_frame_ok(origin, cell) || !(mesh_is_finite(regularisation) && regularisation > 0.0)) return CER_EINVAL;
+    if (ncells == 0) return CER_OK;
+    if (!vertices || !order || !cell_start || !cell_keys || !reps || !took || (colors == nullptr) != (rep_colors == nullptr)) return CER_EINVAL;
+    if (quadric && (!starts || (nf && (!faces || !corner_order)))) return CER_EINVAL;
+    const dim3 grid((unsigned)((ncells + 255) / 256));
+    hipStream_t st = (hipStream_t)stream;
+    if (quadric)
+        hipLaunchKernelGGL(mesh_cluster_reps_kernel<true>, grid, dim3(256), 0, st, vertices, (long)nv, faces, (int)(3 * nf), starts, corner_order,
+                           order, cell_start, cell_keys, (long)ncells, origin[0], origin[1], origin[2], cell, regularisation, colors, reps,
+                           rep_colors, took);
+    else
+        hipLaunchKernelGGL(mesh_cluster_reps_kernel<false>, grid, dim3(256), 0, st, vertices, (long)nv, faces, (int)(3 * nf), starts, corner_order,
+                           order, cell_start, cell_keys, (long)ncells, origin[0], origin[1], origin[2], cell, regularisation, colors, reps,
+                           rep_colors, took);
+    CER_RETURN_IF_LAUNCH_FAILED();
+    return CER_OK;
+}
+
+extern "C" int cer_mesh_cluster_faces_i32(const int* faces, long long nf, const int* cluster, long long nv, int* triples, unsigned char* valid,
+                                          void* stream) {
+    const int rc = mesh_cluster_sizes(nv, nf, 0);
+    if (rc != CER_OK) return rc;
+    if (nf == 0) return CER_OK;
+    if (!faces || !triples || !valid || (nv && !cluster)) return CER_EINVAL;
+    hipLaunchKernelGGL(mesh_cluster_faces_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, (hipStream_t)stream, faces, (long)nf, cluster,
+                       (long)nv, triples, valid);
+    CER_RETURN_IF_LAUNCH_FAILED();
+    return CER_OK;
+}
+
+extern "C" int cer_mesh_face_heads_u8(const int* triples, const unsigned char* valid, const long long* perm, long long nf, unsigned char* keep,
+                                      void* stream) {
+    const int rc = mesh_cluster_sizes(0, nf, 0);
+    if (rc != CER_OK) return rc;
+    if (nf == 0) return CER_OK;
+    if (!triples || !valid || !perm || !keep) return CER_EINVAL;
+    hipLaunchKernelGGL(mesh_face_heads_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, (hipStream_t)stream, triples, valid, perm,
+                       (long)nf, keep);
+    CER_RETURN_IF_LAUNCH_FAILED();
     return CER_OK;
 }

@@ -5,6 +5,7 @@ all coordinate arithmetic is fp64 with fixed associations: tests/mesh_reference.
 (C ABI 1180; tests/mesh_attr_reference.py): ``vertex_colors`` from the views that see a vertex, ``vertex_normals`` from the
 faces of any indexed triangle mesh, and both through the PLY writer and reader.  Cleaning (C ABI 1190, DESIGN.md 3zc;
 tests/mesh_clean_reference.py): ``mesh_components``, ``select_faces`` and ``remove_small_components`` for any indexed triangle mesh.
+Simplification (C ABI 1200; tests/mesh_simplify_reference.py): ``simplify_vertex_clustering``, likewise.
 
 Every argument check that needs no device runs before the library is loaded."""
 import ctypes
@@ -299,6 +300,11 @@ def vertex_faces(faces, nv):
     """The faces around every vertex as a CSR list over the 3 nf corner entries ``faces.reshape(-1)`` (corner id = 3 * face + corner):
     faces int32 [nf,3] with indices in 0 .. nv-1 (ValueError otherwise) -> (starts int32 [nv + 1], order int32 [3 nf]) on the faces'
     device: ``order[starts[v] : starts[v + 1]]`` are the corner ids that name vertex v, ascending (a stable sort).  Torch ops only."""
+    return _corner_list(_corner_keys(faces, nv), int(nv))
+
+
+def _corner_keys(faces, nv):
+    """``vertex_faces``' checks -> the flat corner entries"""
     if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
         raise ValueError("vertex_faces: faces int32 [nf, 3] expected")
     nv = int(nv)
@@ -307,8 +313,13 @@ def vertex_faces(faces, nv):
     keys = faces.reshape(-1)
     if keys.numel() and (int(keys.min()) < 0 or int(keys.max()) >= nv):
         raise ValueError(f"vertex_faces: faces must hold indices in 0 .. {nv - 1}")
+    return keys
+
+
+def _corner_list(keys, nv):
+    """``vertex_faces`` on the flat corner entries; entries below 0 sort in front of starts[0] and are in nobody's list"""
     ordered, order = torch.sort(keys, stable=True)
-    starts = torch.searchsorted(ordered, torch.arange(nv + 1, device=faces.device, dtype=torch.int32))
+    starts = torch.searchsorted(ordered, torch.arange(nv + 1, device=keys.device, dtype=torch.int32))
     return starts.to(torch.int32), order.to(torch.int32)
 
 
@@ -508,13 +519,105 @@ def remove_small_components(vertices, faces, min_faces=None, keep_largest=None, 
     return out
 
 
-MESH_OPTION_KEYS = ("voxel", "resolution", "trunc", "min_weight", "margin", "colors", "normals", "min_component", "keep_largest")
+# ---------------------------------------------------------------- simplification by vertex clustering (C ABI 1200)
+REPRESENTATIVES = ("quadric", "mean")
+SIMPLIFY_KEYS = ("voxels", "cell", "representative", "regularisation")
+
+
+def _positive(value, name, who):
+    """a positive finite number as a float (bool refused)"""
+    if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)) or not (math.isfinite(value) and value > 0):
+        raise ValueError(f"{who}: {name} must be a positive finite number")
+    return float(value)
+
+
+def _representative(value, who):
+    if not isinstance(value, str) or value not in REPRESENTATIVES:
+        raise ValueError(f"{who}: representative must be one of {list(REPRESENTATIVES)}")
+    return value
+
+
+def simplify_vertex_clustering(vertices, faces, cell, representative="quadric", regularisation=1e-3, colors=None, info=None):
+    """Vertex clustering (Rossignac-Borrel; Open3D's ``simplify_vertex_clustering``) of any indexed triangle mesh: vertices float32 [nv,3] and
+    faces int32 [nf,3] with indices in 0 .. nv-1 (ValueError otherwise) on the device, ``colors`` uint8 [nv,3] optional -> (vertices', faces',
+    cluster int32 [nv], colors' | None) on the device.  The vertices inside one cell of edge ``cell`` (the occupied cells of
+    ``cloud_eval.CloudIndex(vertices, cell)``: origin at the per-axis minimum of the finite vertices; more than 2^20 cells along an axis is
+    its ValueError) become one vertex: with ``representative`` "mean" their mean, with "quadric" (Lindstrom) the point that minimises the
+    summed squared distances to the planes of the faces around them, regularised towards the mean with weight ``regularisation`` (a finite
+    number > 0) times the quadric's mean eigenvalue, and the mean itself where that point is not well defined or leaves the cell.  Colours
+    are the members' integer mean.  A face stays iff its three vertices fall into three different cells; it is rotated so that its smallest
+    new index comes first (orientation kept); of faces that are then equal the one with the lowest index stays (opposite orientations are
+    different faces); faces keep their order.  A cell that no surviving face names is dropped.  ``cluster[v]``: the output index of v's cell,
+    -1 for a non-finite vertex or a dropped cell.  ``info`` (a dict) gains "clusters" (occupied cells), "degenerate_faces" (not valid),
+    "duplicate_faces", "dropped_clusters" and "quadric" (cells that took the minimiser).
+
+    Guaranteed: distinct indices per face, no two faces equal up to rotation, every vertex referenced, and if every directed edge of the
+    input has its reverse, so has every directed edge of the output.  NOT guaranteed: manifoldness - one directed edge may appear in two
+    faces, and the Euler characteristic changes.  Normals are not carried: call ``vertex_normals`` on the result.  The contract is
+    cer_mvs.h's, "Mesh simplification"."""
+    who = "simplify_vertex_clustering"
+    _check_mesh(vertices, faces, None, colors, who)
+    cell = _positive(cell, "cell", who)
+    regularisation = _positive(regularisation, "regularisation", who)
+    quadric = _representative(representative, who) == "quadric"
+    nv, nf = int(vertices.shape[0]), int(faces.shape[0])
+    if quadric:
+        starts, corner_order = vertex_faces(faces, nv)
+    else:                                                    # the mean walks no face: the range check alone
+        _corner_keys(faces, nv)
+        starts = corner_order = None
+    if not vertices.is_cuda:
+        raise RuntimeError(f"{who}: vertices must be a CUDA tensor (no CPU fallback)")
+    from .cloud_eval import CloudIndex
+    dev, lib = vertices.device, L.load()
+    vertices, faces = vertices.contiguous(), faces.contiguous()
+    colors = None if colors is None else colors.contiguous()
+    index = CloudIndex(vertices, cell)                       # keys, the stable sort and the cell table: the clusters and their member order
+    nc = int(index.cells)
+    p_order, p_start = L.dev_ptr(index.order, "order", torch.int64), L.dev_ptr(index.cell_start, "cell_start", torch.int64)
+    pv, pf = L.dev_ptr(vertices, "vertices"), L.dev_ptr(faces, "faces", torch.int32)
+    cluster = torch.empty(nv, device=dev, dtype=torch.int32)
+    L.check(lib.cer_mesh_cluster_map_i32(p_order, p_start, nv, nc, L.dev_ptr(cluster, "cluster", torch.int32), L.cur_stream()), "mesh_cluster_map")
+    reps = torch.empty(nc, 3, device=dev, dtype=torch.float32)
+    took = torch.zeros(nc, device=dev, dtype=torch.uint8)
+    rep_colors = None if colors is None else torch.empty(nc, 3, device=dev, dtype=torch.uint8)
+    L.check(lib.cer_mesh_cluster_reps_f32(pv, nv, pf, nf, L.dev_ptr(starts, "starts", torch.int32), L.dev_ptr(corner_order, "order", torch.int32),
+                                          p_order, p_start, L.dev_ptr(index.cell_keys, "cell_keys", torch.int64), nc, index.origin, cell,
+                                          int(quadric), regularisation, L.dev_ptr(colors, "colors", torch.uint8), L.dev_ptr(reps, "reps"),
+                                          L.dev_ptr(rep_colors, "rep_colors", torch.uint8), L.dev_ptr(took, "took", torch.uint8), L.cur_stream()),
+            "mesh_cluster_reps")
+    triples = torch.empty(nf, 3, device=dev, dtype=torch.int32)
+    valid = torch.empty(nf, device=dev, dtype=torch.uint8)
+    keep = torch.empty(nf, device=dev, dtype=torch.uint8)
+    pt, pk = L.dev_ptr(triples, "triples", torch.int32), L.dev_ptr(valid, "valid", torch.uint8)
+    L.check(lib.cer_mesh_cluster_faces_i32(pf, nf, L.dev_ptr(cluster, "cluster", torch.int32), nv, pt, pk, L.cur_stream()), "mesh_cluster_faces")
+    t = triples.long()
+    by_bc = torch.sort((t[:, 1] << 31) | t[:, 2], stable=True).indices                     # lexicographic: (b, c) first, then a, both stable
+    perm = by_bc[torch.sort(t[:, 0][by_bc], stable=True).indices].contiguous()
+    L.check(lib.cer_mesh_face_heads_u8(pt, pk, L.dev_ptr(perm, "perm", torch.int64), nf, L.dev_ptr(keep, "keep", torch.uint8), L.cur_stream()),
+            "mesh_face_heads")
+    t_starts, t_order = _corner_list(triples.reshape(-1), nc)                              # (the -1 of an invalid face is in nobody's list)
+    out_v, out_f, kept, _, out_c = _select(reps, triples, keep, t_starts, t_order, None, rep_colors)
+    nvo = int(out_v.shape[0])
+    new_of = torch.full((nc + 1,), -1, device=dev, dtype=torch.int32)                      # the last slot answers cluster == -1
+    new_of[kept.long()] = torch.arange(nvo, device=dev, dtype=torch.int32)
+    cluster = new_of[cluster.long()]
+    if info is not None:
+        n_valid, n_kept = int(valid.sum()), int(out_f.shape[0])
+        info.update(clusters=nc, degenerate_faces=nf - n_valid, duplicate_faces=n_valid - n_kept, dropped_clusters=nc - nvo,
+                    quadric=int(took.sum()))
+    return out_v, out_f, cluster, out_c
+
+
+MESH_OPTION_KEYS = ("voxel", "resolution", "trunc", "min_weight", "margin", "colors", "normals", "min_component", "keep_largest", "simplify")
 
 
 def mesh_options(mesh):
     """``reconstruct_scan``'s ``mesh`` argument, checked: True or a dict with keys of MESH_OPTION_KEYS -> a dict.  "colors": True or
     {"tol": a positive finite number} (default: the mesh's trunc); "normals": True; "min_component" (``remove_small_components``'s
-    ``min_faces``) and "keep_largest": an int >= 1 each."""
+    ``min_faces``) and "keep_largest": an int >= 1 each; "simplify": a positive finite number k - ``simplify_vertex_clustering`` with a cell
+    of k mesh voxels - or {"voxels": k | "cell": world units, "representative": "quadric" | "mean", "regularisation": a positive finite
+    number}, "voxels" and "cell" exclusive."""
     if mesh is True:
         return {}
     if not isinstance(mesh, dict):
@@ -535,7 +638,21 @@ def mesh_options(mesh):
     for key in ("min_component", "keep_largest"):
         if key in mesh and _count_option(mesh[key], key, "mesh") is None:
             raise ValueError(f"mesh: {key} must be an integer >= 1")
+    if "simplify" in mesh:
+        _simplify_option(mesh["simplify"])
     return dict(mesh)
+
+
+def _simplify_option(value):
+    """the "simplify" option, checked -> (voxels | None, cell | None, representative, regularisation)"""
+    if not isinstance(value, dict):
+        return _positive(value, "simplify", "mesh"), None, "quadric", 1e-3
+    if set(value) - set(SIMPLIFY_KEYS) or ("voxels" in value) == ("cell" in value):
+        raise ValueError(f"mesh: simplify must be a positive finite number or a dictionary with \"voxels\" or \"cell\" (one of them) and keys of {list(SIMPLIFY_KEYS)}")
+    voxels = _positive(value["voxels"], "simplify: voxels", "mesh") if "voxels" in value else None
+    cell = _positive(value["cell"], "simplify: cell", "mesh") if "cell" in value else None
+    return (voxels, cell, _representative(value.get("representative", "quadric"), "mesh: simplify"),
+            _positive(value.get("regularisation", 1e-3), "simplify: regularisation", "mesh"))
 
 
 def mesh_of_scan(xyz, est, masks, Ks, Es, refs, options, colors=None):
@@ -544,18 +661,27 @@ def mesh_of_scan(xyz, est, masks, Ks, Es, refs, options, colors=None):
     [N,3,h,w] (tol: the option's, or the mesh's trunc) / ``vertex_normals``; ``attributes`` then holds "mesh_colors" / "mesh_normals" (device
     tensors) and ``info`` gains "coloured", the number of vertices that a view sees.  With "min_component" / "keep_largest":
     ``remove_small_components`` right after the extraction, before the attributes; ``info``'s "nv" and "nf" then describe the returned mesh
-    and it gains "extracted": (nv, nf) of the extraction, and the removal's figures."""
+    and it gains "extracted": (nv, nf) of the extraction, and the removal's figures.  With "simplify": ``simplify_vertex_clustering`` after
+    the removal and before the attributes; ``info``'s "nv" and "nf" describe the returned mesh and it gains "simplified_from": (nv, nf) before,
+    and the simplification's figures."""
     opt = dict(options)
     min_weight = opt.pop("min_weight", 1)
     trunc = opt.pop("trunc", None)
     want_colors, want_normals = opt.pop("colors", None), opt.pop("normals", None)
     min_component, keep_largest = opt.pop("min_component", None), opt.pop("keep_largest", None)
+    simplify = opt.pop("simplify", None)
     grid = grid_for(xyz, trunc=trunc, **opt)
     info, attributes = {}, {}
     v, f = mesh_from_depth_maps(est, masks, Ks, Es, grid, trunc=trunc, views=refs, min_weight=min_weight, info=info)
     if min_component is not None or keep_largest is not None:            # before the attributes: they are computed on what is returned
         info["extracted"] = (info["nv"], info["nf"])
         v, f, _, _, _ = remove_small_components(v, f, min_faces=min_component, keep_largest=keep_largest, info=info)
+        info.update(nv=int(v.shape[0]), nf=int(f.shape[0]))
+    if simplify is not None:                                             # after the removal, before the attributes
+        voxels, cell, representative, regularisation = _simplify_option(simplify)
+        info["simplified_from"] = (info["nv"], info["nf"])
+        v, f, _, _ = simplify_vertex_clustering(v, f, voxels * info["grid"].voxel if cell is None else cell, representative=representative,
+                                                regularisation=regularisation, info=info)
         info.update(nv=int(v.shape[0]), nf=int(f.shape[0]))
     if want_colors is not None:
         if colors is None:

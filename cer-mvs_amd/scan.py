@@ -387,7 +387,11 @@ def reconstruct_scan(model_or_ckpt, images, poses, intrinsics, names, pairs, sca
     ``result_mesh.ply`` carries what was asked for.  Without these keys nothing changes.  And two: "min_component": n and
     "keep_largest": k, an int >= 1 each - ``mesh.remove_small_components`` right after the extraction: a connected piece stays iff it has at
     least n faces and is among the k largest; colours and normals are those of the returned mesh; ``mesh_info`` "nv" / "nf" describe it and
-    it gains "extracted" (nv, nf before), "components", "removed_components", "removed_faces", "removed_vertices" and "sweeps"."""
+    it gains "extracted" (nv, nf before), "components", "removed_components", "removed_faces", "removed_vertices" and "sweeps".  And one
+    (DESIGN.md 3zd): "simplify": k, a positive finite number - a clustering cell of k mesh voxels - or {"voxels": k | "cell": world units,
+    "representative": "quadric" | "mean", "regularisation": float}: ``mesh.simplify_vertex_clustering`` after the small-piece removal and
+    before colours and normals; ``mesh_info`` "nv" / "nf" describe the returned mesh and it gains "simplified_from" (nv, nf before),
+    "clusters", "degenerate_faces", "duplicate_faces", "dropped_clusters" and "quadric"."""
     two_pass = isinstance(rescale, (tuple, list))
     passes = [r for r in rescale] if two_pass else [rescale]
     if two_pass and (len(passes) != 2 or passes[1] != 2 * passes[0]):

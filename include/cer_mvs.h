@@ -835,6 +835,67 @@ int cer_mesh_select_emit_f32(const float* vertices, long long nv, const int* fac
                              const unsigned char* used, const long long* offsets, long long nv_out, long long nf_out, int* vmap,
                              float* out_vertices, int* index, int* out_faces, void* stream);
 
+/* Mesh simplification (ABI 1200; csrc/mesh.hip, cer-mvs_amd/mesh.py simplify_vertex_clustering): vertex clustering
+ * (Rossignac-Borrel) with the mean or Lindstrom's quadric minimiser as the representative, for any indexed triangle mesh, under the rules
+ * of the section "Surface mesh": fp64 with every association as written, no fused multiply-add, IEEE division, no fast-math, no atomics,
+ * the same bytes on every run.  vertices float32 [nv, 3]; faces int32 [nf, 3]; starts int32 [nv + 1] and corner_order int32 [3 nf]: the CSR
+ * corner list of cer_mesh_vertex_normals_f32.
+ *
+ * Checks, in that section's order, all before any launch: (1) a negative size (nv, nf, ncells) -> CER_EINVAL; (2) nv, 3 nf or ncells >=
+ * 2^31, or ncells > nv -> CER_ESHAPE; (3) origin null or non-finite, cell or regularisation not a positive finite number -> CER_EINVAL (the
+ * representatives only; regularisation is checked in both forms); (4) nothing to do -> CER_OK with nothing launched (the map: nv == 0 - with
+ * ncells == 0 and nv > 0 it DOES launch and writes -1; the representatives: ncells == 0; the faces and the heads: nf == 0); (5) a null
+ * pointer -> CER_EINVAL (the representatives: colors and rep_colors may be null together; in the quadric form faces and corner_order may be
+ * null iff nf == 0; the mean form reads none of faces, starts and corner_order; the faces: cluster may be null iff nv == 0).  An index, a
+ * corner id or a sorted position outside its range is skipped, never read or written through (the Python layer refuses such faces).
+ *
+ * 1. Clusters: the occupied cells of the sparse grid of cer_grid_keys_f32 over the vertices, origin = the per-axis minimum of the finite
+ *    vertices (HOST doubles), c = floor((double(p) - origin) / cell) per axis.  order int64 [nv]: the vertex indices stably sorted by key;
+ *    cell_keys int64 [ncells]: the distinct keys, ascending; cell_start int64 [ncells + 1]: the first sorted position of every cell, and
+ *    cell_start[ncells] = the number of finite vertices.  Cluster r has the members order[cell_start[r] .. cell_start[r + 1] - 1], ascending
+ *    vertex index ("member order").  A vertex with a non-finite coordinate belongs to no cluster.
+ *    cer_mesh_cluster_map_i32: cluster int32 [nv]: cluster[order[p]] = r for cell_start[r] <= p < cell_start[r + 1], -1 for p >=
+ *    cell_start[ncells].  One thread per sorted position; order is a permutation, so every address has one writer.
+ * 2. Representative, mean (quadric == 0): per axis s = the fp64 sum, starting at 0, of the promoted member coordinates in member order;
+ *    mean = s / double(count); reps float32 [ncells, 3] = float(mean).
+ * 3. Representative, quadric (quadric != 0): with (cx, cy, cz) the cell coordinates that cell_keys[r] holds, base = origin + (double(c) +
+ *    0.5) * cell per axis.  For every member v in member order and every corner e = starts[v] .. starts[v + 1] - 1, the face corner_order[e] /
+ *    3 with positions A, B, C promoted to double: U = B - A, W = C - A, n = (Uy Wz - Uz Wy, Uz Wx - Ux Wz, Ux Wy - Uy Wx) (the normals
+ *    kernel's), d = (nx (Ax - basex) + ny (Ay - basey)) + nz (Az - basez); then Mxx += nx nx, Mxy += nx ny, Mxz += nx nz, Myy += ny ny, Myz
+ *    += ny nz, Mzz += nz nz, qx += nx d, qy += ny d, qz += nz d, all fp64 sums that start at 0.  A face that names two members is visited once
+ *    per member (the sum of vertex quadrics).  Then
+ *      lam = (regularisation * ((Mxx + Myy) + Mzz)) / 3.0;  a = Mxx + lam, dd = Myy + lam, ff = Mzz + lam;
+ *      tx = qx + lam * (meanx - basex), ty, tz likewise (mean: item 2's fp64 quotient, not rounded);
+ *      c00 = dd ff - Myz Myz, c01 = Mxz Myz - Mxy ff, c02 = Mxy Myz - Mxz dd, c11 = a ff - Mxz Mxz, c12 = Mxy Mxz - a Myz, c22 = a dd - Mxy Mxy;
+ *      det = (a c00 + Mxy c01) + Mxz c02;
+ *      x = ((c00 tx + c01 ty) + c02 tz) / det, y = ((c01 tx + c11 ty) + c12 tz) / det, z = ((c02 tx + c12 ty) + c22 tz) / det
+ *    - the solution of (M + lam I) x = q + lam (mean - base) by cofactors.  The representative is float(base + x) per axis and took[r] = 1 iff
+ *    lam > 0, det > 0, det, x, y and z are finite and fabs of each of x, y, z <= cell / 2.0 (fp64 compares); otherwise it is item 2's mean and
+ *    took[r] = 0 (took: ncells bytes; all 0 in the mean form).  The regulariser pulls the minimiser to the mean along directions the planes
+ *    leave free and bounds the condition number by 3 / regularisation + 1.
+ * 4. Colours (colors uint8 [nv, 3] or NULL): per channel the integer sum of the member bytes divided by the count, integer division;
+ *    rep_colors uint8 [ncells, 3].
+ *    cer_mesh_cluster_reps_f32: items 2 to 4, ONE thread per cluster for its whole member walk (a wave-wide reduction would change the
+ *    order of the sums).
+ * 5. Faces.  cer_mesh_cluster_faces_i32: a face is VALID iff its three indices are in 0 .. nv-1, all three have a cluster (>= 0) and the
+ *    three clusters are distinct.  triples int32 [nf, 3]: the clusters of a valid face rotated cyclically so that the smallest comes first
+ *    (orientation kept), (-1, -1, -1) for an invalid face; valid: nf bytes.
+ *    cer_mesh_face_heads_u8: perm int64 [nf]: the faces sorted lexicographically by triple, stably (the caller: a stable sort by
+ *    (t1 << 31) | t2 as 64-bit integers, then a stable sort by t0), so equal triples keep ascending face index.  keep[perm[p]] = valid[perm[p]]
+ *    && (p == 0 || triples[perm[p]] != triples[perm[p - 1]]): of the valid faces that are equal after rotation the lowest face index survives;
+ *    opposite orientations are different triples and both stay.  keep: nf bytes, one writer each.
+ * 6. Output: cer_mesh_select_count / cer_mesh_select_emit_f32 on (reps, triples, keep) - surviving faces keep their input order, a cluster
+ *    without a surviving face is dropped, surviving clusters keep ascending order. */
+int cer_mesh_cluster_map_i32(const long long* order, const long long* cell_start, long long nv, long long ncells, int* cluster, void* stream);
+int cer_mesh_cluster_reps_f32(const float* vertices, long long nv, const int* faces, long long nf, const int* starts, const int* corner_order,
+                              const long long* order, const long long* cell_start, const long long* cell_keys, long long ncells,
+                              const double* origin, double cell, int quadric, double regularisation, const unsigned char* colors, float* reps,
+                              unsigned char* rep_colors, unsigned char* took, void* stream);
+int cer_mesh_cluster_faces_i32(const int* faces, long long nf, const int* cluster, long long nv, int* triples, unsigned char* valid,
+                               void* stream);
+int cer_mesh_face_heads_u8(const int* triples, const unsigned char* valid, const long long* perm, long long nf, unsigned char* keep,
+                           void* stream);
+
 /* Multi-GPU row-slab exchange (cer-mvs_amd/slab.py): up to CER_COPY_MAX_SEG contiguous fp32 ranges copied by ONE launch -
  * the pack of a rank's (net, disp) border strips into its send buffer, and the refresh of its halo rows from the gathered
  * strips.  n[i] floats from src[i] to dst[i]; n[i] == 0 skips a segment.  Device pointers; ranges must not overlap. */
