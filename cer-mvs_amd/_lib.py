@@ -9,7 +9,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CER_MVS_LIB") or os.path.join(_HERE, "csrc", "libcermvs.so")
-ABI_VERSION = 1200
+ABI_VERSION = 1210
 CONV_MAX_SRC = 4
 EPI_LINEAR, EPI_RELU, EPI_GATES, EPI_GRU, EPI_DELTA = 0, 1, 2, 3, 4
 EPI_OUT_SPLIT, EPI_AUX_SPLIT = 0x100, 0x200       # cer_mvs.h: split32 activation layout flags, or-ed into `epi`
@@ -157,6 +157,13 @@ _SIGNATURES = {
     "cer_mesh_cluster_reps_f32": (_I, [_P, _LL, _P, _LL, _P, _P, _P, _P, _P, _LL, _c.POINTER(_D), _D, _I, _D, _P, _P, _P, _P, _P]),
     "cer_mesh_cluster_faces_i32": (_I, [_P, _LL, _P, _LL, _P, _P, _P]),
     "cer_mesh_face_heads_u8": (_I, [_P, _P, _P, _LL, _P, _P]),
+    "cer_mesh_edge_partials": (_L, [_LL]),
+    "cer_mesh_edge_keys_i64": (_I, [_P, _LL, _LL, _P, _P]),
+    "cer_mesh_edge_count": (_I, [_P, _LL, _P, _P, _P, _P]),
+    "cer_mesh_edge_emit_i32": (_I, [_P, _LL, _P, _LL, _P, _P, _P, _P, _P]),
+    "cer_mesh_smooth_prepare_f32": (_I, [_P, _LL, _P, _P, _P, _P, _LL, _I, _P, _P, _P, _P]),
+    "cer_mesh_smooth_steps_f64": (_I, [_P, _P, _LL, _P, _P, _LL, _P, _D, _D, _I, _P]),
+    "cer_mesh_smooth_finish_f32": (_I, [_P, _P, _P, _LL, _P, _P]),
 }
 
 # include/cer_mvs_variants.h: exported by csrc/variants/libcermvs_optin.so only (round 4's opt-in kernel forms; CER_MVS_LIB selects the library)

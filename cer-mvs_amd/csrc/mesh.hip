@@ -18,6 +18,10 @@
 // Simplification (ABI 1200; tests/mesh_simplify_reference.py): vertex clustering on the cells of cloud_eval.py's CloudIndex -
 // one thread per cluster sums its members (and their faces' plane quadrics) in member order, faces are remapped, rotated and deduplicated
 // through two stable sorts, and what survives leaves through the selection above.
+//
+// Edges and smoothing (ABI 1210; tests/mesh_smooth_reference.py): the unique-neighbour list of every vertex with a count per
+// direction - six keys per face, the caller's sort, the ordered compaction over the heads of the runs - and Taubin / Laplacian smoothing,
+// one gather kernel per step over that list.
 #include "common.hpp"
 #include "compact.hpp"
 
@@ -946,6 +950,255 @@ extern "C" int cer_mesh_face_heads_u8(const int* triples, const unsigned char* v
     if (!triples || !valid || !perm || !keep) return CER_EINVAL;
     hipLaunchKernelGGL(mesh_face_heads_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, (hipStream_t)stream, triples, valid, perm,
                        (long)nf, keep);
+    CER_RETURN_IF_LAUNCH_FAILED();
+    return CER_OK;
+}
+
+// ---- mesh edges and smoothing (ABI 1210; tests/mesh_smooth_reference.py).  The unique-neighbour list of every vertex,
+// ascending, with a count per direction - the duplicate-free edge table - and Taubin / Laplacian smoothing as one gather kernel over it.
+// Integers and fp64 with the associations of cer_mvs.h; every address has one writer, no atomics, the same bytes on every run.
+//
+// keys: one thread per face writes six 64-bit keys, two per directed edge a -> b: (a << 32) | (b << 1) in a's list ("along") and
+// (b << 32) | (a << 1) | 1 in b's ("against"); -1 for an edge with equal ends or an index out of range.  Sorted ascending (the caller: equal
+// keys are indistinguishable, so any sort), the keys of one (owner, other) pair form one run with the "along" keys in front.
+__global__ __launch_bounds__(256) void mesh_edge_keys_kernel(const int* __restrict__ faces, long nf, unsigned nv, long long* __restrict__ keys) {
+    const long q = (long)blockIdx.x * 256 + threadIdx.x;
+    if (q >= nf) return;
+    const int* f = faces + 3 * q;
+    const int i[3] = {f[0], f[1], f[2]};
+    long long* o = keys + 6 * q;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const int a = i[c], b = i[c == 2 ? 0 : c + 1];
+        const bool ok = (unsigned)a < nv && (unsigned)b < nv && a != b;
+        o[2 * c] = ok ? ((long long)a << 32) | ((long long)b << 1) : -1ll;
+        o[2 * c + 1] = ok ? ((long long)b << 32) | ((long long)a << 1) | 1ll : -1ll;
+    }
+}
+
+// head of a run of the sorted keys: the first key of its (owner, other) pair
+__device__ __forceinline__ bool mesh_edge_head(const long long* __restrict__ keys, long nk, long p) {
+    if (p >= nk) return false;
+    const long long k = keys[p];
+    return k >= 0 && (p == 0 || (keys[p - 1] >> 1) != (k >> 1));
+}
+
+__global__ __launch_bounds__(256) void mesh_edge_count_kernel(const long long* __restrict__ keys, long nk, unsigned* __restrict__ partials) {
+    unsigned long long bal[MESH_ITER];
+    const long seg = compact_seg<MESH_TILE, long>();
+    const unsigned wave = compact_ballots(seg, [&](long p) { return mesh_edge_head(keys, nk, p); }, bal);
+    const unsigned tot = compact_block_total(wave);
+    if (threadIdx.x == 0) partials[blockIdx.x] = tot;
+}
+
+// emit: the head of a run writes its entry - owner, other and the run's keys by direction bit.  The run is walked forward from the head, so
+// the entry has one writer; a run is as long as the edge has faces on it.
+__global__ __launch_bounds__(256) void mesh_edge_emit_kernel(const long long* __restrict__ keys, long nk, const long long* __restrict__ offsets,
+                                                             long long capacity, int* __restrict__ owner, int* __restrict__ nbrs,
+                                                             int* __restrict__ along, int* __restrict__ against) {
+    const int lane = threadIdx.x & 63;
+    const long seg = compact_seg<MESH_TILE, long>();
+    unsigned long long bal[MESH_ITER];
+    const unsigned tot = compact_ballots(seg, [&](long p) { return mesh_edge_head(keys, nk, p); }, bal);
+    long long base = compact_wave_base(tot, offsets, blockIdx.x);
+#pragma unroll
+    for (int jj = 0; jj < MESH_ITER; ++jj) {
+        const long p = seg + 64 * jj;
+        const long long idx = base + compact_rank(bal[jj]);
+        base += __popcll(bal[jj]);
+        if (!((bal[jj] >> lane) & 1ull) || idx >= capacity) continue;    // (never past what the caller allocated)
+        const long long pair = keys[p] >> 1;
+        int n0 = 0, n1 = 0;
+        for (long q = p; q < nk; ++q) {
+            const long long k = keys[q];
+            if ((k >> 1) != pair) break;
+            if (k & 1ll) ++n1; else ++n0;
+        }
+        owner[idx] = (int)(pair >> 31);
+        nbrs[idx] = (int)(pair & 0x7fffffffll);
+        along[idx] = n0;
+        against[idx] = n1;
+    }
+}
+
+// ---- smoothing, prepare: one thread per vertex reads its run once.  flags[v] = 1 (finite in the input) | 2 (frozen) | 4 (boundary: an entry
+// with along + against == 1); walk[e] = the neighbour, or -1 where it is not finite in the input (the step then neither reads nor counts it);
+// state[v] = the promoted position.  A neighbour outside 0 .. nv-1 is not read through and walks as -1.
+__device__ __forceinline__ bool mesh_finite3(const float* __restrict__ p) {
+    const float x = p[0], y = p[1], z = p[2];
+    return x - x == 0.0f && y - y == 0.0f && z - z == 0.0f;
+}
+__global__ __launch_bounds__(256) void mesh_smooth_prepare_kernel(const float* __restrict__ vertices, unsigned nv, const int* __restrict__ starts,
+                                                                  const int* __restrict__ nbrs, const int* __restrict__ along,
+                                                                  const int* __restrict__ against, int nn, int fixed_boundary,
+                                                                  int* __restrict__ walk, unsigned char* __restrict__ flags,
+                                                                  double* __restrict__ state) {
+    const unsigned v = blockIdx.x * 256u + threadIdx.x;
+    if (v >= nv) return;
+    int e0 = starts[v], e1 = starts[v + 1];
+    e0 = e0 < 0 ? 0 : e0;
+    e1 = e1 > nn ? nn : e1;
+    bool boundary = false, any = false;
+    for (int e = e0; e < e1; ++e) {
+        const int u = nbrs[e];
+        const bool fin = (unsigned)u < nv && mesh_finite3(vertices + 3l * u);
+        walk[e] = fin ? u : -1;
+        any |= fin;
+        boundary |= along[e] + against[e] == 1;
+    }
+    const float* p = vertices + 3l * v;
+    const bool finite = mesh_finite3(p);
+    const bool frozen = !finite || !any || (fixed_boundary != 0 && boundary);
+    flags[v] = (unsigned char)((finite ? 1 : 0) | (frozen ? 2 : 0) | (boundary ? 4 : 0));
+    double* s = state + 3l * v;
+    s[0] = (double)p[0];
+    s[1] = (double)p[1];
+    s[2] = (double)p[2];
+}
+
+// ---- smoothing, one step: the hot path.  One thread per vertex walks its run; per axis s = 0.0, s = s + p[u] over the walked neighbours in
+// ascending order, m = s / double(count), q = p + w * (m - p); a frozen vertex copies.  src and dst are different buffers: a step reads only
+// the previous step's values.  Sums in registers; no LDS, no atomics.
+__global__ __launch_bounds__(256) void mesh_smooth_step_kernel(const double* __restrict__ src, double* __restrict__ dst, unsigned nv,
+                                                               const int* __restrict__ starts, const int* __restrict__ walk, int nn,
+                                                               const unsigned char* __restrict__ flags, double w) {
+    const unsigned v = blockIdx.x * 256u + threadIdx.x;
+    if (v >= nv) return;
+    const double* p = src + 3l * v;
+    double qx = p[0], qy = p[1], qz = p[2];
+    if (!(flags[v] & 2)) {
+        int e0 = starts[v], e1 = starts[v + 1];
+        e0 = e0 < 0 ? 0 : e0;
+        e1 = e1 > nn ? nn : e1;
+        double sx = 0.0, sy = 0.0, sz = 0.0;
+        int count = 0;
+        for (int e = e0; e < e1; ++e) {
+            const int u = walk[e];
+            if ((unsigned)u >= nv) continue;
+            const double* r = src + 3l * u;
+            sx = sx + r[0];
+            sy = sy + r[1];
+            sz = sz + r[2];
+            ++count;
+        }
+        if (count > 0) {
+            const double n = (double)count;
+            qx = qx + w * (sx / n - qx);
+            qy = qy + w * (sy / n - qy);
+            qz = qz + w * (sz / n - qz);
+        }
+    }
+    double* o = dst + 3l * v;
+    o[0] = qx;
+    o[1] = qy;
+    o[2] = qz;
+}
+
+// ---- smoothing, finish: the state rounded to float32 once; a frozen vertex gets its input bits back
+__global__ __launch_bounds__(256) void mesh_smooth_finish_kernel(const double* __restrict__ state, const float* __restrict__ vertices,
+                                                                 const unsigned char* __restrict__ flags, unsigned nv, float* __restrict__ out) {
+    const unsigned v = blockIdx.x * 256u + threadIdx.x;
+    if (v >= nv) return;
+    const bool frozen = (flags[v] & 2) != 0;
+    const double* s = state + 3l * v;
+    const float* p = vertices + 3l * v;
+    float* o = out + 3l * v;
+    o[0] = frozen ? p[0] : (float)s[0];
+    o[1] = frozen ? p[1] : (float)s[1];
+    o[2] = frozen ? p[2] : (float)s[2];
+}
+
+// Checks, in the order of the section "Surface mesh": a negative size, too large (nv, 3 nf, 6 nf or nn >= 2^31), a non-finite weight, nothing
+// to do, pointers.
+static int mesh_edge_sizes(long long nv, long long nf, long long nn) {
+    if (nv < 0 || nf < 0 || nn < 0) return CER_EINVAL;
+    if (nv > 0x7fffffffLL || nf > 0x7fffffffLL / 6 || nn > 0x7fffffffLL) return CER_ESHAPE;   // positions 0 .. 6 nf - 1 and list entries are int32
+    return CER_OK;
+}
+
+extern "C" long cer_mesh_edge_partials(long long nf) {
+    const int rc = mesh_edge_sizes(0, nf, 0);
+    if (rc != CER_OK) return rc;
+    return mesh_blocks((long)(6 * nf));
+}
+
+extern "C" int cer_mesh_edge_keys_i64(const int* faces, long long nf, long long nv, long long* keys, void* stream) {
+    const int rc = mesh_edge_sizes(nv, nf, 0);
+    if (rc != CER_OK) return rc;
+    if (nf == 0) return CER_OK;
+    if (!faces || !keys) return CER_EINVAL;
+    hipLaunchKernelGGL(mesh_edge_keys_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, (hipStream_t)stream, faces, (long)nf, (unsigned)nv,
+                       keys);
+    CER_RETURN_IF_LAUNCH_FAILED();
+    return CER_OK;
+}
+
+extern "C" int cer_mesh_edge_count(const long long* sorted_keys, long long nf, unsigned int* partials, long long* offsets, long long* totals,
+                                   void* stream) {
+    const int rc = mesh_edge_sizes(0, nf, 0);
+    if (rc != CER_OK) return rc;
+    if (nf == 0) return CER_OK;                                          // (no key, no entry: totals are the caller's to zero)
+    if (!sorted_keys || !partials || !offsets || !totals) return CER_EINVAL;
+    const long nk = (long)(6 * nf), blocks = mesh_blocks(nk);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(mesh_edge_count_kernel, dim3((unsigned)blocks), dim3(256), 0, st, sorted_keys, nk, partials);
+    CER_RETURN_IF_LAUNCH_FAILED();
+    hipLaunchKernelGGL(mesh_scan_kernel, dim3(2), dim3(1024), 0, st, partials, blocks, 0l, offsets, totals);
+    CER_RETURN_IF_LAUNCH_FAILED();
+    return CER_OK;
+}
+
+extern "C" int cer_mesh_edge_emit_i32(const long long* sorted_keys, long long nf, const long long* offsets, long long nn, int* owner, int* nbrs,
+                                      int* along, int* against, void* stream) {
+    const int rc = mesh_edge_sizes(0, nf, nn);
+    if (rc != CER_OK) return rc;
+    if (nf == 0 || nn == 0) return CER_OK;
+    if (!sorted_keys || !offsets || !owner || !nbrs || !along || !against) return CER_EINVAL;
+    const long nk = (long)(6 * nf);
+    hipLaunchKernelGGL(mesh_edge_emit_kernel, dim3((unsigned)mesh_blocks(nk)), dim3(256), 0, (hipStream_t)stream, sorted_keys, nk, offsets, nn,
+                       owner, nbrs, along, against);
+    CER_RETURN_IF_LAUNCH_FAILED();
+    return CER_OK;
+}
+
+extern "C" int cer_mesh_smooth_prepare_f32(const float* vertices, long long nv, const int* nbr_starts, const int* nbrs, const int* along,
+                                           const int* against, long long nn, int fixed_boundary, int* walk, unsigned char* flags,
+                                           double* state, void* stream) {
+    const int rc = mesh_edge_sizes(nv, 0, nn);
+    if (rc != CER_OK) return rc;
+    if (nv == 0) return CER_OK;
+    if (!vertices || !nbr_starts || !flags || !state || (nn && (!nbrs || !along || !against || !walk))) return CER_EINVAL;
+    hipLaunchKernelGGL(mesh_smooth_prepare_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, (hipStream_t)stream, vertices, (unsigned)nv,
+                       nbr_starts, nbrs, along, against, (int)nn, fixed_boundary, walk, flags, state);
+    CER_RETURN_IF_LAUNCH_FAILED();
+    return CER_OK;
+}
+
+extern "C" int cer_mesh_smooth_steps_f64(double* state_a, double* state_b, long long nv, const int* nbr_starts, const int* walk, long long nn,
+                                         const unsigned char* flags, double w_even, double w_odd, int n_steps, void* stream) {
+    if (n_steps < 0) return CER_EINVAL;
+    const int rc = mesh_edge_sizes(nv, 0, nn);
+    if (rc != CER_OK) return rc;
+    if (!mesh_is_finite(w_even) || !mesh_is_finite(w_odd)) return CER_EINVAL;
+    if (nv == 0 || n_steps == 0) return CER_OK;
+    if (!state_a || !state_b || state_a == state_b || !nbr_starts || !flags || (nn && !walk)) return CER_EINVAL;
+    for (int i = 0; i < n_steps; ++i) {                                  // stream order: step i reads what step i - 1 wrote, no host wait between
+        hipLaunchKernelGGL(mesh_smooth_step_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                           (const double*)((i & 1) ? state_b : state_a), (i & 1) ? state_a : state_b, (unsigned)nv, nbr_starts, walk, (int)nn, flags,
+                           (i & 1) ? w_odd : w_even);
+        CER_RETURN_IF_LAUNCH_FAILED();
+    }
+    return CER_OK;
+}
+
+extern "C" int cer_mesh_smooth_finish_f32(const double* state, const float* vertices, const unsigned char* flags, long long nv, float* out,
+                                          void* stream) {
+    const int rc = mesh_edge_sizes(nv, 0, 0);
+    if (rc != CER_OK) return rc;
+    if (nv == 0) return CER_OK;
+    if (!state || !vertices || !flags || !out) return CER_EINVAL;
+    hipLaunchKernelGGL(mesh_smooth_finish_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, (hipStream_t)stream, state, vertices, flags,
+                       (unsigned)nv, out);
     CER_RETURN_IF_LAUNCH_FAILED();
     return CER_OK;
 }

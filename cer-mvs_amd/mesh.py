@@ -6,6 +6,8 @@ all coordinate arithmetic is fp64 with fixed associations: tests/mesh_reference.
 faces of any indexed triangle mesh, and both through the PLY writer and reader.  Cleaning (C ABI 1190, DESIGN.md 3zc;
 tests/mesh_clean_reference.py): ``mesh_components``, ``select_faces`` and ``remove_small_components`` for any indexed triangle mesh.
 Simplification (C ABI 1200; tests/mesh_simplify_reference.py): ``simplify_vertex_clustering``, likewise.
+Edges (C ABI 1210; tests/mesh_smooth_reference.py): ``mesh_edges`` / ``edge_table``, the report ``mesh_topology`` and
+``smooth_mesh`` (Taubin, Laplacian), likewise.
 
 Every argument check that needs no device runs before the library is loaded."""
 import ctypes
@@ -609,7 +611,196 @@ def simplify_vertex_clustering(vertices, faces, cell, representative="quadric", 
     return out_v, out_f, cluster, out_c
 
 
-MESH_OPTION_KEYS = ("voxel", "resolution", "trunc", "min_weight", "margin", "colors", "normals", "min_component", "keep_largest", "simplify")
+# ---------------------------------------------------------------- edges, topology report and smoothing (C ABI 1210)
+SMOOTH_METHODS = ("taubin", "laplacian")
+SMOOTH_BOUNDARIES = ("fixed", "free")
+SMOOTH_KEYS = ("iterations", "method", "lam", "mu", "boundary")
+DEFAULT_MU = -0.53
+FLAG_FINITE, FLAG_FROZEN, FLAG_BOUNDARY = 1, 2, 4            # cer_mvs.h, cer_mesh_smooth_prepare_f32
+
+
+def _edge_checks(faces, nv, who):
+    """``vertex_faces``' checks in its wording, and 6 nf < 2^31 -> (nv, nf)"""
+    if isinstance(faces, torch.Tensor) and faces.dim() == 2 and 6 * faces.shape[0] >= 2 ** 31:        # (before the range check reads the faces)
+        raise ValueError(f"{who}: 6 nf must be in 0 .. 2^31 - 1")
+    _corner_keys(faces, nv)
+    return int(nv), int(faces.shape[0])
+
+
+def _edges(faces, nv):
+    """``mesh_edges`` on checked, contiguous device faces -> (nbr_starts, nbrs, along, against, owner int32 [nn])"""
+    dev, nf = faces.device, int(faces.shape[0])
+    lib = L.load()
+    nn = 0
+    if nf:
+        P = int(lib.cer_mesh_edge_partials(nf))
+        if P < 0:
+            L.check(P, "mesh_edge_partials")
+        keys = torch.empty(6 * nf, device=dev, dtype=torch.int64)
+        L.check(lib.cer_mesh_edge_keys_i64(L.dev_ptr(faces, "faces", torch.int32), nf, nv, L.dev_ptr(keys, "keys", torch.int64), L.cur_stream()),
+                "mesh_edge_keys")
+        keys = torch.sort(keys).values                       # equal keys are indistinguishable: no stability needed
+        partials = torch.empty(P, device=dev, dtype=torch.int32)
+        offsets = torch.empty(P + 2, device=dev, dtype=torch.int64)
+        totals = torch.zeros(2, device=dev, dtype=torch.int64)
+        pk = L.dev_ptr(keys, "keys", torch.int64)
+        L.check(lib.cer_mesh_edge_count(pk, nf, L.dev_ptr(partials, "partials", torch.int32), L.dev_ptr(offsets, "offsets", torch.int64),
+                                        L.dev_ptr(totals, "totals", torch.int64), L.cur_stream()), "mesh_edge_count")
+        nn = int(totals[0].cpu())                            # the one synchronisation: the outputs are allocated exactly
+    owner, nbrs, along, against = (torch.empty(nn, device=dev, dtype=torch.int32) for _ in range(4))
+    if nn:
+        L.check(lib.cer_mesh_edge_emit_i32(pk, nf, L.dev_ptr(offsets, "offsets", torch.int64), nn, L.dev_ptr(owner, "owner", torch.int32),
+                                           L.dev_ptr(nbrs, "nbrs", torch.int32), L.dev_ptr(along, "along", torch.int32),
+                                           L.dev_ptr(against, "against", torch.int32), L.cur_stream()), "mesh_edge_emit")
+    starts = torch.searchsorted(owner, torch.arange(nv + 1, device=dev, dtype=torch.int32)).to(torch.int32)
+    return starts, nbrs, along, against, owner
+
+
+def mesh_edges(faces, nv):
+    """The unique-neighbour list of every vertex of any indexed triangle mesh - its duplicate-free edge table with a count per direction:
+    faces int32 [nf,3] with indices in 0 .. nv-1 (ValueError otherwise, ``vertex_faces``' rule; 6 nf < 2^31) on the device -> (nbr_starts
+    int32 [nv + 1], nbrs int32 [nn], along int32 [nn], against int32 [nn]) on the device.  Face (i0, i1, i2) has the directed edges i0->i1,
+    i1->i2, i2->i0; one with equal ends is skipped.  ``nbrs[nbr_starts[v] : nbr_starts[v + 1]]`` are the distinct vertices u that share an
+    edge with v, ascending; ``along`` counts the directed edges v->u and ``against`` the directed edges u->v, so the entry (u, v) mirrors
+    (v, u) with the counts swapped and nn is even - the contract is cer_mvs.h's, "Mesh edges and smoothing"."""
+    nv, _ = _edge_checks(faces, nv, "mesh_edges")
+    if not faces.is_cuda:
+        raise RuntimeError("mesh_edges: faces must be a CUDA tensor (no CPU fallback)")
+    return _edges(faces.contiguous(), nv)[:4]
+
+
+def edge_table(nbr_starts, nbrs, along, against):
+    """The undirected edges of ``mesh_edges``' list: its entries with v < u, ordered by (v, u) -> (lo int32 [ne], hi int32 [ne], n_lo_hi
+    int32 [ne], n_hi_lo int32 [ne]): the ends and the number of directed edges lo->hi and hi->lo.  A torch mask."""
+    nv, nn = int(nbr_starts.shape[0]) - 1, int(nbrs.shape[0])
+    counts = (nbr_starts[1:] - nbr_starts[:-1]).long()
+    owner = torch.repeat_interleave(torch.arange(nv, device=nbrs.device, dtype=torch.int32), counts, output_size=nn)
+    mask = owner < nbrs
+    return owner[mask], nbrs[mask], along[mask], against[mask]
+
+
+TOPOLOGY_KEYS = ("vertices", "faces", "edges", "boundary_edges", "nonmanifold_edges", "inconsistent_edges", "boundary_vertices",
+                 "unreferenced_vertices", "degenerate_faces", "boundary_loops", "euler", "closed", "edge_manifold", "oriented")
+
+
+def _boundary_mask(nv, owner, along, against):
+    """bool [nv]: the vertices on an edge with one face"""
+    on = ((along + against) == 1).to(torch.int32)
+    return torch.zeros(nv, device=owner.device, dtype=torch.int32).scatter_reduce_(0, owner.long(), on, "amax") > 0     # (a maximum: order-free)
+
+
+def mesh_topology(faces, nv):
+    """What a mesh is, as a dict of Python ints and bools (TOPOLOGY_KEYS): faces int32 [nf,3] with indices in 0 .. nv-1 (``mesh_edges``'
+    checks) on the device.  With n = the number of faces on an undirected edge (both directions): "edges"; "boundary_edges": n == 1;
+    "nonmanifold_edges": n > 2; "inconsistent_edges": n == 2 with both faces running along it in one direction; "boundary_vertices": on a
+    boundary edge; "unreferenced_vertices": named by no face; "degenerate_faces": a repeated index; "boundary_loops": the connected
+    components of the graph of boundary edges (``mesh_components``' label sweeps on the faces (a, b, b) of the boundary edges, counting the
+    components that own an edge); "euler": V - E + F with V the referenced vertices and F every face; "closed": no boundary edge and at
+    least one face; "edge_manifold": no non-manifold edge; "oriented": edge-manifold and no inconsistent edge.  Torch reductions over the
+    edge table whose figures come back in one host read (after ``mesh_edges``' own), plus the sweeps' reads where there is a boundary."""
+    nv, nf = _edge_checks(faces, nv, "mesh_topology")
+    if not faces.is_cuda:
+        raise RuntimeError("mesh_topology: faces must be a CUDA tensor (no CPU fallback)")
+    faces = faces.contiguous()
+    dev = faces.device
+    starts, nbrs, along, against, owner = _edges(faces, nv)
+    half = owner < nbrs                                      # every edge once
+    total = along + against
+    one_way = (along == 0) | (against == 0)
+    boundary = _boundary_mask(nv, owner, along, against)
+    referenced = torch.zeros(nv, device=dev, dtype=torch.bool)
+    referenced[faces.reshape(-1).long()] = True
+    degenerate = (faces[:, 0] == faces[:, 1]) | (faces[:, 1] == faces[:, 2]) | (faces[:, 0] == faces[:, 2])
+    figures = torch.stack([half.sum(), (half & (total == 1)).sum(), (half & (total > 2)).sum(), (half & (total == 2) & one_way).sum(), boundary.sum(),
+                           referenced.sum(), degenerate.sum()]).cpu().tolist()          # the one host read
+    ne, nb, nm, ni, nbv, nref, ndeg = (int(v) for v in figures)
+    loops = 0
+    if nb:
+        is_b = half & (total == 1)
+        lo, hi = owner[is_b], nbrs[is_b]
+        bfaces = torch.stack([lo, hi, hi], 1).contiguous()
+        bstarts, border = _corner_list(bfaces.reshape(-1), nv)
+        labels, _ = _label_roots(bfaces, nv, bstarts, border)
+        loops = int(((labels == torch.arange(nv, device=dev, dtype=torch.int32)) & boundary).sum())   # a root that owns an edge
+    return dict(vertices=nv, faces=nf, edges=ne, boundary_edges=nb, nonmanifold_edges=nm, inconsistent_edges=ni, boundary_vertices=nbv,
+                unreferenced_vertices=nv - nref, degenerate_faces=ndeg, boundary_loops=loops, euler=nref - ne + nf, closed=nb == 0 and nf >= 1,
+                edge_manifold=nm == 0, oriented=nm == 0 and ni == 0)
+
+
+def _smooth_arguments(iterations, method, lam, mu, boundary, who):
+    """``smooth_mesh``'s scalar arguments, checked -> (iterations, method, lam, mu, boundary)"""
+    if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or iterations < 1:
+        raise ValueError(f"{who}: iterations must be an integer >= 1")
+    if not isinstance(method, str) or method not in SMOOTH_METHODS:
+        raise ValueError(f"{who}: method must be one of {list(SMOOTH_METHODS)}")
+    if not isinstance(boundary, str) or boundary not in SMOOTH_BOUNDARIES:
+        raise ValueError(f"{who}: boundary must be one of {list(SMOOTH_BOUNDARIES)}")
+    number = lambda v: not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)) and math.isfinite(v)
+    if not number(lam) or not 0.0 < lam <= 1.0:
+        raise ValueError(f"{who}: lam must be a finite number in (0, 1]")
+    if not number(mu) or not (mu < -lam or (method == "laplacian" and mu == DEFAULT_MU)):       # (the default left alone where it is not read)
+        raise ValueError(f"{who}: mu must be a finite number below -lam")
+    return int(iterations), method, float(lam), float(mu), boundary
+
+
+def smooth_mesh(vertices, faces, iterations, method="taubin", lam=0.5, mu=-0.53, boundary="fixed", info=None):
+    """Taubin's lambda|mu smoothing (Open3D's ``filter_smooth_taubin``) or plain Laplacian smoothing (``filter_smooth_laplacian``) of any
+    indexed triangle mesh: vertices float32 [nv,3] and faces int32 [nf,3] with indices in 0 .. nv-1 (``mesh_edges``' checks) on the device
+    -> vertices' float32 [nv,3] on the device; the faces are untouched.  One step with weight w moves every movable vertex to
+    p + w * (mean of its finite neighbours in ``mesh_edges``' list - p), in fp64, from the previous step's positions; "laplacian": one step
+    with ``lam`` per iteration, which shrinks the surface; "taubin": a step with ``lam`` then a step with ``mu`` < -lam, which undoes the
+    shrinkage.  ``iterations``: an int >= 1; ``lam``: finite, in (0, 1]; ``mu``: finite, < -lam (read for "taubin" only, but checked whenever it is
+    given: under "laplacian" only the default passes without being below -lam).  A
+    vertex is frozen - it never moves and returns its input bits - iff it is non-finite in the input, has no finite neighbour or, with
+    ``boundary`` "fixed", lies on a boundary edge (``mesh_topology``'s "boundary_vertices"); "free" moves boundary vertices like any other.
+    Non-finite vertices are left out of every neighbour's mean.  The result is rounded to float32 once, after the last step.  ``info`` (a
+    dict) gains "moved" (vertices not frozen), "frozen_boundary" (boundary vertices with "fixed", 0 with "free"), "steps" and "edges".  The
+    contract is cer_mvs.h's, "Mesh edges and smoothing"."""
+    who = "smooth_mesh"
+    _check_mesh(vertices, faces, None, None, who)
+    iterations, method, lam, mu, boundary = _smooth_arguments(iterations, method, lam, mu, boundary, who)
+    nv, _ = _edge_checks(faces, vertices.shape[0], who)
+    if not vertices.is_cuda:
+        raise RuntimeError(f"{who}: vertices must be a CUDA tensor (no CPU fallback)")
+    dev, lib = vertices.device, L.load()
+    vertices = vertices.contiguous()
+    starts, nbrs, along, against, _ = _edges(faces.contiguous(), nv)
+    nn = int(nbrs.shape[0])
+    steps = iterations * (2 if method == "taubin" else 1)
+    fixed = boundary == "fixed"
+    walk = torch.empty(nn, device=dev, dtype=torch.int32)
+    flags = torch.zeros(nv, device=dev, dtype=torch.uint8)
+    state = torch.empty(2, nv, 3, device=dev, dtype=torch.float64)
+    out = torch.empty(nv, 3, device=dev, dtype=torch.float32)
+    ps, pw, pf = L.dev_ptr(starts, "nbr_starts", torch.int32), L.dev_ptr(walk, "walk", torch.int32) if nn else None, L.dev_ptr(flags, "flags", torch.uint8)
+    pa, pb = L.dev_ptr(state[0], "state", torch.float64), L.dev_ptr(state[1], "state", torch.float64)
+    if nv:
+        L.check(lib.cer_mesh_smooth_prepare_f32(L.dev_ptr(vertices, "vertices"), nv, ps, L.dev_ptr(nbrs, "nbrs", torch.int32) if nn else None,
+                                                L.dev_ptr(along, "along", torch.int32) if nn else None,
+                                                L.dev_ptr(against, "against", torch.int32) if nn else None, nn, int(fixed), pw, pf, pa,
+                                                L.cur_stream()), "mesh_smooth_prepare")
+        L.check(lib.cer_mesh_smooth_steps_f64(pa, pb, nv, ps, pw, nn, pf, lam, mu if method == "taubin" else lam, steps, L.cur_stream()),
+                "mesh_smooth_steps")
+        L.check(lib.cer_mesh_smooth_finish_f32(pb if steps & 1 else pa, L.dev_ptr(vertices, "vertices"), pf, nv, L.dev_ptr(out, "out"),
+                                               L.cur_stream()), "mesh_smooth_finish")
+    if info is not None:
+        frozen, on_boundary = (int(v) for v in torch.stack([((flags & FLAG_FROZEN) != 0).sum(), ((flags & FLAG_BOUNDARY) != 0).sum()]).cpu())
+        info.update(moved=nv - frozen, frozen_boundary=on_boundary if fixed else 0, steps=steps, edges=nn // 2)
+    return out
+
+
+def _smooth_option(value):
+    """the "smooth" option, checked -> (iterations, method, lam, mu, boundary)"""
+    if not isinstance(value, dict):
+        return _smooth_arguments(value, "taubin", 0.5, -0.53, "fixed", "mesh: smooth")
+    if set(value) - set(SMOOTH_KEYS) or "iterations" not in value:
+        raise ValueError(f"mesh: smooth must be an integer >= 1 or a dictionary with \"iterations\" and keys of {list(SMOOTH_KEYS)}")
+    return _smooth_arguments(value["iterations"], value.get("method", "taubin"), value.get("lam", 0.5), value.get("mu", -0.53),
+                             value.get("boundary", "fixed"), "mesh: smooth")
+
+
+MESH_OPTION_KEYS = ("voxel", "resolution", "trunc", "min_weight", "margin", "colors", "normals", "min_component", "keep_largest", "simplify",
+                    "smooth", "topology")
 
 
 def mesh_options(mesh):
@@ -617,7 +808,8 @@ def mesh_options(mesh):
     {"tol": a positive finite number} (default: the mesh's trunc); "normals": True; "min_component" (``remove_small_components``'s
     ``min_faces``) and "keep_largest": an int >= 1 each; "simplify": a positive finite number k - ``simplify_vertex_clustering`` with a cell
     of k mesh voxels - or {"voxels": k | "cell": world units, "representative": "quadric" | "mean", "regularisation": a positive finite
-    number}, "voxels" and "cell" exclusive."""
+    number}, "voxels" and "cell" exclusive; "smooth": an int n >= 1 - ``smooth_mesh`` with n Taubin iterations and its defaults - or
+    {"iterations": n, "method", "lam", "mu", "boundary"} with ``smooth_mesh``'s values; "topology": True."""
     if mesh is True:
         return {}
     if not isinstance(mesh, dict):
@@ -640,6 +832,10 @@ def mesh_options(mesh):
             raise ValueError(f"mesh: {key} must be an integer >= 1")
     if "simplify" in mesh:
         _simplify_option(mesh["simplify"])
+    if "smooth" in mesh:
+        _smooth_option(mesh["smooth"])
+    if "topology" in mesh and mesh["topology"] is not True:
+        raise ValueError("mesh: topology must be True")
     return dict(mesh)
 
 
@@ -663,13 +859,15 @@ def mesh_of_scan(xyz, est, masks, Ks, Es, refs, options, colors=None):
     ``remove_small_components`` right after the extraction, before the attributes; ``info``'s "nv" and "nf" then describe the returned mesh
     and it gains "extracted": (nv, nf) of the extraction, and the removal's figures.  With "simplify": ``simplify_vertex_clustering`` after
     the removal and before the attributes; ``info``'s "nv" and "nf" describe the returned mesh and it gains "simplified_from": (nv, nf) before,
-    and the simplification's figures."""
+    and the simplification's figures.  With "smooth": ``smooth_mesh`` after the removal and before "simplify" and the attributes; ``info``
+    gains "smoothed", ``smooth_mesh``'s info.  With "topology": ``info`` gains "topology", ``mesh_topology`` of the returned mesh."""
     opt = dict(options)
     min_weight = opt.pop("min_weight", 1)
     trunc = opt.pop("trunc", None)
     want_colors, want_normals = opt.pop("colors", None), opt.pop("normals", None)
     min_component, keep_largest = opt.pop("min_component", None), opt.pop("keep_largest", None)
     simplify = opt.pop("simplify", None)
+    smooth, want_topology = opt.pop("smooth", None), opt.pop("topology", None)
     grid = grid_for(xyz, trunc=trunc, **opt)
     info, attributes = {}, {}
     v, f = mesh_from_depth_maps(est, masks, Ks, Es, grid, trunc=trunc, views=refs, min_weight=min_weight, info=info)
@@ -677,6 +875,10 @@ def mesh_of_scan(xyz, est, masks, Ks, Es, refs, options, colors=None):
         info["extracted"] = (info["nv"], info["nf"])
         v, f, _, _, _ = remove_small_components(v, f, min_faces=min_component, keep_largest=keep_largest, info=info)
         info.update(nv=int(v.shape[0]), nf=int(f.shape[0]))
+    if smooth is not None:                                               # denoise first, then reduce
+        iterations, method, lam, mu, boundary = _smooth_option(smooth)
+        info["smoothed"] = {}
+        v = smooth_mesh(v, f, iterations, method=method, lam=lam, mu=mu, boundary=boundary, info=info["smoothed"])
     if simplify is not None:                                             # after the removal, before the attributes
         voxels, cell, representative, regularisation = _simplify_option(simplify)
         info["simplified_from"] = (info["nv"], info["nf"])
@@ -691,6 +893,8 @@ def mesh_of_scan(xyz, est, masks, Ks, Es, refs, options, colors=None):
         info["coloured"] = int((seen > 0).sum())
     if want_normals is not None:
         attributes["mesh_normals"] = vertex_normals(v, f)
+    if want_topology is not None:
+        info["topology"] = mesh_topology(f, int(v.shape[0]))
     return v, f, info, attributes
 
 

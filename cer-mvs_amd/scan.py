@@ -391,7 +391,11 @@ def reconstruct_scan(model_or_ckpt, images, poses, intrinsics, names, pairs, sca
     (DESIGN.md 3zd): "simplify": k, a positive finite number - a clustering cell of k mesh voxels - or {"voxels": k | "cell": world units,
     "representative": "quadric" | "mean", "regularisation": float}: ``mesh.simplify_vertex_clustering`` after the small-piece removal and
     before colours and normals; ``mesh_info`` "nv" / "nf" describe the returned mesh and it gains "simplified_from" (nv, nf before),
-    "clusters", "degenerate_faces", "duplicate_faces", "dropped_clusters" and "quadric"."""
+    "clusters", "degenerate_faces", "duplicate_faces", "dropped_clusters" and "quadric".  And two: "smooth": n, an int
+    >= 1 - Taubin smoothing with n iterations - or {"iterations": n, "method": "taubin" | "laplacian", "lam", "mu", "boundary": "fixed" |
+    "free"}: ``mesh.smooth_mesh`` after the small-piece removal and before "simplify", colours and normals; ``mesh_info`` gains "smoothed"
+    ({"moved", "frozen_boundary", "steps", "edges"}); "topology": True - ``mesh_info`` gains "topology", ``mesh.mesh_topology`` of the
+    returned mesh."""
     two_pass = isinstance(rescale, (tuple, list))
     passes = [r for r in rescale] if two_pass else [rescale]
     if two_pass and (len(passes) != 2 or passes[1] != 2 * passes[0]):

@@ -896,6 +896,62 @@ int cer_mesh_cluster_faces_i32(const int* faces, long long nf, const int* cluste
 int cer_mesh_face_heads_u8(const int* triples, const unsigned char* valid, const long long* perm, long long nf, unsigned char* keep,
                            void* stream);
 
+/* Mesh edges and smoothing (ABI 1210; csrc/mesh.hip, cer-mvs_amd/mesh.py mesh_edges / mesh_topology / smooth_mesh): the
+ * unique-neighbour list of every vertex of any indexed triangle mesh - its duplicate-free edge table with a count per direction - and
+ * Taubin's lambda|mu (or plain Laplacian) smoothing as one gather kernel over that list, under the rules of the section "Surface mesh":
+ * fp64 with every association as written, no fused multiply-add, IEEE division, no atomics, one writer per address, the same bytes on
+ * every run.  faces int32 [nf, 3]; vertices float32 [nv, 3].
+ *
+ * Checks, in that section's order, all before any launch: (1) a negative size (nv, nf, nn, n_steps) -> CER_EINVAL; (2) nv, 6 nf (hence
+ * 3 nf) or nn >= 2^31 -> CER_ESHAPE; (3) a non-finite weight (the steps) -> CER_EINVAL; (4) nothing to do -> CER_OK with nothing launched
+ * (the keys and the count: nf == 0 - totals are the caller's to zero; the emit: nf == 0 or nn == 0; prepare and finish: nv == 0; the steps:
+ * nv == 0 or n_steps == 0); (5) a null pointer -> CER_EINVAL (prepare: nbrs, along, against and walk may be null iff nn == 0; the steps:
+ * walk may be null iff nn == 0, and state_a == state_b is refused).  An index, a list position or an output row outside its range is
+ * skipped, never read or written through (the Python layer refuses such faces).
+ *
+ * 1. Directed edges.  Face (i0, i1, i2) has the directed edges i0->i1, i1->i2, i2->i0; one with equal ends is skipped, so a face with a
+ *    repeated index contributes only its edges between distinct indices.
+ *    cer_mesh_edge_keys_i64: keys int64 [6 nf]: face q writes keys[6 q ..], two per directed edge a->b: (a << 32) | (b << 1) - the entry
+ *    (owner a, other b), "along" - and (b << 32) | (a << 1) | 1 - the entry (owner b, other a), "against"; -1 for a skipped edge or an index
+ *    outside 0 .. nv-1.  The CALLER sorts the keys ascending (equal keys are indistinguishable: any sort): the -1 come first, and the keys of
+ *    one (owner, other) pair form one run, ordered by owner, then other.
+ * 2. Neighbour list.  One entry per run: nbrs[e] = other, along[e] = the run's keys with bit 0 clear = the directed edges owner->other,
+ *    against[e] = those with bit 0 set = the directed edges other->owner; entries ordered by (owner, other).  The entry (u, v) mirrors (v, u)
+ *    with the two counts swapped; nn, the number of entries, is even; the undirected edge table is the entries with owner < other.  Runs
+ *    leave through the ordered compaction of cer_mesh_count over the 6 nf sorted positions, CER_MESH_TILE per block: a position is a head
+ *    iff its key is >= 0 and (it is position 0 or key >> 1 differs from the key before it >> 1).
+ *    cer_mesh_edge_partials: HOST function: ceil(6 nf / CER_MESH_TILE): partials [that many] unsigned, offsets [that many + 2] 64-bit.
+ *    cer_mesh_edge_count: one count launch and the scan; totals[0] = nn (totals: 2 DEVICE 64-bit integers, the second is written 0).
+ *    cer_mesh_edge_emit_i32: nn: what the count found, and the rows of the outputs - never a byte beyond them.  The head of a run walks its
+ *    run forward and writes owner, nbrs, along, against int32 [nn].  nbr_starts int32 [nv + 1] is the caller's: the first entry of every
+ *    owner (a binary search of 0 .. nv in owner).
+ * 3. Smoothing.  cer_mesh_smooth_prepare_f32, one thread per vertex v over its run e = nbr_starts[v] .. nbr_starts[v + 1] - 1: a vertex is
+ *    FINITE iff its three input floats are; walk int32 [nn]: walk[e] = nbrs[e] if that vertex is finite, else -1; BOUNDARY iff an entry of
+ *    its run has along + against == 1; FROZEN iff it is not finite, or no entry of its run is finite, or fixed_boundary != 0 and it is
+ *    boundary.  flags [nv] bytes = 1 (finite) | 2 (frozen) | 4 (boundary); state double [nv, 3] = the promoted input.  All of this is
+ *    computed once, from the input.
+ *    cer_mesh_smooth_steps_f64: n_steps steps in stream order, one launch each and no host wait between them; step i = 0, 1, .. reads
+ *    state_a and writes state_b if i is even and the reverse if i is odd, with weight w = w_even or w_odd, so the result is in state_b
+ *    iff n_steps is odd.  (Laplacian: w_even = w_odd = lambda; Taubin: w_even = lambda, w_odd = mu, two steps per iteration.)  One thread
+ *    per vertex: a frozen vertex copies its three doubles; any other, per axis, with p its value in the source buffer:
+ *      s = 0.0;  s = s + source[walk[e]] for e ascending, skipping walk[e] outside 0 .. nv-1, count = the entries taken;
+ *      m = s / double(count);  q = p + w * (m - p).
+ *    Sums in registers, no shared memory.
+ *    cer_mesh_smooth_finish_f32: out float32 [nv, 3] = float(state), rounded once; a frozen vertex gets the bits of its input. */
+long cer_mesh_edge_partials(long long nf);
+int cer_mesh_edge_keys_i64(const int* faces, long long nf, long long nv, long long* keys, void* stream);
+int cer_mesh_edge_count(const long long* sorted_keys, long long nf, unsigned int* partials, long long* offsets, long long* totals,
+                        void* stream);
+int cer_mesh_edge_emit_i32(const long long* sorted_keys, long long nf, const long long* offsets, long long nn, int* owner, int* nbrs,
+                           int* along, int* against, void* stream);
+int cer_mesh_smooth_prepare_f32(const float* vertices, long long nv, const int* nbr_starts, const int* nbrs, const int* along,
+                                const int* against, long long nn, int fixed_boundary, int* walk, unsigned char* flags, double* state,
+                                void* stream);
+int cer_mesh_smooth_steps_f64(double* state_a, double* state_b, long long nv, const int* nbr_starts, const int* walk, long long nn,
+                              const unsigned char* flags, double w_even, double w_odd, int n_steps, void* stream);
+int cer_mesh_smooth_finish_f32(const double* state, const float* vertices, const unsigned char* flags, long long nv, float* out,
+                               void* stream);
+
 /* Multi-GPU row-slab exchange (cer-mvs_amd/slab.py): up to CER_COPY_MAX_SEG contiguous fp32 ranges copied by ONE launch -
  * the pack of a rank's (net, disp) border strips into its send buffer, and the refresh of its halo rows from the gathered
  * strips.  n[i] floats from src[i] to dst[i]; n[i] == 0 skips a segment.  Device pointers; ranges must not overlap. */
