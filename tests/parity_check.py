@@ -1,6 +1,7 @@
 """Element-wise parity checking at production shapes: helpers shared by tests/test_parity_check_cpu.py (which proves on planted
 corruptions that the checker sees what a global mean cannot) and tests/test_fullsize_parity_gpu.py (which applies it to the HIP
-kernels of one GRU iteration and to the cost volume) and tests/test_encoder_parity_gpu.py (the encoder kernels, one launch at a time: the
+kernels of one GRU iteration - through tests/s16_iteration_check.py, which tests/test_s16_ragged_parity_gpu.py runs at ragged sizes with
+forced tile heights - and to the cost volume) and tests/test_encoder_parity_gpu.py (the encoder kernels, one launch at a time: the
 float64 pieces and tile geometries further down), by tests/test_train_parity_{cpu,gpu}.py (the training-row kernels) and by
 tests/test_postproc_parity_{cpu,gpu}.py (the last section: geometric consistency as a float64 chain that carries, next to every value, a
 bound on what a correct fp32 evaluation may deviate by - ``geo_ref64`` / ``check_geo`` / ``GeoReport``: every element is inside its
