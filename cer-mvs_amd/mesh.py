@@ -8,6 +8,7 @@ tests/mesh_clean_reference.py): ``mesh_components``, ``select_faces`` and ``remo
 Simplification (C ABI 1200; tests/mesh_simplify_reference.py): ``simplify_vertex_clustering``, likewise.
 Edges (C ABI 1210; tests/mesh_smooth_reference.py): ``mesh_edges`` / ``edge_table``, the report ``mesh_topology`` and
 ``smooth_mesh`` (Taubin, Laplacian), likewise.
+Hole filling (csrc/mesh_fill.hip, C ABI 1220; tests/mesh_fill_reference.py): ``mesh_holes`` and ``fill_holes``, likewise.
 
 Every argument check that needs no device runs before the library is loaded."""
 import ctypes
@@ -799,8 +800,132 @@ def _smooth_option(value):
                              value.get("boundary", "fixed"), "mesh: smooth")
 
 
+# ---------------------------------------------------------------- hole filling (csrc/mesh_fill.hip, C ABI 1220)
+FILL_INFO_KEYS = ("holes", "added_vertices", "added_faces", "pinched_vertices", "boundary_edges_before")
+NEXT_PINCHED = -2                                            # cer_mvs.h, cer_mesh_hole_next_i32
+
+
+def _max_edges(value, who):
+    """an int >= 3 (bool and float refused), held to what a C int carries - no cycle is longer than nv < 2^31"""
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < 3:
+        raise ValueError(f"{who}: max_edges must be an integer >= 3")
+    return min(int(value), 2 ** 31 - 1)
+
+
+def _hole_tables(faces, nv, max_edges, vertices):
+    """``mesh_edges``, then the two walks on checked, contiguous device arrays -> (next int32 [nv], length int32 [nv], along, against)"""
+    dev, lib = faces.device, L.load()
+    starts, nbrs, along, against, _ = _edges(faces, nv)
+    nn = int(nbrs.shape[0])
+    nxt = torch.empty(nv, device=dev, dtype=torch.int32)
+    length = torch.empty(nv, device=dev, dtype=torch.int32)
+    if nv:
+        pn = L.dev_ptr(nxt, "next", torch.int32)
+        L.check(lib.cer_mesh_hole_next_i32(L.dev_ptr(starts, "nbr_starts", torch.int32), L.dev_ptr(nbrs, "nbrs", torch.int32) if nn else None,
+                                           L.dev_ptr(along, "along", torch.int32) if nn else None,
+                                           L.dev_ptr(against, "against", torch.int32) if nn else None, nv, nn, pn, L.cur_stream()), "mesh_hole_next")
+        L.check(lib.cer_mesh_hole_heads_i32(pn, L.dev_ptr(vertices, "vertices"), nv, max_edges, L.dev_ptr(length, "length", torch.int32),
+                                            L.cur_stream()), "mesh_hole_heads")
+    return nxt, length, along, against
+
+
+def mesh_holes(faces, nv, max_edges, vertices=None):
+    """The small boundary loops of any indexed triangle mesh: faces int32 [nf,3] with indices in 0 .. nv-1 (``mesh_edges``' checks) on the
+    device, ``max_edges`` an int >= 3, ``vertices`` float32 [nv,3] optional -> (head int32 [nh], length int32 [nh]) on the device, heads
+    ascending.  With ``mesh_edges``' counts the directed edge a->b is a boundary half-edge iff along(a, b) == 1 and against(a, b) == 0; a
+    vertex is simple iff exactly one leaves it and exactly one enters it, and its successor is the head of the one that leaves.  A hole is a
+    cycle of successors through simple vertices only, 3 .. ``max_edges`` edges long, named by its smallest index; with ``vertices`` a cycle
+    that holds a non-finite vertex is not one.  A cycle through a pinched vertex (a bow tie, the ends of an inconsistent edge, beside a
+    non-manifold edge) or a longer one - the outer rim of an open scan - is left alone.  The contract is cer_mvs.h's, "Mesh hole filling"."""
+    who = "mesh_holes"
+    max_edges = _max_edges(max_edges, who)
+    nv, _ = _edge_checks(faces, nv, who)
+    if vertices is not None:
+        _check_vertices(vertices, who)
+        if int(vertices.shape[0]) != nv:
+            raise ValueError(f"{who}: vertices float32 [{nv}, 3] (or None) expected")
+        if vertices.device != faces.device:
+            raise ValueError(f"{who}: vertices and faces must be on one device")
+    if not faces.is_cuda:
+        raise RuntimeError(f"{who}: faces must be a CUDA tensor (no CPU fallback)")
+    _, length, _, _ = _hole_tables(faces.contiguous(), nv, max_edges, None if vertices is None else vertices.contiguous())
+    heads = torch.nonzero(length).reshape(-1)                # ascending
+    return heads.to(torch.int32), length[heads]
+
+
+def fill_holes(vertices, faces, max_edges, colors=None, info=None):
+    """The mesh with its small holes closed: vertices float32 [nv,3] and faces int32 [nf,3] with indices in 0 .. nv-1 (``mesh_edges``'
+    checks) on the device, ``max_edges`` an int >= 3, ``colors`` uint8 [nv,3] optional -> (vertices', faces', hole int32 [nf'], colors' |
+    None) on the device.  The nv vertices and nf faces come first, bit-identical and in order; then the fill of every hole of
+    ``mesh_holes(faces, nv, max_edges, vertices)``, hole by hole in head order.  A hole a0 -> a1 -> a2 of three edges gets the one face
+    (a0, a2, a1) and no vertex; a hole a0 .. a(n-1) of four and more gets one new vertex c - per axis the fp64 sum of its members in cycle
+    order divided by n, rounded to float32 once - and the fan (a(k+1), a_k, c), k = 0 .. n-1; the new vertices sit behind the old ones in head
+    order, and the colour of c is the members' integer mean per channel.  ``hole[f]``: -1 for an input face, otherwise the position of its
+    hole in ``mesh_holes``' list.  Every fill face runs against the half-edge it closes: a hole in an oriented mesh leaves the mesh
+    oriented, and every filled boundary edge becomes interior.  ``info`` (a dict) gains "holes" (filled), "added_vertices", "added_faces",
+    "pinched_vertices" (touched by a boundary half-edge but not simple) and "boundary_edges_before"; how many loops there are in all is
+    ``mesh_topology``'s "boundary_loops".
+
+    A loop and the rim of an island are the same thing topologically - a small floating piece of k boundary edges <= ``max_edges`` gets a
+    cap as well: call ``remove_small_components`` first.  A fan around the mean suits the near-planar, near-convex loops that unobserved
+    nodes leave; it is not curvature-aware.  Normals are not carried: call ``vertex_normals`` on the result.  ValueError (the one raised
+    after the device's counts are known): more than 2^31 - 1 vertices or face corners in the result.  The contract is cer_mvs.h's,
+    "Mesh hole filling"."""
+    who = "fill_holes"
+    _check_mesh(vertices, faces, None, colors, who)
+    max_edges = _max_edges(max_edges, who)
+    nv, nf = _edge_checks(faces, vertices.shape[0], who)
+    if not vertices.is_cuda:
+        raise RuntimeError(f"{who}: vertices must be a CUDA tensor (no CPU fallback)")
+    dev = vertices.device
+    vertices, faces = vertices.contiguous(), faces.contiguous()
+    colors = None if colors is None else colors.contiguous()
+    nxt, length, along, against = _hole_tables(faces, nv, max_edges, vertices)
+    heads = torch.nonzero(length).reshape(-1)                # ascending
+    nh = int(heads.shape[0])
+    lens = length[heads]
+    n_faces = torch.where(lens == 3, torch.ones_like(lens), lens).long()
+    n_vertices = (lens > 3).long()
+    face_offsets = (torch.cumsum(n_faces, 0) - n_faces).contiguous()                        # exclusive
+    vertex_offsets = (torch.cumsum(n_vertices, 0) - n_vertices).contiguous()
+    figures = torch.stack([n_faces.sum(), n_vertices.sum(), (nxt == NEXT_PINCHED).sum(), ((along + against) == 1).sum()]).cpu().tolist()
+    added_faces, added_vertices, pinched, boundary_entries = (int(x) for x in figures)      # the one host read after mesh_edges' own
+    if nv + added_vertices >= 2 ** 31 or 3 * (nf + added_faces) >= 2 ** 31:
+        raise ValueError(f"{who}: {nv + added_vertices} vertices / {nf + added_faces} faces is beyond int32 indices")
+    out_v = torch.empty(nv + added_vertices, 3, device=dev, dtype=torch.float32)
+    out_f = torch.empty(nf + added_faces, 3, device=dev, dtype=torch.int32)
+    hole = torch.empty(nf + added_faces, device=dev, dtype=torch.int32)
+    out_c = None if colors is None else torch.empty(nv + added_vertices, 3, device=dev, dtype=torch.uint8)
+    out_v[:nv] = vertices
+    out_f[:nf] = faces
+    hole[:nf] = -1
+    if colors is not None:
+        out_c[:nv] = colors
+    if nh:
+        heads32, lens = heads.to(torch.int32), lens.contiguous()
+        L.check(L.load().cer_mesh_hole_fill_f32(L.dev_ptr(nxt, "next", torch.int32), L.dev_ptr(heads32, "heads", torch.int32),
+                                                L.dev_ptr(lens, "lengths", torch.int32), L.dev_ptr(face_offsets, "face_offsets", torch.int64),
+                                                L.dev_ptr(vertex_offsets, "vertex_offsets", torch.int64), nh,
+                                                L.dev_ptr(vertices, "vertices") if added_vertices else None,
+                                                L.dev_ptr(colors, "colors", torch.uint8), nv, nf, added_vertices, added_faces,
+                                                L.dev_ptr(out_v, "vertices") if added_vertices else None, L.dev_ptr(out_f, "faces", torch.int32),
+                                                L.dev_ptr(hole, "hole", torch.int32), L.dev_ptr(out_c, "colors", torch.uint8), L.cur_stream()),
+                "mesh_hole_fill")
+    if info is not None:
+        info.update(holes=nh, added_vertices=added_vertices, added_faces=added_faces, pinched_vertices=pinched,
+                    boundary_edges_before=boundary_entries // 2)                            # (every edge is in the list from both ends)
+    return out_v, out_f, hole, out_c
+
+
+def _fill_option(value):
+    """the "fill_holes" option, checked -> max_edges"""
+    if isinstance(value, bool) or not isinstance(value, int) or value < 3:
+        raise ValueError("mesh: fill_holes must be an integer >= 3 (the longest loop to close, in edges)")
+    return value
+
+
 MESH_OPTION_KEYS = ("voxel", "resolution", "trunc", "min_weight", "margin", "colors", "normals", "min_component", "keep_largest", "simplify",
-                    "smooth", "topology")
+                    "smooth", "topology", "fill_holes")
 
 
 def mesh_options(mesh):
@@ -809,7 +934,8 @@ def mesh_options(mesh):
     ``min_faces``) and "keep_largest": an int >= 1 each; "simplify": a positive finite number k - ``simplify_vertex_clustering`` with a cell
     of k mesh voxels - or {"voxels": k | "cell": world units, "representative": "quadric" | "mean", "regularisation": a positive finite
     number}, "voxels" and "cell" exclusive; "smooth": an int n >= 1 - ``smooth_mesh`` with n Taubin iterations and its defaults - or
-    {"iterations": n, "method", "lam", "mu", "boundary"} with ``smooth_mesh``'s values; "topology": True."""
+    {"iterations": n, "method", "lam", "mu", "boundary"} with ``smooth_mesh``'s values; "topology": True; "fill_holes": an int n >= 3 -
+    ``fill_holes`` with ``max_edges`` = n."""
     if mesh is True:
         return {}
     if not isinstance(mesh, dict):
@@ -836,6 +962,8 @@ def mesh_options(mesh):
         _smooth_option(mesh["smooth"])
     if "topology" in mesh and mesh["topology"] is not True:
         raise ValueError("mesh: topology must be True")
+    if "fill_holes" in mesh:
+        _fill_option(mesh["fill_holes"])
     return dict(mesh)
 
 
@@ -860,7 +988,10 @@ def mesh_of_scan(xyz, est, masks, Ks, Es, refs, options, colors=None):
     and it gains "extracted": (nv, nf) of the extraction, and the removal's figures.  With "simplify": ``simplify_vertex_clustering`` after
     the removal and before the attributes; ``info``'s "nv" and "nf" describe the returned mesh and it gains "simplified_from": (nv, nf) before,
     and the simplification's figures.  With "smooth": ``smooth_mesh`` after the removal and before "simplify" and the attributes; ``info``
-    gains "smoothed", ``smooth_mesh``'s info.  With "topology": ``info`` gains "topology", ``mesh_topology`` of the returned mesh."""
+    gains "smoothed", ``smooth_mesh``'s info.  With "topology": ``info`` gains "topology", ``mesh_topology`` of the returned mesh.  With
+    "fill_holes": ``fill_holes`` after the removal - an island's rim is a loop too - and before "smooth", "simplify" and the attributes, so
+    that fewer vertices are frozen on a boundary and colours and normals belong to the returned mesh; ``info``'s "nv" and "nf" describe the
+    returned mesh and it gains "filled", ``fill_holes``' info."""
     opt = dict(options)
     min_weight = opt.pop("min_weight", 1)
     trunc = opt.pop("trunc", None)
@@ -868,12 +999,17 @@ def mesh_of_scan(xyz, est, masks, Ks, Es, refs, options, colors=None):
     min_component, keep_largest = opt.pop("min_component", None), opt.pop("keep_largest", None)
     simplify = opt.pop("simplify", None)
     smooth, want_topology = opt.pop("smooth", None), opt.pop("topology", None)
+    fill = opt.pop("fill_holes", None)
     grid = grid_for(xyz, trunc=trunc, **opt)
     info, attributes = {}, {}
     v, f = mesh_from_depth_maps(est, masks, Ks, Es, grid, trunc=trunc, views=refs, min_weight=min_weight, info=info)
     if min_component is not None or keep_largest is not None:            # before the attributes: they are computed on what is returned
         info["extracted"] = (info["nv"], info["nf"])
         v, f, _, _, _ = remove_small_components(v, f, min_faces=min_component, keep_largest=keep_largest, info=info)
+        info.update(nv=int(v.shape[0]), nf=int(f.shape[0]))
+    if fill is not None:                                                 # after the removal: an island's rim is a loop too
+        info["filled"] = {}
+        v, f, _, _ = fill_holes(v, f, _fill_option(fill), info=info["filled"])
         info.update(nv=int(v.shape[0]), nf=int(f.shape[0]))
     if smooth is not None:                                               # denoise first, then reduce
         iterations, method, lam, mu, boundary = _smooth_option(smooth)

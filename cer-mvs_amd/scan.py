@@ -395,7 +395,11 @@ def reconstruct_scan(model_or_ckpt, images, poses, intrinsics, names, pairs, sca
     >= 1 - Taubin smoothing with n iterations - or {"iterations": n, "method": "taubin" | "laplacian", "lam", "mu", "boundary": "fixed" |
     "free"}: ``mesh.smooth_mesh`` after the small-piece removal and before "simplify", colours and normals; ``mesh_info`` gains "smoothed"
     ({"moved", "frozen_boundary", "steps", "edges"}); "topology": True - ``mesh_info`` gains "topology", ``mesh.mesh_topology`` of the
-    returned mesh."""
+    returned mesh.  And one: "fill_holes": n, an int >= 3 - ``mesh.fill_holes`` with ``max_edges`` = n: every boundary loop
+    of at most n edges through simple vertices is closed, by one face (three edges) or by a fan around the loop's mean; it runs after the
+    small-piece removal (an island's rim is a loop too) and before "smooth", "simplify", colours and normals; ``mesh_info`` "nv" / "nf"
+    describe the returned mesh and it gains "filled" ({"holes", "added_vertices", "added_faces", "pinched_vertices",
+    "boundary_edges_before"}).  Without the key nothing changes."""
     two_pass = isinstance(rescale, (tuple, list))
     passes = [r for r in rescale] if two_pass else [rescale]
     if two_pass and (len(passes) != 2 or passes[1] != 2 * passes[0]):

@@ -952,6 +952,61 @@ int cer_mesh_smooth_steps_f64(double* state_a, double* state_b, long long nv, co
 int cer_mesh_smooth_finish_f32(const double* state, const float* vertices, const unsigned char* flags, long long nv, float* out,
                                void* stream);
 
+/* Mesh hole filling (ABI 1220; csrc/mesh_fill.hip, cer-mvs_amd/mesh.py mesh_holes / fill_holes): the small boundary loops
+ * of any indexed triangle mesh closed by one face or by a fan around the loop's mean, starting from the neighbour list of the section "Mesh
+ * edges and smoothing" and under the rules of the section "Surface mesh": integers, fp64 with every association as written, no fused
+ * multiply-add, IEEE division, no atomics, one writer per address, the same bytes on every run.  faces int32 [nf, 3]; vertices float32
+ * [nv, 3]; nbr_starts int32 [nv + 1], nbrs, along, against int32 [nn]: what cer_mesh_edge_emit_i32 and its caller produce.
+ *
+ * Checks, in that section's order, all before any launch: (1) a negative size (nv, nn, nh, nf, added_vertices, added_faces) ->
+ * CER_EINVAL; (2) nv, nn, nh, nv + added_vertices or 3 (nf + added_faces) >= 2^31, nh > nv, added_vertices > nh, or max_edges < 3 ->
+ * CER_ESHAPE; (3) nothing to do -> CER_OK with nothing launched (the successors and the heads: nv == 0; the fill: nh == 0); (4) a null
+ * pointer -> CER_EINVAL.  The optional pointers are null iff absent: the successors: nbrs, along and against iff nn == 0; the heads:
+ * vertices iff the finiteness test is not wanted; the fill: vertices and out_vertices iff added_vertices == 0 (holes of three edges only),
+ * colors and out_colors together iff there are no colours - one of the two alone is refused.  An index, a list position or an output row
+ * outside its range is skipped, never read or written through (the Python layer refuses such faces).
+ *
+ * 1. Boundary half-edges and simple vertices.  With the counts of the neighbour list, the directed edge a->b is a BOUNDARY HALF-EDGE iff
+ *    along(a, b) == 1 and against(a, b) == 0: one face runs along it and none against it.  Vertex v is SIMPLE iff exactly one boundary
+ *    half-edge leaves it and exactly one enters it (in v's run: exactly one entry with along == 1 and against == 0, and exactly one with
+ *    along == 0 and against == 1).  next int32 [nv]: next[v] = the head of the leaving half-edge of a simple vertex; -1 where no boundary
+ *    half-edge touches v; -2 ("pinched") where some do but v is not simple - a bow-tie vertex, the ends of an inconsistent edge, a vertex
+ *    beside a non-manifold edge.
+ *    cer_mesh_hole_next_i32: one thread per vertex walks its run of the list once and writes next[v].
+ * 2. Holes.  A HOLE is a cycle h = a0 -> a1 -> .. -> a(n-1) -> a0 of next through simple vertices only, a(k+1) = next[a_k]; h is its
+ *    smallest index and 3 <= n <= max_edges.  (A cycle of two edges is impossible: a->b and b->a would both be boundary half-edges, but
+ *    each is counted against the other.)  With vertices given, a cycle that holds a vertex with a non-finite coordinate is not a hole.  A
+ *    cycle through a pinched vertex, or longer than max_edges - the outer rim of an open scan - is left alone.  next is injective on the
+ *    simple vertices, so a walk along it either returns to its start or ends at a pinched vertex.
+ *    cer_mesh_hole_heads_i32: length int32 [nv]: length[v] = n if v is the head of a hole of n edges, else 0.  One thread per vertex
+ *    with next[v] >= 0 follows next for at most max_edges steps and stops at a negative entry (no hole), at an index below v (v is not
+ *    the head), at a non-finite member (with vertices) or back at v.
+ *    The holes, in the order of their heads (ascending), are numbered 0 .. nh-1 ("position"): heads int32 [nh] and lengths int32 [nh] are
+ *    the caller's compaction of length's non-zero entries.
+ * 3. Fill.  The nv vertices and nf faces of the input come first in the output, bit-identical and in order (the caller's copies); then
+ *    the fill follows, hole by hole in head order.  For n == 3 the fill is the ONE face (a0, a2, a1) and no vertex.  For n >= 4 it is one
+ *    new vertex c, per axis in fp64
+ *      s = 0.0;  s = s + double(p[a_k]) for k = 0 .. n-1;  m = s / double(n);  c = float(m), rounded once,
+ *    and the n faces (a(k+1), a_k, c) for k = 0 .. n-1, indices mod n.  The new vertices sit behind the old ones in head order: c = nv +
+ *    vertex_offsets[i]; the faces of hole i start at nf + face_offsets[i]: face_offsets and vertex_offsets int64 [nh] are the caller's
+ *    exclusive sums of (n == 3 ? 1 : n) and (n >= 4 ? 1 : 0), and added_faces and added_vertices their totals - the rows of the outputs
+ *    behind nf and nv, never a byte beyond them.  hole int32 [nf + added_faces]: -1 for an input face (the caller's), otherwise the position
+ *    of the face's hole.  colors uint8 [nv, 3]: the colour of c is the members' integer sum per channel divided by n, integer division (the
+ *    rule of "Mesh simplification", item 4).
+ *    Every fill face runs against the half-edge it closes - (a(k+1), a_k, .) holds a(k+1)->a_k, and (a0, a2, a1) holds a1->a0, a2->a1 and
+ *    a0->a2 - so a hole in an oriented mesh leaves the mesh oriented, every filled boundary edge becomes interior, and the spokes c-a_k
+ *    are interior and consistent.
+ *    cer_mesh_hole_fill_f32: one thread per hole walks its cycle once more, sums in registers in the order above, and writes the centre,
+ *    its colour, the faces and hole[] of its hole; no shared memory.  out_vertices float32 [nv + added_vertices, 3], out_faces int32
+ *    [nf + added_faces, 3], out_colors uint8 [nv + added_vertices, 3]: only the rows behind nv and nf are written. */
+int cer_mesh_hole_next_i32(const int* nbr_starts, const int* nbrs, const int* along, const int* against, long long nv, long long nn,
+                           int* next, void* stream);
+int cer_mesh_hole_heads_i32(const int* next, const float* vertices, long long nv, int max_edges, int* length, void* stream);
+int cer_mesh_hole_fill_f32(const int* next, const int* heads, const int* lengths, const long long* face_offsets,
+                           const long long* vertex_offsets, long long nh, const float* vertices, const unsigned char* colors, long long nv,
+                           long long nf, long long added_vertices, long long added_faces, float* out_vertices, int* out_faces, int* hole,
+                           unsigned char* out_colors, void* stream);
+
 /* Multi-GPU row-slab exchange (cer-mvs_amd/slab.py): up to CER_COPY_MAX_SEG contiguous fp32 ranges copied by ONE launch -
  * the pack of a rank's (net, disp) border strips into its send buffer, and the refresh of its halo rows from the gathered
  * strips.  n[i] floats from src[i] to dst[i]; n[i] == 0 skips a segment.  Device pointers; ranges must not overlap. */
