@@ -9,7 +9,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CER_MVS_LIB") or os.path.join(_HERE, "csrc", "libcermvs.so")
-ABI_VERSION = 1220
+ABI_VERSION = 1230
 CONV_MAX_SRC = 4
 EPI_LINEAR, EPI_RELU, EPI_GATES, EPI_GRU, EPI_DELTA = 0, 1, 2, 3, 4
 EPI_OUT_SPLIT, EPI_AUX_SPLIT = 0x100, 0x200       # cer_mvs.h: split32 activation layout flags, or-ed into `epi`
@@ -27,6 +27,7 @@ _L = _c.c_long
 _F = _c.c_float
 _D = _c.c_double
 _LL = _c.c_longlong
+_ULL = _c.c_ulonglong
 
 
 class ConvInputs(ctypes.Structure):
@@ -167,6 +168,9 @@ _SIGNATURES = {
     "cer_mesh_hole_next_i32": (_I, [_P, _P, _P, _P, _LL, _LL, _P, _P]),
     "cer_mesh_hole_heads_i32": (_I, [_P, _P, _LL, _I, _P, _P]),
     "cer_mesh_hole_fill_f32": (_I, [_P, _P, _P, _P, _P, _LL, _P, _P, _LL, _LL, _LL, _LL, _P, _P, _P, _P, _P]),
+    "cer_mesh_face_areas_f64": (_I, [_P, _LL, _P, _LL, _P, _P]),
+    "cer_mesh_face_weights_i64": (_I, [_P, _LL, _I, _P, _P]),
+    "cer_mesh_sample_f32": (_I, [_P, _LL, _P, _LL, _P, _ULL, _ULL, _P, _LL, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 # include/cer_mvs_variants.h: exported by csrc/variants/libcermvs_optin.so only (round 4's opt-in kernel forms; CER_MVS_LIB selects the library)

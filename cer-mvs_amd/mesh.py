@@ -9,6 +9,8 @@ Simplification (C ABI 1200; tests/mesh_simplify_reference.py): ``
 Edges (C ABI 1210; tests/mesh_smooth_reference.py): ``mesh_edges`` / ``edge_table``, the report ``mesh_topology`` and
 ``smooth_mesh`` (Taubin, Laplacian), likewise.
 Hole filling (csrc/mesh_fill.hip, C ABI 1220; tests/mesh_fill_reference.py): ``mesh_holes`` and ``fill_holes``, likewise.
+Surface sampling (csrc/mesh_sample.hip, C ABI 1230; tests/mesh_sample_reference.py): ``face_areas``, ``sample_mesh``,
+``sample_mesh_even`` and ``evaluate_mesh``, likewise.
 
 Every argument check that needs no device runs before the library is loaded."""
 import ctypes
@@ -924,8 +926,238 @@ def _fill_option(value):
     return value
 
 
+# ---------------------------------------------------------------- surface sampling (csrc/mesh_sample.hip, C ABI 1230)
+SAMPLE_INFO_KEYS = ("n", "area", "faces_with_weight", "shift")
+SAMPLE_MAX = 2 ** 31 - 1                                     # samples per call, and 3 nf
+SAMPLE_OPTION_KEYS = ("n", "density", "spacing", "seed")
+
+
+def _sample_mesh_checks(vertices, faces, colors, who):
+    """the mesh of the sampling calls, checked without a device -> (nv, nf)"""
+    _check_mesh(vertices, faces, None, colors, who)
+    nv, nf = int(vertices.shape[0]), int(faces.shape[0])
+    if 3 * nf > SAMPLE_MAX:
+        raise ValueError(f"{who}: 3 nf must be in 0 .. 2^31 - 1")
+    return nv, nf
+
+
+def _word64(value, name, who):
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not 0 <= int(value) < 2 ** 64:
+        raise ValueError(f"{who}: {name} must be an integer in 0 .. 2^64 - 1")
+    return int(value)
+
+
+def _sample_count(value, name, who):
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not 0 <= int(value) <= SAMPLE_MAX:
+        raise ValueError(f"{who}: {name} must be an integer in 0 .. 2^31 - 1")
+    return int(value)
+
+
+def _areas(vertices, faces, nv, nf):
+    """``face_areas`` on checked, contiguous device arrays"""
+    areas = torch.empty(nf, device=vertices.device, dtype=torch.float64)
+    if nf:
+        L.check(L.load().cer_mesh_face_areas_f64(L.dev_ptr(vertices, "vertices") if nv else None, nv, L.dev_ptr(faces, "faces", torch.int32), nf,
+                                                 L.dev_ptr(areas, "areas", torch.float64), L.cur_stream()), "mesh_face_areas")
+    return areas
+
+
+def face_areas(vertices, faces):
+    """The area of every face of any indexed triangle mesh: vertices float32 [nv,3] and faces int32 [nf,3] on the device -> float64 [nf] on
+    the device.  In fp64 on the float32 coordinates: e1 = b - a, e2 = c - a, n = e1 x e2 with every product and difference rounded on its
+    own, area = 0.5 * sqrt((nx*nx + ny*ny) + nz*nz).  A face with an index outside 0 .. nv-1, with a repeated index or with a non-finite
+    coordinate has area 0: it is not refused.  The contract is cer_mvs.h's, "Mesh surface sampling"."""
+    who = "face_areas"
+    nv, nf = _sample_mesh_checks(vertices, faces, None, who)
+    if not vertices.is_cuda:
+        raise RuntimeError(f"{who}: vertices must be a CUDA tensor (no CPU fallback)")
+    return _areas(vertices.contiguous(), faces.contiguous(), nv, nf)
+
+
+def _sample_table(vertices, faces, nv, nf):
+    """the prefix sums of the integer weights on checked, contiguous device arrays -> (cum int64 [nf] | None, W, shift, faces with weight);
+    W == 0 (and no table) for a mesh without area.  Two host reads: the largest area, then the total with the count."""
+    if nf == 0:
+        return None, 0, 0, 0
+    areas = _areas(vertices, faces, nv, nf)
+    amax = float(areas.max().cpu())                          # a maximum is exact under any association
+    if not (amax > 0.0 and math.isfinite(amax)):
+        return None, 0, 0, 0
+    shift = 32 - math.frexp(amax)[1]                         # the largest weight lands in [2^31, 2^32)
+    weights = torch.empty(nf, device=vertices.device, dtype=torch.int64)
+    L.check(L.load().cer_mesh_face_weights_i64(L.dev_ptr(areas, "areas", torch.float64), nf, shift, L.dev_ptr(weights, "weights", torch.int64),
+                                               L.cur_stream()), "mesh_face_weights")
+    cum = torch.cumsum(weights, 0)                           # integers: exact whatever the scan's shape
+    total, count = (int(x) for x in torch.stack([cum[-1], (weights > 0).sum()]).cpu().tolist())
+    return cum.contiguous(), total, shift, count
+
+
+def _draw(vertices, faces, nv, nf, cum, seed, offset, words, n, normals, colors, uv):
+    """the sample kernel on checked, contiguous device arrays -> (points, face, normals | None, colors | None, uv | None)"""
+    dev = vertices.device
+    points = torch.empty(n, 3, device=dev, dtype=torch.float32)
+    face = torch.empty(n, device=dev, dtype=torch.int32)
+    out_n = torch.empty(n, 3, device=dev, dtype=torch.float32) if normals else None
+    out_c = None if colors is None else torch.empty(n, 3, device=dev, dtype=torch.uint8)
+    out_uv = torch.empty(n, 2, device=dev, dtype=torch.float64) if uv else None
+    if n:
+        L.check(L.load().cer_mesh_sample_f32(L.dev_ptr(vertices, "vertices") if nv else None, nv, L.dev_ptr(faces, "faces", torch.int32), nf,
+                                             L.dev_ptr(cum, "cum", torch.int64), seed, offset, L.dev_ptr(words, "words", torch.uint32), n,
+                                             L.dev_ptr(colors, "colors", torch.uint8), L.dev_ptr(points, "points"),
+                                             L.dev_ptr(face, "face", torch.int32), L.dev_ptr(out_uv, "uv", torch.float64),
+                                             L.dev_ptr(out_n, "normals"), L.dev_ptr(out_c, "colors", torch.uint8), L.cur_stream()), "mesh_sample")
+    return points, face, out_n, out_c, out_uv
+
+
+def sample_mesh(vertices, faces, n=None, density=None, seed=0, offset=0, words=None, normals=False, colors=None, uv=False, info=None):
+    """Points on the surface of any indexed triangle mesh, drawn with a density proportional to area: vertices float32 [nv,3] and faces int32
+    [nf,3] on the device -> (points float32 [n,3], face int32 [n], normals float32 [n,3] | None, colors uint8 [n,3] | None, uv float64 [n,2]
+    | None) on the device.  Exactly one of ``n`` (an int >= 0), ``density`` (samples per unit area, a positive finite number: n = ceil(area *
+    density)) and ``words`` (uint32 [n,4] on the device: the caller's own four random words per sample - a low-discrepancy sequence, or a
+    test's planted values) fixes the count.
+
+    Every face gets the integer weight floor(area * 2^shift), the shift chosen so that the largest weight lies in [2^31, 2^32): the prefix
+    sums and their total W are exact, a face smaller than 2^-32 of the largest has weight 0 and is never drawn, and the sampling density is
+    uniform to 2^-31 of the largest face per face.  Faces that ``face_areas`` gives area 0 (an index out of range, a repeated index, a
+    non-finite coordinate) are never drawn either.  Sample i has the global index k = ``offset`` + i and, without ``words``, the words
+    Philox4x32-10(counter (k, 0, 0) in 32-bit halves, key ``seed``); x0 and x1 pick the face - t = floor((x0 * 2^32 + x1) * W / 2^64), the
+    first face whose prefix sum exceeds t - and x2 and x3 the point: (a, b) mirrored through the square's centre when a + b >= 2^32, u = (a +
+    0.5) / 2^32, v = (b + 0.5) / 2^32, w = 1 - u - v, p = float((w*A + u*B) + v*C).  Sample k is a pure function of (seed, k, mesh):
+    ``n=100`` gives the first 100 rows of ``n=1000``, and ``offset=50, n=50`` rows 50 .. 99.  ``normals``: the face's unit normal;
+    ``colors`` uint8 [nv,3]: the corners' colours mixed with (w, u, v) and rounded; ``uv``: (u, v).  ``info`` (a dict) gains "n", "area"
+    (what the weights stand for: W / 2^shift), "faces_with_weight" and "shift".
+
+    ValueError: bad arguments (before any device work); n > 0 on a mesh whose largest area is 0 or that has no face; more than 2^31 - 1
+    samples from a density.  n == 0 returns empties.  RuntimeError: tensors that are not on the device.  The contract is cer_mvs.h's,
+    "Mesh surface sampling"."""
+    who = "sample_mesh"
+    nv, nf = _sample_mesh_checks(vertices, faces, colors, who)
+    if sum(x is not None for x in (n, density, words)) != 1:
+        raise ValueError(f"{who}: exactly one of n, density and words expected")
+    if n is not None:
+        n = _sample_count(n, "n", who)
+    if density is not None:
+        density = _positive(density, "density", who)
+    if words is not None:
+        if not isinstance(words, torch.Tensor) or words.dtype != torch.uint32 or words.dim() != 2 or words.shape[1] != 4:
+            raise ValueError(f"{who}: words uint32 [n, 4] expected")
+        if words.shape[0] > SAMPLE_MAX:
+            raise ValueError(f"{who}: {words.shape[0]} rows of words is beyond 2^31 - 1 samples")
+        if words.device != vertices.device:
+            raise ValueError(f"{who}: vertices and words must be on one device")
+        n = int(words.shape[0])
+    seed, offset = _word64(seed, "seed", who), _word64(offset, "offset", who)
+    for name, flag in (("normals", normals), ("uv", uv)):
+        if not isinstance(flag, bool):
+            raise ValueError(f"{who}: {name} must be True or False")
+    if not vertices.is_cuda:
+        raise RuntimeError(f"{who}: vertices must be a CUDA tensor (no CPU fallback)")
+    vertices, faces = vertices.contiguous(), faces.contiguous()
+    colors = None if colors is None else colors.contiguous()
+    cum, W, shift, count = _sample_table(vertices, faces, nv, nf)
+    area = math.ldexp(float(W), -shift)
+    if density is not None:
+        wanted = math.ceil(area * density)
+        if wanted > SAMPLE_MAX:
+            raise ValueError(f"{who}: density {density} on an area of {area} asks for {wanted} samples, beyond 2^31 - 1")
+        n = int(wanted)
+    if n and W == 0:
+        raise ValueError(f"{who}: {n} samples asked of a mesh without area ({nf} faces)")
+    if info is not None:
+        info.update(n=n, area=area, faces_with_weight=count, shift=shift)
+    return _draw(vertices, faces, nv, nf, cum, seed, offset, None if words is None else words.contiguous(), n, normals, colors, uv)
+
+
+def sample_mesh_even(vertices, faces, spacing, oversample=8.0, seed=0, normals=False, colors=None, info=None):
+    """Evenly spaced points on the surface of a mesh (Poisson-disk sampling by elimination): ``sample_mesh`` draws n0 = ceil(``oversample`` *
+    area / ``spacing``^2) samples, ``cloud_eval.radius_thin(points, spacing, order="index")`` thins them - the samples' own order already is a
+    random order - and the kept rows come back in index order with their attributes -> (points float32 [m,3], face int32 [m], normals
+    float32 [m,3] | None, colors uint8 [m,3] | None) on the device.  ``radius_thin``'s two properties hold: kept points are pairwise farther
+    apart than ``spacing``, and every drawn sample has a kept one within ``spacing``.  With the default ``oversample`` a disk of that radius
+    around a surface point holds about 8 pi drawn samples, so the surface itself is covered to about the spacing as well.  ``info`` (a
+    dict) gains "drawn", "kept", ``sample_mesh``'s "area", "faces_with_weight" and "shift", and ``radius_thin``'s "rounds", "compactions"
+    and "n_finite".  ValueError: bad arguments; n0 beyond 2^31 - 1; a mesh without area (n0 == 0 returns empties).  The set is
+    ``radius_thin``'s: unique, whatever the schedule of the device."""
+    from .cloud_eval import radius_thin
+    who = "sample_mesh_even"
+    nv, nf = _sample_mesh_checks(vertices, faces, colors, who)
+    spacing, oversample = _positive(spacing, "spacing", who), _positive(oversample, "oversample", who)
+    if not float(np.float32(spacing)) > 0.0 or not math.isfinite(float(np.float32(spacing))):
+        raise ValueError(f"{who}: spacing must be a positive finite float32")
+    seed = _word64(seed, "seed", who)
+    if not isinstance(normals, bool):
+        raise ValueError(f"{who}: normals must be True or False")
+    if not vertices.is_cuda:
+        raise RuntimeError(f"{who}: vertices must be a CUDA tensor (no CPU fallback)")
+    vertices, faces = vertices.contiguous(), faces.contiguous()
+    colors = None if colors is None else colors.contiguous()
+    cum, W, shift, count = _sample_table(vertices, faces, nv, nf)
+    area = math.ldexp(float(W), -shift)
+    n0 = math.ceil(oversample * area / (spacing * spacing))
+    if n0 > SAMPLE_MAX:
+        raise ValueError(f"{who}: spacing {spacing} on an area of {area} asks for {n0} samples, beyond 2^31 - 1; take a larger spacing")
+    n0 = int(n0)
+    points, face, out_n, out_c, _ = _draw(vertices, faces, nv, nf, cum, seed, 0, None, n0, normals, colors, False)
+    thin = {}
+    kept = radius_thin(points, spacing, order="index", info=thin)
+    if info is not None:
+        info.update(drawn=n0, kept=int(kept.shape[0]), area=area, faces_with_weight=count, shift=shift, **thin)
+    return tuple(None if a is None else a.index_select(0, kept) for a in (points, face, out_n, out_c))
+
+
+def evaluate_mesh(vertices, faces, gt, spacing, max_dist=20.0, tau=None, seed=0, align=None, oversample=8.0):
+    """A mesh against a ground-truth cloud, by way of evenly spaced samples of its surface - the route of the Tanks-and-Temples and Open3D
+    evaluations: ``sample_mesh_even(vertices, faces, spacing, oversample, seed)``, then ``cloud_eval.accuracy_completeness(samples, gt,
+    max_dist, align=align)`` and, with ``tau``, ``cloud_eval.fscore(samples, gt, tau, align=align)`` -> one dict: the keys of both, and
+    "samples" (how many points stand for the mesh) and "spacing".  ``gt`` float32 [m,3] on the mesh's device.
+
+    What this measures: distances to SAMPLES of the surface, not to the surface.  On the mesh's side (accuracy, precision) a sample is a
+    surface point and its figure is exact for that point.  On the ground truth's side (completeness, recall) the nearest sample is farther
+    than the surface is, by up to about the spacing: those figures carry an upward bias of that size - take a spacing well below ``tau``
+    and below the accuracy that is to be resolved.  The exact point-to-triangle search is future work."""
+    from .cloud_eval import accuracy_completeness, fscore
+    who = "evaluate_mesh"
+    if not isinstance(gt, torch.Tensor) or gt.dim() != 2 or gt.shape[1] != 3 or gt.dtype != torch.float32:
+        raise ValueError(f"{who}: gt float32 [m, 3] expected")
+    if not (isinstance(max_dist, (int, float)) and not isinstance(max_dist, bool) and math.isfinite(max_dist) and max_dist > 0):
+        raise ValueError(f"{who}: max_dist must be a positive finite number")
+    if tau is not None:
+        tau = _positive(tau, "tau", who)
+    if isinstance(vertices, torch.Tensor) and gt.device != vertices.device:
+        raise ValueError(f"{who}: vertices and gt must be on one device")
+    samples = sample_mesh_even(vertices, faces, spacing, oversample=oversample, seed=seed)[0]
+    out = accuracy_completeness(samples, gt, max_dist, align=align)
+    if tau is not None:
+        out.update(fscore(samples, gt, tau, align=align))
+    out.update(samples=int(samples.shape[0]), spacing=float(spacing))
+    return out
+
+
+def _sample_option(value):
+    """the "sample" option, checked -> (kind, amount, seed), kind one of "n", "density", "spacing\""""
+    text = ("mesh: sample must be an integer n >= 1 or a dictionary with \"n\", \"density\" or \"spacing\" (exactly one of them) and "
+            "optionally \"seed\"")
+    if not isinstance(value, dict):
+        if isinstance(value, bool) or not isinstance(value, int) or not 1 <= value <= SAMPLE_MAX:
+            raise ValueError(text)
+        return "n", value, 0
+    kinds = [k for k in ("n", "density", "spacing") if k in value]
+    if set(value) - set(SAMPLE_OPTION_KEYS) or len(kinds) != 1:
+        raise ValueError(text)
+    kind, amount = kinds[0], value[kinds[0]]
+    if kind == "n":
+        if isinstance(amount, bool) or not isinstance(amount, int) or not 1 <= amount <= SAMPLE_MAX:
+            raise ValueError("mesh: sample: n must be an integer in 1 .. 2^31 - 1")
+    else:
+        amount = _positive(amount, f"sample: {kind}", "mesh")
+    seed = value.get("seed", 0)
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
+        raise ValueError("mesh: sample: seed must be an integer in 0 .. 2^64 - 1")
+    return kind, amount, seed
+
+
 MESH_OPTION_KEYS = ("voxel", "resolution", "trunc", "min_weight", "margin", "colors", "normals", "min_component", "keep_largest", "simplify",
-                    "smooth", "topology", "fill_holes")
+                    "smooth", "topology", "fill_holes", "sample")
 
 
 def mesh_options(mesh):
@@ -935,7 +1167,8 @@ def mesh_options(mesh):
     of k mesh voxels - or {"voxels": k | "cell": world units, "representative": "quadric" | "mean", "regularisation": a positive finite
     number}, "voxels" and "cell" exclusive; "smooth": an int n >= 1 - ``smooth_mesh`` with n Taubin iterations and its defaults - or
     {"iterations": n, "method", "lam", "mu", "boundary"} with ``smooth_mesh``'s values; "topology": True; "fill_holes": an int n >= 3 -
-    ``fill_holes`` with ``max_edges`` = n."""
+    ``fill_holes`` with ``max_edges`` = n; "sample": an int n >= 1 - ``sample_mesh`` with n samples and seed 0 - or {"n": samples |
+    "density": samples per unit area | "spacing": world units (``sample_mesh_even``), "seed": an int}, exactly one of the three."""
     if mesh is True:
         return {}
     if not isinstance(mesh, dict):
@@ -964,6 +1197,8 @@ def mesh_options(mesh):
         raise ValueError("mesh: topology must be True")
     if "fill_holes" in mesh:
         _fill_option(mesh["fill_holes"])
+    if "sample" in mesh:
+        _sample_option(mesh["sample"])
     return dict(mesh)
 
 
@@ -991,7 +1226,10 @@ def mesh_of_scan(xyz, est, masks, Ks, Es, refs, options, colors=None):
     gains "smoothed", ``smooth_mesh``'s info.  With "topology": ``info`` gains "topology", ``mesh_topology`` of the returned mesh.  With
     "fill_holes": ``fill_holes`` after the removal - an island's rim is a loop too - and before "smooth", "simplify" and the attributes, so
     that fewer vertices are frozen on a boundary and colours and normals belong to the returned mesh; ``info``'s "nv" and "nf" describe the
-    returned mesh and it gains "filled", ``fill_holes``' info."""
+    returned mesh and it gains "filled", ``fill_holes``' info.  With "sample": last of all, on the returned mesh, ``sample_mesh`` ("n",
+    "density") or ``sample_mesh_even`` ("spacing"); ``attributes`` gains "mesh_samples" (float32 [n,3]) and "mesh_sample_faces" (int32 [n])
+    and, when colours were asked for, "mesh_sample_colors" (uint8 [n,3], mixed from the vertex colours); ``info`` gains "sampled", the
+    call's info."""
     opt = dict(options)
     min_weight = opt.pop("min_weight", 1)
     trunc = opt.pop("trunc", None)
@@ -999,7 +1237,7 @@ def mesh_of_scan(xyz, est, masks, Ks, Es, refs, options, colors=None):
     min_component, keep_largest = opt.pop("min_component", None), opt.pop("keep_largest", None)
     simplify = opt.pop("simplify", None)
     smooth, want_topology = opt.pop("smooth", None), opt.pop("topology", None)
-    fill = opt.pop("fill_holes", None)
+    fill, sample = opt.pop("fill_holes", None), opt.pop("sample", None)
     grid = grid_for(xyz, trunc=trunc, **opt)
     info, attributes = {}, {}
     v, f = mesh_from_depth_maps(est, masks, Ks, Es, grid, trunc=trunc, views=refs, min_weight=min_weight, info=info)
@@ -1031,6 +1269,17 @@ def mesh_of_scan(xyz, est, masks, Ks, Es, refs, options, colors=None):
         attributes["mesh_normals"] = vertex_normals(v, f)
     if want_topology is not None:
         info["topology"] = mesh_topology(f, int(v.shape[0]))
+    if sample is not None:                                               # last: the samples belong to the returned mesh and its colours
+        kind, amount, seed = _sample_option(sample)
+        info["sampled"] = {}
+        vertex_cols = attributes.get("mesh_colors")
+        if kind == "spacing":
+            points, face, _, cols = sample_mesh_even(v, f, amount, seed=seed, colors=vertex_cols, info=info["sampled"])
+        else:
+            points, face, _, cols, _ = sample_mesh(v, f, seed=seed, colors=vertex_cols, info=info["sampled"], **{kind: amount})
+        attributes["mesh_samples"], attributes["mesh_sample_faces"] = points, face
+        if cols is not None:
+            attributes["mesh_sample_colors"] = cols
     return v, f, info, attributes
 
 

@@ -24,6 +24,7 @@ stack, ``depths`` and ``inference_scan`` run ``pipeline.checked`` (the latter th
 import time
 from pathlib import Path
 
+import numpy as np
 import torch
 
 from . import fusion as FU
@@ -331,7 +332,7 @@ def _cloud_tail(masks, est, Ks, Es, colors, refs, clean, normals, mesh=None):
         from .mesh import mesh_of_scan
         mv, mf, out["mesh_info"], attributes = mesh_of_scan(xyz, est, masks, Ks, Es, refs, mesh, colors=colors)
         out["mesh_vertices"], out["mesh_faces"] = mv.cpu().numpy(), mf.cpu().numpy()
-        out.update({k: a.cpu().numpy() for k, a in attributes.items()})          # "mesh_colors" / "mesh_normals", if asked for
+        out.update({k: a.cpu().numpy() for k, a in attributes.items()})          # "mesh_colors" / "mesh_normals" / "mesh_sample*", if asked for
     if clean is not None:
         from .cloud_eval import clean_cloud
         kept, cleaned = clean_cloud(xyz, clean)
@@ -348,7 +349,8 @@ def _cloud_tail(masks, est, Ks, Es, colors, refs, clean, normals, mesh=None):
         out["normals"] = nrm.cpu().numpy()
     out.update(xyz=xyz.cpu().numpy(), rgb=rgb.cpu().numpy(), masks=masks.cpu().numpy().astype(bool), depth_est=est.cpu().numpy())
     nbytes = int(xyz.numel() * 4 + rgb.numel() + masks.numel() + est.numel() * 4)
-    nbytes += sum(int(out[k].nbytes) for k in ("mesh_vertices", "mesh_faces", "mesh_colors", "mesh_normals") if k in out)
+    nbytes += sum(int(out[k].nbytes) for k in ("mesh_vertices", "mesh_faces", "mesh_colors", "mesh_normals", "mesh_samples", "mesh_sample_faces",
+                                                 "mesh_sample_colors") if k in out)
     return out, nbytes + (int(out["normals"].nbytes) if normals is not None else 0)
 
 
@@ -399,7 +401,12 @@ def reconstruct_scan(model_or_ckpt, images, poses, intrinsics, names, pairs, sca
     of at most n edges through simple vertices is closed, by one face (three edges) or by a fan around the loop's mean; it runs after the
     small-piece removal (an island's rim is a loop too) and before "smooth", "simplify", colours and normals; ``mesh_info`` "nv" / "nf"
     describe the returned mesh and it gains "filled" ({"holes", "added_vertices", "added_faces", "pinched_vertices",
-    "boundary_edges_before"}).  Without the key nothing changes."""
+    "boundary_edges_before"}).  Without the key nothing changes.  And one: "sample": n, an int >= 1, or {"n": samples |
+    "density": samples per unit area | "spacing": world units, "seed": an int} with exactly one of the three - points on the surface of the
+    returned mesh with a density proportional to area (``mesh.sample_mesh``; "spacing": ``mesh.sample_mesh_even``, thinned to that spacing).
+    It runs last; the result gains "mesh_samples" (float32 [n, 3]), "mesh_sample_faces" (int32 [n], the face of every sample) and, when
+    colours were asked for, "mesh_sample_colors" (uint8 [n, 3]); ``mesh_info`` gains "sampled", the call's info; ``write`` puts
+    ``result_mesh_samples.ply`` beside ``result_mesh.ply``.  Without the key nothing changes."""
     two_pass = isinstance(rescale, (tuple, list))
     passes = [r for r in rescale] if two_pass else [rescale]
     if two_pass and (len(passes) != 2 or passes[1] != 2 * passes[0]):
@@ -449,8 +456,12 @@ def reconstruct_scan(model_or_ckpt, images, poses, intrinsics, names, pairs, sca
             from .mesh import write_mesh_ply
             write_mesh_ply(str(Path(output_folder) / "result_mesh.ply"), cloud["mesh_vertices"], cloud["mesh_faces"],
                            normals=cloud.get("mesh_normals"), colors=cloud.get("mesh_colors"))
+            if "mesh_samples" in cloud:                     # a cloud: positions and the mixed vertex colours (black without colours)
+                samples = cloud["mesh_samples"]
+                FU.write_ply(str(Path(output_folder) / "result_mesh_samples.ply"), samples,
+                             cloud.get("mesh_sample_colors", np.zeros((len(samples), 3), np.uint8)))
     t["tail_s"] = time.perf_counter() - tic
     out = {"masks": cloud["masks"], "depth_est": cloud["depth_est"], "xyz": cloud["xyz"], "rgb": cloud["rgb"], "threshold": thre, "history": hist}
-    out.update({k: cloud[k] for k in ("clean", "normals", "normal_info", "mesh_vertices", "mesh_faces", "mesh_info", "mesh_colors", "mesh_normals")
-                if k in cloud})
+    out.update({k: cloud[k] for k in ("clean", "normals", "normal_info", "mesh_vertices", "mesh_faces", "mesh_info", "mesh_colors", "mesh_normals",
+                                     "mesh_samples", "mesh_sample_faces", "mesh_sample_colors") if k in cloud})
     return out

@@ -1007,6 +1007,55 @@ int cer_mesh_hole_fill_f32(const int* next, const int* heads, const int* lengths
                            long long nf, long long added_vertices, long long added_faces, float* out_vertices, int* out_faces, int* hole,
                            unsigned char* out_colors, void* stream);
 
+/* Mesh surface sampling (ABI 1230; csrc/mesh_sample.hip, cer-mvs_amd/mesh.py face_areas / sample_mesh / sample_mesh_even / evaluate_mesh,
+ * DESIGN.md 3zg): points on the surface of any indexed triangle mesh with a density proportional to area, under the rules of the section
+ * "Surface mesh": integers, fp64 with every association as written, no fused multiply-add, IEEE division and square root, no atomics, one
+ * writer per address, the same bytes on every run.  vertices float32 [nv, 3]; faces int32 [nf, 3]; colors uint8 [nv, 3].
+ *
+ * Checks, in that section's order, all before any launch: (1) a negative size (nv, nf, n) -> CER_EINVAL; (2) nv >= 2^31, 3 nf >= 2^31,
+ * n >= 2^31, a shift outside CER_SAMPLE_SHIFT_MIN .. CER_SAMPLE_SHIFT_MAX, or samples wanted from no face (n > 0 and nf == 0) ->
+ * CER_ESHAPE; (3) nothing to do -> CER_OK with nothing launched (the areas and the weights: nf == 0; the samples: n == 0); (4) a null
+ * pointer -> CER_EINVAL.  vertices may be null iff nv == 0.  The optional pointers of the samples are null iff absent: words, uv, normals
+ * each on its own, colors and out_colors together - one of the two alone is refused.  An index outside [0, nv) is skipped, never read
+ * through, and the search of item 3 ends inside its table whatever the table holds.
+ *
+ * 1. Areas.  areas float64 [nf]: 0 when an index of the face is outside [0, nv), two of its indices are equal, or one of its nine
+ *    coordinates is not finite.  Otherwise, in fp64 on the float32 coordinates of its corners a, b, c,
+ *      e1 = b - a;  e2 = c - a;  nx = e1y*e2z - e1z*e2y;  ny = e1z*e2x - e1x*e2z;  nz = e1x*e2y - e1y*e2x;
+ *      area = 0.5 * sqrt((nx*nx + ny*ny) + nz*nz),
+ *    the square root correctly rounded.
+ *    cer_mesh_face_areas_f64: one thread per face.
+ * 2. Weights.  weights int64 [nf]: weights[f] = (long long)floor(ldexp(areas[f], shift)); the scaling by a power of two is exact.  The
+ *    caller takes amax = the largest area (a maximum is exact under any association), (m, e) = frexp(amax) and shift = 32 - e: the largest
+ *    weight is then in [2^31, 2^32), and with 3 nf < 2^31 the sum of all weights is below 2^63.  The weights are integers, so the caller's
+ *    inclusive prefix sum cum int64 [nf] and the total W = cum[nf - 1] are exact whatever the shape of its scan.  A face smaller than
+ *    2^-32 of the largest gets weight 0 and is never drawn; the sampling density is uniform to 2^-31 of the largest face per face; the
+ *    area that the weights stand for is ldexp(double(W), -shift).  An area that is not a number, is negative or scales to 2^63 and beyond
+ *    (none of the table the shift was taken from does) gets 0.  shift = 32 - e of any double lies in CER_SAMPLE_SHIFT_MIN ..
+ *    CER_SAMPLE_SHIFT_MAX.
+ *    cer_mesh_face_weights_i64: one thread per face.
+ * 3. Samples.  Sample i of a call has the global index k = offset + i, 64-bit unsigned (it wraps).  Its four random words x0 .. x3 are
+ *    row i of words uint32 [n, 4] when given; otherwise Philox4x32-10 (Salmon et al. 2011; multipliers 0xD2511F53 and 0xCD9E8D57, key
+ *    increments 0x9E3779B9 and 0xBB67AE85) of the counter (k & 0xffffffff, k >> 32, 0, 0) under the key (seed & 0xffffffff, seed >> 32).
+ *    Face: r = x0 * 2^32 + x1; t = floor(r * W / 2^64), the high half of the 128-bit product; f = the smallest index with cum[f] > t - a
+ *    bisection on [0, nf - 1]; a W below 1 (not a caller's table) counts as 0.
+ *    Position: a = x2, b = x3; if a + b >= 2^32 (in 64 bits) then a = 2^32 - 1 - a and b = 2^32 - 1 - b - the fold of the unit square onto
+ *    the triangle, uniform and without a square root;  u = (double(a) + 0.5) * 2^-32, v = (double(b) + 0.5) * 2^-32, w = (1.0 - u) - v: all
+ *    three exact, and w >= 0.  Per axis p = float((w*A + u*B) + v*C) with the face's corners A, B, C, rounded once.  A face whose indices
+ *    are out of range or equal gives NaN in points and normals, and colour 0.
+ *    points float32 [n, 3]; face int32 [n]; uv float64 [n, 2] = (u, v); normals float32 [n, 3]: the face's (nx, ny, nz) of item 1, each
+ *    divided in fp64 by sqrt((nx*nx + ny*ny) + nz*nz) and rounded once (NaN for a face without area); out_colors uint8 [n, 3]: per
+ *    channel min(255, floor(((w*cA + u*cB) + v*cC) + 0.5)) in fp64 on the corners' bytes.
+ *    Sample k is a pure function of (seed, k, mesh): it does not depend on n, on the launch grid or on the run.
+ *    cer_mesh_sample_f32: one thread per sample; about log2(nf) dependent reads of cum, then the face's corners. */
+#define CER_SAMPLE_SHIFT_MIN (-992)
+#define CER_SAMPLE_SHIFT_MAX 1105
+int cer_mesh_face_areas_f64(const float* vertices, long long nv, const int* faces, long long nf, double* areas, void* stream);
+int cer_mesh_face_weights_i64(const double* areas, long long nf, int shift, long long* weights, void* stream);
+int cer_mesh_sample_f32(const float* vertices, long long nv, const int* faces, long long nf, const long long* cum, unsigned long long seed,
+                        unsigned long long offset, const unsigned* words, long long n, const unsigned char* colors, float* points, int* face,
+                        double* uv, float* normals, unsigned char* out_colors, void* stream);
+
 /* Multi-GPU row-slab exchange (cer-mvs_amd/slab.py): up to CER_COPY_MAX_SEG contiguous fp32 ranges copied by ONE launch -
  * the pack of a rank's (net, disp) border strips into its send buffer, and the refresh of its halo rows from the gathered
  * strips.  n[i] floats from src[i] to dst[i]; n[i] == 0 skips a segment.  Device pointers; ranges must not overlap. */
