@@ -441,7 +441,8 @@ int cer_enc_pc_conv(const float* srcA, const float* statsA, const float* srcB, c
                     int Cin, int Cout, int taps, int stride, int epi, int out_border, float out_scale, void* stream);
 
 /* NCHW [C,h,w] -> NHWC [h*w,C] with a scale (feature maps: scale = 1/8, core/corr.py:30-31)
- * and NHWC -> NCHW; C % 4 == 0. */
+ * and NHWC -> NCHW, dst = src * scale in one fp32 rounding.  Any C >= 1 and P >= 1 (64 x 64 tiles through LDS, ragged edges masked;
+ * no alignment requirement): the update block passes C = 64 and, for the concatenated GRU input of ConvGRU.forward, C = 177. */
 int cer_nchw_to_nhwc_f32(const float* src, float* dst, int C, long P, float scale, void* stream);
 int cer_nhwc_to_nchw_f32(const float* src, float* dst, int C, long P, float scale, void* stream);
 /* Batched NCHW [N,C,h,w] -> channels-last [N,(h+2b)*(w+2b),C] * scale with a b-texel zero border (the source-map
