@@ -59,6 +59,10 @@ __device__ __forceinline__ void cer_split8(const float (&v)[8], cer_h8& hi, cer_
 
 // process-wide sticky overflow flag (cer_overflow_flag in capi.hip): a device int that saturating conversions or into, or null
 int* cer_overflow_flag_get();
+// Largest |disparity| the writers of the update loop's disparity (cer_delta_sum_f32, the delta prologue of the lookup) leave unreported
+// (bit 8): the s16 convs generate 100 * (d[q] - d[p]) at scale 2^6 and clamp it at the f16 maximum, i.e. at |d[q] - d[p]| > 10.235 - with
+// both disparities within this limit no difference inside a window gets there.  (Real disparities are ~1e-3.)
+#define CER_DISP_LIMIT 5.1175f
 // CUs of the current device (capi.hip; cached per device)
 int cer_num_cus();
 // LDS bytes per CU of the current device (capi.hip; cached per device)

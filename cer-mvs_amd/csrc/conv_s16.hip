@@ -807,7 +807,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_s16_kernel(const S16Args a) {
         static_assert(WN_ * MT * 9 * 32 * 4 <= 2 * ABUF, "reduction scratch does not fit");
         barrier();                                         // every wave has finished reading the activation buffers
         const float hs = a.invS * (float)(1 << SX_HID_LOG2);
-        float hmax = 0.f;                                  // largest hidden activation of this lane (the map never reaches HBM: checked here)
+        const float hlim = 65504.0f / hs;                  // (a power-of-two scale: x * hs <= 65504 exactly when x <= hlim)
+        // a hidden activation of this lane is clamped (the map never reaches HBM: checked here).  Every value is compared with the limit
+        // BEFORE the ReLU: fmaxf(NaN, 0) is 0, and a maximum drops a NaN too (an accumulator NaN comes with either sign).
+        bool hsat = false;
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
             floatx16 tm;
@@ -819,10 +822,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_s16_kernel(const S16Args a) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[m][8 * jp + e]), __float_as_uint(acc[m][8 * jp + 4 + e]), false, false);
+                    hsat |= !(__uint_as_float(sw[0]) <= hlim) || !(__uint_as_float(sw[1]) <= hlim);
                     v[e] = fmaxf(__uint_as_float(sw[0]), 0.f);
                     v[4 + e] = fmaxf(__uint_as_float(sw[1]), 0.f);
                 }
-                hmax = fmaxf(hmax, fmaxf(fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])), fmaxf(fmaxf(v[4], v[5]), fmaxf(v[6], v[7]))));
                 half8 hh, hl;
                 sx_split8(v, hs, hh, hl);
                 const half8 wh = *reinterpret_cast<const half8*>(w2 + (jp * 2 + 0) * 512 + lane * 8);
@@ -837,7 +840,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_s16_kernel(const S16Args a) {
             for (int r = 0; r < 4; ++r) rp[(r + 4 * kg) * 32] = tm[r];
             if (kg == 0) rp[8 * 32] = tm[4];
         }
-        if (a.flag && __ballot(!(hmax * hs <= 65504.0f)) != 0ull && lane == 0) atomicOr(a.flag, 2);     // saturated (or not finite)
+        if (a.flag && __ballot(hsat) != 0ull && lane == 0) atomicOr(a.flag, 2);     // saturated (or not finite)
         barrier();
         const long P = (long)a.h * a.w;
         for (int idx = tid; idx < MT * 9 * 32; idx += 256) {
@@ -888,6 +891,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_s16_kernel(const S16Args a) {
                     }
             }
             // (2) math + stores
+            // RELU (c2): the launch checks what st_split clamps, like the DELTA epilogue above - a value that is not <= the clamp before
+            // the ReLU (NaN included: fmaxf would turn it into 0) raises bit 4; rows past the image are skipped
+            [[maybe_unused]] const float vlim = 65504.0f / a.out_scale;     // (a power-of-two scale: v * s <= 65504 exactly when v <= vlim)
+            [[maybe_unused]] bool vsat = false;
 #pragma unroll
             for (int m = 0; m < MT; ++m) {
 #pragma unroll
@@ -908,10 +915,18 @@ __global__ __launch_bounds__(256, 2) void conv3x3_s16_kernel(const S16Args a) {
                         *reinterpret_cast<half8*>(reinterpret_cast<char*>(base) + off + 1024) = lo;
                     };
                     if (EPI == CER_EPI_LINEAR || EPI == CER_EPI_RELU) {
-                        if (EPI == CER_EPI_RELU)
+                        if constexpr (EPI == CER_EPI_RELU) {
 #pragma unroll
-                            for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
-                        st_split(a.out, v);
+                            for (int e = 0; e < 8; ++e) vsat |= !(v[e] <= vlim);
+                            // the ReLU is the lower bound of the split's clamp (the same bytes as fmaxf(v, 0) in front of the split, eight
+                            // operations less: what the check above costs)
+                            half8 hi, lo;
+                            sx_split8<true>(v, a.out_scale, hi, lo);
+                            *reinterpret_cast<half8*>(reinterpret_cast<char*>(a.out) + off) = hi;
+                            *reinterpret_cast<half8*>(reinterpret_cast<char*>(a.out) + off + 1024) = lo;
+                        } else {
+                            st_split(a.out, v);
+                        }
                     } else if (EPI == CER_EPI_GATES) {
 #pragma unroll
                         for (int e = 0; e < 8; ++e) v[e] = sx_sigmoid(v[e]);
@@ -935,6 +950,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_s16_kernel(const S16Args a) {
                     }
                 }
             }
+            if constexpr (EPI == CER_EPI_RELU)
+                if (a.flag && __ballot(vsat) != 0ull && lane == 0) atomicOr(a.flag, 4);     // saturated (or not finite)
         }
     }
 #if SX_TRACE

@@ -60,13 +60,16 @@ struct S16Args {
     int* flag;                             // sticky overflow flag (cer_overflow_flag) or null
 };
 
-// ---- operand split: 8 fp32 -> hi | lo halves of v * scale (packed conversions)
+// ---- operand split: 8 fp32 -> hi | lo halves of v * scale (packed conversions).  RELU: the clamp's lower bound is 0, i.e. the halves of
+// max(v, 0) * scale - bit for bit what the split of fmaxf(v, 0) gives (a negative v, -0 and NaN all come out as +0)
+template <bool RELU = false>
 __device__ __forceinline__ void sx_split8(const float (&v)[8], float scale, half8& hi, half8& lo) {
+    constexpr float low = RELU ? 0.0f : -65504.0f;
     cer_h2 h[4], l[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         cer_f2 x = (cer_f2){v[2 * i], v[2 * i + 1]} * scale;
-        x = __builtin_elementwise_min(__builtin_elementwise_max(x, (cer_f2){-65504.0f, -65504.0f}), (cer_f2){65504.0f, 65504.0f});
+        x = __builtin_elementwise_min(__builtin_elementwise_max(x, (cer_f2){low, low}), (cer_f2){65504.0f, 65504.0f});
         h[i] = __builtin_convertvector(x, cer_h2);
         l[i] = __builtin_convertvector(x - __builtin_convertvector(h[i], cer_f2), cer_h2);
     }

@@ -628,7 +628,8 @@ extern "C" int cer_conv3x3_f16x3(const cer_conv_inputs* in, const void* packed_w
 // ---- delta head tail for the fused path ------------------------------------------------------------------
 // delta[p] = 0.01 * (bias + sum_half sum_tap T[half][tap][p + (ky-1, kx-1)]) (zero outside), disp_out = disp_in + delta
 __global__ __launch_bounds__(256) void delta_sum_kernel(const float* __restrict__ T, int nhalf, float bias, const float* __restrict__ disp_in,
-                                                        float* __restrict__ disp_out, float* __restrict__ delta, int h, int w) {
+                                                        float* __restrict__ disp_out, float* __restrict__ delta, int h, int w,
+                                                        int* __restrict__ flag) {
     const long P = (long)h * w;
     const long p = (long)blockIdx.x * 256 + threadIdx.x;
     if (p >= P) return;
@@ -642,7 +643,11 @@ __global__ __launch_bounds__(256) void delta_sum_kernel(const float* __restrict_
         }
     const float dl = 0.01f * (s + bias);
     if (delta) delta[p] = dl;
-    disp_out[p] = disp_in[p] + dl;
+    const float dn = disp_in[p] + dl;
+    disp_out[p] = dn;
+    // the s16 convs generate 100 * (d[q] - d[p]) at scale 2^6 and clamp it at the f16 range without a check of their own: the writer of
+    // the disparity reports instead (bit 8) - with every |d| <= CER_DISP_LIMIT no difference inside a window reaches the clamp; NaN is caught
+    if (flag && !(fabsf(dn) <= CER_DISP_LIMIT)) atomicOr(flag, 8);
 }
 
 extern "C" int cer_delta_sum_f32(const float* T, int nhalf, float bias, const float* disp_in, float* disp_out, float* delta, int h, int w,
@@ -650,7 +655,7 @@ extern "C" int cer_delta_sum_f32(const float* T, int nhalf, float bias, const fl
     if (!T || !disp_in || !disp_out || nhalf <= 0 || h <= 0 || w <= 0) return CER_EINVAL;
     const long P = (long)h * w;
     hipLaunchKernelGGL(delta_sum_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, (hipStream_t)stream, T, nhalf, bias, disp_in, disp_out,
-                       delta, h, w);
+                       delta, h, w, cer_overflow_flag_get());
     CER_RETURN_IF_LAUNCH_FAILED();
     return CER_OK;
 }

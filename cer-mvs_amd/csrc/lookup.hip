@@ -200,6 +200,7 @@ __global__ __launch_bounds__(256, MAXPRE <= 4 ? LK_OCC4 : MAXPRE <= 8 ? 4 : 3) v
             for (int i = 0; i < 18; ++i) s += tp[i];
             const float dn = pre_d + 0.01f * (s + dl.bias);
             dl.disp_rw[p0 + pix] = dn;
+            if (dl.flag && !(fabsf(dn) <= CER_DISP_LIMIT)) atomicOr(dl.flag, 8);      // as cer_delta_sum_f32: the disparity's writer reports
             dnew[pix] = dn;
         }
         {
@@ -243,10 +244,13 @@ __global__ __launch_bounds__(256, MAXPRE <= 4 ? LK_OCC4 : MAXPRE <= 8 ? 4 : 3) v
             char* dst = reinterpret_cast<char*>(out) + ((mt * 4 + grp) * 2) * 1024 + (((y & 1) << 4) | (x & 15)) * 16;
             // saturation is never silent: the largest value of this thread's 16 outputs is checked against the clamp here -
             // round 5: the tensor's buffer is reused for r * h later in the iteration, so nothing can scan it after the fact
-            float amax = 0.f;
+            // (each value against the limit, before the ReLU: a maximum would drop a NaN - it comes with either sign - and the ReLU below
+            // stores it as 0)
+            const float alim = 65504.0f / out_scale;         // (a power-of-two scale: x * s <= 65504 exactly when x <= alim)
+            bool asat = false;
 #pragma unroll
-            for (int j = 0; j < 16; ++j) amax = fmaxf(amax, acc[j]);
-            if (dl.flag && __ballot(!(amax * out_scale <= 65504.0f)) != 0ull && (threadIdx.x & 63) == 0) atomicOr(dl.flag, 4);
+            for (int j = 0; j < 16; ++j) asat |= !(acc[j] <= alim);
+            if (dl.flag && __ballot(asat) != 0ull && (threadIdx.x & 63) == 0) atomicOr(dl.flag, 4);
 #pragma unroll
             for (int j = 0; j < 16; j += 8) {
                 cer_h2 h[4], l[4];

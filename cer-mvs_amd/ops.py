@@ -114,7 +114,8 @@ def scan_overflow(t, bit=4):
 
 def check_overflow(device, reset=True):
     """Non-zero if any kernel since the last reset saturated an operand on ``device`` (one device->host read): bit 1 = cost-volume
-    feature rows, 2 = hidden map of the delta head, 4 = an update-block activation tensor (``scan_overflow``)."""
+    feature rows, 2 = hidden map of the delta head, 4 = an update-block activation tensor (c1 / c2: checked by the kernels that write
+    them; inp: ``scan_overflow``), 8 = a disparity written by the update loop beyond +-5.1175."""
     f = overflow_flag(device)
     hit = int(f.item())
     if reset and hit:

@@ -148,7 +148,8 @@ class RAFT(nn.Module):
             self._sig = sig
 
     _OVERFLOW_WHAT = {1: "cost-volume feature rows beyond +-1023 (after the reference's /8)", 2: "hidden map of the delta head beyond 4094",
-                      4: "a ReLU-class activation of the update block (inp, corr features) beyond 4094"}
+                      4: "a ReLU-class activation of the update block (inp, corr features) beyond 4094",
+                      8: "a disparity of the update loop beyond +-5.1175 (its generated 7x7 difference features clamp at 10.235)"}
 
     def check_overflow(self, device=None, raise_error=True):
         """Read (and clear) the sticky saturation flag of the split-f16 kernels; returns the bits, raises RuntimeError on a hit."""
@@ -161,7 +162,9 @@ class RAFT(nn.Module):
     def _raise_overflow(self, bits):
         what = "; ".join(v for k, v in self._OVERFLOW_WHAT.items() if bits & k)
         raise SaturationError(f"cer-mvs_amd: a split-f16 kernel saturated an operand ({what}): the result of that forward is not fp32-class. "
-                           "Use RAFT(..., gru_precision='f16x3') / _lib.load().cer_cost_build_algo(1), or overflow_policy='fallback'.")
+                           "Use RAFT(..., gru_precision='f16x3') / _lib.load().cer_cost_build_algo(1), or overflow_policy='fallback'.  "
+                           "(f16x3 carries activations at scale 1: its own clamp, at 65504, is 16 x further out and is NOT reported.  A disparity "
+                           "beyond +-5.1175 has no arithmetic remedy: it is reported in every form, and such a depth range is a wrong input.)")
 
     def refresh_weights(self):
         """Call after mutating parameters in place: drops every packed copy (encoder engines, update-block packs)."""
@@ -288,7 +291,7 @@ class RAFT(nn.Module):
             if bits:                                   # fallback: repeat with the wide-range arithmetic
                 from . import _lib as L
                 mode, algo = self.update_block.conv_mode, L.load().cer_cost_build_algo(1 if bits & 1 else -1)
-                self.update_block.conv_mode = "f16x3" if bits & 6 else mode
+                self.update_block.conv_mode = "f16x3" if bits & 14 else mode
                 try:
                     out = run()
                 finally:

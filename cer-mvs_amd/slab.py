@@ -290,14 +290,12 @@ def unpack_halo(net, disp, allbuf, w, g, G, r0, r1, e0, e1, halo=HALO, copy=_dev
 P2P_HALO = True           # halo refresh by neighbour point-to-point exchange (False: one all-gather of every rank's strips)
 
 
-def _finish_overflow(model, ex, dev, workspaces, loop):
+def _finish_overflow(model, ex, dev):
     """End-of-forward overflow handling of the sharded path.  "lazy": asynchronous snapshot, polled by the next forward (every rank
     polls its own flag; the ranks run the same GRU on overlapping rows, but a rank can saturate alone - a hit then raises on that
     rank at its next forward).  "raise": the flag is read here and MAX-reduced over the ranks, so that every rank raises together
     instead of one rank leaving the collective sequence.  "fallback" has no sharded form: it is refused up front (sharded_forward)."""
     from . import ops
-    for ws in workspaces:
-        loop.finish(ws)
     policy = getattr(model, "overflow_policy", "lazy")
     if policy == "lazy":
         ops.overflow_snapshot(dev)
@@ -428,10 +426,13 @@ def sharded_forward(model, images, poses, intrinsics, scale, ex):
                                       rows=d["rows"])
                 else:
                     d["plan_halo"].replay()
+        if T > 0:                                 # what UpdateBlock.run does after a stage's last iteration, with THIS stage's loop
+            for g in ex.ranks:
+                loop.finish(st[g]["ws"])
 
-    # ---- saturation is never silent on the sharded path either: the slab loop calls step, not UpdateBlock.run, so the
-    # loop's scans of the corr features happen here; bits 1 / 2 were or-ed into the flag by the kernels themselves
-    _finish_overflow(model, ex, dev, [st[g]["ws"] for g in ex.ranks], loop)
+    # ---- saturation is never silent on the sharded path either: every bit was or-ed into the flag by the kernels
+    # themselves (the slab loop calls step, not UpdateBlock.run: the loop's own end-of-stage step ran per stage above)
+    _finish_overflow(model, ex, dev)
 
     # ---- gather the owned rows of every rank (persistent send / receive buffers)
     rows_max = (h + G - 1) // G

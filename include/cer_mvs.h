@@ -39,10 +39,18 @@ int cer_device_count(void);
 /* Saturation is never silent.  The split-f16 kernels clamp an operand whose scaled value leaves the f16 range (update block,
  * "s16" path: ReLU-class activations beyond 4094 = 65504 / 2^4; cost-volume feature rows beyond 1023).  cer_overflow_flag
  * registers a caller-owned DEVICE int for the CURRENT device (hipGetDevice; one per device, NULL = off, the default; launches use
- * the flag of the device they run on) that such kernels or into when they clamp in
- * registers (bit 2: the hidden map of the fused delta head, which never reaches memory).  Tensors that do reach memory are
- * checked after the fact: cer_f16_scan_overflow ors `bit` into *flag if any half of a split-f16 buffer (frag16 tensors, split
- * feature rows; `bytes` % 16 == 0) sits at the f16 maximum or is not finite.  The host reads the flag when convenient. */
+ * the flag of the device they run on) that such kernels or into when they clamp.  The kernels of the s16 update loop check
+ * what they clamp themselves, in every launch, before the ReLU (so that a NaN is reported, not turned into 0): bit 2 the hidden
+ * map of the fused delta head (it never reaches memory), bit 4 the frag16 output of the lookup (c1) and of the RELU epilogue of
+ * cer_conv3x3_s16 (c2).  The disparity features that the s16 convs generate (100 * (d[q] - d[p]) at scale 2^6) are clamped
+ * beyond |d[q] - d[p]| = 10.235 without a check in the generator: the writers of the disparity (cer_delta_sum_f32, the delta
+ * form of cer_lookup_encode_f32) raise bit 8 when !(|d| <= 5.1175) instead.  Tensors written by other kernels are checked after
+ * the fact: cer_f16_scan_overflow ors `bit` into *flag if any half of a split-f16 buffer (frag16 tensors, split feature rows;
+ * `bytes` % 16 == 0) sits at the f16 maximum or is not finite - a value in (4093, 4094] at scale 2^4 rounds to that half
+ * without being clamped, so a scan may report it.  The host reads the flag when convenient.
+ * NOT reported (tests/saturation_cases.py lists every clamp): the split of the wide-range "f16x3" kernels and of the encoders'
+ * trunk (cer_split1/2/8, the stem, the point-wise convs' PC_YMAX) clamps at +-65504 in the operand's own units, silently - the
+ * remedy the saturation error names (activations at scale 1 instead of 2^4) is 16 x wider than the s16 path, not unlimited. */
 int cer_overflow_flag(int* flag);
 int cer_f16_scan_overflow(const void* data, long bytes, int* flag, int bit, void* stream);
 

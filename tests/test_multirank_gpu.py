@@ -28,17 +28,63 @@ import datetime
 _PG_TIMEOUT = datetime.timedelta(seconds=300)
 
 
+_INIT_MARK = "CER_TEST_SPAWN_MARK"       # path prefix, set by ``_spawn``: a worker leaves <prefix>.<rank>.begin / .done around its rendezvous
+
+
+def _init_group(rank, world):
+    """init_process_group of a worker, bracketed by two marker files: ``_spawn`` can tell a process that died IN the rendezvous (test
+    infrastructure) from one that died in the product's code."""
+    import torch.distributed as dist
+    mark = os.environ.get(_INIT_MARK)
+    if mark:
+        open(f"{mark}.{rank}.begin", "w").close()
+    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=_PG_TIMEOUT)
+    if mark:
+        open(f"{mark}.{rank}.done", "w").close()
+
+
+def _transport_failure(e, nprocs, mark):
+    """Is ``e`` (what mp.spawn raised) a failure of the tests' transport - rendezvous, timeout, gloo - and not of the code under test?
+    A worker's exception arrives as a ProcessRaisedException whose text carries the worker's traceback: only its last line - the exception's
+    own "Type: message" - is looked at (a product assert that merely quotes such words further up is a result): DistNetworkError,
+    DistBackendError or a RuntimeError / TimeoutError saying "timed out" (or one of these raised directly) count; a process that EXITED counts only if it died inside init_process_group.  Everything
+    else - a worker's assert, a SaturationError, a crash in a kernel - is a result."""
+    lines = [ln for ln in f"{type(e).__name__}: {e}".splitlines() if ln.strip()]
+    last = lines[-1].strip() if isinstance(e, mp.ProcessRaisedException) else f"{type(e).__name__}: {e}"      # the worker's "ExcType: message" line
+    kind = last.split(":", 1)[0].rsplit(".", 1)[-1]
+    if kind in ("DistNetworkError", "DistBackendError") or (kind in ("RuntimeError", "TimeoutError", "DistStoreError") and "timed out" in last.lower()):
+        return True
+    if isinstance(e, mp.ProcessExitedException):
+        return any(os.path.exists(f"{mark}.{r}.begin") and not os.path.exists(f"{mark}.{r}.done") for r in range(nprocs))
+    return False
+
+
 def _spawn(fn, args, nprocs):
-    """mp.spawn with ONE retry on a fresh port: the transport of these tests (gloo between processes that share one GPU) is test infrastructure -
-    the product's collectives run over RCCL - and a stuck rendezvous / host-staged copy must not be mistaken for a wrong result.  A second failure
-    is a failure; the retry is reported."""
-    try:
-        mp.spawn(fn, args=args, nprocs=nprocs, join=True)
-    except Exception as e:                                   # (ProcessRaisedException / ProcessExitedException)
-        import warnings
-        warnings.warn(f"multi-process test: first attempt failed ({type(e).__name__}: {str(e)[:200]}); retrying once")
-        args = tuple(_free_port() if (isinstance(a, int) and 20000 < a < 65536 and i == 1) else a for i, a in enumerate(args))
-        mp.spawn(fn, args=args, nprocs=nprocs, join=True)
+    """mp.spawn with ONE retry on a fresh port, for failures of the transport only: the transport of these tests (gloo between processes
+    that share one GPU) is test infrastructure - the product's collectives run over RCCL - and a stuck rendezvous / host-staged copy must
+    not be mistaken for a wrong result.  A wrong result must not be mistaken for a stuck rendezvous either: anything that is not a
+    ``_transport_failure`` is re-raised on the first attempt.  A second failure is a failure; the retry is reported."""
+    import tempfile
+    with tempfile.TemporaryDirectory() as tmp:
+        mark = os.path.join(tmp, "rank")
+        old = os.environ.get(_INIT_MARK)
+        os.environ[_INIT_MARK] = mark
+        try:
+            try:
+                mp.spawn(fn, args=args, nprocs=nprocs, join=True)
+            except Exception as e:                               # (ProcessRaisedException / ProcessExitedException / raised by the launcher)
+                if not _transport_failure(e, nprocs, mark):
+                    raise
+                import warnings
+                warnings.warn(f"multi-process test: first attempt failed in the transport ({type(e).__name__}: {str(e)[:200]}); retrying once")
+                args = tuple(_free_port() if (isinstance(a, int) and 20000 < a < 65536 and i == 1) else a for i, a in enumerate(args))
+                os.environ[_INIT_MARK] = mark + "_retry"
+                mp.spawn(fn, args=args, nprocs=nprocs, join=True)
+        finally:
+            if old is None:
+                os.environ.pop(_INIT_MARK, None)
+            else:
+                os.environ[_INIT_MARK] = old
 
 
 def _free_port():
@@ -57,7 +103,7 @@ def _worker(rank, world, port, shard, name, out_path, aggregation=None):
     from cer_mvs_amd.synthetic import fill_state_dict, synthetic_scene
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=_PG_TIMEOUT)
+    _init_group(rank, world)
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     g = np.load(os.path.join(REPO, "tests", "golden", name + ".npz"))
@@ -182,7 +228,7 @@ def _ragged_worker(rank, world, port, shard, H, W, V, out_path):
     from cer_mvs_amd.synthetic import fill_state_dict, synthetic_scene
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=_PG_TIMEOUT)
+    _init_group(rank, world)
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     images, poses, intr, scale = synthetic_scene(H, W, V, seed=31)
@@ -227,7 +273,7 @@ def _worker_pipelined(rank, world, port, shard, name, out_path, streams):
     from cer_mvs_amd.synthetic import fill_state_dict, synthetic_scene
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=_PG_TIMEOUT)
+    _init_group(rank, world)
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     g = np.load(os.path.join(REPO, "tests", "golden", name + ".npz"))
