@@ -9,7 +9,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CER_MVS_LIB") or os.path.join(_HERE, "csrc", "libcermvs.so")
-ABI_VERSION = 1230
+ABI_VERSION = 1240
 CONV_MAX_SRC = 4
 EPI_LINEAR, EPI_RELU, EPI_GATES, EPI_GRU, EPI_DELTA = 0, 1, 2, 3, 4
 EPI_OUT_SPLIT, EPI_AUX_SPLIT = 0x100, 0x200       # cer_mvs.h: split32 activation layout flags, or-ed into `epi`
@@ -171,6 +171,10 @@ _SIGNATURES = {
     "cer_mesh_face_areas_f64": (_I, [_P, _LL, _P, _LL, _P, _P]),
     "cer_mesh_face_weights_i64": (_I, [_P, _LL, _I, _P, _P]),
     "cer_mesh_sample_f32": (_I, [_P, _LL, _P, _LL, _P, _ULL, _ULL, _P, _LL, _P, _P, _P, _P, _P, _P, _P]),
+    "cer_mesh_tri_cells_i64": (_I, [_P, _LL, _P, _LL, _P, _c.POINTER(_D), _D, _P, _P, _P]),
+    "cer_mesh_tri_pairs_i64": (_I, [_P, _LL, _P, _LL, _P, _c.POINTER(_D), _D, _P, _LL, _P, _P, _P]),
+    "cer_mesh_tri_pack_f32": (_I, [_P, _LL, _P, _LL, _P, _P]),
+    "cer_mesh_tri_nearest_f32": (_I, [_P, _LL, _P, _LL, _P, _P, _LL, _c.POINTER(_D), _D, _P, _P, _LL, _F, _P, _P, _P, _P]),
 }
 
 # include/cer_mvs_variants.h: exported by csrc/variants/libcermvs_optin.so only (round 4's opt-in kernel forms; CER_MVS_LIB selects the library)

@@ -2,7 +2,7 @@
 #include "common.hpp"
 #include <string.h>
 
-extern "C" int cer_abi_version(void) { return 1230; }
+extern "C" int cer_abi_version(void) { return 1240; }
 
 extern "C" const char* cer_error_string(int code) {
     switch (code) {

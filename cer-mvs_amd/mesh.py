@@ -11,6 +11,8 @@ Edges (C ABI 1210; tests/mesh_smooth_reference.py): ``mesh_edges`
 Hole filling (csrc/mesh_fill.hip, C ABI 1220; tests/mesh_fill_reference.py): ``mesh_holes`` and ``fill_holes``, likewise.
 Surface sampling (csrc/mesh_sample.hip, C ABI 1230; tests/mesh_sample_reference.py): ``face_areas``, ``sample_mesh``,
 ``sample_mesh_even`` and ``evaluate_mesh``, likewise.
+Exact point-to-mesh distance (csrc/mesh_dist.hip, C ABI 1240; tests/mesh_dist_reference.py): ``MeshIndex``, ``mesh_distances``
+and ``evaluate_mesh(method="exact")``, likewise.
 
 Every argument check that needs no device runs before the library is loaded."""
 import ctypes
@@ -1105,17 +1107,28 @@ def sample_mesh_even(vertices, faces, spacing, oversample=8.0, seed=0, normals=F
     return tuple(None if a is None else a.index_select(0, kept) for a in (points, face, out_n, out_c))
 
 
-def evaluate_mesh(vertices, faces, gt, spacing, max_dist=20.0, tau=None, seed=0, align=None, oversample=8.0):
+EVALUATE_METHODS = ("samples", "exact")
+
+
+def evaluate_mesh(vertices, faces, gt, spacing, max_dist=20.0, tau=None, seed=0, align=None, oversample=8.0, method="samples"):
     """A mesh against a ground-truth cloud, by way of evenly spaced samples of its surface - the route of the Tanks-and-Temples and Open3D
     evaluations: ``sample_mesh_even(vertices, faces, spacing, oversample, seed)``, then ``cloud_eval.accuracy_completeness(samples, gt,
     max_dist, align=align)`` and, with ``tau``, ``cloud_eval.fscore(samples, gt, tau, align=align)`` -> one dict: the keys of both, and
     "samples" (how many points stand for the mesh) and "spacing".  ``gt`` float32 [m,3] on the mesh's device.
 
-    What this measures: distances to SAMPLES of the surface, not to the surface.  On the mesh's side (accuracy, precision) a sample is a
-    surface point and its figure is exact for that point.  On the ground truth's side (completeness, recall) the nearest sample is farther
-    than the surface is, by up to about the spacing: those figures carry an upward bias of that size - take a spacing well below ``tau``
-    and below the accuracy that is to be resolved.  The exact point-to-triangle search is future work."""
-    from .cloud_eval import accuracy_completeness, fscore
+    ``method="samples"`` (the default) measures distances to SAMPLES of the surface, not to the surface.  On the mesh's side (accuracy,
+    precision) a sample is a surface point and its figure is exact for that point.  On the ground truth's side (completeness, recall) the
+    nearest sample is farther than the surface is, by up to about the spacing: those figures carry an upward bias of that size - take a
+    spacing well below ``tau`` and below the accuracy that is to be resolved, or take ``method="exact"``.
+
+    ``method="exact"``: the mesh's side is the same - the samples against ``gt`` - and the ground truth's side is the exact distance of
+    every ``gt`` point to the surface, ``MeshIndex(vertices, faces).nearest(gt, ...)``: no bias, whatever the spacing.  With ``tau`` the
+    search runs again under the float32 cut-off that ``fscore`` forms; with ``align`` the vertices go through ``rigid_transform`` before
+    they are indexed, as the samples do before they are measured.  The dict gains "method".
+
+    What remains future work: a hierarchy for meshes whose triangles are far larger than any workable cell (``MeshIndex`` refuses a face of
+    more than 4096 cells), and a signed distance."""
+    from .cloud_eval import accuracy_completeness, cloud_distances, fscore, metrics_from_distances, rigid_transform
     who = "evaluate_mesh"
     if not isinstance(gt, torch.Tensor) or gt.dim() != 2 or gt.shape[1] != 3 or gt.dtype != torch.float32:
         raise ValueError(f"{who}: gt float32 [m, 3] expected")
@@ -1123,14 +1136,222 @@ def evaluate_mesh(vertices, faces, gt, spacing, max_dist=20.0, tau=None, seed=0,
         raise ValueError(f"{who}: max_dist must be a positive finite number")
     if tau is not None:
         tau = _positive(tau, "tau", who)
+    if not isinstance(method, str) or method not in EVALUATE_METHODS:
+        raise ValueError(f"{who}: method must be one of {list(EVALUATE_METHODS)}")
     if isinstance(vertices, torch.Tensor) and gt.device != vertices.device:
         raise ValueError(f"{who}: vertices and gt must be on one device")
     samples = sample_mesh_even(vertices, faces, spacing, oversample=oversample, seed=seed)[0]
-    out = accuracy_completeness(samples, gt, max_dist, align=align)
+    if method == "samples":
+        out = accuracy_completeness(samples, gt, max_dist, align=align)
+        if tau is not None:
+            out.update(fscore(samples, gt, tau, align=align))
+        out.update(samples=int(samples.shape[0]), spacing=float(spacing))
+        return out
+    pred, moved = (samples, vertices) if align is None else (rigid_transform(samples, align), rigid_transform(vertices, align))
+    gt = gt.contiguous()
+    index = MeshIndex(moved, faces, max_dist=max_dist)
+    out = metrics_from_distances(cloud_distances(pred, gt, max_dist), index.nearest(gt, max_dist)[0], max_dist)
     if tau is not None:
-        out.update(fscore(samples, gt, tau, align=align))
-    out.update(samples=int(samples.shape[0]), spacing=float(spacing))
+        tau32 = float(np.float32(tau))
+        cut = float(np.nextafter(np.float32(tau32), np.float32(np.inf))) if tau32 < float(tau) else tau32      # fscore's cut: a float32 not below tau
+        m = metrics_from_distances(cloud_distances(pred, gt, cut), index.nearest(gt, cut)[0], cut, tau=tau)
+        out.update({k: m[k] for k in ("precision", "recall", "fscore", "tau", "n_pred", "n_gt")})
+    out.update(samples=int(samples.shape[0]), spacing=float(spacing), method=method)
     return out
+
+
+# ---------------------------------------------------------------- exact point-to-mesh distance (csrc/mesh_dist.hip, C ABI 1240)
+DIST_INFO_KEYS = ("cell", "pairs", "faces_indexed", "cells")
+TRI_MAX_CELLS = 4096                                         # cer_mvs.h CER_TRI_MAX_CELLS: the cells one face may be entered in
+TRI_MAX_RINGS = 4096                                         # mesh_dist.hip TRI_MAX_RINGS: ceil(max_dist / cell) beyond this is refused
+TRI_KEY_SENTINEL = 2 ** 63 - 1
+# The default cell is max(DEFAULT_CELL_EDGES * sqrt(area / faces with weight), max_dist / DEFAULT_CELL_RINGS): some twenty faces per cell and
+# two cells per face on a mesh of even triangles, and never more than DEFAULT_CELL_RINGS rings of rows for a query that finds nothing.
+# Results do not depend on it.  Measured by tools/bench_mesh_dist.py against 1, 2 and 8 edges (profiles/mesh_dist_bench.json
+# "cell_sweep_edge_factors"): 4 wins on both query sets; the first guess was 2.
+DEFAULT_CELL_EDGES = 4.0
+DEFAULT_CELL_RINGS = 32
+
+
+def _dist_reach(value, who):
+    """``max_dist`` as the float32 the kernel takes: a number >= 0 (+inf is a number; the index refuses what its cell cannot reach)"""
+    if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)):
+        raise ValueError(f"{who}: max_dist must be a number >= 0")
+    value = float(np.float32(value))
+    if not value >= 0.0:
+        raise ValueError(f"{who}: max_dist must be a number >= 0")
+    return value
+
+
+def _dist_queries(queries, vertices, who):
+    if not isinstance(queries, torch.Tensor) or queries.dim() != 2 or queries.shape[1] != 3 or queries.dtype != torch.float32:
+        raise ValueError(f"{who}: queries float32 [m, 3] expected")
+    if queries.shape[0] >= 2 ** 31:
+        raise ValueError(f"{who}: fewer than 2^31 queries expected")
+    if queries.device != vertices.device:
+        raise ValueError(f"{who}: vertices and queries must be on one device")
+
+
+class MeshIndex:
+    """Sparse uniform grid over the faces of any indexed triangle mesh (vertices float32 [nv,3], faces int32 [nf,3] on the device) with cell
+    edge ``cell``, built once: what ``cloud_eval.CloudIndex`` is for a cloud.  A face is entered in every cell of the box of cells that its
+    corners span; faces that ``face_areas`` gives area 0 (an index out of range, a repeated index, a non-finite coordinate, a computed area
+    of 0) are not indexed and are never anybody's nearest face.  The grid's origin is the per-axis minimum of the vertices that indexed
+    faces use, promoted to fp64.  ``cell=None``: max(4 * sqrt(area / faces with weight), ``max_dist`` / 32) with ``sample_mesh``'s exact
+    "area" and "faces_with_weight" (the second term only with ``max_dist``); results do not depend on the cell.  Attributes: ``cell``,
+    ``pairs`` (entries of faces in cells), ``faces_indexed``, ``cells`` (occupied).
+
+    ValueError: bad arguments (before any device work); a face that spans more than 4096 cells, a mesh that spans more than 2^20 cells
+    along an axis, or 2^31 pairs and more - each names the cell and advises a larger one.  RuntimeError: tensors that are not on the device.
+    The contract is cer_mvs.h's, "Mesh distance"."""
+
+    def __init__(self, vertices, faces, cell=None, max_dist=None, _stages=None, _keep_pairs=False):
+        who = "MeshIndex"
+
+        def stage(name):                                     # tools/bench_mesh_dist.py: an event at the end of every stage of the build
+            if _stages is not None:
+                event = torch.cuda.Event(enable_timing=True)
+                event.record()
+                _stages.append((name, event))
+        nv, nf = _sample_mesh_checks(vertices, faces, None, who)
+        if cell is not None:
+            cell = _positive(cell, "cell", who)
+        if max_dist is not None:
+            max_dist = _dist_reach(max_dist, who)
+        if not vertices.is_cuda:
+            raise RuntimeError(f"{who}: vertices must be a CUDA tensor (no CPU fallback)")
+        vertices, faces = vertices.contiguous(), faces.contiguous()
+        dev, lib = vertices.device, L.load()
+        self.nv, self.nf = nv, nf
+        self.origin = (ctypes.c_double * 3)(0.0, 0.0, 0.0)
+        self.pairs = self.faces_indexed = self.cells = 0
+        self.records = self.pair_face = self.cell_keys = self.cell_start = None
+        if cell is None:
+            _, W, shift, count = _sample_table(vertices, faces, nv, nf)
+            cell = DEFAULT_CELL_EDGES * math.sqrt(math.ldexp(float(W), -shift) / count) if W > 0 and count > 0 else 0.0
+            if max_dist is not None and math.isfinite(max_dist):
+                cell = max(cell, max_dist / DEFAULT_CELL_RINGS)
+            if not (cell > 0.0 and math.isfinite(cell)):
+                cell = 1.0                                   # a mesh without area: nothing will be indexed
+        self.cell = cell
+        if nf == 0:
+            return
+        stage("start")
+        areas = _areas(vertices, faces, nv, nf)
+        indexed = areas > 0.0
+        used = faces[indexed].reshape(-1).long()             # (area > 0: the three indices are in range)
+        self.faces_indexed = int(used.shape[0]) // 3         # (read 1: sizes the gather)
+        if self.faces_indexed == 0:
+            return
+        lo = vertices.index_select(0, used).amin(0).double().cpu()                                      # (read 2: the origin travels as an argument)
+        self.origin = (ctypes.c_double * 3)(*[float(v) for v in lo])
+        pv, pf, pa = L.dev_ptr(vertices, "vertices"), L.dev_ptr(faces, "faces", torch.int32), L.dev_ptr(areas, "areas", torch.float64)
+        stage("areas_origin")
+        counts = torch.empty(nf, device=dev, dtype=torch.int64)
+        flag = torch.empty(2, device=dev, dtype=torch.int32)
+        rc = lib.cer_mesh_tri_cells_i64(pv, nv, pf, nf, pa, self.origin, cell, L.dev_ptr(counts, "cells", torch.int64),
+                                        L.dev_ptr(flag, "flag", torch.int32), L.cur_stream())
+        if rc == -2:
+            beyond, large = (int(v) for v in flag.cpu())
+            if large and not beyond:
+                raise ValueError(f"{who}: a face spans more than {TRI_MAX_CELLS} cells of {cell}; use a larger cell")
+            raise ValueError(f"{who}: the mesh spans more than 2^20 cells of {cell} along an axis; use a larger cell")
+        L.check(rc, "mesh_tri_cells")
+        cum = torch.cumsum(counts, 0).contiguous()           # integers: exact whatever the scan's shape
+        npairs = int(cum[-1])                                # (read 3: sizes the pair list)
+        if npairs >= 2 ** 31:
+            raise ValueError(f"{who}: {npairs} entries of faces in cells of {cell} is beyond 2^31 - 1; use a larger cell")
+        stage("cells_scan")
+        keys = torch.full((npairs,), TRI_KEY_SENTINEL, device=dev, dtype=torch.int64)
+        ids = torch.full((npairs,), -1, device=dev, dtype=torch.int32)
+        L.check(lib.cer_mesh_tri_pairs_i64(pv, nv, pf, nf, pa, self.origin, cell, L.dev_ptr(cum, "cum", torch.int64), npairs,
+                                           L.dev_ptr(keys, "keys", torch.int64), L.dev_ptr(ids, "ids", torch.int32), L.cur_stream()), "mesh_tri_pairs")
+        stage("pairs")
+        self._pairs_unsorted = (keys, ids) if _keep_pairs else None              # (what the tests hold to the restatement)
+        keys, perm = torch.sort(keys, stable=True)           # faces stay ascending inside a cell
+        self.pair_face = ids.index_select(0, perm).contiguous()
+        del perm, ids
+        stage("sort")
+        P = int(lib.cer_grid_partials(npairs))
+        partials, offsets, totals = (torch.empty(k, device=dev, dtype=t) for k, t in ((P, torch.int32), (P + 1, torch.int64), (2, torch.int64)))
+        pk = L.dev_ptr(keys, "keys", torch.int64)
+        L.check(lib.cer_grid_cells_count_i64(pk, npairs, L.dev_ptr(partials, "partials", torch.int32), L.dev_ptr(offsets, "offsets", torch.int64),
+                                             L.dev_ptr(totals, "totals", torch.int64), L.cur_stream()), "grid_cells_count")
+        self.cells, self.pairs = (int(v) for v in totals.cpu())                                          # (read 4: sizes the cell table)
+        self.cell_keys = torch.empty(self.cells, device=dev, dtype=torch.int64)
+        self.cell_start = torch.empty(self.cells + 1, device=dev, dtype=torch.int64)
+        L.check(lib.cer_grid_cells_i64(pk, npairs, L.dev_ptr(offsets, "offsets", torch.int64), self.cells,
+                                       L.dev_ptr(self.cell_keys, "cell_keys", torch.int64), L.dev_ptr(self.cell_start, "cell_start", torch.int64),
+                                       L.cur_stream()), "grid_cells")
+        stage("cell_table")
+        self.records = torch.empty(nf, 12, device=dev, dtype=torch.int32)
+        L.check(lib.cer_mesh_tri_pack_f32(pv, nv, pf, nf, L.dev_ptr(self.records, "records", torch.int32), L.cur_stream()), "mesh_tri_pack")
+        stage("pack")
+
+    def info(self):
+        return dict(cell=self.cell, pairs=self.pairs, faces_indexed=self.faces_indexed, cells=self.cells)
+
+    def _walk_order(self, queries, m):                       # CloudIndex._walk_order: the queries' positions in the order of their own cell keys
+        qkeys = torch.empty(m, device=queries.device, dtype=torch.int64)
+        L.check(L.load().cer_grid_keys_f32(L.dev_ptr(queries, "queries"), m, self.origin, self.cell, 1, L.dev_ptr(qkeys, "keys", torch.int64), None,
+                                           L.cur_stream()), "grid_keys")
+        return torch.sort(qkeys, stable=True).indices
+
+    def nearest(self, queries, max_dist, closest=False, sort_queries=True):
+        """-> (dist float32 [m], face int32 [m]) and, with ``closest``, the closest point float32 [m,3], in the queries' order: the indexed
+        face with the smallest (dist2, face index) among those with dist2 <= double(max_dist)^2, dist2 in fp64 as cer_mvs.h's section
+        "Mesh distance" pins it; dist = float32(sqrt(dist2)); (inf, -1, NaN) where there is none or the query is not finite.
+        ``sort_queries``: walk the queries in the order of their own cells (faster; the result is the same)."""
+        who = "MeshIndex.nearest"
+        max_dist = _dist_reach(max_dist, who)
+        for name, flag in (("closest", closest), ("sort_queries", sort_queries)):
+            if not isinstance(flag, bool):
+                raise ValueError(f"{who}: {name} must be True or False")
+        if not isinstance(queries, torch.Tensor) or queries.dim() != 2 or queries.shape[1] != 3 or queries.dtype != torch.float32:
+            raise ValueError(f"{who}: queries float32 [m, 3] expected")
+        if queries.shape[0] >= 2 ** 31:
+            raise ValueError(f"{who}: fewer than 2^31 queries expected")
+        if not queries.is_cuda:
+            raise RuntimeError(f"{who}: queries must be a CUDA tensor (no CPU fallback)")
+        if max_dist / self.cell > TRI_MAX_RINGS:                                  # (ceil(x) > 4096 iff x > 4096; +inf lands here)
+            raise ValueError(f"{who}: max_dist {max_dist} is more than {TRI_MAX_RINGS} cells of {self.cell}; index the mesh with a larger cell")
+        queries = queries.contiguous()
+        m, dev = int(queries.shape[0]), queries.device
+        empty = m == 0 or self.pairs == 0 or self.cells == 0                     # (the entry point launches nothing for an empty side)
+        make = (lambda shape, dt, fill: torch.full(shape, fill, device=dev, dtype=dt)) if empty else \
+            (lambda shape, dt, fill: torch.empty(shape, device=dev, dtype=dt))
+        dist, face = make((m,), torch.float32, float("inf")), make((m,), torch.int32, -1)
+        near = make((m, 3), torch.float32, float("nan")) if closest else None
+        if not empty:
+            qorder = self._walk_order(queries, m) if sort_queries else None
+            L.check(L.load().cer_mesh_tri_nearest_f32(
+                L.dev_ptr(self.records, "records", torch.int32), self.nf, L.dev_ptr(self.pair_face, "pair_face", torch.int32), self.pairs,
+                L.dev_ptr(self.cell_keys, "cell_keys", torch.int64), L.dev_ptr(self.cell_start, "cell_start", torch.int64), self.cells, self.origin,
+                self.cell, L.dev_ptr(queries, "queries"), L.dev_ptr(qorder, "qorder", torch.int64), m, max_dist,
+                L.dev_ptr(face, "face", torch.int32), L.dev_ptr(dist, "dist"), L.dev_ptr(near, "closest"), L.cur_stream()), "mesh_tri_nearest")
+        return (dist, face, near) if closest else (dist, face)
+
+
+def mesh_distances(vertices, faces, queries, max_dist, cell=None, info=None):
+    """float32 [m]: the distance from every query point (float32 [m,3] on the mesh's device) to the surface of the mesh within ``max_dist``
+    (inf where there is none) - ``MeshIndex(vertices, faces, cell, max_dist).nearest(queries, max_dist)[0]``.  ``cell`` defaults as
+    ``MeshIndex`` says; ``info`` (a dict) gains "cell", "pairs", "faces_indexed" and "cells".  ValueError: bad arguments (before any device
+    work), and what ``MeshIndex`` refuses.  RuntimeError: tensors that are not on the device.  The contract is cer_mvs.h's,
+    "Mesh distance"."""
+    who = "mesh_distances"
+    _sample_mesh_checks(vertices, faces, None, who)
+    _dist_queries(queries, vertices, who)
+    max_dist = _dist_reach(max_dist, who)
+    if cell is not None:
+        cell = _positive(cell, "cell", who)
+    if info is not None and not isinstance(info, dict):
+        raise ValueError(f"{who}: info must be a dictionary or None")
+    if not vertices.is_cuda:
+        raise RuntimeError(f"{who}: vertices must be a CUDA tensor (no CPU fallback)")
+    index = MeshIndex(vertices, faces, cell, max_dist)
+    if info is not None:
+        info.update(index.info())
+    return index.nearest(queries, max_dist)[0]
 
 
 def _sample_option(value):

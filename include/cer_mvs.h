@@ -1065,6 +1065,64 @@ int cer_mesh_sample_f32(const float* vertices, long long nv, const int* faces, l
                         unsigned long long offset, const unsigned* words, long long n, const unsigned char* colors, float* points, int* face,
                         double* uv, float* normals, unsigned char* out_colors, void* stream);
 
+/* Mesh distance (ABI 1240; csrc/mesh_dist.hip, csrc/grid_walk.hpp, cer-mvs_amd/mesh.py MeshIndex / mesh_distances /
+ * evaluate_mesh(method="exact")): for every query point the nearest face of any indexed triangle mesh within a cut-off - what
+ * cer_grid_nearest_f32 is for clouds - under the rules of the section "Surface mesh": integers, fp64 on the float32 inputs with every
+ * association as written, no fused multiply-add, IEEE division and square root, no atomics, one writer per address, the same bytes on every
+ * run.  vertices float32 [nv, 3]; faces int32 [nf, 3]; areas float64 [nf]: cer_mesh_face_areas_f64's.
+ *
+ * The distance of a point p to a triangle (a, b, c): Ericson's closest point by regions.  dot(x, y) = (x0*y0 + x1*y1) + x2*y2;
+ *   ab = b-a, ac = c-a, ap = p-a, bp = p-b, cp = p-c;
+ *   d1 = dot(ab,ap), d2 = dot(ac,ap), d3 = dot(ab,bp), d4 = dot(ac,bp), d5 = dot(ab,cp), d6 = dot(ac,cp);
+ *   vc = d1*d4 - d3*d2, vb = d5*d2 - d1*d6, va = d3*d6 - d5*d4.
+ * The first region that holds decides:
+ *   1. d1 <= 0 && d2 <= 0: the closest point q is the corner a itself;
+ *   2. d3 >= 0 && d4 <= d3: the corner b itself;
+ *   3. vc <= 0 && d1 >= 0 && d3 <= 0: v = d1 / (d1 - d3), w = 0;
+ *   4. d6 >= 0 && d5 <= d6: the corner c itself;
+ *   5. vb <= 0 && d2 >= 0 && d6 <= 0: v = 0, w = d2 / (d2 - d6);
+ *   6. va <= 0 && (d4 - d3) >= 0 && (d5 - d6) >= 0: w = (d4 - d3) / ((d4 - d3) + (d5 - d6)), v = 1 - w;
+ *   7. otherwise: den = (va + vb) + vc, v = vb / den, w = vc / den.
+ * In the regions 3 and 5 to 7, per axis, q = (a + v*ab) + w*ac.  Then r = q - p and dist2 = (rx*rx + ry*ry) + rz*rz.
+ * A face is a candidate iff dist2 <= double(max_dist)^2: inclusive, and false for a NaN (the 0 / 0 of a near-degenerate face loses).  The
+ * winner is the smallest (dist2, face index).  Faces with areas[f] not above 0 - an index outside [0, nv), a repeated index, a coordinate
+ * that is not finite, a computed area of 0 - are not indexed and are never anybody's nearest face.  A query that is not finite gets no face.
+ * Per query: dist float32 = float(sqrt(dist2)), +inf without a face; face int32, -1 without; closest float32 [m, 3] (optional): q rounded
+ * once, NaN without a face.
+ *
+ * The index is the grid of "Cloud evaluation" with triangles in place of points: the frame (origin, cell) and the 63-bit key are
+ * cer_grid_keys_f32's, cell coordinate c = floor((double(x) - origin) / cell).  A face is entered in every cell of the box [cell of its
+ * smallest corner coordinate, cell of its largest] per axis.
+ *   cer_mesh_tri_cells_i64: cells int64 [nf] = the product of the box's three extents, 0 for a face that is left out.  A cell coordinate
+ *     outside the key range (flag[0]) or a face of more than CER_TRI_MAX_CELLS cells (flag[1]) returns CER_ESHAPE after the launch - flag,
+ *     two device ints of the caller's, carries the finding; the call synchronises the stream to read it.  One thread per face.
+ *   The caller forms cum int64 [nf], the inclusive prefix sums of cells (integers: exact under any scan), and npairs = cum[nf - 1] < 2^31.
+ *   cer_mesh_tri_pairs_i64: face f writes keys[p] = the cell's key and ids[p] = f for p in [cum[f - 1], cum[f]), z-major, then y, then x;
+ *     a face whose box does not have exactly that many cells or whose positions leave [0, npairs) writes nothing (the caller's keys start
+ *     as the sentinel 2^63 - 1).  One thread per face.
+ *   The caller sorts the pairs by key with a stable sort (faces stay ascending inside a cell) and runs cer_grid_cells_count_i64 /
+ *   cer_grid_cells_i64 on the sorted keys: cell_keys [ncells], cell_start [ncells + 1].
+ *   cer_mesh_tri_pack_f32: records [nf] of 48 bytes, (x, y, z, 0) of the corners a, b, c - three 16-byte loads per candidate; zeros for an
+ *     index outside [0, nv).  One thread per face.
+ *   cer_mesh_tri_nearest_f32: one thread per query, in the order qorder int64 [m] (a permutation; null: 0 .. m-1), walking the rows of cells
+ *     around the query, nearest first, against the best dist2 so far; pair_face int32 [npairs]: ids in sorted order.  A face id outside
+ *     [0, nf), a pair position outside [0, npairs) and a vertex index outside [0, nv) are skipped, never read through.
+ *
+ * Checks, in the order of the section "Surface mesh", all before any launch: (1) a negative size, an origin or cell that is not finite, a
+ * cell not above 0, a max_dist that is negative or no number -> CER_EINVAL; (2) nv >= 2^31, 3 nf >= 2^31, npairs >= 2^31, m >= 2^31, more
+ * cells than pairs, ceil(max_dist / cell) beyond 4096 rings -> CER_ESHAPE; (3) nothing to do (nf == 0; the pairs also npairs == 0; the
+ * search also m == 0 or ncells == 0) -> CER_OK with nothing launched; (4) a null pointer -> CER_EINVAL (vertices may be null iff nv == 0;
+ * qorder and closest are null iff absent), then records that are not 16-byte aligned -> CER_EALIGN. */
+#define CER_TRI_MAX_CELLS 4096
+int cer_mesh_tri_cells_i64(const float* vertices, long long nv, const int* faces, long long nf, const double* areas, const double* origin,
+                           double cell, long long* cells, int* flag, void* stream);
+int cer_mesh_tri_pairs_i64(const float* vertices, long long nv, const int* faces, long long nf, const double* areas, const double* origin,
+                           double cell, const long long* cum, long long npairs, long long* keys, int* ids, void* stream);
+int cer_mesh_tri_pack_f32(const float* vertices, long long nv, const int* faces, long long nf, void* records, void* stream);
+int cer_mesh_tri_nearest_f32(const void* records, long long nf, const int* pair_face, long long npairs, const long long* cell_keys,
+                             const long long* cell_start, long long ncells, const double* origin, double cell, const float* queries,
+                             const long long* qorder, long long m, float max_dist, int* face, float* dist, float* closest, void* stream);
+
 /* Multi-GPU row-slab exchange (cer-mvs_amd/slab.py): up to CER_COPY_MAX_SEG contiguous fp32 ranges copied by ONE launch -
  * the pack of a rank's (net, disp) border strips into its send buffer, and the refresh of its halo rows from the gathered
  * strips.  n[i] floats from src[i] to dst[i]; n[i] == 0 skips a segment.  Device pointers; ranges must not overlap. */
