@@ -342,5 +342,13 @@ def dev_ptr(t, name, dtype=torch.float32):
     return ctypes.c_void_p(t.data_ptr())
 
 
+def compaction_buffers(P, dev, extra=2, totals=2):
+    """The buffers of one count / scan / emit (csrc/compact.hpp) with ``P`` partials on ``dev``: (partials int32 [P], offsets int64 [P + extra],
+    totals int64 [totals], zeroed - an entry point that has nothing to count leaves them).  ``extra``: 2 where one launch scans two ranges (vertices
+    then faces), 1 for one range."""
+    return (torch.empty(P, device=dev, dtype=torch.int32), torch.empty(P + extra, device=dev, dtype=torch.int64),
+            torch.zeros(totals, device=dev, dtype=torch.int64))
+
+
 def cur_stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)

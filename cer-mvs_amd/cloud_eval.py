@@ -107,12 +107,6 @@ def _reach(value, name, finite=False):
     return value
 
 
-def _compaction_scratch(lib, n, dev, results):
-    """(partials int32, offsets int64, ``results`` int64 words for the host to read): what one count / scan / emit over ``n`` entries needs"""
-    P = int(lib.cer_grid_partials(n))
-    return tuple(torch.empty(k, device=dev, dtype=t) for k, t in ((P, torch.int32), (P + 1, torch.int64), (results, torch.int64)))
-
-
 class CloudIndex:
     """Sparse uniform grid over ``points`` (CUDA float32 [n, 3]) with cell edge ``cell``: keys, one stable sort and the cell table, built once.
     The grid's origin is the per-axis minimum of the finite points, promoted to fp64.  ``n``: the indexed (finite) points; points with a NaN
@@ -147,7 +141,7 @@ class CloudIndex:
             raise ValueError(f"CloudIndex: the cloud spans more than 2^20 cells of {self.cell} along an axis; use a larger cell")
         L.check(rc, "grid_keys")
         keys, self.order = torch.sort(keys, stable=True)
-        partials, offsets, totals = _compaction_scratch(lib, n_all, dev, 2)
+        partials, offsets, totals = L.compaction_buffers(int(lib.cer_grid_partials(n_all)), dev, extra=1)
         pk = L.dev_ptr(keys, "keys", torch.int64)
         L.check(lib.cer_grid_cells_count_i64(pk, n_all, L.dev_ptr(partials, "partials", torch.int32), L.dev_ptr(offsets, "offsets", torch.int64),
                                              L.dev_ptr(totals, "totals", torch.int64), L.cur_stream()), "grid_cells_count")
@@ -328,7 +322,7 @@ def radius_thin(points, radius, order="random", seed=0, cell=None, max_rounds=40
         return torch.empty(0, device=dev, dtype=torch.int64)
     lib = L.load()
     state = torch.zeros(n_all, device=dev, dtype=torch.uint8)
-    partials, offsets, total = _compaction_scratch(lib, index.n, dev, 1)
+    partials, offsets, total = L.compaction_buffers(int(lib.cer_grid_partials(index.n)), dev, extra=1, totals=1)
     lists = [torch.empty(index.n, device=dev, dtype=torch.int32) for _ in range(2)]
     grid, pstate = index.grid_args(), L.dev_ptr(state, "state", torch.uint8)
     active, n_active = None, index.n                         # (None: the list 0 .. n-1)

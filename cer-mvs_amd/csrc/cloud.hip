@@ -9,24 +9,22 @@
 #include "compact.hpp"
 
 #define CLOUD_TILE CER_CLOUD_TILE                    // pixels of one view per block
-#define CLOUD_ITER (CLOUD_TILE / 256)                // 64-pixel rows per wave
 #define CLOUD_ORDER_CHUNK 128                        // listed views per launch (they travel as kernel arguments: the list is host memory)
 
 struct CloudOrder {
     int view[CLOUD_ORDER_CHUNK];
 };
 
-// the tile walk of both passes over view m: bal[j] = the set pixels of the wave's row j; returns the wave's total
-__device__ __forceinline__ unsigned cloud_ballots(const unsigned char* __restrict__ m, unsigned P, unsigned seg, unsigned long long (&bal)[CLOUD_ITER]) {
-    return compact_ballots(seg, [=](unsigned p) { return p < P && m[p] != 0; }, bal);
+// the predicate of both passes over view m: pixel p is set
+__device__ __forceinline__ auto cloud_set(const unsigned char* __restrict__ m, unsigned P) {
+    return [=](unsigned p) { return p < P && m[p] != 0; };
 }
 
 // ---- count: partials[(k0 + blockIdx.y) * bpv + blockIdx.x] = set pixels of the block's tile
 __global__ __launch_bounds__(256) void cloud_count_kernel(const CloudOrder ord, int k0, const unsigned char* __restrict__ masks, unsigned P,
                                                           int bpv, unsigned* __restrict__ partials) {
-    unsigned long long bal[CLOUD_ITER];
-    const unsigned tot = compact_block_total(cloud_ballots(masks + (long)ord.view[blockIdx.y] * P, P, compact_seg<CLOUD_TILE, unsigned>(), bal));
-    if (threadIdx.x == 0) partials[(long)(k0 + blockIdx.y) * bpv + blockIdx.x] = tot;
+    compact_count<CLOUD_TILE>(compact_seg<CLOUD_TILE, unsigned>(), cloud_set(masks + (long)ord.view[blockIdx.y] * P, P), partials,
+                              (long)(k0 + blockIdx.y) * bpv + blockIdx.x);
 }
 
 // ---- scan: one block; offsets[i] = sum of partials[0 .. i), offsets[n] = the total; view_base[k] = offsets[k * bpv] (k <= views)
@@ -44,21 +42,13 @@ __global__ __launch_bounds__(256) void cloud_emit_kernel(const CloudOrder ord, i
                                                          const float* __restrict__ colors, unsigned P, int w, int bpv,
                                                          const long long* __restrict__ offsets, long long capacity, float* __restrict__ xyz,
                                                          unsigned char* __restrict__ rgb) {
-    const int lane = threadIdx.x & 63;
     const int view = ord.view[blockIdx.y];
-    const unsigned seg = compact_seg<CLOUD_TILE, unsigned>();
-    unsigned long long bal[CLOUD_ITER];
-    const unsigned tot = cloud_ballots(masks + (long)view * P, P, seg, bal);
-    long long base = compact_wave_base(tot, offsets, (long)(k0 + blockIdx.y) * bpv + blockIdx.x);
     const double* c = cams + (long)view * CER_CLOUD_CAM_DOUBLES;         // wave-uniform: scalar loads
     const float* dep = depth + (long)view * P;
     const float* col = colors + (long)view * 3 * P;
-#pragma unroll
-    for (int j = 0; j < CLOUD_ITER; ++j) {
-        const unsigned p = seg + 64 * j;
-        const long long idx = base + compact_rank(bal[j]);
-        base += __popcll(bal[j]);
-        if (!((bal[j] >> lane) & 1ull) || idx >= capacity) continue;     // (never past what the caller allocated)
+    compact_emit<CLOUD_TILE>(compact_seg<CLOUD_TILE, unsigned>(), cloud_set(masks + (long)view * P, P), offsets,
+                             (long)(k0 + blockIdx.y) * bpv + blockIdx.x, [&](unsigned p, long long idx) {
+        if (idx >= capacity) return;                                     // (never past what the caller allocated)
         const unsigned yi = p / (unsigned)w, xi = p - yi * (unsigned)w;
         const double d = (double)dep[p];
         const double vx = (double)xi * d, vy = (double)yi * d;           // exact: an integer times a float32 in fp64
@@ -75,7 +65,7 @@ __global__ __launch_bounds__(256) void cloud_emit_kernel(const CloudOrder ord, i
         unsigned char* q = rgb + idx * 3;
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) q[ch] = (unsigned char)(int)(col[(long)ch * P + p] * 255.0f);     // fusion(): (img * 255).astype(uint8)
-    }
+    });
 }
 
 static int cloud_check(const void* masks, int N, int h, int w, const int* order, int n_order) {

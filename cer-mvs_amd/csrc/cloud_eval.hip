@@ -65,15 +65,13 @@ __device__ __forceinline__ bool grid_head(const long long* __restrict__ keys, lo
     return k != GRID_SENTINEL && (i == 0 || keys[i - 1] != k);
 }
 
-// the tile walk of both passes: bal[j] = the heads of the wave's row j; returns the wave's total
+// the tile walk of the emit pass: bal[j] = the heads of the wave's row j; returns the wave's total
 __device__ __forceinline__ unsigned grid_ballots(const long long* __restrict__ keys, long n, long seg, unsigned long long (&bal)[GRID_ITER]) {
     return compact_ballots(seg, [=](long i) { return grid_head(keys, n, i); }, bal);
 }
 
 __global__ __launch_bounds__(256) void grid_count_kernel(const long long* __restrict__ keys, long n, unsigned* __restrict__ partials) {
-    unsigned long long bal[GRID_ITER];
-    const unsigned tot = compact_block_total(grid_ballots(keys, n, compact_seg<GRID_TILE, long>(), bal));
-    if (threadIdx.x == 0) partials[blockIdx.x] = tot;
+    compact_count<GRID_TILE>(compact_seg<GRID_TILE, long>(), [=](long i) { return grid_head(keys, n, i); }, partials, blockIdx.x);
 }
 
 // one block: offsets[i] = sum of partials[0 .. i), offsets[np] = totals[0] = the number of cells; totals[1] = the number of keys below the
@@ -87,7 +85,8 @@ __global__ __launch_bounds__(1024) void grid_scan_kernel(const unsigned* __restr
     }
 }
 
-// cell_keys[r] = key and cell_start[r] = sorted position of head r; cell_start[ncells] = the number of keys below the sentinel
+// cell_keys[r] = key and cell_start[r] = sorted position of head r; cell_start[ncells] = the number of keys below the sentinel - written from
+// the last real key's position, which need not be a head: the one emit kernel on compact.hpp's pieces, not on compact_emit
 __global__ __launch_bounds__(256) void grid_emit_kernel(const long long* __restrict__ keys, long n, const long long* __restrict__ offsets,
                                                         long long ncells, long long* __restrict__ cell_keys, long long* __restrict__ cell_start) {
     const int lane = threadIdx.x & 63;
@@ -423,10 +422,8 @@ __device__ __forceinline__ bool thin_undecided(const uint4* __restrict__ rec, co
 
 __global__ __launch_bounds__(256) void thin_count_kernel(const uint4* __restrict__ rec, const int* __restrict__ active, long m,
                                                          const unsigned char* __restrict__ state, unsigned* __restrict__ partials) {
-    unsigned long long bal[GRID_ITER];
-    const unsigned tot = compact_block_total(
-        compact_ballots(compact_seg<GRID_TILE, long>(), [=](long i) { return thin_undecided(rec, active, m, state, i); }, bal));
-    if (threadIdx.x == 0) partials[blockIdx.x] = tot;
+    compact_count<GRID_TILE>(compact_seg<GRID_TILE, long>(), [=](long i) { return thin_undecided(rec, active, m, state, i); }, partials,
+                             blockIdx.x);
 }
 
 __global__ __launch_bounds__(1024) void thin_scan_kernel(const unsigned* __restrict__ partials, long np, long long* __restrict__ offsets,
@@ -438,19 +435,10 @@ __global__ __launch_bounds__(1024) void thin_scan_kernel(const unsigned* __restr
 __global__ __launch_bounds__(256) void thin_emit_kernel(const uint4* __restrict__ rec, const int* __restrict__ active, long m,
                                                         const unsigned char* __restrict__ state, const long long* __restrict__ offsets,
                                                         int* __restrict__ out) {
-    const int lane = threadIdx.x & 63;
-    const long seg = compact_seg<GRID_TILE, long>();
-    unsigned long long bal[GRID_ITER];
-    const unsigned tot = compact_ballots(seg, [=](long i) { return thin_undecided(rec, active, m, state, i); }, bal);
-    long long base = compact_wave_base(tot, offsets, blockIdx.x);
-#pragma unroll
-    for (int j = 0; j < GRID_ITER; ++j) {
-        const long p = seg + 64 * j;
-        const long long r = base + compact_rank(bal[j]);
-        base += __popcll(bal[j]);
-        if (!((bal[j] >> lane) & 1ull) || r >= m) continue;                      // (never past the list's own length: what the caller allocated)
-        out[r] = active ? active[p] : (int)p;
-    }
+    const auto set = [=](long i) { return thin_undecided(rec, active, m, state, i); };
+    compact_emit<GRID_TILE>(compact_seg<GRID_TILE, long>(), set, offsets, blockIdx.x, [=](long p, long long r) {
+        if (r < m) out[r] = active ? active[p] : (int)p;                         // (never past the list's own length: what the caller allocated)
+    });
 }
 
 // ---- entry points.  Sizes: negative -> CER_EINVAL, 2^31 and beyond -> CER_ESHAPE, zero -> nothing to do (CER_OK, nothing launched, before
@@ -459,10 +447,6 @@ static int grid_size_check(long n) {
     if (n < 0) return CER_EINVAL;
     if (n >= 0x80000000L) return CER_ESHAPE;
     return CER_OK;
-}
-static bool grid_is_finite(double v) { return v - v == 0.0; }
-static bool grid_frame_ok(const double* origin, double cell) {
-    return origin && grid_is_finite(origin[0]) && grid_is_finite(origin[1]) && grid_is_finite(origin[2]) && grid_is_finite(cell) && cell > 0.0;
 }
 static unsigned grid_blocks(long n, long per) { return (unsigned)((n + per - 1) / per); }
 
@@ -475,7 +459,7 @@ extern "C" int cer_grid_keys_f32(const float* points, long n, const double* orig
                                  void* stream) {
     const int rc = grid_size_check(n);
     if (rc != CER_OK) return rc;
-    if (!grid_frame_ok(origin, cell)) return CER_EINVAL;
+    if (!cer_frame_ok(origin, cell)) return CER_EINVAL;
     if (n == 0) return CER_OK;
     if (!points || !keys || (!clamp && !flag)) return CER_EINVAL;
     hipStream_t st = (hipStream_t)stream;
@@ -543,7 +527,7 @@ static int grid_search_rings(const void* records, long n, const long long* cell_
     if (rc == CER_OK) rc = grid_size_check(m);
     if (rc == CER_OK) rc = grid_size_check(ncells);
     if (rc != CER_OK) return rc;
-    if (!grid_frame_ok(origin, cell) || !reach_ok) return CER_EINVAL;
+    if (!cer_frame_ok(origin, cell) || !reach_ok) return CER_EINVAL;
     if (ncells > n || !shape_ok) return CER_ESHAPE;
     const double rings = ceil((double)reach / cell);
     if (!(rings <= (double)GRID_MAX_RINGS)) return CER_ESHAPE;
@@ -626,7 +610,7 @@ extern "C" int cer_grid_thin_round_f32(const void* records, long n, const long l
                                        unsigned char* state, void* stream) {
     GridView g;
     const int rings = grid_search_rings(records, n, cell_keys, cell_start, ncells, origin, cell, n_active, radius,
-                                        radius > 0.0f && grid_is_finite((double)radius), n_active <= n, state != nullptr, g);
+                                        radius > 0.0f && cer_is_finite((double)radius), n_active <= n, state != nullptr, g);
     if (rings <= 0) return rings;                            // (active may be NULL: the list 0 .. n_active-1)
     hipLaunchKernelGGL(grid_thin_round_kernel, dim3(grid_blocks(n_active, 256)), dim3(256), 0, (hipStream_t)stream, g, active, n_active, radius,
                        state);

@@ -69,6 +69,11 @@ int cer_num_cus();
 int cer_lds_per_cu();
 
 static inline bool cer_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// host-side argument checks of the cloud and mesh entry points: a finite double; a frame = three finite origin coordinates and a finite cell > 0
+static inline bool cer_is_finite(double v) { return v - v == 0.0; }
+static inline bool cer_frame_ok(const double* origin, double cell) {
+    return origin && cer_is_finite(origin[0]) && cer_is_finite(origin[1]) && cer_is_finite(origin[2]) && cer_is_finite(cell) && cell > 0.0;
+}
 
 // ---- cross-lane sum over one 16-lane DPP row (4 v_add_f32_dpp, no LDS) -------------------
 template <int CTRL>

@@ -1,9 +1,16 @@
-// Ordered stream compaction in three passes, the one copy (cloud.hip: set mask pixels; cloud_eval.hip: heads of the sorted cell keys).
+// Ordered stream compaction in three passes, the one copy.  Users: cloud.hip (the set mask pixels), cloud_eval.hip (the heads of the sorted cell
+// keys; the undecided points of a thinning round) and mesh.hip (the extraction's vertex and face slots, the selection's vertices and faces, the
+// heads of the sorted edge keys).
 // count: a 256-thread block walks a tile of TILE positions - wave v owns positions [v, v + 1) * TILE / 4 in ITER = TILE / 256 rows of 64, one
 // ballot per row - and writes one partial; scan: ONE block turns the partials into 64-bit exclusive offsets; emit: the ballots again, and a
 // set position goes to offsets[block] + the totals of the block's earlier waves + the set bits of the wave's earlier rows + its lane rank.
 // The output order is the position order and a pure function of the flags: no atomics, no output cursor, the same bytes on every run.
-// The kernels stay with their callers, which supply the predicate, the addresses and the emit body.
+//
+// Which form to reach for: a kernel is its predicate, its addresses and one call - compact_count in the count kernel, compact_emit with the
+// body of a set position in the emit kernel, compact_scan in a scan kernel of the caller's own (what follows the scan differs per caller).
+// The pieces underneath (compact_ballots, compact_block_total, compact_wave_base, compact_rank) are for a kernel that does more in the row
+// loop than emit set positions; grid_emit_kernel (cloud_eval.hip) is the one that does: it also writes cell_start[ncells] from a position that
+// need not be set.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -46,6 +53,32 @@ __device__ __forceinline__ long long compact_wave_base(unsigned wave_total, cons
     long long base = offsets[block];
     for (int i = 0; i < wave; ++i) base += wave_cnt[i];
     return base;
+}
+
+// the whole count pass of a block: partials[slot] = the set positions of the tile that starts at lane position seg (compact_seg, less the
+// caller's shift if its grid holds several ranges).  Block-uniform call sites only: there is a barrier inside.
+template <int TILE, typename Pos, typename Set>
+__device__ __forceinline__ void compact_count(Pos seg, Set set, unsigned* __restrict__ partials, long slot) {
+    unsigned long long bal[TILE / 256];
+    const unsigned tot = compact_block_total(compact_ballots(seg, set, bal));
+    if (threadIdx.x == 0) partials[slot] = tot;
+}
+
+// the whole emit pass of a block: body(position, output index) for every set position of the tile, by the lane that owns it.  Output indices
+// ascend with the position - rows in order, lanes in order inside a row - from offsets[block].  The index is not bounded here: a body tests
+// it against what its caller allocated before it stores anything at it.
+template <int TILE, typename Pos, typename Set, typename Body>
+__device__ __forceinline__ void compact_emit(Pos seg, Set set, const long long* __restrict__ offsets, long block, Body body) {
+    const int lane = threadIdx.x & 63;
+    unsigned long long bal[TILE / 256];
+    const unsigned tot = compact_ballots(seg, set, bal);
+    long long base = compact_wave_base(tot, offsets, block);
+#pragma unroll
+    for (int j = 0; j < TILE / 256; ++j) {
+        const long long idx = base + compact_rank(bal[j]);
+        base += __popcll(bal[j]);
+        if ((bal[j] >> lane) & 1ull) body(seg + 64 * j, idx);
+    }
 }
 
 // scan pass, one block of 1024 threads (128 B of LDS): offsets[i] = sum of partials[0 .. i), offsets[n] = the total, which every thread gets

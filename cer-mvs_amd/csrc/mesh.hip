@@ -26,7 +26,6 @@
 #include "compact.hpp"
 
 #define MESH_TILE CER_MESH_TILE                      // slots per block of the count and emit passes
-#define MESH_ITER (MESH_TILE / 256)
 
 // ---- the case table, derived (not copied): for tet t and the 4-bit mask of its inside corners in listing order, the number of triangles and
 // up to six lattice edges, 6 bits each: (lower corner << 3) | d.  Triangle s takes edges 3 s .. 3 s + 2.
@@ -85,6 +84,25 @@ struct MeshGrid {
     int nx, ny, nz;
 };
 
+// linear index n of a lattice [., ny, nx], x fastest (the nodes, or the cells with nx - 1 and ny - 1) -> (i, j, k)
+__device__ __forceinline__ void mesh_split(unsigned n, unsigned nx, unsigned ny, unsigned& i, unsigned& j, unsigned& k) {
+    const unsigned row = n / nx;
+    i = n - row * nx;
+    k = row / ny;
+    j = row - k * ny;
+}
+
+// world point -> camera -> homogeneous pixel (ux, uy, uz) of the view with camera doubles c: the one projection of the integration and of the
+// vertex colours, every association written out.  The pixel is (ux / uz, uy / uz); the callers divide and test.
+__device__ __forceinline__ void mesh_project(const double* c, double px, double py, double pz, double& ux, double& uy, double& uz) {
+    const double cx = ((c[9] * px + c[10] * py) + c[11] * pz) + c[12];
+    const double cy = ((c[13] * px + c[14] * py) + c[15] * pz) + c[16];
+    const double cz = ((c[17] * px + c[18] * py) + c[19] * pz) + c[20];
+    ux = (c[0] * cx + c[1] * cy) + c[2] * cz;
+    uy = (c[3] * cx + c[4] * cy) + c[5] * cz;
+    uz = (c[6] * cx + c[7] * cy) + c[8] * cz;
+}
+
 // ---- integration: one thread owns a node for the whole view loop, x along the lanes.  cams: per view CER_CLOUD_CAM_DOUBLES doubles =
 // K [9] | rows 0-2 of E [12] (the float32 matrices promoted on the host): wave-uniform, scalar loads.  views: n_views DEVICE ints.
 __global__ __launch_bounds__(256) void tsdf_integrate_kernel(const float* __restrict__ depths, const unsigned char* __restrict__ masks,
@@ -93,8 +111,8 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(const float* __rest
                                                              unsigned nodes, float* __restrict__ tsdf, int* __restrict__ weight) {
     const unsigned n = blockIdx.x * 256u + threadIdx.x;
     if (n >= nodes) return;
-    const unsigned row = n / (unsigned)g.nx, i = n - row * (unsigned)g.nx;
-    const unsigned k = row / (unsigned)g.ny, j = row - k * (unsigned)g.ny;
+    unsigned i, j, k;
+    mesh_split(n, (unsigned)g.nx, (unsigned)g.ny, i, j, k);
     const double px = g.ox + (double)i * g.voxel, py = g.oy + (double)j * g.voxel, pz = g.oz + (double)k * g.voxel;
     const long P = (long)h * w;
     const double dw = (double)w, dh = (double)h;
@@ -103,13 +121,8 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(const float* __rest
     for (int v = 0; v < n_views; ++v) {
         const int view = views[v];
         if (view < 0 || view >= N) continue;                             // (uniform; the caller has checked the list: never taken)
-        const double* c = cams + (long)view * CER_CLOUD_CAM_DOUBLES;
-        const double cx = ((c[9] * px + c[10] * py) + c[11] * pz) + c[12];
-        const double cy = ((c[13] * px + c[14] * py) + c[15] * pz) + c[16];
-        const double cz = ((c[17] * px + c[18] * py) + c[19] * pz) + c[20];
-        const double ux = (c[0] * cx + c[1] * cy) + c[2] * cz;
-        const double uy = (c[3] * cx + c[4] * cy) + c[5] * cz;
-        const double uz = (c[6] * cx + c[7] * cy) + c[8] * cz;
+        double ux, uy, uz;
+        mesh_project(cams + (long)view * CER_CLOUD_CAM_DOUBLES, px, py, pz, ux, uy, uz);
         const double a = ux / uz + 0.5, b = uy / uz + 0.5;
         if (!(uz > 0.0 && a >= 0.0 && a < dw && b >= 0.0 && b < dh)) continue;       // (NaN fails every comparison)
         const long p = (long)view * P + (long)(int)floor(b) * w + (int)floor(a);
@@ -131,9 +144,8 @@ __global__ __launch_bounds__(256) void mesh_cells_kernel(const float* __restrict
                                                          int min_weight, unsigned ncells, unsigned short* __restrict__ cells) {
     const unsigned c = blockIdx.x * 256u + threadIdx.x;
     if (c >= ncells) return;
-    const unsigned cx = (unsigned)nx - 1, cy = (unsigned)ny - 1;
-    const unsigned row = c / cx, i = c - row * cx;
-    const unsigned k = row / cy, j = row - k * cy;
+    unsigned i, j, k;
+    mesh_split(c, (unsigned)nx - 1, (unsigned)ny - 1, i, j, k);
     const long base = ((long)k * ny + j) * nx + i;
     unsigned m = 0, ok = 1;
 #pragma unroll
@@ -157,8 +169,8 @@ __device__ __forceinline__ bool mesh_vertex_set(const unsigned short* __restrict
     if (p >= D.vslots) return false;
     const unsigned d = (unsigned)p & 7u, n = (unsigned)(p >> 3);
     if (d == 0) return false;
-    const unsigned row = n / (unsigned)D.nx, i = n - row * (unsigned)D.nx;
-    const unsigned k = row / (unsigned)D.ny, j = row - k * (unsigned)D.ny;
+    unsigned i, j, k;
+    mesh_split(n, (unsigned)D.nx, (unsigned)D.ny, i, j, k);
     bool set = false;
 #pragma unroll
     for (unsigned o = 0; o < 8; ++o) {
@@ -190,13 +202,10 @@ __device__ __forceinline__ bool mesh_face_set(const unsigned short* __restrict__
 // ---- count: grid = vertex blocks then face blocks, one partial each
 __global__ __launch_bounds__(256) void mesh_count_kernel(const unsigned short* __restrict__ cells, MeshDims D, unsigned vblocks,
                                                          unsigned* __restrict__ partials) {
-    unsigned long long bal[MESH_ITER];
     const bool faces = blockIdx.x >= vblocks;                            // (uniform)
     const long seg = compact_seg<MESH_TILE, long>() - (faces ? (long)vblocks * MESH_TILE : 0);
-    const unsigned wave = faces ? compact_ballots(seg, [&](long q) { return mesh_face_set(cells, D, q); }, bal)
-                                : compact_ballots(seg, [&](long p) { return mesh_vertex_set(cells, D, p); }, bal);
-    const unsigned tot = compact_block_total(wave);
-    if (threadIdx.x == 0) partials[blockIdx.x] = tot;
+    if (faces) compact_count<MESH_TILE>(seg, [&](long q) { return mesh_face_set(cells, D, q); }, partials, blockIdx.x);
+    else compact_count<MESH_TILE>(seg, [&](long p) { return mesh_vertex_set(cells, D, p); }, partials, blockIdx.x);
 }
 
 // ---- scan: block 0 the vertex partials -> offsets[0 .. vblocks], totals[0] = nv; block 1 the face partials -> offsets[vblocks + 1 ..],
@@ -213,22 +222,13 @@ __global__ __launch_bounds__(1024) void mesh_scan_kernel(const unsigned* __restr
 __global__ __launch_bounds__(256) void mesh_vertex_emit_kernel(const float* __restrict__ tsdf, const unsigned short* __restrict__ cells,
                                                                MeshDims D, MeshGrid g, const long long* __restrict__ offsets,
                                                                long long capacity, int* __restrict__ vmap, float* __restrict__ vertices) {
-    const int lane = threadIdx.x & 63;
-    const long seg = compact_seg<MESH_TILE, long>();
-    unsigned long long bal[MESH_ITER];
-    const unsigned tot = compact_ballots(seg, [&](long p) { return mesh_vertex_set(cells, D, p); }, bal);
-    long long base = compact_wave_base(tot, offsets, blockIdx.x);
-#pragma unroll
-    for (int jj = 0; jj < MESH_ITER; ++jj) {
-        const long p = seg + 64 * jj;
-        const long long idx = base + compact_rank(bal[jj]);
-        base += __popcll(bal[jj]);
-        if (!((bal[jj] >> lane) & 1ull)) continue;
+    const auto set = [&](long p) { return mesh_vertex_set(cells, D, p); };
+    compact_emit<MESH_TILE>(compact_seg<MESH_TILE, long>(), set, offsets, blockIdx.x, [&](long p, long long idx) {
         vmap[p] = (int)idx;
-        if (idx >= capacity) continue;                                   // (never past what the caller allocated)
+        if (idx >= capacity) return;                                     // (never past what the caller allocated)
         const unsigned d = (unsigned)p & 7u, n = (unsigned)(p >> 3);
-        const unsigned row = n / (unsigned)D.nx, i = n - row * (unsigned)D.nx;
-        const unsigned k = row / (unsigned)D.ny, j = row - k * (unsigned)D.ny;
+        unsigned i, j, k;
+        mesh_split(n, (unsigned)D.nx, (unsigned)D.ny, i, j, k);
         const long n1 = (long)n + (d & 1) + (long)((d >> 1) & 1) * D.nx + (long)(d >> 2) * D.nx * D.ny;
         const double f0 = (double)tsdf[n], f1 = (double)tsdf[n1];
         const double t = f0 / (f0 - f1);
@@ -236,29 +236,20 @@ __global__ __launch_bounds__(256) void mesh_vertex_emit_kernel(const float* __re
         o[0] = (float)(g.ox + ((double)i + ((d & 1) ? t : 0.0)) * g.voxel);
         o[1] = (float)(g.oy + ((double)j + ((d & 2) ? t : 0.0)) * g.voxel);
         o[2] = (float)(g.oz + ((double)k + ((d & 4) ? t : 0.0)) * g.voxel);
-    }
+    });
 }
 
 // ---- face emit: the three lattice edges of triangle s of the tet -> their vertex slots -> vmap
 __global__ __launch_bounds__(256) void mesh_face_emit_kernel(const unsigned short* __restrict__ cells, MeshDims D,
                                                              const long long* __restrict__ offsets, long long capacity,
                                                              const int* __restrict__ vmap, int* __restrict__ faces) {
-    const int lane = threadIdx.x & 63;
-    const long seg = compact_seg<MESH_TILE, long>();
-    unsigned long long bal[MESH_ITER];
-    const unsigned tot = compact_ballots(seg, [&](long q) { return mesh_face_set(cells, D, q); }, bal);
-    long long base = compact_wave_base(tot, offsets, blockIdx.x);
-#pragma unroll
-    for (int jj = 0; jj < MESH_ITER; ++jj) {
-        const long q = seg + 64 * jj;
-        const long long idx = base + compact_rank(bal[jj]);
-        base += __popcll(bal[jj]);
-        if (!((bal[jj] >> lane) & 1ull) || idx >= capacity) continue;    // (never past what the caller allocated)
+    const auto set = [&](long q) { return mesh_face_set(cells, D, q); };
+    compact_emit<MESH_TILE>(compact_seg<MESH_TILE, long>(), set, offsets, blockIdx.x, [&](long q, long long idx) {
+        if (idx >= capacity) return;                                     // (never past what the caller allocated)
         const long cell = q / 12;
         const unsigned r = (unsigned)(q - cell * 12);
-        const unsigned cx = (unsigned)D.nx - 1, cy = (unsigned)D.ny - 1;
-        const unsigned row = (unsigned)cell / cx, i = (unsigned)cell - row * cx;
-        const unsigned k = row / cy, j = row - k * cy;
+        unsigned i, j, k;
+        mesh_split((unsigned)cell, (unsigned)D.nx - 1, (unsigned)D.ny - 1, i, j, k);
         const long node = ((long)k * D.ny + j) * D.nx + i;
         const unsigned long long code = mesh_table.tri[r >> 1][mesh_tet_mask(cells[cell], r >> 1)] >> (18 * (r & 1u));
         int* o = faces + idx * 3;
@@ -268,12 +259,12 @@ __global__ __launch_bounds__(256) void mesh_face_emit_kernel(const unsigned shor
             const long na = node + (a & 1) + (long)((a >> 1) & 1) * D.nx + (long)(a >> 2) * D.nx * D.ny;
             o[e] = vmap[na * 8 + (c6 & 7u)];
         }
-    }
+    });
 }
 
 // ---- vertex colours from the views: one thread owns a vertex for the whole view loop, laid out as tsdf_integrate_kernel is - the view's 21
 // camera doubles and its list entry are wave-uniform (scalar loads), depth, mask and colour are gathered per pixel.  The projection is the
-// integration's, association for association; a view colours the vertex iff it projects inside, the pixel is masked in, its depth is finite
+// integration's (mesh_project); a view colours the vertex iff it projects inside, the pixel is masked in, its depth is finite
 // and positive and |d - uz| <= tol (the occlusion test).  The sample is bilinear over pixel centres at integer coordinates, taps clamped.
 __device__ __forceinline__ double mesh_bilinear(const float* __restrict__ plane, long r0, long r1, int x0, int x1, double fx, double fy) {
     const double c00 = (double)plane[r0 + x0], c01 = (double)plane[r0 + x1], c10 = (double)plane[r1 + x0], c11 = (double)plane[r1 + x1];
@@ -300,13 +291,8 @@ __global__ __launch_bounds__(256) void mesh_vertex_color_kernel(const float* __r
     for (int v = 0; v < n_views; ++v) {
         const int view = views[v];
         if (view < 0 || view >= N) continue;                             // (uniform; the caller has checked the list: never taken)
-        const double* c = cams + (long)view * CER_CLOUD_CAM_DOUBLES;
-        const double cx = ((c[9] * px + c[10] * py) + c[11] * pz) + c[12];
-        const double cy = ((c[13] * px + c[14] * py) + c[15] * pz) + c[16];
-        const double cz = ((c[17] * px + c[18] * py) + c[19] * pz) + c[20];
-        const double ux = (c[0] * cx + c[1] * cy) + c[2] * cz;
-        const double uy = (c[3] * cx + c[4] * cy) + c[5] * cz;
-        const double uz = (c[6] * cx + c[7] * cy) + c[8] * cz;
+        double ux, uy, uz;
+        mesh_project(cams + (long)view * CER_CLOUD_CAM_DOUBLES, px, py, pz, ux, uy, uz);
         const double x = ux / uz, y = uy / uz;
         const double a = x + 0.5, b = y + 0.5;
         if (!(uz > 0.0 && a >= 0.0 && a < dw && b >= 0.0 && b < dh)) continue;       // (NaN fails every comparison)
@@ -440,17 +426,14 @@ __global__ __launch_bounds__(256) void mesh_select_count_kernel(const int* __res
                                                                 const int* __restrict__ starts, const int* __restrict__ order, unsigned nv,
                                                                 long nf, unsigned vblocks, unsigned char* __restrict__ used,
                                                                 unsigned* __restrict__ partials) {
-    unsigned long long bal[MESH_ITER];
     const bool fpart = blockIdx.x >= vblocks;                            // (uniform)
     const long seg = compact_seg<MESH_TILE, long>() - (fpart ? (long)vblocks * MESH_TILE : 0);
-    const unsigned wave = fpart ? compact_ballots(seg, [&](long q) { return mesh_face_kept(faces, keep, nv, nf, q); }, bal)
-                                : compact_ballots(seg, [&](long p) {
-                                      const bool u = mesh_vertex_used(faces, keep, starts, order, nv, nf, p);
-                                      if (p < (long)nv) used[p] = (unsigned char)u;
-                                      return u;
-                                  }, bal);
-    const unsigned tot = compact_block_total(wave);
-    if (threadIdx.x == 0) partials[blockIdx.x] = tot;
+    if (fpart) compact_count<MESH_TILE>(seg, [&](long q) { return mesh_face_kept(faces, keep, nv, nf, q); }, partials, blockIdx.x);
+    else compact_count<MESH_TILE>(seg, [&](long p) {
+        const bool u = mesh_vertex_used(faces, keep, starts, order, nv, nf, p);
+        if (p < (long)nv) used[p] = (unsigned char)u;
+        return u;
+    }, partials, blockIdx.x);
 }
 
 // vertex emit: vmap[p] = the vertex's new index (for every used vertex: the faces read it); below the caller's capacity the position's bits
@@ -459,55 +442,34 @@ __global__ __launch_bounds__(256) void mesh_select_vertex_emit_kernel(const floa
                                                                       const unsigned char* __restrict__ used,
                                                                       const long long* __restrict__ offsets, long long capacity,
                                                                       int* __restrict__ vmap, float* __restrict__ out, int* __restrict__ index) {
-    const int lane = threadIdx.x & 63;
-    const long seg = compact_seg<MESH_TILE, long>();
-    unsigned long long bal[MESH_ITER];
-    const unsigned tot = compact_ballots(seg, [&](long p) { return p < (long)nv && used[p] != 0; }, bal);
-    long long base = compact_wave_base(tot, offsets, blockIdx.x);
-#pragma unroll
-    for (int jj = 0; jj < MESH_ITER; ++jj) {
-        const long p = seg + 64 * jj;
-        const long long idx = base + compact_rank(bal[jj]);
-        base += __popcll(bal[jj]);
-        if (!((bal[jj] >> lane) & 1ull)) continue;
+    const auto set = [&](long p) { return p < (long)nv && used[p] != 0; };
+    compact_emit<MESH_TILE>(compact_seg<MESH_TILE, long>(), set, offsets, blockIdx.x, [&](long p, long long idx) {
         vmap[p] = (int)idx;
-        if (idx >= capacity) continue;                                   // (never past what the caller allocated)
+        if (idx >= capacity) return;                                     // (never past what the caller allocated)
         const float* s = vertices + 3 * p;
         float* o = out + idx * 3;
         o[0] = s[0];
         o[1] = s[1];
         o[2] = s[2];
         index[idx] = (int)p;
-    }
+    });
 }
 
 __global__ __launch_bounds__(256) void mesh_select_face_emit_kernel(const int* __restrict__ faces, const unsigned char* __restrict__ keep,
                                                                     unsigned nv, long nf, const long long* __restrict__ offsets,
                                                                     long long capacity, const int* __restrict__ vmap, int* __restrict__ out) {
-    const int lane = threadIdx.x & 63;
-    const long seg = compact_seg<MESH_TILE, long>();
-    unsigned long long bal[MESH_ITER];
-    const unsigned tot = compact_ballots(seg, [&](long q) { return mesh_face_kept(faces, keep, nv, nf, q); }, bal);
-    long long base = compact_wave_base(tot, offsets, blockIdx.x);
-#pragma unroll
-    for (int jj = 0; jj < MESH_ITER; ++jj) {
-        const long q = seg + 64 * jj;
-        const long long idx = base + compact_rank(bal[jj]);
-        base += __popcll(bal[jj]);
-        if (!((bal[jj] >> lane) & 1ull) || idx >= capacity) continue;    // (never past what the caller allocated)
+    const auto set = [&](long q) { return mesh_face_kept(faces, keep, nv, nf, q); };
+    compact_emit<MESH_TILE>(compact_seg<MESH_TILE, long>(), set, offsets, blockIdx.x, [&](long q, long long idx) {
+        if (idx >= capacity) return;                                     // (never past what the caller allocated)
         const int* f = faces + q * 3;
         int* o = out + idx * 3;
         o[0] = vmap[f[0]];
         o[1] = vmap[f[1]];
         o[2] = vmap[f[2]];
-    }
+    });
 }
 
 // ---- host side.  The order of the checks is the documented one (cer_mvs.h): negative sizes, too large, the frame, nothing to do, pointers.
-static bool mesh_is_finite(double v) { return v - v == 0.0; }
-static bool mesh_frame_ok(const double* origin, double voxel) {
-    return origin && mesh_is_finite(origin[0]) && mesh_is_finite(origin[1]) && mesh_is_finite(origin[2]) && mesh_is_finite(voxel) && voxel > 0.0;
-}
 // CER_OK and the node count, or the error of a negative or too large grid
 static int mesh_nodes(int nx, int ny, int nz, long* nodes) {
     if (nx < 0 || ny < 0 || nz < 0) return CER_EINVAL;
@@ -541,7 +503,7 @@ extern "C" int cer_tsdf_integrate_f32(const float* depths, const unsigned char* 
     const int rc = mesh_nodes(nx, ny, nz, &nodes);
     if (rc != CER_OK) return rc;
     if ((long)h * w > 0x7fffffffL) return CER_ESHAPE;
-    if (!mesh_frame_ok(origin, voxel) || !(mesh_is_finite(trunc) && trunc > 0.0)) return CER_EINVAL;
+    if (!cer_frame_ok(origin, voxel) || !(cer_is_finite(trunc) && trunc > 0.0)) return CER_EINVAL;
     if (nodes == 0 || n_views == 0) return CER_OK;                       // (no views: weight 0 and tsdf 1 are the caller's to fill)
     if (!depths || !cams || !views || !tsdf || !weight || N == 0 || h == 0 || w == 0) return CER_EINVAL;
     const MeshGrid g = {origin[0], origin[1], origin[2], voxel, nx, ny, nz};
@@ -590,7 +552,7 @@ extern "C" int cer_mesh_emit_f32(const float* tsdf, const unsigned short* cells,
     const int rc = mesh_nodes(nx, ny, nz, &nodes);
     if (rc != CER_OK) return rc;
     if (nv > 0x7fffffffLL || nf > 0x7fffffffLL) return CER_ESHAPE;       // indices are int32
-    if (!mesh_frame_ok(origin, voxel)) return CER_EINVAL;
+    if (!cer_frame_ok(origin, voxel)) return CER_EINVAL;
     if (nodes == 0 || nx == 1 || ny == 1 || nz == 1 || (nv == 0 && nf == 0) || (vcap == 0 && fcap == 0)) return CER_OK;
     if (!tsdf || !cells || !offsets || !vmap || (vcap && !vertices) || (fcap && !faces)) return CER_EINVAL;
     const MeshDims D = mesh_dims(nx, ny, nz);
@@ -613,7 +575,7 @@ extern "C" int cer_mesh_vertex_colors_u8(const float* vertices, long long nv, co
                                          double tol, unsigned char* rgb, int* seen, void* stream) {
     if (nv < 0 || N < 0 || h < 0 || w < 0 || n_views < 0) return CER_EINVAL;
     if (nv > 0x7fffffffLL || (long)h * w > 0x7fffffffL) return CER_ESHAPE;
-    if (!(mesh_is_finite(tol) && tol > 0.0)) return CER_EINVAL;
+    if (!(cer_is_finite(tol) && tol > 0.0)) return CER_EINVAL;
     if (nv == 0 || n_views == 0) return CER_OK;                          // (no views: rgb 0 and seen 0 are the caller's to fill)
     if (!vertices || !depths || !colors || !cams || !views || !rgb || !seen || N == 0 || h == 0 || w == 0) return CER_EINVAL;
     hipLaunchKernelGGL(mesh_vertex_color_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, (hipStream_t)stream, vertices, (unsigned)nv,
@@ -912,7 +874,7 @@ extern "C" int cer_mesh_cluster_reps_f32(const float* vertices, long long nv, co
                                          unsigned char* took, void* stream) {
     const int rc = mesh_cluster_sizes(nv, nf, ncells);
     if (rc != CER_OK) return rc;
-    if (!mesh_frame_ok(origin, cell) || !(mesh_is_finite(regularisation) && regularisation > 0.0)) return CER_EINVAL;
+    if (!cer_frame_ok(origin, cell) || !(cer_is_finite(regularisation) && regularisation > 0.0)) return CER_EINVAL;
     if (ncells == 0) return CER_OK;
     if (!vertices || !order || !cell_start || !cell_keys || !reps || !took || (colors == nullptr) != (rep_colors == nullptr)) return CER_EINVAL;
     if (quadric && (!starts || (nf && (!faces || !corner_order)))) return CER_EINVAL;
@@ -984,11 +946,7 @@ __device__ __forceinline__ bool mesh_edge_head(const long long* __restrict__ key
 }
 
 __global__ __launch_bounds__(256) void mesh_edge_count_kernel(const long long* __restrict__ keys, long nk, unsigned* __restrict__ partials) {
-    unsigned long long bal[MESH_ITER];
-    const long seg = compact_seg<MESH_TILE, long>();
-    const unsigned wave = compact_ballots(seg, [&](long p) { return mesh_edge_head(keys, nk, p); }, bal);
-    const unsigned tot = compact_block_total(wave);
-    if (threadIdx.x == 0) partials[blockIdx.x] = tot;
+    compact_count<MESH_TILE>(compact_seg<MESH_TILE, long>(), [&](long p) { return mesh_edge_head(keys, nk, p); }, partials, blockIdx.x);
 }
 
 // emit: the head of a run writes its entry - owner, other and the run's keys by direction bit.  The run is walked forward from the head, so
@@ -996,17 +954,9 @@ __global__ __launch_bounds__(256) void mesh_edge_count_kernel(const long long* _
 __global__ __launch_bounds__(256) void mesh_edge_emit_kernel(const long long* __restrict__ keys, long nk, const long long* __restrict__ offsets,
                                                              long long capacity, int* __restrict__ owner, int* __restrict__ nbrs,
                                                              int* __restrict__ along, int* __restrict__ against) {
-    const int lane = threadIdx.x & 63;
-    const long seg = compact_seg<MESH_TILE, long>();
-    unsigned long long bal[MESH_ITER];
-    const unsigned tot = compact_ballots(seg, [&](long p) { return mesh_edge_head(keys, nk, p); }, bal);
-    long long base = compact_wave_base(tot, offsets, blockIdx.x);
-#pragma unroll
-    for (int jj = 0; jj < MESH_ITER; ++jj) {
-        const long p = seg + 64 * jj;
-        const long long idx = base + compact_rank(bal[jj]);
-        base += __popcll(bal[jj]);
-        if (!((bal[jj] >> lane) & 1ull) || idx >= capacity) continue;    // (never past what the caller allocated)
+    const auto set = [&](long p) { return mesh_edge_head(keys, nk, p); };
+    compact_emit<MESH_TILE>(compact_seg<MESH_TILE, long>(), set, offsets, blockIdx.x, [&](long p, long long idx) {
+        if (idx >= capacity) return;                                     // (never past what the caller allocated)
         const long long pair = keys[p] >> 1;
         int n0 = 0, n1 = 0;
         for (long q = p; q < nk; ++q) {
@@ -1018,7 +968,7 @@ __global__ __launch_bounds__(256) void mesh_edge_emit_kernel(const long long* __
         nbrs[idx] = (int)(pair & 0x7fffffffll);
         along[idx] = n0;
         against[idx] = n1;
-    }
+    });
 }
 
 // ---- smoothing, prepare: one thread per vertex reads its run once.  flags[v] = 1 (finite in the input) | 2 (frozen) | 4 (boundary: an entry
@@ -1179,7 +1129,7 @@ extern "C" int cer_mesh_smooth_steps_f64(double* state_a, double* state_b, long 
     if (n_steps < 0) return CER_EINVAL;
     const int rc = mesh_edge_sizes(nv, 0, nn);
     if (rc != CER_OK) return rc;
-    if (!mesh_is_finite(w_even) || !mesh_is_finite(w_odd)) return CER_EINVAL;
+    if (!cer_is_finite(w_even) || !cer_is_finite(w_odd)) return CER_EINVAL;
     if (nv == 0 || n_steps == 0) return CER_OK;
     if (!state_a || !state_b || state_a == state_b || !nbr_starts || !flags || (nn && !walk)) return CER_EINVAL;
     for (int i = 0; i < n_steps; ++i) {                                  // stream order: step i reads what step i - 1 wrote, no host wait between

@@ -202,15 +202,11 @@ __global__ __launch_bounds__(256) void mesh_tri_nearest_kernel(GridView g, const
 // that is no number of its kind -> CER_EINVAL; (2) too large -> CER_ESHAPE; (3) nothing to do -> CER_OK, nothing launched; (4) null
 // pointers -> CER_EINVAL, then records that are not 16-byte aligned -> CER_EALIGN.
 static const long long TRI_INT_MAX = 0x7fffffffLL;
-static bool tri_is_finite(double v) { return v - v == 0.0; }
-static bool tri_frame_ok(const double* origin, double cell) {
-    return origin && tri_is_finite(origin[0]) && tri_is_finite(origin[1]) && tri_is_finite(origin[2]) && tri_is_finite(cell) && cell > 0.0;
-}
 static unsigned tri_blocks(long long n) { return (unsigned)((n + 255) / 256); }
 
 extern "C" int cer_mesh_tri_cells_i64(const float* vertices, long long nv, const int* faces, long long nf, const double* areas,
                                       const double* origin, double cell, long long* cells, int* flag, void* stream) {
-    if (nv < 0 || nf < 0 || !tri_frame_ok(origin, cell)) return CER_EINVAL;
+    if (nv < 0 || nf < 0 || !cer_frame_ok(origin, cell)) return CER_EINVAL;
     if (nv > TRI_INT_MAX || nf > TRI_INT_MAX / 3) return CER_ESHAPE;
     if (nf == 0) return CER_OK;
     if (!faces || !areas || !cells || !flag || (nv && !vertices)) return CER_EINVAL;
@@ -230,7 +226,7 @@ extern "C" int cer_mesh_tri_cells_i64(const float* vertices, long long nv, const
 extern "C" int cer_mesh_tri_pairs_i64(const float* vertices, long long nv, const int* faces, long long nf, const double* areas,
                                       const double* origin, double cell, const long long* cum, long long npairs, long long* keys, int* ids,
                                       void* stream) {
-    if (nv < 0 || nf < 0 || npairs < 0 || !tri_frame_ok(origin, cell)) return CER_EINVAL;
+    if (nv < 0 || nf < 0 || npairs < 0 || !cer_frame_ok(origin, cell)) return CER_EINVAL;
     if (nv > TRI_INT_MAX || nf > TRI_INT_MAX / 3 || npairs > TRI_INT_MAX) return CER_ESHAPE;
     if (nf == 0 || npairs == 0) return CER_OK;
     if (!faces || !areas || !cum || !keys || !ids || (nv && !vertices)) return CER_EINVAL;
@@ -256,7 +252,7 @@ extern "C" int cer_mesh_tri_nearest_f32(const void* records, long long nf, const
                                         const long long* cell_start, long long ncells, const double* origin, double cell, const float* queries,
                                         const long long* qorder, long long m, float max_dist, int* face, float* dist, float* closest,
                                         void* stream) {
-    if (nf < 0 || npairs < 0 || ncells < 0 || m < 0 || !tri_frame_ok(origin, cell) || !(max_dist >= 0.0f)) return CER_EINVAL;
+    if (nf < 0 || npairs < 0 || ncells < 0 || m < 0 || !cer_frame_ok(origin, cell) || !(max_dist >= 0.0f)) return CER_EINVAL;
     if (nf > TRI_INT_MAX / 3 || npairs > TRI_INT_MAX || m > TRI_INT_MAX || ncells > npairs) return CER_ESHAPE;
     const double rings = ceil((double)max_dist / cell);
     if (!(rings <= (double)TRI_MAX_RINGS)) return CER_ESHAPE;

@@ -169,9 +169,7 @@ def point_cloud(masks, depth_est, Ks, Es, colors, order, view_base=False):
         raise ValueError(f"point_cloud: {N} cameras expected")
     cams = cams.to(dev)
     order_c = (ctypes.c_int * len(order))(*order)
-    P = int(lib.cer_cloud_partials(len(order), h, w))
-    partials = torch.empty(P, device=dev, dtype=torch.int32)
-    offsets = torch.empty(P + 1, device=dev, dtype=torch.int64)
+    partials, offsets, _ = L.compaction_buffers(int(lib.cer_cloud_partials(len(order), h, w)), dev, extra=1, totals=0)     # (view_base has the totals)
     want_base, view_base = bool(view_base), torch.empty(len(order) + 1, device=dev, dtype=torch.int64)
     pm, pd, pc = L.dev_ptr(masks, "masks", torch.uint8), L.dev_ptr(depth_est, "depth_est"), L.dev_ptr(colors, "colors")
     L.check(lib.cer_cloud_count_u8(pm, N, h, w, order_c, len(order), L.dev_ptr(partials, "partials", torch.int32),

@@ -191,9 +191,7 @@ def mesh_counts(tsdf, weight, grid, min_weight=1):
     if P < 0:
         L.check(P, "mesh_partials")
     cells = torch.empty((nz - 1, ny - 1, nx - 1), device=dev, dtype=torch.int16)
-    partials = torch.empty(P, device=dev, dtype=torch.int32)
-    offsets = torch.empty(P + 2, device=dev, dtype=torch.int64)
-    totals = torch.zeros(2, device=dev, dtype=torch.int64)
+    partials, offsets, totals = L.compaction_buffers(P, dev)
     pc = L.dev_ptr(cells, "cells", torch.int16)
     L.check(lib.cer_mesh_cells_u16(L.dev_ptr(tsdf, "tsdf"), L.dev_ptr(weight, "weight", torch.int32), nx, ny, nz, min_weight, pc,
                                    L.cur_stream()), "mesh_cells")
@@ -450,9 +448,7 @@ def _select(vertices, faces, keep, starts, order, normals, colors):
     nvo = nfo = 0
     if P:
         used = torch.empty(nv, device=dev, dtype=torch.uint8)
-        partials = torch.empty(P, device=dev, dtype=torch.int32)
-        offsets = torch.empty(P + 2, device=dev, dtype=torch.int64)
-        totals = torch.zeros(2, device=dev, dtype=torch.int64)
+        partials, offsets, totals = L.compaction_buffers(P, dev)
         pf, pk, pu = L.dev_ptr(faces, "faces", torch.int32), L.dev_ptr(keep, "keep", torch.uint8), L.dev_ptr(used, "used", torch.uint8)
         L.check(lib.cer_mesh_select_count(pf, nf, L.dev_ptr(starts, "starts", torch.int32), L.dev_ptr(order, "order", torch.int32), nv, pk, pu,
                                           L.dev_ptr(partials, "partials", torch.int32), L.dev_ptr(offsets, "offsets", torch.int64),
@@ -645,9 +641,7 @@ def _edges(faces, nv):
         L.check(lib.cer_mesh_edge_keys_i64(L.dev_ptr(faces, "faces", torch.int32), nf, nv, L.dev_ptr(keys, "keys", torch.int64), L.cur_stream()),
                 "mesh_edge_keys")
         keys = torch.sort(keys).values                       # equal keys are indistinguishable: no stability needed
-        partials = torch.empty(P, device=dev, dtype=torch.int32)
-        offsets = torch.empty(P + 2, device=dev, dtype=torch.int64)
-        totals = torch.zeros(2, device=dev, dtype=torch.int64)
+        partials, offsets, totals = L.compaction_buffers(P, dev)
         pk = L.dev_ptr(keys, "keys", torch.int64)
         L.check(lib.cer_mesh_edge_count(pk, nf, L.dev_ptr(partials, "partials", torch.int32), L.dev_ptr(offsets, "offsets", torch.int64),
                                         L.dev_ptr(totals, "totals", torch.int64), L.cur_stream()), "mesh_edge_count")
@@ -1273,7 +1267,7 @@ class MeshIndex:
         del perm, ids
         stage("sort")
         P = int(lib.cer_grid_partials(npairs))
-        partials, offsets, totals = (torch.empty(k, device=dev, dtype=t) for k, t in ((P, torch.int32), (P + 1, torch.int64), (2, torch.int64)))
+        partials, offsets, totals = L.compaction_buffers(P, dev, extra=1)
         pk = L.dev_ptr(keys, "keys", torch.int64)
         L.check(lib.cer_grid_cells_count_i64(pk, npairs, L.dev_ptr(partials, "partials", torch.int32), L.dev_ptr(offsets, "offsets", torch.int64),
                                              L.dev_ptr(totals, "totals", torch.int64), L.cur_stream()), "grid_cells_count")

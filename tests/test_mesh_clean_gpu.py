@@ -187,6 +187,26 @@ def test_select_faces_equals_the_restatement(dev, spheres):
         ME.select_faces(torch.from_numpy(hv[:8]).to(dev), torch.from_numpy(hf).to(dev), torch.ones(4, dtype=torch.bool, device=dev))
 
 
+def test_select_faces_at_the_boundaries_of_the_compaction(dev):
+    """2050 disjoint triangles (6150 vertices) with exactly the faces kept that sit at the seams of compact.hpp's tile walk: the first and last
+    lane of a row (0, 63), the next row's first (64), the last and first position of a wave's segment (511, 512), the last position of a tile
+    and the first of the next (2047, 2048), and the last face (2049).  An off-by-one in the rank, the row sum, the wave base or the block
+    offset moves or drops one of them; the vertex pass crosses the same seams at three times the positions."""
+    from cer_mvs_amd import mesh as ME
+    assert ME.MESH_TILE == 2048
+    nf = 2050
+    rng = np.random.default_rng(7)
+    v = rng.normal(size=(3 * nf, 3)).astype(np.float32)
+    f = np.arange(3 * nf, dtype=np.int32).reshape(nf, 3)
+    kept = [0, 63, 64, 511, 512, 2047, 2048, 2049]
+    keep = np.zeros(nf, bool)
+    keep[kept] = True
+    want = C.select_faces(v, f, keep)
+    got = dev_select(dev, ME.select_faces, v, f, keep)
+    assert_same_selection(got, want, "the seams")
+    assert got[2].tolist() == [3 * q + c for q in kept for c in range(3)] and got[1].tolist() == np.arange(24).reshape(8, 3).tolist()
+
+
 # ---------------------------------------------------------------- removal
 def test_remove_small_components_on_the_three_spheres(dev, spheres):
     from cer_mvs_amd import mesh as ME
